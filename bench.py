@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- episodes/s of the LSTM-baseline train step on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, ONE timed region of exactly K steps
+(value and ms_per_step come from it), the outputs if --dump-outputs is given, the result line.  --dump-outputs DIR writes
+what the timed path computed in its last step, as a caller of the train step receives it: the loss (loss.npy) and every
+parameter after the update (<name>.npy), float32, a fixed seeded sample of each parameter when all of them together
+would pass 64 MB; the inputs (pool and initial parameters) are seeded, so two builds compare output for output.
+--full adds everything else below: FSMG_BENCH_REPEATS (default 5) timed regions with their median as the headline, the
+fused-cell roofline leg, the clock probe, the other configurations, the eval and host-path legs, the per-kernel breakdown,
+the fp32-MFMA GEMM leg, the CPU baseline with its NLL agreement and, for N > 1, the exchange-cost legs; the --no-* options
+switch single legs of a --full run off.
 
 Workload (BASELINE.json configs[1] = "cfg-B"): synthetic vocab 10 000 (V1 = 10 001), seq_len
 128, 5-way / 5-shot / 4 query songs -> B = 45 sequences per episode, LSTM E=250 H=512 L=1, lr 5e-3, clip 5,
@@ -77,7 +87,8 @@ PEAK_F32_MFMA_TFLOPS = 157.3       # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32
 PEAK_BF16_MFMA_TFLOPS = 2500.0
 PEAK_BX3_TFLOPS = PEAK_BF16_MFMA_TFLOPS / 6.0
 HBM_ACHIEVABLE_TBPS = 6.3          # ~6.3 of the 8.0 TB/s spec is achievable
-REPEATS = max(1, int(os.environ.get('FSMG_BENCH_REPEATS', 5)))       # timed regions of K steps each; value = their median
+REPEATS = max(1, int(os.environ.get('FSMG_BENCH_REPEATS', 5)))       # --full: timed regions of K steps each; value = their median
+DUMP_BYTES = 60 * 10 ** 6          # --dump-outputs: array data in all (the .npy headers on top stay far below 64 MB)
 ARITHMETIC_GEMM = ('fp32 storage, fp32 accumulation everywhere.  GEMMs (default, FSMG_GEMM=bx3): every operand value is split EXACTLY into three '
                    'bf16 numbers and the six partial products >= 2^-23 of the fp32 product are summed in fp32 by v_mfma_f32_32x32x16_bf16 -- '
                    'error against fp64 below the fp32-MFMA kernel\'s on every shape of the step (tools/gemm_bench.cpp, BX3=0/1 with verify; '
@@ -219,7 +230,7 @@ def other_configs(log, steps=20, warmup=5):
         val_steps = env_over.pop('_val', None)
         env = dict(os.environ, FSMG_BENCH_REPEATS='1', **env_over)
         cmd = [sys.executable, os.path.abspath(__file__), '--config', config, '--steps', str(steps), '--warmup', str(warmup), '--pool', pool,
-               '--no-cpu-baseline', '--no-breakdown', '--no-other-configs', '--no-extras'] + (['--val-nll', val_steps] if val_steps else [])
+               '--full', '--no-cpu-baseline', '--no-breakdown', '--no-other-configs', '--no-extras'] + (['--val-nll', val_steps] if val_steps else [])
         try:
             proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=env, timeout=180)
             line = [l for l in proc.stdout.splitlines() if l.startswith('{"metric"')][-1]
@@ -450,6 +461,20 @@ def exchange_plans(world, env, same_gpu=False):
     return plans
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: array} -> out_dir/<name>.npy, float32.  When the arrays together pass
+    DUMP_BYTES, each keeps the same share of its elements: a sample drawn from a fixed seed, flattened, in index order --
+    the same elements in every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in sorted(arrays.items()):
+        keep = max(1, a.size * DUMP_BYTES // total) if total > DUMP_BYTES else a.size
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(1234).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` outside torchrun: start N ranks of this script under torch.distributed.run (rank r -> GPU r,
     rendezvous on 127.0.0.1), pass their output through and print rank 0's JSON line LAST."""
@@ -503,6 +528,11 @@ def main():
     ap.add_argument('--pool', default='uniform', choices=['uniform', 'padded-zipf'],
                     help='token pool: SURVEY 8(d)\'s i.i.d. uniform ids (the headline), or zero-padded Zipf songs (what real data looks like; a diagnostic leg)')
     ap.add_argument('--config', default='cfg-B', choices=['cfg-B', 'cfg-C', 'cfg-C-T128', 'cfg-D', 'cfg-Bx4', 'cfg-Bx8', 'cfg-E', 'ref-default'])
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps: the loss and the parameters their last step computed -> DIR/<name>.npy (float32, at most 64 MB in all)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: FSMG_BENCH_REPEATS timed regions (median), roofline / clock / breakdown legs, other configurations, '
+                         'eval and host-path legs, fp32-MFMA GEMM leg, CPU baseline, exchange-cost legs (N > 1)')
     args = ap.parse_args()
     if args.gpus > 1 and 'RANK' not in os.environ and int(os.environ.get('WORLD_SIZE', '1')) == 1:
         sys.exit(self_launch(args))
@@ -528,7 +558,9 @@ def main():
     if same_gpu:
         os.environ['LOCAL_RANK'] = '0'
     torch.cuda.set_device(local)
-    global N_WAY, K_SHOT, Q_QUERY
+    global N_WAY, K_SHOT, Q_QUERY, REPEATS
+    if not args.full:
+        REPEATS = 1                # a plain run times exactly --steps steps
     base = CFG_B
     if args.config != 'cfg-B':
         base, N_WAY, K_SHOT, Q_QUERY = OTHER[args.config]
@@ -689,6 +721,10 @@ def main():
     guard['ok'] = schedules[used]['guard_ok']
     if not guard['ok']:
         log('GUARD FAILED: %r' % schedules[used]['guard_per_rank'])
+    if args.dump_outputs and rank == 0:
+        # before any other leg trains on: what the last timed step left
+        dump_outputs(args.dump_outputs, dict(eng.get_params(), loss=eng.read_losses(1)))
+        log('outputs written to %s' % args.dump_outputs)
 
     def step(i):
         e = i % POOL
@@ -708,6 +744,7 @@ def main():
                       'distinct_devices': len({(d['local_device'], d['uuid'], d['pci_bus_id']) for d in devs}),
                       'launcher': 'bench.py self-launch' if os.environ.get('FSMG_BENCH_SELF_LAUNCHED') == '1' else 'torchrun',
                       'same_gpu_dry_run': same_gpu}
+    if world > 1 and args.full:
         # the same loop with NO exchange (replicas diverge: timing only, on its own model) -> what each schedule's exchange adds
         try:
             m0, p0 = make({})
@@ -724,7 +761,7 @@ def main():
     # ---- roofline leg: the same K steps again with HIP events around every launch of the fused-cell kernels on the library's
     # stream, in the schedule of the timed region (event timing replaces the hipGraph replay by the same launches, eagerly)
     cell = {}
-    if not maml:
+    if not maml and args.full:
         try:
             for cls in CELL_CLASSES:
                 eng.timing_select(cls)
@@ -746,7 +783,7 @@ def main():
     # real-time counter while a few train steps run (the peaks of every `frac` are quoted at the 2.4 GHz spec clock)
     clock_ghz = None
     try:
-        if args.no_extras:
+        if args.no_extras or not args.full:
             raise StopIteration
         n_clk = max(4, min(args.steps, 12))
         eng.synchronize()
@@ -765,7 +802,7 @@ def main():
     # communication (N > 1): the all-reduce of the flat gradient buffer alone on the library's stream, and per schedule what the
     # exchange adds to the same timed loop without any exchange (= the exposed, un-overlapped part)
     comm = None
-    if world > 1:
+    if world > 1 and args.full:
         ar_ms, nbytes = None, None
         try:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -907,7 +944,7 @@ def main():
                 out['roofline'].update({'schedule': 'xcd_partitioned', 'xcds_occupied': nx,
                                         'frac_of_occupied_xcds_peak': ach / (PEAK_F32_MFMA_TFLOPS * nx / 8.0),
                                         'frac_bf16_split_of_occupied_xcds': ach / (PEAK_BX3_TFLOPS * nx / 8.0)})
-    if rank == 0 and world == 1 and args.config == 'cfg-B' and not args.no_other_configs:
+    if rank == 0 and world == 1 and args.config == 'cfg-B' and args.full and not args.no_other_configs:
         # the other BASELINE.json configurations and the serial-order fused cell on the driver's record -- 20 steps
         # each on fresh handles inside this run (one timed region between two synchronisations; a diagnostic, never the headline)
         try:
@@ -932,7 +969,7 @@ def main():
         except Exception as e:                 # noqa: BLE001
             log('other_configs leg failed: %r' % (e,))
             extras_failed['other_configs'] = repr(e)
-    if rank == 0 and not maml and not args.no_extras:
+    if rank == 0 and not maml and args.full and not args.no_extras:
         try:
             # the other half of BASELINE.json's metric: the validation path (query-only forward, batched 16 episodes
             # per call like train.evaluate does); inputs resident in HBM, NLLs read back per call
@@ -949,7 +986,7 @@ def main():
         except Exception as e:                 # noqa: BLE001 -- an extra leg must not cost the result line
             log('eval leg failed: %r' % (e,))
             extras_failed['eval'] = repr(e)
-    if rank == 0 and world == 1 and not maml and not args.no_extras:
+    if rank == 0 and world == 1 and not maml and args.full and not args.no_extras:
         try:
             # the reference's calling convention: host numpy episodes in, the loss read back every step (one 23 KB H2D
             # token copy + one synchronising 4-byte D2H per step) -- PCIe-inclusive, never the headline value
@@ -978,7 +1015,7 @@ def main():
         except Exception as e:                 # noqa: BLE001 -- an extra leg must not cost the result line
             log('host_paths leg failed: %r' % (e,))
             extras_failed['host_paths'] = repr(e)
-    if rank == 0 and world == 1 and not args.no_breakdown and not maml:
+    if rank == 0 and world == 1 and args.full and not args.no_breakdown and not maml:
         try:
             # second, fully instrumented pass: every kernel class bracketed by HIP events (extra information)
             eng.timing_select(None)
@@ -1015,7 +1052,7 @@ def main():
         except Exception as e:                 # noqa: BLE001 -- an extra leg must not cost the result line
             log('breakdown leg failed: %r' % (e,))
             extras_failed['breakdown'] = repr(e)
-    if rank == 0 and world == 1 and not args.no_breakdown and not maml and os.environ.get('FSMG_GEMM', 'bx3') != 'f32':
+    if rank == 0 and world == 1 and args.full and not args.no_breakdown and not maml and os.environ.get('FSMG_GEMM', 'bx3') != 'f32':
         # the same timed loop with every GEMM on the fp32 MFMA (v_mfma_f32_32x32x2_f32): what the bf16-split GEMMs buy
         try:
             alt = Model(dict(cfg, gemm='f32'))
@@ -1052,7 +1089,7 @@ def main():
         except Exception as e:                 # noqa: BLE001 -- an extra leg must not cost the result line
             log('val-nll leg failed: %r' % (e,))
             extras_failed['val_nll'] = repr(e)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not maml:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not maml:
         out['cpu_baseline'] = cpu_baseline(base, pool_host, shape)
         try:
             # GPU against CPU AFTER training (at Glorot init every model scores ln V1, right or wrong): a fresh handle

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,7 +45,7 @@ def test_default_exchange_plan_is_graph_end_alone_and_the_others_are_opt_in():
 
 @pytest.mark.gpu
 def test_bench_starts_its_own_ranks_and_reports_every_schedule():
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full',
                            '--no-cpu-baseline', '--no-breakdown'], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                           universal_newlines=True, timeout=900, env=_clean_env(FSMG_BENCH_SAME_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0', FSMG_BENCH_REPEATS='2',
                                                                                FSMG_BENCH_SCHEDULES='all'))
@@ -77,8 +78,8 @@ def test_bench_starts_its_own_ranks_and_reports_every_schedule():
 
 @pytest.mark.gpu
 def test_single_gpu_bench_prints_one_json_line_with_the_contract_keys():
-    """`python bench.py --steps K --warmup W` as the driver runs it at N = 1 (short, without the CPU leg): stdout is ONE JSON line."""
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--no-cpu-baseline'],
+    """`python bench.py --steps K --warmup W --full` at N = 1 (short, without the CPU leg): stdout is ONE JSON line."""
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--full', '--no-cpu-baseline'],
                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=900, env=_clean_env(FSMG_BENCH_REPEATS='2'))
     assert proc.returncode == 0, (proc.stdout[-2000:], proc.stderr[-4000:])
     printed = [ln for ln in proc.stdout.splitlines() if ln.strip()]
@@ -92,3 +93,57 @@ def test_single_gpu_bench_prints_one_json_line_with_the_contract_keys():
     r = out['roofline']
     assert r['bound'] == 'mfma' and abs(r['frac'] - r['achieved'] / r['peak']) < 1e-9 and r['achieved'] > 0
     assert out['guard']['ok'], out['guard']
+
+
+def test_dump_outputs_samples_the_same_elements_when_the_arrays_pass_64_mb(tmp_path):
+    """--dump-outputs at a configuration whose parameters pass the budget (cfg-C: 78 MB): every array keeps its share of the
+    elements, drawn from a fixed seed, float32, within 64 MB in all; a one-element array (the loss) survives whole."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.RandomState(0)
+    arrays = {'softmax_w': rng.rand(1024, 4709).astype(np.float32), 'kernel_0': rng.rand(1274, 4096).astype(np.float32),
+              'kernel_1': rng.rand(2048, 4096).astype(np.float32), 'loss': np.float32([2.5])}
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    files = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert files == ['kernel_0.npy', 'kernel_1.npy', 'loss.npy', 'softmax_w.npy']
+    assert sum(p.stat().st_size for p in (tmp_path / 'a').iterdir()) <= 64 * 10 ** 6
+    got = {f: np.load(str(tmp_path / 'a' / f)) for f in files}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got['loss.npy'].tolist() == [2.5]
+    assert 0 < got['softmax_w.npy'].size < arrays['softmax_w'].size
+    assert np.isin(got['softmax_w.npy'], arrays['softmax_w']).all()
+    for f in files:
+        assert np.array_equal(got[f], np.load(str(tmp_path / 'b' / f))), f
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_exactly_its_steps_and_dumps_what_the_last_one_computed(tmp_path):
+    """A plain run (no --full): one timed region of exactly --steps steps, none of the --full legs, and --dump-outputs writes the loss
+    and the parameters the last timed step left, float32, within 64 MB; the inputs are seeded, so a second run writes the same
+    arrays up to the step's floating-point reassociation."""
+    outs = []
+    for run in ('a', 'b'):
+        d = tmp_path / run
+        proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--dump-outputs', str(d)],
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=600, env=_clean_env())
+        assert proc.returncode == 0, (proc.stdout[-2000:], proc.stderr[-4000:])
+        printed = [ln for ln in proc.stdout.splitlines() if ln.strip()]
+        assert len(printed) == 1, printed[:5]
+        out = json.loads(printed[0])
+        for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert key in out, key
+        assert out['steps'] == 5 and out['warmup'] == 2 and out['spread']['repeats'] == 1 and out['guard']['ok'], out['guard']
+        assert out['guard']['advanced_by'] == 5 and out['guard']['warmup_advanced_by'] == 2
+        assert abs(out['value'] - 1e3 / out['ms_per_step']) < 1e-6 * out['value']
+        assert out['cpu_baseline'] is None and 'roofline' not in out and 'kernels' not in out and 'other_configs' not in out and 'eval' not in out
+        files = sorted(p.name for p in d.iterdir())
+        assert files == sorted(['loss.npy', 'embedding.npy', 'kernel_0.npy', 'bias_0.npy', 'softmax_w.npy', 'softmax_b.npy']), files
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 * 10 ** 6
+        arrays = {f[:-4]: np.load(str(d / f)) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert arrays['loss'].shape == (1,) and abs(float(arrays['loss'][0]) - out['final_loss']) <= 1e-6 * abs(out['final_loss'])
+        assert arrays['softmax_w'].size == 512 * 10001
+        outs.append(arrays)
+    for name in outs[0]:
+        np.testing.assert_allclose(outs[1][name], outs[0][name], rtol=1e-4, atol=1e-6, err_msg=name)
