@@ -353,6 +353,7 @@ int fsmg_destroy(fsmg_handle h) {
     if (h->scratch) hipFree(h->scratch);
     if (h->d_step) hipFree(h->d_step);
     if (h->dec) hipFree(h->dec);
+    if (h->gen) hipFree(h->gen);
     if (h->khf) hipFree(h->khf);
     if (h->khx) hipFree(h->khx);
     if (h->P_saved) hipFree(h->P_saved);

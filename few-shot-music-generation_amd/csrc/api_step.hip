@@ -319,6 +319,41 @@ int fsmg_maml_eval(fsmg_handle h, const int32_t* support, const int32_t* query, 
     return rc;
 }
 
+// the device error flag the adaptation's passes left (fsmg_maml_eval's query pass reads it in check_tokens_and_read)
+static int adapt_flag(fsmg_handle h) {
+    int err = 0;
+    HIPCK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (!err) return FSMG_OK;
+    HIPCK(h, hipMemsetAsync(h->d_err, 0, sizeof(int), h->stream));
+    if (err == 2) on_timeout(h);
+    else if (err == 4) on_softmax_range(h);
+    return report(h, err);
+}
+
+// adapt on the support rows like fsmg_maml_eval, generate at theta' (api_generate.hip), restore theta whatever happened
+int fsmg_maml_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,
+                       float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    int rc = check_gen_config(h, g, primer, out_tokens);
+    if (rc != FSMG_OK) return rc;
+    if (!support || n_support_rows <= 0 || inner_steps < 0 || inner_steps > 64 || !(inner_lr >= 0.f) || !std::isfinite(inner_lr) ||
+        (support_on_device != 0 && support_on_device != 1))
+        return fail(h, FSMG_ERR_INVALID, "bad support / n_support_rows / inner_steps / inner_lr");
+    BEGIN_CALL(h);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        rc = maml_adapt(h, support, 1, n_support_rows, inner_steps, inner_lr, support_on_device);
+        if (rc == FSMG_OK) rc = adapt_flag(h);           // a time-out / token error inside the adaptation: theta' is not usable
+        if (rc == FSMG_OK) rc = generate_core(h, g, primer, out_tokens, out_logprob);
+        const int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
+        h->have_grads = false;
+        if (rc == FSMG_OK) rc = rc2;
+        if (!(is_retry(rc) && h->retry_armed)) break;
+        h->retry_armed = false;                        // adapted with garbage (skipped) steps: repeat on per-step launches
+    }
+    return rc;
+}
+
 int fsmg_eval_batch(fsmg_handle h, const int32_t* queries, int32_t n_episodes, int32_t N, int32_t Q,
                     int32_t tokens_on_device, float* nll) {
     if (!h || !queries || !nll || n_episodes <= 0) return FSMG_ERR_INVALID;

@@ -1,0 +1,385 @@
+// Batched sampling decode (fsmg_generate, DESIGN.md "Batched generation"): one LSTM position for B independent rows per
+// (L cell launches + logits + pick).  Generation is weight-streaming -- one position reads [Kx;Kh] of every layer and softmax_w
+// whatever B is -- so the GEMV kernels load their 16-column weight tile straight to VGPRs and loop the row tiles of the
+// workgroup over it; the products run on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation).
+//
+// Row independence: every output element is an fp32 fma chain over k in an order fixed by the kernel's shape (in_dim, Hp),
+// and the cross-wave sums / the pick's reductions have a fixed tree: nothing depends on B or on the other rows.
+#include <math.h>
+
+#include <algorithm>
+#include <atomic>
+
+#include "fsmg_kernels.h"
+
+namespace fsmg {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int GEN_THREADS = 256;   // 4 waves
+constexpr int GEN_ROWS = 64;       // rows per workgroup: 4 row tiles of 16 (grid.y covers the rest)
+constexpr int GEN_CH = 16;         // k per lane held in registers at a time
+constexpr int PICK_THREADS = 1024;
+constexpr int PICK_LDS_FLOATS = 32 * 1024;   // rows up to 128 KiB are staged in LDS
+
+// Partial products of one 16-column weight tile with up to 4 row tiles over one K segment of n rows (n % 16 == 0).
+// The segment is split into 16 slots of m = n / 16 consecutive k (slot = 4 * wave + lane group); lane (c = l & 15, g = l >> 4)
+// holds W[k][c] as the MFMA's B operand and act[row c of the tile][k] as its A operand, so one MFMA sums 4 k of 4 slots.
+// `w` points at column c of the tile (nullptr: a column past the end, read as zeros); ap[rt] at the segment's row of the lane's
+// row in tile rt (nullptr: a row past B).  acc[rt] is the 16 x 16 D tile (col = l & 15, row = 4 * (l >> 4) + reg).
+__device__ __forceinline__ void gemv_segment(const float* __restrict__ w, long long ldw, int n, const float* const (&ap)[4], int nrt,
+                                             f32x4 (&acc)[4]) {
+    const int m = n >> 4;
+    const int slot = (threadIdx.x >> 6) * 4 + ((threadIdx.x & 63) >> 4);
+    const int kb = slot * m;
+    for (int c0 = 0; c0 < m; c0 += GEN_CH) {
+        float wr[GEN_CH];
+#pragma unroll
+        for (int s = 0; s < GEN_CH; ++s) wr[s] = (w != nullptr && c0 + s < m) ? w[(long long)(kb + c0 + s) * ldw] : 0.0f;
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt) {
+            if (rt >= nrt) break;
+            const float* a = ap[rt];
+            float av[GEN_CH];
+#pragma unroll
+            for (int s = 0; s < GEN_CH; ++s) av[s] = (a != nullptr && c0 + s < m) ? a[kb + c0 + s] : 0.0f;
+#pragma unroll
+            for (int s = 0; s < GEN_CH; ++s)
+                if (c0 + s < m) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], wr[s], acc[rt], 0, 0, 0);
+        }
+    }
+}
+
+// the four waves' partial tiles -> LDS [wave][row][col] (col padded to 17: the transposed reads of the epilogue)
+__device__ __forceinline__ void store_partials(float (&part)[4][GEN_ROWS][17], const f32x4 (&acc)[4], int nrt) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) {
+        if (rt >= nrt) break;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part[wave][rt * 16 + 4 * (lane >> 4) + r][lane & 15] = acc[rt][r];
+    }
+}
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// One LSTM layer at one position for rows [64 * blockIdx.y, +64) and unit block nb = blockIdx.x (units 4nb..4nb+3, packed
+// columns 16nb..16nb+15 of the gate-interleaved [Kx;Kh]).  Layer 0 (emb != nullptr) gathers its x rows from the embedding by
+// the device-resident token tok[r * ldtok + pos]; other layers read x = the layer below's h at this position ([B][Hp]).
+__global__ __launch_bounds__(GEN_THREADS) void k_gen_cell(const float* __restrict__ Kx, int in_dim, const float* __restrict__ Kh,
+                                                          const float* __restrict__ bias, int Hp, const float* __restrict__ emb, int ldemb,
+                                                          const int* __restrict__ tok, int ldtok, int pos, const float* __restrict__ x,
+                                                          const float* __restrict__ h_in, float* __restrict__ h_out, float* __restrict__ c,
+                                                          int B) {
+    __shared__ float part[4][GEN_ROWS][17];
+    const int nb = blockIdx.x, r0 = blockIdx.y * GEN_ROWS;
+    const int lane = threadIdx.x & 63;
+    const int G4 = 4 * Hp;
+    const int nrt = min(4, (B - r0 + 15) >> 4);
+    f32x4 acc[4];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    const float* ap[4];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) {
+        const int r = r0 + rt * 16 + (lane & 15);
+        ap[rt] = r >= B ? nullptr : emb != nullptr ? emb + (long long)tok[(long long)r * ldtok + pos] * ldemb : x + (long long)r * Hp;
+    }
+    gemv_segment(Kx + 16 * nb + (lane & 15), G4, in_dim, ap, nrt, acc);
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) {
+        const int r = r0 + rt * 16 + (lane & 15);
+        ap[rt] = r < B ? h_in + (long long)r * Hp : nullptr;
+    }
+    gemv_segment(Kh + 16 * nb + (lane & 15), G4, Hp, ap, nrt, acc);
+    store_partials(part, acc, nrt);
+    __syncthreads();
+    const int row = threadIdx.x >> 2, uu = threadIdx.x & 3, r = r0 + row;
+    if (r >= B) return;
+    float z[4];
+#pragma unroll
+    for (int gi = 0; gi < 4; ++gi) {
+        const int col = 4 * gi + uu;
+        float t = part[0][row][col];
+        t += part[1][row][col];
+        t += part[2][row][col];
+        t += part[3][row][col];
+        z[gi] = t + bias[16 * nb + col];
+    }
+    // gates i, j, f, o; forget bias 1 (BasicLSTMCell(forget_bias=1.)), exactly as k_decode_cell
+    const long long u = (long long)r * Hp + 4 * nb + uu;
+    const float si = sigmoidf_(z[0]), tj = tanhf(z[1]), sf = sigmoidf_(z[2] + 1.0f), so = sigmoidf_(z[3]);
+    const float cn = c[u] * sf + si * tj;
+    c[u] = cn;
+    h_out[u] = tanhf(cn) * so;
+}
+
+// logits[r][v] = h[r] . W[:, v] + bias[v] for v < ncols; column tile 16 * blockIdx.x, rows 64 * blockIdx.y
+__global__ __launch_bounds__(GEN_THREADS) void k_gen_logits(const float* __restrict__ W, int ldw, const float* __restrict__ bias, int ncols,
+                                                            const float* __restrict__ h, int Hp, int B, float* __restrict__ logits, int ldl) {
+    __shared__ float part[4][GEN_ROWS][17];
+    const int col0 = 16 * blockIdx.x, r0 = blockIdx.y * GEN_ROWS;
+    const int lane = threadIdx.x & 63;
+    const int nrt = min(4, (B - r0 + 15) >> 4);
+    f32x4 acc[4];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    const float* ap[4];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) {
+        const int r = r0 + rt * 16 + (lane & 15);
+        ap[rt] = r < B ? h + (long long)r * Hp : nullptr;
+    }
+    const int cl = col0 + (lane & 15);
+    gemv_segment(cl < ncols ? W + cl : nullptr, ldw, Hp, ap, nrt, acc);
+    store_partials(part, acc, nrt);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < GEN_ROWS * 16 / GEN_THREADS; ++i) {
+        const int idx = threadIdx.x + GEN_THREADS * i, row = idx >> 4, col = idx & 15;
+        const int r = r0 + row, v = col0 + col;
+        if (r >= B || v >= ncols) continue;
+        float t = part[0][row][col];
+        t += part[1][row][col];
+        t += part[2][row][col];
+        t += part[3][row][col];
+        logits[(long long)r * ldl + v] = t + bias[v];
+    }
+}
+
+// ---------------------------------------------------------------- the pick
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants)
+__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned lo0 = 0xD2511F53u * ctr.x, hi0 = __umulhi(0xD2511F53u, ctr.x);
+        const unsigned lo1 = 0xCD9E8D57u * ctr.z, hi1 = __umulhi(0xCD9E8D57u, ctr.z);
+        ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
+        key.x += 0x9E3779B9u; key.y += 0xBB67AE85u;
+    }
+    return ctr;
+}
+
+// -log(-log(u)), u = ((x >> 8) + 0.5) * 2^-24 in (0, 1).  Every u and 1 - u of this grid is exact in fp32, so -log(u) is taken
+// as log1p(-(1 - u)) where u >= 1/2 (no cancellation next to 1) and the result is good to a few fp32 ulps.
+__device__ __forceinline__ float gumbel_of(unsigned x) {
+    const unsigned i = x >> 8;
+    float nl;
+    if (i < (1u << 23)) nl = -logf(((float)i + 0.5f) * 0x1p-24f);
+    else nl = -log1pf(-(((float)((1u << 24) - i) - 0.5f) * 0x1p-24f));
+    return -logf(nl);
+}
+
+// order-preserving uint key of a float (larger float -> larger key)
+__device__ __forceinline__ unsigned fkey(float f) {
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_float(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
+struct PickShared {
+    float fv[PICK_THREADS / 64];
+    int iv[PICK_THREADS / 64];
+    double dv[PICK_THREADS / 64];
+    int hist[256];
+    unsigned prefix;
+    int kleft;
+};
+
+// block-wide (max, lowest index) -- every thread gets the result
+__device__ __forceinline__ void block_argmax(PickShared& sh, float& v, int& i) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o);
+        const int oi = __shfl_xor(i, o);
+        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+    }
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { sh.fv[w] = v; sh.iv[w] = i; }
+    __syncthreads();
+    v = sh.fv[0]; i = sh.iv[0];
+    for (int k = 1; k < PICK_THREADS / 64; ++k)
+        if (sh.fv[k] > v || (sh.fv[k] == v && sh.iv[k] < i)) { v = sh.fv[k]; i = sh.iv[k]; }
+}
+__device__ __forceinline__ double block_sum(PickShared& sh, double s) {
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh.dv[w] = s;
+    __syncthreads();
+    double t = 0.0;
+    for (int k = 0; k < PICK_THREADS / 64; ++k) t += sh.dv[k];
+    return t;
+}
+
+// One row per workgroup.  Token = argmax over the allowed set of logit / T + Gumbel(Philox(key = seed, ctr = (v >> 2, t, b, 0))),
+// lowest index on ties; T == 0 or top_k == 1: argmax of the logits.  Allowed set: logit >= the top_k-th largest logit (radix
+// select on order-preserving keys), every column when top_k is 0 or ncols.  Writes the token into the token buffer (the next
+// position's input), out_tok / out_lp [b][t], lp = logit_tok - logsumexp(all ncols logits).
+template <bool STAGED>
+__global__ __launch_bounds__(PICK_THREADS) void k_gen_pick(const float* __restrict__ logits, int ldl, int ncols, float temperature, int top_k,
+                                                           unsigned seed_lo, unsigned seed_hi, int t, int* __restrict__ tok, int ldtok,
+                                                           int pos_out, int* __restrict__ out_tok, float* __restrict__ out_lp, int num) {
+    extern __shared__ float srow[];
+    __shared__ PickShared sh;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* row = logits + (long long)b * ldl;
+    auto val = [&](int v) -> float { return STAGED ? srow[v] : row[v]; };
+
+    // staging and the row maximum in one sweep, 8 loads in flight per thread (the sweep is latency-bound at small B)
+    // the index starts at column 0 (like k_decode_pick), so that a row without a comparable logit (all NaN) still yields a column
+    float mx = -INFINITY; int mi = 0;
+    for (int v0 = tid; v0 < ncols; v0 += 8 * PICK_THREADS) {
+        float l[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) l[j] = v0 + j * PICK_THREADS < ncols ? row[v0 + j * PICK_THREADS] : -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int v = v0 + j * PICK_THREADS;
+            if (v >= ncols) break;
+            if (STAGED) srow[v] = l[j];
+            if (l[j] > mx || (l[j] == mx && v < mi)) { mx = l[j]; mi = v; }
+        }
+    }
+    block_argmax(sh, mx, mi);          // (its barriers also order the staging stores before the reads below)
+    double se = 0.0;
+    for (int v = tid; v < ncols; v += PICK_THREADS) se += (double)expf(val(v) - mx);
+    se = block_sum(sh, se);
+    const float lse = mx + (float)log(se);
+
+    int best = mi;
+    if (temperature > 0.0f && top_k != 1) {
+        float thr = -INFINITY;
+        if (top_k > 1 && top_k < ncols) {
+            // k-th largest key, MSB-first radix select over 8-bit digits
+            if (tid == 0) { sh.prefix = 0u; sh.kleft = top_k; }
+            unsigned mask = 0u;
+            for (int shift = 24; shift >= 0; shift -= 8) {
+                if (tid < 256) sh.hist[tid] = 0;
+                __syncthreads();
+                const unsigned prefix = sh.prefix;
+                for (int v = tid; v < ncols; v += PICK_THREADS) {
+                    const unsigned k = fkey(val(v));
+                    if ((k & mask) == prefix) atomicAdd(&sh.hist[(k >> shift) & 255u], 1);
+                }
+                __syncthreads();
+                if (tid < 64) {       // wave 0: lane l owns digits 255 - 4l .. 252 - 4l; counts from the top digit down
+                    int cnt[4], s = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { cnt[j] = sh.hist[255 - 4 * tid - j]; s += cnt[j]; }
+                    int incl = s;
+                    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o); if (tid >= o) incl += y; }
+                    int before = incl - s;
+                    const int kl = sh.kleft;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (before < kl && kl <= before + cnt[j]) {
+                            sh.prefix = prefix | ((unsigned)(255 - 4 * tid - j) << shift);
+                            sh.kleft = kl - before;
+                        }
+                        before += cnt[j];
+                    }
+                }
+                mask |= 255u << shift;
+                __syncthreads();
+            }
+            thr = key_float(sh.prefix);
+        }
+        const uint2 key = make_uint2(seed_lo, seed_hi);
+        float bs = -INFINITY; int bi = 0;
+        for (int q = tid; 4 * q < ncols; q += PICK_THREADS) {
+            const uint4 x = philox4x32_10(make_uint4((unsigned)q, (unsigned)t, (unsigned)b, 0u), key);
+            const unsigned xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = 4 * q + j;
+                if (v >= ncols) break;
+                const float l = val(v);
+                if (!(l >= thr)) continue;
+                const float s = l / temperature + gumbel_of(xs[j]);
+                if (s > bs || (s == bs && v < bi)) { bs = s; bi = v; }
+            }
+        }
+        block_argmax(sh, bs, bi);
+        best = bi;
+    }
+    best = min(max(best, 0), ncols - 1);      // the token gathers an embedding row at the next position: never outside [0, ncols)
+    if (tid == 0) {
+        tok[(long long)b * ldtok + pos_out] = best;
+        out_tok[(long long)b * num + t] = best;
+        out_lp[(long long)b * num + t] = val(best) - lse;
+    }
+}
+
+// token buffer row b: [start, primer[b][0..P-1]]; *err = 1 for a primer id outside [0, vocab)
+__global__ void k_gen_primer(const int* __restrict__ primer, int B, int P, int vocab, int start, int* __restrict__ tok, int ldtok,
+                             int* __restrict__ err) {
+    const long long n = (long long)B * (P + 1);
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / (P + 1)), p = (int)(i % (P + 1));
+        int w = start;
+        if (p > 0) {
+            w = primer[(long long)b * P + p - 1];
+            if (w < 0 || w >= vocab) { atomicOr(err, 1); w = start; }
+        }
+        tok[(long long)b * ldtok + p] = w;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_gen_cell(hipStream_t s, const float* Kx, int in_dim, const float* Kh, const float* bias, int Hp, const float* emb, int ldemb,
+                           const int* tok, int ldtok, int pos, const float* x, const float* h_in, float* h_out, float* c, int B) {
+    if (B <= 0) return hipSuccess;
+    if ((in_dim & 15) || (Hp & 15) || B > 65535 * GEN_ROWS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_gen_cell, dim3(Hp / 4, (B + GEN_ROWS - 1) / GEN_ROWS), dim3(GEN_THREADS), 0, s, Kx, in_dim, Kh, bias, Hp, emb, ldemb,
+                       tok, ldtok, pos, x, h_in, h_out, c, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_gen_logits(hipStream_t s, const float* W, int ldw, const float* bias, int ncols, const float* h, int Hp, int B,
+                             float* logits, int ldl) {
+    if (B <= 0) return hipSuccess;
+    if ((Hp & 15) || ncols > ldw || ncols > ldl || B > 65535 * GEN_ROWS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_gen_logits, dim3((ncols + 15) / 16, (B + GEN_ROWS - 1) / GEN_ROWS), dim3(GEN_THREADS), 0, s, W, ldw, bias, ncols, h, Hp,
+                       B, logits, ldl);
+    return hipGetLastError();
+}
+
+hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, uint64_t seed, int t,
+                           int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num) {
+    if (B <= 0) return hipSuccess;
+    if (ncols <= 0 || ncols > ldl || t < 0 || t >= num || pos_out >= ldtok) return hipErrorInvalidValue;
+    const unsigned lo = (unsigned)(seed & 0xFFFFFFFFull), hi = (unsigned)(seed >> 32);
+    // the staged row may take up to 128 KiB of the 160 KiB LDS: raise the kernel's limit once per device (a second caller racing
+    // the first sets the same value again, harmless)
+    static std::atomic<unsigned long long> attr_set{0};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
+        e = hipFuncSetAttribute((const void*)k_gen_pick<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(float) * PICK_LDS_FLOATS);
+        if (e != hipSuccess) return e;
+        attr_set.fetch_or(bit, std::memory_order_release);
+    }
+    if (ncols <= PICK_LDS_FLOATS)
+        hipLaunchKernelGGL((k_gen_pick<true>), dim3(B), dim3(PICK_THREADS), sizeof(float) * (size_t)ncols, s, logits, ldl, ncols, temperature,
+                           top_k, lo, hi, t, tok, ldtok, pos_out, out_tok, out_lp, num);
+    else
+        hipLaunchKernelGGL((k_gen_pick<false>), dim3(B), dim3(PICK_THREADS), 0, s, logits, ldl, ncols, temperature, top_k, lo, hi, t, tok,
+                           ldtok, pos_out, out_tok, out_lp, num);
+    return hipGetLastError();
+}
+
+hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err) {
+    if (B <= 0) return hipSuccess;
+    if (P + 1 > ldtok || (P > 0 && primer == nullptr)) return hipErrorInvalidValue;
+    const long long n = (long long)B * (P + 1);
+    const int blocks = (int)std::min<long long>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_gen_primer, dim3(blocks), dim3(256), 0, s, primer, B, P, vocab, start, tok, ldtok, err);
+    return hipGetLastError();
+}
+
+}  // namespace fsmg

@@ -407,5 +407,19 @@ hipError_t launch_decode_cell(hipStream_t s, const float* Kx, int in_dim, const 
                               const float* x, const float* h_in, float* h_out, float* c, int Hp);
 hipError_t launch_decode_argmax(hipStream_t s, const float* W, int ldw, const float* bias, const float* h,
                                 int Hp, int n_vocab, int* out_token, float* scratch);
+// batched sampling decode (decode.hip, fsmg_generate): no allocation, no synchronisation -- graph-capturable.
+// One LSTM layer at one position for B rows: layer 0 (emb != nullptr) gathers x from the embedding rows tok[r * ldtok + pos];
+// other layers read x [B][Hp].  h_in / h_out / c are [B][Hp]; in_dim and Hp multiples of 16.
+hipError_t launch_gen_cell(hipStream_t s, const float* Kx, int in_dim, const float* Kh, const float* bias, int Hp, const float* emb, int ldemb,
+                           const int* tok, int ldtok, int pos, const float* x, const float* h_in, float* h_out, float* c, int B);
+// logits [B][ldl] = h [B][Hp] . W [Hp][ldw] + bias, the first ncols columns
+hipError_t launch_gen_logits(hipStream_t s, const float* W, int ldw, const float* bias, int ncols, const float* h, int Hp, int B,
+                             float* logits, int ldl);
+// per row b: Gumbel-max draw of generated token t (temperature, top_k, Philox key = seed) -> tok[b * ldtok + pos_out],
+// out_tok[b * num + t], out_lp[b * num + t] = logit - logsumexp
+hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, uint64_t seed, int t,
+                           int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num);
+// tok rows [start, primer[b][0..P-1]]; *err |= 1 for a primer id outside [0, vocab)
+hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err);
 
 }  // namespace fsmg

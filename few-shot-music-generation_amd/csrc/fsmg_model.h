@@ -207,6 +207,9 @@ struct fsmg_model {
     std::map<std::string, LaunchCounts> graph_counts;   // recurrent launches one replay of a graph stands for (fsmg_get_stats)
     // decode
     float* dec = nullptr;
+    // batched generation (fsmg_generate): its own scratch, grown between calls after a stream sync
+    char* gen = nullptr;
+    size_t gen_bytes = 0;
 
 #ifdef FSMG_PHASE_DEBUG
     hipEvent_t ph[8] = {}; bool ph_init = false; int ph_step = 0;      // per handle (was file scope: shared by all handles)
@@ -606,6 +609,10 @@ int restore_theta(fsmg_model* h);
 void on_timeout(fsmg_model* h);
 void on_softmax_range(fsmg_model* h);
 inline bool is_retry(int rc) { return rc == FSMG_ERR_TIMEOUT || rc == FSMG_ERR_SOFTMAX_RANGE; }
+// ------------------------------------------------------------------ batched generation (api_generate.hip)
+// fsmg_generate's work at the parameters the handle holds now (no BEGIN_CALL: fsmg_maml_generate calls it at theta')
+int generate_core(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens, float* out_logprob);
+int check_gen_config(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens);
 int poll_skipped(fsmg_model* h);
 int report(fsmg_model* h, int what);
 int check_tokens_and_read(fsmg_model* h, const float* d_src, float scale, float* host_out, int n, bool train_tail = false);

@@ -48,6 +48,15 @@ class FsmgStats(C.Structure):
                 ('aux_stream_tries', C.c_int32), ('reserved0', C.c_int32)]
 
 
+FSMG_GEN_CONFIG_VERSION = 1
+
+
+class FsmgGenConfig(C.Structure):
+    _fields_ = [('version', C.c_int32), ('n_seq', C.c_int32), ('num', C.c_int32), ('primer_len', C.c_int32),
+                ('temperature', C.c_float), ('top_k', C.c_int32), ('seed', C.c_uint64), ('primer_on_device', C.c_int32),
+                ('reserved', C.c_int32 * 7)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -91,6 +100,8 @@ SIGNATURES = {
     'fsmg_eval_step': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _F32P]),
     'fsmg_eval_batch': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F32P]),
     'fsmg_sample': (C.c_int, [_P, C.c_int32, _I32P]),
+    'fsmg_generate': (C.c_int, [_P, C.POINTER(FsmgGenConfig), _P, _I32P, _F32P]),
+    'fsmg_maml_generate': (C.c_int, [_P, C.POINTER(FsmgGenConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P, _F32P]),
     'fsmg_read_losses': (C.c_int, [_P, _F32P, C.c_int32]),
     'fsmg_get_stats': (C.c_int, [_P, C.POINTER(FsmgStats)]),
     'fsmg_debug_read': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
@@ -424,6 +435,49 @@ class FsmgModel(object):
         out = np.empty(max(int(num), 1), np.int32)
         self._ck(self._lib.fsmg_sample(self._h, int(num), out.ctypes.data_as(_I32P)))
         return [int(t) for t in out[:int(num)]]
+
+    # -- batched on-device generation (include/fsmg.h fsmg_generate) ---------------------------------------
+    @staticmethod
+    def gen_config(n_seq, num, temperature=1.0, top_k=0, seed=0, primer_len=0, primer_on_device=0):
+        return FsmgGenConfig(version=FSMG_GEN_CONFIG_VERSION, n_seq=int(n_seq), num=int(num), primer_len=int(primer_len),
+                             temperature=float(temperature), top_k=int(top_k), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                             primer_on_device=int(primer_on_device))
+
+    def _gen_args(self, n_seq, num, temperature, top_k, seed, primer):
+        if primer is None:
+            return self.gen_config(n_seq, num, temperature, top_k, seed), None, None
+        if isinstance(primer, tuple):                 # (device address, primer_len)
+            return self.gen_config(n_seq, num, temperature, top_k, seed, int(primer[1]), 1), C.c_void_p(int(primer[0])), None
+        a = np.ascontiguousarray(primer, dtype=np.int32)
+        if a.ndim == 1:
+            a = np.ascontiguousarray(np.broadcast_to(a, (int(n_seq), a.size)))
+        if a.ndim != 2 or a.shape[0] != int(n_seq):
+            raise ValueError('primer must be [n_seq, P] (or one [P] row for every sequence), got %r' % (a.shape,))
+        return self.gen_config(n_seq, num, temperature, top_k, seed, a.shape[1]), C.c_void_p(a.ctypes.data), a
+
+    def generate(self, n_seq, num, temperature=1.0, top_k=0, seed=0, primer=None, logprobs=False):
+        """n_seq independent samples of num tokens -> int32 [n_seq, num] (, float32 [n_seq, num] log-probs with logprobs=True).
+        primer: int32 [n_seq, P] (or [P] for every row) continued by each row, or (device address, P)."""
+        g, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
+        toks = np.empty((int(n_seq), int(num)), np.int32)
+        lp = np.empty((int(n_seq), int(num)), np.float32) if logprobs else None
+        self._ck(self._lib.fsmg_generate(self._h, C.byref(g), pp, toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None))
+        return (toks, lp) if logprobs else toks
+
+    def maml_generate(self, support, num, inner_steps, inner_lr, n_seq=1, temperature=1.0, top_k=0, seed=0, primer=None,
+                      logprobs=False, n_support_rows=None):
+        """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), generate at theta', restore theta"""
+        if isinstance(support, (int, np.integer)):
+            sp, dev, _k1, rows = C.c_void_p(int(support)), 1, None, int(n_support_rows)
+        else:
+            s = np.ascontiguousarray(support, dtype=np.int32).reshape(-1, self.max_len)
+            sp, dev, _k1, rows = C.c_void_p(s.ctypes.data), 0, s, s.shape[0]
+        g, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
+        toks = np.empty((int(n_seq), int(num)), np.int32)
+        lp = np.empty((int(n_seq), int(num)), np.float32) if logprobs else None
+        self._ck(self._lib.fsmg_maml_generate(self._h, C.byref(g), sp, rows, int(inner_steps), float(inner_lr), dev, pp,
+                                              toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None))
+        return (toks, lp) if logprobs else toks
 
     def read_losses(self, n):
         out = np.empty(n, np.float32)

@@ -11,6 +11,9 @@ are replaced by libfsmg (hand-written gfx950 kernels behind include/fsmg.h):
   sample(s, num)  greedy argmax decode from the start word; the support set is ignored, as in
                   the reference                              (reference :135-156)
 
+Beyond the reference: generate(s, num, n, temperature, top_k, seed, primer_len) draws n samples at once on the device,
+optionally continuing the first primer_len tokens of the support songs.
+
 Optional config keys beyond the reference's: device, clip_norm_mode ('tf1_slices' | 'dense'),
 max_sequences, use_graph, gemm / schedule / recurrence / dp_split_backward (fsmg_config), dp_exchange ('torch': the
 all-reduce is issued through torch.distributed; 'library': libfsmg issues the RCCL calls itself).  When torch.distributed is initialised, train() runs episode-parallel
@@ -110,3 +113,21 @@ class LSTMBaseline(HIPModel):
     def sample(self, support_set, num):
         self._require_init()
         return self._model.sample(int(num))
+
+    @staticmethod
+    def _primer(support_set, n, primer_len):
+        """the first primer_len tokens of the support songs, dealt round-robin over the n rows"""
+        if primer_len <= 0:
+            return None
+        songs = np.ascontiguousarray(support_set, dtype=np.int32).reshape(-1, np.shape(support_set)[-1])
+        if primer_len > songs.shape[1]:
+            raise ValueError('primer_len %d exceeds the song length %d' % (primer_len, songs.shape[1]))
+        return np.ascontiguousarray(songs[np.arange(n) % songs.shape[0], :primer_len])
+
+    def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False):
+        """n independent samples of num tokens (int32 [n, num]), drawn on the device (temperature, top_k, seed; include/fsmg.h
+        fsmg_generate).  Each row continues the first primer_len tokens of a support song (dealt round-robin); with
+        primer_len 0 the support set is not used."""
+        self._require_init()
+        return self._model.generate(int(n), int(num), temperature=temperature, top_k=top_k, seed=seed,
+                                    primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs)

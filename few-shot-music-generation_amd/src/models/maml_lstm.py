@@ -11,6 +11,8 @@ adaptation of deep networks") as the direction the project was heading.  This pl
                   communication, the query gradients are all-reduced exactly like a baseline step's.
   eval(episode)   adapt on the support set, mean NLL of the query set at theta', then theta is restored.
   sample(s, num)  greedy decode at theta (the support set is not used, as in the baseline).
+  generate(s, num, n, ...)  n samples drawn at theta' adapted on the support set s (fsmg_maml_generate): generation AS the
+                  episode's artist.
 
 Extra config keys: inner_steps (default 1), inner_lr (default 0.1).
 """
@@ -55,6 +57,14 @@ class MAMLLSTM(LSTMBaseline):
         self._log_scalar('Eval/Avg_NLL', nll, self._eval_calls)
         self._eval_calls += 1
         return nll
+
+    def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False):
+        """like LSTMBaseline.generate, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored"""
+        self._require_init()
+        support = self._tokens(support_set, 2)
+        return self._model.maml_generate(support, int(num), self._inner_steps, self._inner_lr, n_seq=int(n),
+                                         temperature=temperature, top_k=top_k, seed=seed,
+                                         primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs)
 
     def eval_many(self, episodes):
         """adaptation is per episode, so there is nothing to batch: one maml_eval per episode"""

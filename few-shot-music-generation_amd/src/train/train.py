@@ -55,6 +55,14 @@ def write_seq(seq, dir, name):
         seq.write(os.path.join(dir, name + '.mid'))
 
 
+def sample_seed(base, episode_index):
+    """the generation seed of sample episode i: sample_seed and i mixed (splitmix64), so that episodes draw different noise"""
+    z = (int(base) * 0x9E3779B97F4A7C15 + int(episode_index) + 1) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return z ^ (z >> 31)
+
+
 def evaluate(model, episode_sampler, n_episodes):
     """Mean of model.eval over n_episodes fresh episodes (train.py:27-33)."""
     total, done = 0.0, 0
@@ -203,10 +211,20 @@ def main(argv=None):
         os.makedirs(curr_sample_dir, exist_ok=True)
         episode = episode_sampler['test'].get_episode()
         support_set = episode.support[0]
-        sample = model.sample(support_set, max_len)
+        if 'sample_temperature' not in config:
+            sample = model.sample(support_set, max_len)
+        else:        # opt-in: samples_per_episode draws from model.generate, conditioned on the episode's support set
+            gen = model.generate(support_set, max_len, n=int(config.get('samples_per_episode', 1)),
+                                 temperature=float(config['sample_temperature']), top_k=int(config.get('sample_top_k', 0)),
+                                 seed=sample_seed(config.get('sample_seed', 0), i),
+                                 primer_len=int(config.get('sample_primer_len', 0)))
         for j in range(support_set.shape[0]):
             write_seq(episode_sampler['test'].detokenize(support_set[j]), curr_sample_dir, 'support_%d' % j)
-        write_seq(episode_sampler['test'].detokenize(sample), curr_sample_dir, 'model_sample')
+        if 'sample_temperature' not in config:
+            write_seq(episode_sampler['test'].detokenize(sample), curr_sample_dir, 'model_sample')
+        else:
+            for j, row in enumerate(gen):
+                write_seq(episode_sampler['test'].detokenize([int(w) for w in row]), curr_sample_dir, 'model_sample_%d' % j)
 
 
 if __name__ == '__main__':

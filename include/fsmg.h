@@ -243,6 +243,43 @@ int fsmg_maml_step_indexed(fsmg_handle h, int32_t table_id, const int32_t* suppo
  * `num` tokens from the start word and a zero state (the support set is ignored there). */
 int fsmg_sample(fsmg_handle h, int32_t num, int32_t* out_tokens);
 
+/* ---- batched on-device generation (DESIGN.md "Batched generation").  n_seq independent rows, each the input sequence
+ * [start, primer[b][0..P-1], g_0, g_1, ...] (start = input_size, the training shift), zero initial state; token g_t is drawn from
+ * the output after the input just before it (P = 0: the first token comes from the start word's output, like fsmg_sample).
+ * logit = h_L . softmax_w + softmax_b over all V1 = input_size + 1 columns.  The draw is Gumbel-max: g_t = argmax over the allowed
+ * set of logit_v / temperature + gumbel_v, lowest index on ties, gumbel_v = -log(-log(u)), u = ((x >> 8) + 0.5) * 2^-24, x = word
+ * v & 3 of Philox4x32-10(key = (seed & 0xffffffff, seed >> 32), counter = (v >> 2, t, b, 0)) -- b the row index in the call.
+ * Allowed set: every column when top_k is 0 or V1, else the columns whose logit is >= the top_k-th largest (ties included).
+ * temperature == 0 (or top_k == 1): the argmax of the logits, no noise.  out_logprob[b][t] = logit_tok - logsumexp(all V1 logits):
+ * the untempered, untruncated model log-probability.  A row's tokens and log-probs are bitwise independent of n_seq and of the
+ * other rows.  fsmg_generate changes no handle state (parameters, Adam moments, global_step, the loss ring, gradients, statistics,
+ * captured graphs).  fsmg_maml_generate first adapts like fsmg_maml_eval and restores theta whatever happens; exactly as fsmg_maml_eval, its inner
+ * forward / backward passes overwrite the gradient buffer and advance the recurrent-launch counters of fsmg_stats (xcd_launches,
+ * persistent_launches, step_launches), and a time-out inside them is counted and handled like any other (timeouts, fallback_steps_left).
+ * Parameters, Adam moments, global_step and the loss ring stay as they were.
+ * Errors: FSMG_ERR_INVALID for a bad config (version, n_seq < 1, num < 0, primer_len < 0, temperature negative or not finite, top_k
+ * outside [0, V1], nonzero reserved fields); FSMG_ERR_TOKEN_RANGE for a primer id outside [0, input_size) (out_tokens left
+ * unwritten).  A row whose logits are not comparable (NaN) still yields a token in [0, V1). */
+#define FSMG_GEN_CONFIG_VERSION 1
+typedef struct fsmg_gen_config {
+    int32_t version;          /* FSMG_GEN_CONFIG_VERSION, else FSMG_ERR_INVALID            */
+    int32_t n_seq;            /* B >= 1 independent sequences                              */
+    int32_t num;              /* tokens generated per sequence, >= 0                       */
+    int32_t primer_len;       /* P >= 0 primer tokens per sequence (teacher-forced)        */
+    float temperature;        /* >= 0, finite; 0 = greedy argmax (no noise)                */
+    int32_t top_k;            /* 0 = all V1 columns, else 1..V1                            */
+    uint64_t seed;
+    int32_t primer_on_device; /* primer pointer is host (0) or device (1)                  */
+    int32_t reserved[7];      /* must be 0                                                 */
+} fsmg_gen_config;
+
+/* primer [B,P] (NULL if P == 0), out_tokens host [B,num], out_logprob host [B,num] or NULL */
+int fsmg_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens, float* out_logprob);
+/* adapt on support [n_support_rows, max_len] (host, or device when support_on_device) for inner_steps clipped SGD steps of
+ * inner_lr, generate at theta', restore theta */
+int fsmg_maml_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,
+                       float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_logprob);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
