@@ -37,6 +37,16 @@ GenLayout gen_layout(const fsmg_model* h, int B, int P, int num) {
 }
 }  // namespace
 
+int gen_reserve(fsmg_model* h, size_t bytes) {
+    if (bytes <= h->gen_bytes) return FSMG_OK;
+    HIPCK(h, hipStreamSynchronize(h->stream));     // grown between calls, never inside the token loop
+    if (h->gen) hipFree(h->gen);
+    h->gen = nullptr; h->gen_bytes = 0;
+    if (hipMalloc((void**)&h->gen, bytes) != hipSuccess) return fail(h, FSMG_ERR_NOMEM, "hipMalloc(generation scratch) failed");
+    h->gen_bytes = bytes;
+    return FSMG_OK;
+}
+
 int check_gen_config(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens) {
     if (!g) return fail(h, FSMG_ERR_INVALID, "null fsmg_gen_config");
     if (g->version != FSMG_GEN_CONFIG_VERSION)
@@ -64,13 +74,8 @@ int generate_core(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer
     }
     hipStream_t s = h->stream;
     const GenLayout lay = gen_layout(h, B, P, num);
-    if (lay.total > h->gen_bytes) {                 // grown between calls, never inside the token loop
-        HIPCK(h, hipStreamSynchronize(s));
-        if (h->gen) hipFree(h->gen);
-        h->gen = nullptr; h->gen_bytes = 0;
-        if (hipMalloc((void**)&h->gen, lay.total) != hipSuccess) return fail(h, FSMG_ERR_NOMEM, "hipMalloc(generation scratch) failed");
-        h->gen_bytes = lay.total;
-    }
+    const int rc = gen_reserve(h, lay.total);
+    if (rc != FSMG_OK) return rc;
     char* base = h->gen;
     float* hb = (float*)(base + lay.state);                       // [L][2][B][Hp]
     float* cb = hb + (size_t)L * 2 * B * Hp;                      // [L][B][Hp]

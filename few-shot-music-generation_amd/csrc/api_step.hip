@@ -331,20 +331,22 @@ static int adapt_flag(fsmg_handle h) {
     return report(h, err);
 }
 
-// adapt on the support rows like fsmg_maml_eval, generate at theta' (api_generate.hip), restore theta whatever happened
-int fsmg_maml_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,
-                       float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
-    if (!h) return FSMG_ERR_INVALID;
-    int rc = check_gen_config(h, g, primer, out_tokens);
-    if (rc != FSMG_OK) return rc;
+}  // extern "C"
+
+namespace fsmg_host {
+// adapt on the support rows like fsmg_maml_eval, run the body at theta', restore theta whatever happened; one repeat on per-step
+// launches when the adaptation ran garbage (skipped) steps.  fsmg_maml_generate and fsmg_maml_beam_search run through here.
+int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
+                       int32_t support_on_device, const std::function<int()>& at_theta_prime) {
     if (!support || n_support_rows <= 0 || inner_steps < 0 || inner_steps > 64 || !(inner_lr >= 0.f) || !std::isfinite(inner_lr) ||
         (support_on_device != 0 && support_on_device != 1))
         return fail(h, FSMG_ERR_INVALID, "bad support / n_support_rows / inner_steps / inner_lr");
     BEGIN_CALL(h);
+    int rc = FSMG_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
         rc = maml_adapt(h, support, 1, n_support_rows, inner_steps, inner_lr, support_on_device);
         if (rc == FSMG_OK) rc = adapt_flag(h);           // a time-out / token error inside the adaptation: theta' is not usable
-        if (rc == FSMG_OK) rc = generate_core(h, g, primer, out_tokens, out_logprob);
+        if (rc == FSMG_OK) rc = at_theta_prime();
         const int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
         h->have_grads = false;
         if (rc == FSMG_OK) rc = rc2;
@@ -352,6 +354,30 @@ int fsmg_maml_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* s
         h->retry_armed = false;                        // adapted with garbage (skipped) steps: repeat on per-step launches
     }
     return rc;
+}
+}  // namespace fsmg_host
+
+extern "C" {
+
+// generate at theta' (api_generate.hip)
+int fsmg_maml_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,
+                       float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    const int rc = check_gen_config(h, g, primer, out_tokens);
+    if (rc != FSMG_OK) return rc;
+    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
+                              [&] { return generate_core(h, g, primer, out_tokens, out_logprob); });
+}
+
+// beam search at theta' (api_beam.hip)
+int fsmg_maml_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,
+                          float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_scores,
+                          float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    const int rc = check_beam_config(h, b, primer, out_tokens, out_scores);
+    if (rc != FSMG_OK) return rc;
+    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
+                              [&] { return beam_core(h, b, primer, out_tokens, out_scores, out_logprob); });
 }
 
 int fsmg_eval_batch(fsmg_handle h, const int32_t* queries, int32_t n_episodes, int32_t N, int32_t Q,

@@ -22,6 +22,8 @@ constexpr int GEN_ROWS = 64;       // rows per workgroup: 4 row tiles of 16 (gri
 constexpr int GEN_CH = 16;         // k per lane held in registers at a time
 constexpr int PICK_THREADS = 1024;
 constexpr int PICK_LDS_FLOATS = 32 * 1024;   // rows up to 128 KiB are staged in LDS
+constexpr int BEAM_MAX_W = 64;
+constexpr int SEL_THREADS = 1024;
 
 // Partial products of one 16-column weight tile with up to 4 row tiles over one K segment of n rows (n % 16 == 0).
 // The segment is split into 16 slots of m = n / 16 consecutive k (slot = 4 * wave + lane group); lane (c = l & 15, g = l >> 4)
@@ -213,23 +215,15 @@ __device__ __forceinline__ double block_sum(PickShared& sh, double s) {
     return t;
 }
 
-// One row per workgroup.  Token = argmax over the allowed set of logit / T + Gumbel(Philox(key = seed, ctr = (v >> 2, t, b, 0))),
-// lowest index on ties; T == 0 or top_k == 1: argmax of the logits.  Allowed set: logit >= the top_k-th largest logit (radix
-// select on order-preserving keys), every column when top_k is 0 or ncols.  Writes the token into the token buffer (the next
-// position's input), out_tok / out_lp [b][t], lp = logit_tok - logsumexp(all ncols logits).
+// The row's maximum (lowest index on ties; column 0 when no logit exceeds -inf) and logsumexp over ncols logits: one sweep that
+// also stages the row in LDS (STAGED), then the double-accumulated sum of expf(logit - max) over a fixed tree.  Shared by
+// k_gen_pick and k_beam_rowtop, so that fsmg_generate's and fsmg_beam_search's log-probs are the same numbers.
 template <bool STAGED>
-__global__ __launch_bounds__(PICK_THREADS) void k_gen_pick(const float* __restrict__ logits, int ldl, int ncols, float temperature, int top_k,
-                                                           unsigned seed_lo, unsigned seed_hi, int t, int* __restrict__ tok, int ldtok,
-                                                           int pos_out, int* __restrict__ out_tok, float* __restrict__ out_lp, int num) {
-    extern __shared__ float srow[];
-    __shared__ PickShared sh;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* row = logits + (long long)b * ldl;
-    auto val = [&](int v) -> float { return STAGED ? srow[v] : row[v]; };
-
+__device__ __forceinline__ float row_max_lse(PickShared& sh, const float* __restrict__ row, float* srow, int ncols, float& mx, int& mi) {
+    const int tid = threadIdx.x;
     // staging and the row maximum in one sweep, 8 loads in flight per thread (the sweep is latency-bound at small B)
     // the index starts at column 0 (like k_decode_pick), so that a row without a comparable logit (all NaN) still yields a column
-    float mx = -INFINITY; int mi = 0;
+    mx = -INFINITY; mi = 0;
     for (int v0 = tid; v0 < ncols; v0 += 8 * PICK_THREADS) {
         float l[8];
 #pragma unroll
@@ -244,48 +238,72 @@ __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick(const float* __restri
     }
     block_argmax(sh, mx, mi);          // (its barriers also order the staging stores before the reads below)
     double se = 0.0;
-    for (int v = tid; v < ncols; v += PICK_THREADS) se += (double)expf(val(v) - mx);
+    for (int v = tid; v < ncols; v += PICK_THREADS) se += (double)expf((STAGED ? srow[v] : row[v]) - mx);
     se = block_sum(sh, se);
-    const float lse = mx + (float)log(se);
+    return mx + (float)log(se);
+}
+
+// The k-th largest of key_of(logit) over the row's ncols columns, MSB-first radix select over 8-bit digits.  Returns the key;
+// sh.kleft is then the number of columns with exactly that key that complete the top k (k - the count of larger keys).
+template <bool STAGED, class KeyOf>
+__device__ __forceinline__ unsigned radix_select_kth(PickShared& sh, const float* __restrict__ row, const float* srow, int ncols, int k,
+                                                     KeyOf key_of) {
+    const int tid = threadIdx.x;
+    if (tid == 0) { sh.prefix = 0u; sh.kleft = k; }
+    unsigned mask = 0u;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        if (tid < 256) sh.hist[tid] = 0;
+        __syncthreads();
+        const unsigned prefix = sh.prefix;
+        for (int v = tid; v < ncols; v += PICK_THREADS) {
+            const unsigned key = key_of(STAGED ? srow[v] : row[v]);
+            if ((key & mask) == prefix) atomicAdd(&sh.hist[(key >> shift) & 255u], 1);
+        }
+        __syncthreads();
+        if (tid < 64) {       // wave 0: lane l owns digits 255 - 4l .. 252 - 4l; counts from the top digit down
+            int cnt[4], s = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { cnt[j] = sh.hist[255 - 4 * tid - j]; s += cnt[j]; }
+            int incl = s;
+            for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o); if (tid >= o) incl += y; }
+            int before = incl - s;
+            const int kl = sh.kleft;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (before < kl && kl <= before + cnt[j]) {
+                    sh.prefix = prefix | ((unsigned)(255 - 4 * tid - j) << shift);
+                    sh.kleft = kl - before;
+                }
+                before += cnt[j];
+            }
+        }
+        mask |= 255u << shift;
+        __syncthreads();
+    }
+    return sh.prefix;
+}
+
+// One row per workgroup.  Token = argmax over the allowed set of logit / T + Gumbel(Philox(key = seed, ctr = (v >> 2, t, b, 0))),
+// lowest index on ties; T == 0 or top_k == 1: argmax of the logits.  Allowed set: logit >= the top_k-th largest logit (radix
+// select on order-preserving keys), every column when top_k is 0 or ncols.  Writes the token into the token buffer (the next
+// position's input), out_tok / out_lp [b][t], lp = logit_tok - logsumexp(all ncols logits).
+template <bool STAGED>
+__global__ __launch_bounds__(PICK_THREADS) void k_gen_pick(const float* __restrict__ logits, int ldl, int ncols, float temperature, int top_k,
+                                                           unsigned seed_lo, unsigned seed_hi, int t, int* __restrict__ tok, int ldtok,
+                                                           int pos_out, int* __restrict__ out_tok, float* __restrict__ out_lp, int num) {
+    extern __shared__ float srow[];
+    __shared__ PickShared sh;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* row = logits + (long long)b * ldl;
+    auto val = [&](int v) -> float { return STAGED ? srow[v] : row[v]; };
+
+    float mx; int mi;
+    const float lse = row_max_lse<STAGED>(sh, row, srow, ncols, mx, mi);
 
     int best = mi;
     if (temperature > 0.0f && top_k != 1) {
         float thr = -INFINITY;
-        if (top_k > 1 && top_k < ncols) {
-            // k-th largest key, MSB-first radix select over 8-bit digits
-            if (tid == 0) { sh.prefix = 0u; sh.kleft = top_k; }
-            unsigned mask = 0u;
-            for (int shift = 24; shift >= 0; shift -= 8) {
-                if (tid < 256) sh.hist[tid] = 0;
-                __syncthreads();
-                const unsigned prefix = sh.prefix;
-                for (int v = tid; v < ncols; v += PICK_THREADS) {
-                    const unsigned k = fkey(val(v));
-                    if ((k & mask) == prefix) atomicAdd(&sh.hist[(k >> shift) & 255u], 1);
-                }
-                __syncthreads();
-                if (tid < 64) {       // wave 0: lane l owns digits 255 - 4l .. 252 - 4l; counts from the top digit down
-                    int cnt[4], s = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { cnt[j] = sh.hist[255 - 4 * tid - j]; s += cnt[j]; }
-                    int incl = s;
-                    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o); if (tid >= o) incl += y; }
-                    int before = incl - s;
-                    const int kl = sh.kleft;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (before < kl && kl <= before + cnt[j]) {
-                            sh.prefix = prefix | ((unsigned)(255 - 4 * tid - j) << shift);
-                            sh.kleft = kl - before;
-                        }
-                        before += cnt[j];
-                    }
-                }
-                mask |= 255u << shift;
-                __syncthreads();
-            }
-            thr = key_float(sh.prefix);
-        }
+        if (top_k > 1 && top_k < ncols) thr = key_float(radix_select_kth<STAGED>(sh, row, srow, ncols, top_k, [](float f) { return fkey(f); }));
         const uint2 key = make_uint2(seed_lo, seed_hi);
         float bs = -INFINITY; int bi = 0;
         for (int q = tid; 4 * q < ncols; q += PICK_THREADS) {
@@ -312,18 +330,185 @@ __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick(const float* __restri
     }
 }
 
-// token buffer row b: [start, primer[b][0..P-1]]; *err = 1 for a primer id outside [0, vocab)
+// token buffer row b: [start, primer[b / rows_per_primer][0..P-1]]; *err = 1 for a primer id outside [0, vocab)
 __global__ void k_gen_primer(const int* __restrict__ primer, int B, int P, int vocab, int start, int* __restrict__ tok, int ldtok,
-                             int* __restrict__ err) {
+                             int* __restrict__ err, int rows_per_primer) {
     const long long n = (long long)B * (P + 1);
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int b = (int)(i / (P + 1)), p = (int)(i % (P + 1));
         int w = start;
         if (p > 0) {
-            w = primer[(long long)b * P + p - 1];
+            w = primer[(long long)(b / rows_per_primer) * P + p - 1];
             if (w < 0 || w >= vocab) { atomicOr(err, 1); w = start; }
         }
         tok[(long long)b * ldtok + p] = w;
+    }
+}
+
+// ---------------------------------------------------------------- beam search (fsmg_beam_search, DESIGN.md "Beam search")
+// Rows r = g * W + j (group g, slot j).  Per generated position: k_beam_rowtop (each row's W best candidates), k_beam_select (the
+// group's W best of its W x W), k_beam_reorder (each slot takes its parent's h and c).  A candidate (j, v) has lp = logit_v - lse_j
+// and score s = cum_j + lp; the ranking is s descending, then j ascending, then logit descending, then v ascending, NaN below -inf.
+// Within a row lp and s are nondecreasing in the logit, so a row's order is (logit descending, v ascending): a row's own W best
+// are the only ones of its candidates that can enter the group's W best.
+
+// order-preserving key of a score or logit for the beam ranking: NaN lowest (below -inf), -0 ranked equal to +0
+__device__ __forceinline__ unsigned beam_key(float f) { return f != f ? 0u : fkey(f == 0.0f ? 0.0f : f); }
+
+// One row per workgroup: lse (the sweep k_gen_pick runs), then the row's min(W, ncols) best columns in rank order ->
+// cand_*[r * W + rank] (cand_v = -1 pads a row with fewer than W columns).  The W-th key comes from the radix select; the columns
+// above it are gathered in any order and the boundary ties by an ordered scan (lowest columns first), then ranked in LDS.
+template <bool STAGED>
+__global__ __launch_bounds__(PICK_THREADS) void k_beam_rowtop(const float* __restrict__ logits, int ldl, int ncols, int W,
+                                                              const float* __restrict__ cum, float* __restrict__ cand_s,
+                                                              float* __restrict__ cand_lp, int* __restrict__ cand_v) {
+    extern __shared__ float srow[];
+    __shared__ PickShared sh;
+    __shared__ unsigned ck[BEAM_MAX_W];
+    __shared__ int cv[BEAM_MAX_W];
+    __shared__ int wave_eq[PICK_THREADS / 64];
+    __shared__ int n_gt;
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* row = logits + (long long)r * ldl;
+    auto val = [&](int v) -> float { return STAGED ? srow[v] : row[v]; };
+
+    if (tid == 0) n_gt = 0;            // (ordered before its first use by the sweep's barriers)
+    float mx; int mi;
+    const float lse = row_max_lse<STAGED>(sh, row, srow, ncols, mx, mi);
+    const int wr = min(W, ncols);
+    if (wr == 1 && mx > -INFINITY) {
+        // the sweep's column is the best one already: the largest comparable logit, lowest index on ties
+        if (tid == 0) { ck[0] = beam_key(mx); cv[0] = mi; }
+    } else {
+        const unsigned kth = radix_select_kth<STAGED>(sh, row, srow, ncols, wr, [](float f) { return beam_key(f); });
+        const int need_eq = sh.kleft, n_above = wr - need_eq;
+        int eq_base = 0;
+        for (int v0 = 0; v0 < ncols; v0 += PICK_THREADS) {
+            const int v = v0 + tid;
+            const unsigned key = v < ncols ? beam_key(val(v)) : 0u;
+            const bool eq = v < ncols && key == kth;
+            if (v < ncols && key > kth) {           // fewer than wr of these in the row: slot < n_above
+                const int slot = atomicAdd(&n_gt, 1);
+                if (slot < BEAM_MAX_W) { ck[slot] = key; cv[slot] = v; }
+            }
+            const unsigned long long m = __ballot(eq);
+            if (lane == 0) wave_eq[wave] = __popcll(m);
+            __syncthreads();
+            int before = 0, total = 0;
+            for (int w = 0; w < PICK_THREADS / 64; ++w) {
+                const int c = wave_eq[w];
+                if (w < wave) before += c;
+                total += c;
+            }
+            const int gt_seen = n_gt;               // (no thread adds to it before the barrier below)
+            const int rank = eq_base + before + __popcll(m & ((1ull << lane) - 1ull));
+            if (eq && rank < need_eq) { ck[n_above + rank] = key; cv[n_above + rank] = v; }
+            eq_base += total;
+            __syncthreads();
+            if (eq_base >= need_eq && gt_seen == n_above) break;     // uniform: every thread read the same counts
+        }
+    }
+    __syncthreads();
+    if (tid < W) {
+        if (tid < wr) {
+            const unsigned ki = ck[tid];
+            const int vi = cv[tid];
+            int rank = 0;
+            for (int m = 0; m < wr; ++m) rank += (ck[m] > ki || (ck[m] == ki && cv[m] < vi)) ? 1 : 0;
+            const float lp = val(vi) - lse;
+            const long long o = (long long)r * W + rank;
+            cand_v[o] = vi;
+            cand_lp[o] = lp;
+            cand_s[o] = cum[r] + lp;
+        } else {
+            cand_v[(long long)r * W + tid] = -1;
+        }
+    }
+}
+
+// One group per workgroup: bitonic sort (descending) of the W x W candidates' 64-bit keys
+// [score key:32 | valid:1 | 63 - j:6 | 63 - rank in row:6] in LDS (distinct keys: the order is total), the first W become the
+// next slots: parent slot, token, lp, cum, and the token each row reads at the next position.
+__global__ __launch_bounds__(SEL_THREADS) void k_beam_select(int W, int ncols, const float* __restrict__ cand_s, const float* __restrict__ cand_lp,
+                                                             const int* __restrict__ cand_v, float* __restrict__ cum, int* __restrict__ tok,
+                                                             int ldtok, int pos_out, int* __restrict__ par, int* __restrict__ htok,
+                                                             float* __restrict__ hlp) {
+    __shared__ unsigned long long keys[BEAM_MAX_W * BEAM_MAX_W];
+    const int g = blockIdx.x, tid = threadIdx.x, WW = W * W;
+    int N = 1;
+    while (N < WW) N <<= 1;
+    const long long c0 = (long long)g * WW;
+    for (int i = tid; i < N; i += SEL_THREADS) {
+        unsigned long long k = 0ull;
+        if (i < WW && cand_v[c0 + i] >= 0) {
+            const int j = i / W, q = i - j * W;
+            k = ((unsigned long long)beam_key(cand_s[c0 + i]) << 32) | (1ull << 12) | ((unsigned long long)(63 - j) << 6) |
+                (unsigned long long)(63 - q);
+        }
+        keys[i] = k;
+    }
+    __syncthreads();
+    for (int k = 2; k <= N; k <<= 1) {
+        for (int jj = k >> 1; jj > 0; jj >>= 1) {
+            for (int q = tid; q < (N >> 1); q += SEL_THREADS) {      // pair q: i (bit jj clear) and i + jj
+                const int i = ((q & ~(jj - 1)) << 1) | (q & (jj - 1)), ixj = i + jj;
+                const unsigned long long a = keys[i], b = keys[ixj];
+                if (((i & k) == 0) ? (a < b) : (a > b)) { keys[i] = b; keys[ixj] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int n = tid; n < W; n += SEL_THREADS) {
+        const unsigned long long k = keys[n];
+        const int j = 63 - (int)((k >> 6) & 63ull), q = 63 - (int)(k & 63ull);
+        // a valid key always names a live candidate (W x min(W, ncols) >= W of them); the guard only keeps the indices in range
+        const bool ok = ((k >> 12) & 1ull) && j < W && q < W;
+        const long long c = c0 + (ok ? (long long)j * W + q : 0);
+        const int r = g * W + n;
+        const int v = min(max(cand_v[c], 0), ncols - 1);
+        par[r] = ok ? j : 0;
+        htok[r] = v;
+        hlp[r] = cand_lp[c];
+        cum[r] = cand_s[c];
+        tok[(long long)r * ldtok + pos_out] = v;
+    }
+}
+
+// h_dst[l][r] = h_src[l][parent row of r], c likewise (float4 per thread); parent row = (r / W) * W + par[r]
+__global__ void k_beam_reorder(int L, int R, int W, int Hp, const int* __restrict__ par, const float* __restrict__ h_src,
+                               float* __restrict__ h_dst, const float* __restrict__ c_src, float* __restrict__ c_dst) {
+    const int q4 = Hp >> 2;
+    const long long n = (long long)L * R * q4;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int u = (int)(i % q4);
+        const long long lr = i / q4;
+        const int r = (int)(lr % R), l = (int)(lr / R);
+        const long long src = ((long long)l * R + (long long)(r / W) * W + par[r]) * Hp + 4 * u, dst = lr * Hp + 4 * u;
+        *(float4*)(h_dst + dst) = *(const float4*)(h_src + src);
+        *(float4*)(c_dst + dst) = *(const float4*)(c_src + src);
+    }
+}
+
+// cum[r] = 0 for slot 0 of each group, -inf for the others
+__global__ void k_beam_init(float* __restrict__ cum, int R, int W) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < R) cum[r] = (r % W) == 0 ? 0.0f : -INFINITY;
+}
+
+// one thread per final hypothesis (g, n): follow the parents from the last position back -> out_tok / out_lp [r][num], score
+__global__ void k_beam_backtrace(int R, int W, int num, const int* __restrict__ par, const int* __restrict__ htok, const float* __restrict__ hlp,
+                                 const float* __restrict__ cum, int* __restrict__ out_tok, float* __restrict__ out_lp,
+                                 float* __restrict__ out_score) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const int g0 = r - r % W;
+    int slot = r - g0;
+    out_score[r] = cum[r];
+    for (int t = num - 1; t >= 0; --t) {
+        const long long e = (long long)t * R + g0 + slot;
+        out_tok[(long long)r * num + t] = htok[e];
+        out_lp[(long long)r * num + t] = hlp[e];
+        slot = par[e];
     }
 }
 
@@ -373,12 +558,70 @@ hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncol
     return hipGetLastError();
 }
 
-hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err) {
+hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err,
+                             int rows_per_primer) {
     if (B <= 0) return hipSuccess;
-    if (P + 1 > ldtok || (P > 0 && primer == nullptr)) return hipErrorInvalidValue;
+    if (P + 1 > ldtok || (P > 0 && primer == nullptr) || rows_per_primer < 1) return hipErrorInvalidValue;
     const long long n = (long long)B * (P + 1);
     const int blocks = (int)std::min<long long>((n + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_gen_primer, dim3(blocks), dim3(256), 0, s, primer, B, P, vocab, start, tok, ldtok, err);
+    hipLaunchKernelGGL(k_gen_primer, dim3(blocks), dim3(256), 0, s, primer, B, P, vocab, start, tok, ldtok, err,
+                       rows_per_primer);
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_init(hipStream_t s, float* cum, int R, int W) {
+    if (R <= 0) return hipSuccess;
+    if (W < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_beam_init, dim3((R + 255) / 256), dim3(256), 0, s, cum, R, W);
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_rowtop(hipStream_t s, const float* logits, int ldl, int ncols, int R, int W, const float* cum, float* cand_s,
+                              float* cand_lp, int* cand_v) {
+    if (R <= 0) return hipSuccess;
+    if (ncols <= 0 || ncols > ldl || W < 1 || W > BEAM_MAX_W) return hipErrorInvalidValue;
+    static std::atomic<unsigned long long> attr_set{0};       // as launch_gen_pick: the staged row may take 128 KiB of LDS
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
+        e = hipFuncSetAttribute((const void*)k_beam_rowtop<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(float) * PICK_LDS_FLOATS);
+        if (e != hipSuccess) return e;
+        attr_set.fetch_or(bit, std::memory_order_release);
+    }
+    if (ncols <= PICK_LDS_FLOATS)
+        hipLaunchKernelGGL((k_beam_rowtop<true>), dim3(R), dim3(PICK_THREADS), sizeof(float) * (size_t)ncols, s, logits, ldl, ncols, W, cum,
+                           cand_s, cand_lp, cand_v);
+    else
+        hipLaunchKernelGGL((k_beam_rowtop<false>), dim3(R), dim3(PICK_THREADS), 0, s, logits, ldl, ncols, W, cum, cand_s, cand_lp, cand_v);
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_select(hipStream_t s, int G, int W, int ncols, const float* cand_s, const float* cand_lp, const int* cand_v,
+                              float* cum, int* tok, int ldtok, int pos_out, int* par, int* htok, float* hlp) {
+    if (G <= 0) return hipSuccess;
+    if (W < 1 || W > BEAM_MAX_W || ncols <= 0 || pos_out >= ldtok) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_beam_select, dim3(G), dim3(SEL_THREADS), 0, s, W, ncols, cand_s, cand_lp, cand_v, cum, tok, ldtok, pos_out, par,
+                       htok, hlp);
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_reorder(hipStream_t s, int L, int R, int W, int Hp, const int* par, const float* h_src, float* h_dst,
+                               const float* c_src, float* c_dst) {
+    if (R <= 0) return hipSuccess;
+    if ((Hp & 3) || W < 1 || R % W) return hipErrorInvalidValue;
+    const long long n = (long long)L * R * (Hp / 4);
+    const int blocks = (int)std::min<long long>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_beam_reorder, dim3(blocks), dim3(256), 0, s, L, R, W, Hp, par, h_src, h_dst, c_src, c_dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_backtrace(hipStream_t s, int R, int W, int num, const int* par, const int* htok, const float* hlp, const float* cum,
+                                 int* out_tok, float* out_lp, float* out_score) {
+    if (R <= 0) return hipSuccess;
+    if (W < 1 || R % W || num < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_beam_backtrace, dim3((R + 255) / 256), dim3(256), 0, s, R, W, num, par, htok, hlp, cum, out_tok, out_lp, out_score);
     return hipGetLastError();
 }
 

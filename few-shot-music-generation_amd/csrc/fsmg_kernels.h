@@ -419,7 +419,23 @@ hipError_t launch_gen_logits(hipStream_t s, const float* W, int ldw, const float
 // out_tok[b * num + t], out_lp[b * num + t] = logit - logsumexp
 hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, uint64_t seed, int t,
                            int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num);
-// tok rows [start, primer[b][0..P-1]]; *err |= 1 for a primer id outside [0, vocab)
-hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err);
+// tok rows [start, primer[b / rows_per_primer][0..P-1]]; *err |= 1 for a primer id outside [0, vocab)
+hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err,
+                             int rows_per_primer = 1);
+// beam search (decode.hip, fsmg_beam_search): R = G * W rows, row r = slot r % W of group r / W; no allocation, no synchronisation.
+// cum[r] = 0 for slot 0, -inf for the others
+hipError_t launch_beam_init(hipStream_t s, float* cum, int R, int W);
+// per row: lse and the min(W, ncols) best columns in rank order -> cand_v / cand_lp / cand_s [R][W] (s = cum[r] + lp; cand_v = -1 pads)
+hipError_t launch_beam_rowtop(hipStream_t s, const float* logits, int ldl, int ncols, int R, int W, const float* cum, float* cand_s,
+                              float* cand_lp, int* cand_v);
+// per group: the W best of its W x W candidates -> par / htok / hlp / cum [R] and tok[r * ldtok + pos_out]
+hipError_t launch_beam_select(hipStream_t s, int G, int W, int ncols, const float* cand_s, const float* cand_lp, const int* cand_v,
+                              float* cum, int* tok, int ldtok, int pos_out, int* par, int* htok, float* hlp);
+// h / c [L][R][Hp]: each row takes its parent row's (r / W * W + par[r])
+hipError_t launch_beam_reorder(hipStream_t s, int L, int R, int W, int Hp, const int* par, const float* h_src, float* h_dst,
+                               const float* c_src, float* c_dst);
+// par / htok / hlp [num][R] -> out_tok / out_lp [R][num], out_score [R] = cum
+hipError_t launch_beam_backtrace(hipStream_t s, int R, int W, int num, const int* par, const int* htok, const float* hlp, const float* cum,
+                                 int* out_tok, float* out_lp, float* out_score);
 
 }  // namespace fsmg

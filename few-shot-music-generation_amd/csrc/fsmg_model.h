@@ -19,6 +19,7 @@
 #include <new>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -613,6 +614,14 @@ inline bool is_retry(int rc) { return rc == FSMG_ERR_TIMEOUT || rc == FSMG_ERR_S
 // fsmg_generate's work at the parameters the handle holds now (no BEGIN_CALL: fsmg_maml_generate calls it at theta')
 int generate_core(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens, float* out_logprob);
 int check_gen_config(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens);
+// h->gen holds at least `bytes` (the generation / beam-search scratch; each call lays it out its own way)
+int gen_reserve(fsmg_model* h, size_t bytes);
+// ------------------------------------------------------------------ beam search (api_beam.hip)
+int beam_core(fsmg_model* h, const fsmg_beam_config* b, const int32_t* primer, int32_t* out_tokens, float* out_scores, float* out_logprob);
+int check_beam_config(fsmg_model* h, const fsmg_beam_config* b, const int32_t* primer, int32_t* out_tokens, float* out_scores);
+// adapt on the support rows like fsmg_maml_eval, run `at_theta_prime` there, restore theta whatever happened (api_step.hip)
+int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
+                       int32_t support_on_device, const std::function<int()>& at_theta_prime);
 int poll_skipped(fsmg_model* h);
 int report(fsmg_model* h, int what);
 int check_tokens_and_read(fsmg_model* h, const float* d_src, float scale, float* host_out, int n, bool train_tail = false);

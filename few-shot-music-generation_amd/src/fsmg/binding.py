@@ -57,6 +57,14 @@ class FsmgGenConfig(C.Structure):
                 ('reserved', C.c_int32 * 7)]
 
 
+FSMG_BEAM_CONFIG_VERSION = 1
+
+
+class FsmgBeamConfig(C.Structure):
+    _fields_ = [('version', C.c_int32), ('n_groups', C.c_int32), ('beam_width', C.c_int32), ('num', C.c_int32),
+                ('primer_len', C.c_int32), ('primer_on_device', C.c_int32), ('reserved', C.c_int32 * 8)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -102,6 +110,9 @@ SIGNATURES = {
     'fsmg_sample': (C.c_int, [_P, C.c_int32, _I32P]),
     'fsmg_generate': (C.c_int, [_P, C.POINTER(FsmgGenConfig), _P, _I32P, _F32P]),
     'fsmg_maml_generate': (C.c_int, [_P, C.POINTER(FsmgGenConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P, _F32P]),
+    'fsmg_beam_search': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, _I32P, _F32P, _F32P]),
+    'fsmg_maml_beam_search': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P, _F32P,
+                                        _F32P]),
     'fsmg_read_losses': (C.c_int, [_P, _F32P, C.c_int32]),
     'fsmg_get_stats': (C.c_int, [_P, C.POINTER(FsmgStats)]),
     'fsmg_debug_read': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
@@ -478,6 +489,55 @@ class FsmgModel(object):
         self._ck(self._lib.fsmg_maml_generate(self._h, C.byref(g), sp, rows, int(inner_steps), float(inner_lr), dev, pp,
                                               toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None))
         return (toks, lp) if logprobs else toks
+
+    # -- batched on-device beam search (include/fsmg.h fsmg_beam_search) ----------------------------------------
+    @staticmethod
+    def beam_config(n_groups, beam_width, num, primer_len=0, primer_on_device=0):
+        return FsmgBeamConfig(version=FSMG_BEAM_CONFIG_VERSION, n_groups=int(n_groups), beam_width=int(beam_width), num=int(num),
+                              primer_len=int(primer_len), primer_on_device=int(primer_on_device))
+
+    def _beam_args(self, n_groups, beam_width, num, primer):
+        if primer is None:
+            return self.beam_config(n_groups, beam_width, num), None, None
+        if isinstance(primer, tuple):                 # (device address, primer_len)
+            return self.beam_config(n_groups, beam_width, num, int(primer[1]), 1), C.c_void_p(int(primer[0])), None
+        a = np.ascontiguousarray(primer, dtype=np.int32)
+        if a.ndim == 1:
+            a = np.ascontiguousarray(np.broadcast_to(a, (int(n_groups), a.size)))
+        if a.ndim != 2 or a.shape[0] != int(n_groups):
+            raise ValueError('primer must be [n_groups, P] (or one [P] row for every group), got %r' % (a.shape,))
+        return self.beam_config(n_groups, beam_width, num, a.shape[1]), C.c_void_p(a.ctypes.data), a
+
+    def _beam_outputs(self, n_groups, beam_width, num, logprobs):
+        G, W, num = int(n_groups), int(beam_width), int(num)
+        toks = np.empty((G, W, num), np.int32)
+        scores = np.empty((G, W), np.float32)
+        lp = np.empty((G, W, num), np.float32) if logprobs else None
+        return toks, scores, lp
+
+    def beam_search(self, num, beam_width, n_groups=1, primer=None, logprobs=False):
+        """n_groups independent beam searches of width beam_width, num tokens each -> tokens int32 [G, W, num], scores float32
+        [G, W] (, log-probs float32 [G, W, num] with logprobs=True), each group's hypotheses best first.  primer: int32 [G, P]
+        (or [P] for every group) continued by every hypothesis of its group, or (device address, P)."""
+        b, pp, _keep = self._beam_args(n_groups, beam_width, num, primer)
+        toks, scores, lp = self._beam_outputs(n_groups, beam_width, num, logprobs)
+        self._ck(self._lib.fsmg_beam_search(self._h, C.byref(b), pp, toks.ctypes.data_as(_I32P), _f32p(scores),
+                                            _f32p(lp) if logprobs else None))
+        return (toks, scores, lp) if logprobs else (toks, scores)
+
+    def maml_beam_search(self, support, num, inner_steps, inner_lr, beam_width, n_groups=1, primer=None, logprobs=False,
+                         n_support_rows=None):
+        """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), beam search at theta', restore theta"""
+        if isinstance(support, (int, np.integer)):
+            sp, dev, _k1, rows = C.c_void_p(int(support)), 1, None, int(n_support_rows)
+        else:
+            s = np.ascontiguousarray(support, dtype=np.int32).reshape(-1, self.max_len)
+            sp, dev, _k1, rows = C.c_void_p(s.ctypes.data), 0, s, s.shape[0]
+        b, pp, _keep = self._beam_args(n_groups, beam_width, num, primer)
+        toks, scores, lp = self._beam_outputs(n_groups, beam_width, num, logprobs)
+        self._ck(self._lib.fsmg_maml_beam_search(self._h, C.byref(b), sp, rows, int(inner_steps), float(inner_lr), dev, pp,
+                                                 toks.ctypes.data_as(_I32P), _f32p(scores), _f32p(lp) if logprobs else None))
+        return (toks, scores, lp) if logprobs else (toks, scores)
 
     def read_losses(self, n):
         out = np.empty(n, np.float32)

@@ -12,7 +12,8 @@ are replaced by libfsmg (hand-written gfx950 kernels behind include/fsmg.h):
                   the reference                              (reference :135-156)
 
 Beyond the reference: generate(s, num, n, temperature, top_k, seed, primer_len) draws n samples at once on the device,
-optionally continuing the first primer_len tokens of the support songs.
+optionally continuing the first primer_len tokens of the support songs; beam_search(s, num, beam_width, n, primer_len) returns
+the beam_width highest-scoring continuations of each of n groups, searched on the device.
 
 Optional config keys beyond the reference's: device, clip_norm_mode ('tf1_slices' | 'dense'),
 max_sequences, use_graph, gemm / schedule / recurrence / dp_split_backward (fsmg_config), dp_exchange ('torch': the
@@ -131,3 +132,11 @@ class LSTMBaseline(HIPModel):
         self._require_init()
         return self._model.generate(int(n), int(num), temperature=temperature, top_k=top_k, seed=seed,
                                     primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs)
+
+    def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False):
+        """n independent beam searches of width beam_width, num tokens each, on the device (include/fsmg.h fsmg_beam_search):
+        -> tokens int32 [n, beam_width, num], scores float32 [n, beam_width] (, per-token log-probs with logprobs=True), best
+        first.  Group i continues the first primer_len tokens of a support song, dealt round-robin like generate's rows."""
+        self._require_init()
+        return self._model.beam_search(int(num), int(beam_width), n_groups=int(n),
+                                       primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs)

@@ -13,6 +13,7 @@ adaptation of deep networks") as the direction the project was heading.  This pl
   sample(s, num)  greedy decode at theta (the support set is not used, as in the baseline).
   generate(s, num, n, ...)  n samples drawn at theta' adapted on the support set s (fsmg_maml_generate): generation AS the
                   episode's artist.
+  beam_search(s, num, beam_width, n, ...)  the same at theta' (fsmg_maml_beam_search).
 
 Extra config keys: inner_steps (default 1), inner_lr (default 0.1).
 """
@@ -65,6 +66,13 @@ class MAMLLSTM(LSTMBaseline):
         return self._model.maml_generate(support, int(num), self._inner_steps, self._inner_lr, n_seq=int(n),
                                          temperature=temperature, top_k=top_k, seed=seed,
                                          primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs)
+
+    def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False):
+        """like LSTMBaseline.beam_search, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored"""
+        self._require_init()
+        support = self._tokens(support_set, 2)
+        return self._model.maml_beam_search(support, int(num), self._inner_steps, self._inner_lr, int(beam_width), n_groups=int(n),
+                                            primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs)
 
     def eval_many(self, episodes):
         """adaptation is per episode, so there is nothing to batch: one maml_eval per episode"""

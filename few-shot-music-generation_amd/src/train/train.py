@@ -225,6 +225,13 @@ def main(argv=None):
         else:
             for j, row in enumerate(gen):
                 write_seq(episode_sampler['test'].detokenize([int(w) for w in row]), curr_sample_dir, 'model_sample_%d' % j)
+        if 'sample_beam_width' in config:      # opt-in: the beam's hypotheses, best first, and their scores
+            toks, scores = model.beam_search(support_set, max_len, int(config['sample_beam_width']), n=1,
+                                             primer_len=int(config.get('sample_primer_len', 0)))
+            for j, row in enumerate(toks[0]):
+                write_seq(episode_sampler['test'].detokenize([int(w) for w in row]), curr_sample_dir, 'model_beam_%d' % j)
+            with open(os.path.join(curr_sample_dir, 'beam_scores.txt'), 'w') as f:
+                f.write(''.join('%.9g\n' % float(x) for x in scores[0]))
 
 
 if __name__ == '__main__':

@@ -280,6 +280,42 @@ int fsmg_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* primer
 int fsmg_maml_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,
                        float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_logprob);
 
+/* ---- batched on-device beam search (DESIGN.md "Beam search").  G independent searches of width W.  Every hypothesis of group g
+ * reads [start, primer[g][0..P-1], y_0, y_1, ...] from a zero state, exactly as a row of fsmg_generate does, and the logits are
+ * fsmg_generate's (all V1 = input_size + 1 columns).  At generated position t, slot j of a group and column v give
+ *   lp = fl(logit_v - lse_j)   (lse_j the logsumexp fsmg_generate's log-probs use, bitwise the same number)
+ *   s  = fl(cum_j + lp)        (cum_j the slot's score so far: 0 for slot 0 and -inf for the others at t = 0)
+ * and the group's W x V1 candidates are ranked by s descending, then j ascending, then logit descending, then v ascending, a NaN
+ * s or logit ranking below -inf (and -0 equal to +0); the W best become the next slots in that order.  No length normalisation,
+ * no end token: every hypothesis has num tokens.
+ * Outputs: out_tokens[g][w][t], out_scores[g][w] = the final cum, out_logprob[g][w][t] = each token's lp.  A group's hypotheses
+ * are best first and distinct, and a score is bitwise the fp32 left-to-right sum of its lps.  W = 1 is fsmg_generate at
+ * temperature 0, tokens and log-probs bitwise (for rows with a logit above -inf at every position).  A group's output is bitwise
+ * independent of G and of the other groups.
+ * fsmg_beam_search changes no handle state, like fsmg_generate.  fsmg_maml_beam_search adapts, searches and restores theta with
+ * fsmg_maml_generate's wrapper and the same documented side effects (the gradient buffer and the recurrent-launch counters).
+ * Errors: FSMG_ERR_INVALID for a bad config (version, nonzero reserved fields, G < 1, W outside [1, 64] or W > V1^num, num < 1,
+ * P < 0, primer_on_device not 0 / 1, G * W * (P + num + 1) > 2^30, G * W > 2^20, null outputs); FSMG_ERR_TOKEN_RANGE for a
+ * primer id outside [0, input_size) (outputs left unwritten). */
+#define FSMG_BEAM_CONFIG_VERSION 1
+typedef struct fsmg_beam_config {
+    int32_t version;          /* FSMG_BEAM_CONFIG_VERSION                                  */
+    int32_t n_groups;         /* G >= 1 independent searches                               */
+    int32_t beam_width;       /* W, 1 <= W <= 64, and W <= V1^num                          */
+    int32_t num;              /* tokens generated per hypothesis, >= 1                     */
+    int32_t primer_len;       /* P >= 0 primer tokens per GROUP (shared by its W beams)    */
+    int32_t primer_on_device; /* 0 host, 1 device                                          */
+    int32_t reserved[8];      /* must be 0                                                 */
+} fsmg_beam_config;
+
+/* primer [G,P] (NULL if P == 0); out_tokens host [G,W,num]; out_scores host [G,W]; out_logprob host [G,W,num] or NULL */
+int fsmg_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_t* primer,
+                     int32_t* out_tokens, float* out_scores, float* out_logprob);
+/* adapt on support [n_support_rows, max_len] like fsmg_maml_generate, search at theta', restore theta */
+int fsmg_maml_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_t* support, int32_t n_support_rows,
+                          int32_t inner_steps, float inner_lr, int32_t support_on_device, const int32_t* primer,
+                          int32_t* out_tokens, float* out_scores, float* out_logprob);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
