@@ -66,7 +66,30 @@ int check_gen_config(fsmg_model* h, const fsmg_gen_config* g, const int32_t* pri
     return FSMG_OK;
 }
 
-int generate_core(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
+int check_gen_filters(fsmg_model* h, const fsmg_gen_filters* f) {
+    if (!f) return FSMG_OK;
+    if (f->version != FSMG_GEN_FILTERS_VERSION)
+        return fail(h, FSMG_ERR_INVALID, "fsmg_gen_filters.version is " + std::to_string(f->version) + ", this library expects " +
+                                             std::to_string(FSMG_GEN_FILTERS_VERSION));
+    for (int i = 0; i < 8; ++i)
+        if (f->reserved[i] != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_gen_filters.reserved must be zero");
+    if (!(f->top_p >= 0.f && f->top_p <= 1.f)) return fail(h, FSMG_ERR_INVALID, "top_p must be in [0, 1]");
+    if (!(f->min_p >= 0.f && f->min_p <= 1.f)) return fail(h, FSMG_ERR_INVALID, "min_p must be in [0, 1]");
+    if (!(f->repetition_penalty >= 0.f) || !std::isfinite(f->repetition_penalty))
+        return fail(h, FSMG_ERR_INVALID, "repetition_penalty must be finite and >= 0");
+    if (f->repeat_window < 0) return fail(h, FSMG_ERR_INVALID, "repeat_window must be >= 0");
+    if (f->repetition_penalty != 0.f && f->repetition_penalty != 1.f && h->V1 > (1 << 20))
+        return fail(h, FSMG_ERR_INVALID, "repetition_penalty needs input_size + 1 <= 2^20");
+    return FSMG_OK;
+}
+
+bool gen_filters_neutral(const fsmg_gen_filters* f) {
+    return !f || ((f->top_p == 0.f || f->top_p == 1.f) && f->min_p == 0.f && (f->repetition_penalty == 0.f || f->repetition_penalty == 1.f));
+}
+
+int generate_core(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens, float* out_logprob,
+                  const fsmg_gen_filters* f) {
+    if (gen_filters_neutral(f)) f = nullptr;       // neutral filters: exactly fsmg_generate's pick
     const int B = g->n_seq, P = g->primer_len, num = g->num, L = h->L, Hp = h->Hp;
     if (P > 0 && !g->primer_on_device) {           // a host primer is checked before any device work
         for (int64_t i = 0; i < (int64_t)B * P; ++i)
@@ -115,8 +138,14 @@ int generate_core(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer
         }
         if (p < P) continue;
         HIPCK(h, launch_gen_logits(s, h->P + h->off_w, h->V1p, h->P + h->off_d, h->V1, x, Hp, B, logits, lay.ldl));
-        HIPCK(h, launch_gen_pick(s, logits, lay.ldl, h->V1, B, g->temperature, g->top_k, g->seed, p - P, tok, lay.ldtok, p + 1, out_tok,
-                                 out_lp, num));
+        if (!f) {
+            HIPCK(h, launch_gen_pick(s, logits, lay.ldl, h->V1, B, g->temperature, g->top_k, g->seed, p - P, tok, lay.ldtok, p + 1, out_tok,
+                                     out_lp, num));
+        } else {
+            const float theta = f->repetition_penalty == 0.f ? 1.f : f->repetition_penalty;
+            HIPCK(h, launch_gen_pick_filtered(s, logits, lay.ldl, h->V1, B, g->temperature, g->top_k, f->top_p, f->min_p, theta,
+                                              f->repeat_window, g->seed, p - P, tok, lay.ldtok, p + 1, out_tok, out_lp, num));
+        }
     }
     const size_t n = (size_t)B * num;
     std::vector<char> host(n * (sizeof(int) + sizeof(float)));
@@ -138,6 +167,16 @@ int fsmg_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* primer
     if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
     return generate_core(h, g, primer, out_tokens, out_logprob);
+}
+
+int fsmg_generate_filtered(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* primer, int32_t* out_tokens,
+                           float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    int rc = check_gen_config(h, g, primer, out_tokens);
+    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return generate_core(h, g, primer, out_tokens, out_logprob, f);
 }
 
 }  // extern "C"

@@ -369,6 +369,18 @@ int fsmg_maml_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* s
                               [&] { return generate_core(h, g, primer, out_tokens, out_logprob); });
 }
 
+// generate with sampling filters at theta' (api_generate.hip)
+int fsmg_maml_generate_filtered(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* support,
+                                int32_t n_support_rows, int32_t inner_steps, float inner_lr, int32_t support_on_device,
+                                const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    int rc = check_gen_config(h, g, primer, out_tokens);
+    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    if (rc != FSMG_OK) return rc;
+    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
+                              [&] { return generate_core(h, g, primer, out_tokens, out_logprob, f); });
+}
+
 // beam search at theta' (api_beam.hip)
 int fsmg_maml_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,
                           float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_scores,

@@ -243,11 +243,10 @@ __device__ __forceinline__ float row_max_lse(PickShared& sh, const float* __rest
     return mx + (float)log(se);
 }
 
-// The k-th largest of key_of(logit) over the row's ncols columns, MSB-first radix select over 8-bit digits.  Returns the key;
+// The k-th largest of key_at(v) over the columns v < ncols, MSB-first radix select over 8-bit digits.  Returns the key;
 // sh.kleft is then the number of columns with exactly that key that complete the top k (k - the count of larger keys).
-template <bool STAGED, class KeyOf>
-__device__ __forceinline__ unsigned radix_select_kth(PickShared& sh, const float* __restrict__ row, const float* srow, int ncols, int k,
-                                                     KeyOf key_of) {
+template <class KeyAt>
+__device__ __forceinline__ unsigned radix_select_kth_at(PickShared& sh, int ncols, int k, KeyAt key_at) {
     const int tid = threadIdx.x;
     if (tid == 0) { sh.prefix = 0u; sh.kleft = k; }
     unsigned mask = 0u;
@@ -256,7 +255,7 @@ __device__ __forceinline__ unsigned radix_select_kth(PickShared& sh, const float
         __syncthreads();
         const unsigned prefix = sh.prefix;
         for (int v = tid; v < ncols; v += PICK_THREADS) {
-            const unsigned key = key_of(STAGED ? srow[v] : row[v]);
+            const unsigned key = key_at(v);
             if ((key & mask) == prefix) atomicAdd(&sh.hist[(key >> shift) & 255u], 1);
         }
         __syncthreads();
@@ -281,6 +280,13 @@ __device__ __forceinline__ unsigned radix_select_kth(PickShared& sh, const float
         __syncthreads();
     }
     return sh.prefix;
+}
+
+// radix_select_kth_at over key_of(logit) of the row (staged in srow, or read from global memory)
+template <bool STAGED, class KeyOf>
+__device__ __forceinline__ unsigned radix_select_kth(PickShared& sh, const float* __restrict__ row, const float* srow, int ncols, int k,
+                                                     KeyOf key_of) {
+    return radix_select_kth_at(sh, ncols, k, [&](int v) { return key_of(STAGED ? srow[v] : row[v]); });
 }
 
 // One row per workgroup.  Token = argmax over the allowed set of logit / T + Gumbel(Philox(key = seed, ctr = (v >> 2, t, b, 0))),
@@ -512,6 +518,160 @@ __global__ void k_beam_backtrace(int R, int W, int num, const int* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------- the filtered pick (fsmg_generate_filtered, DESIGN.md "Sampling filters")
+struct FilterShared {
+    unsigned long long hist[256];
+    unsigned long long left;
+    unsigned prefix;
+};
+
+// Top-p boundary over the survivors (z' >= thr1): the largest key x with M(>= x) >= ceil(p * Z), M(>= x) the mass of the survivors
+// with key >= x and Z the mass of all of them.  A survivor's mass is exp((z' - zmax) / T) in fixed point, 2^32 for z' = zmax, so
+// the histograms are integer LDS adds whose sums do not depend on the order the threads arrive in.  MSB-first over 8-bit digits
+// like radix_select_kth_at, with a mass per digit instead of a count.  Returns 0 when no survivor has mass (no comparable column).
+template <class ValAt>
+__device__ __forceinline__ unsigned radix_select_mass(FilterShared& fs, int ncols, float p, float thr1, float zmax, float temperature,
+                                                      ValAt val) {
+    const int tid = threadIdx.x;
+    if (tid == 0) fs.prefix = 0u;
+    unsigned mask = 0u;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        if (tid < 256) fs.hist[tid] = 0ull;
+        __syncthreads();
+        const unsigned prefix = fs.prefix;
+        for (int v = tid; v < ncols; v += PICK_THREADS) {
+            const float z = val(v);
+            const unsigned key = beam_key(z);
+            if ((key & mask) != prefix || !(z >= thr1)) continue;
+            const float d = z == zmax ? 0.0f : (z - zmax) / temperature;
+            const unsigned long long m = (unsigned long long)(expf(d) * 0x1p32f);
+            if (m) atomicAdd(&fs.hist[(key >> shift) & 255u], m);
+        }
+        __syncthreads();
+        if (tid < 64) {       // wave 0: lane l owns digits 255 - 4l .. 252 - 4l; masses from the top digit down
+            unsigned long long cnt[4], s = 0ull;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { cnt[j] = fs.hist[255 - 4 * tid - j]; s += cnt[j]; }
+            unsigned long long incl = s;
+            for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(incl, o); if (tid >= o) incl += y; }
+            unsigned long long before = incl - s, kl;
+            if (shift == 24) {      // the first pass sees every survivor: Z, and the mass the boundary key must reach
+                const unsigned long long Z = __shfl(incl, 63);
+                const double want = ceil((double)p * (double)Z);
+                kl = want < 1.0 ? 1ull : (unsigned long long)want;
+                if (kl > Z) kl = Z;
+            } else {
+                kl = fs.left;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (before < kl && kl <= before + cnt[j]) {
+                    fs.prefix = prefix | ((unsigned)(255 - 4 * tid - j) << shift);
+                    fs.left = kl - before;
+                }
+                before += cnt[j];
+            }
+        }
+        mask |= 255u << shift;
+        __syncthreads();
+    }
+    return fs.prefix;
+}
+
+// k_gen_pick with the sampling filters; one row per workgroup.  lse and out_lp come from the raw row exactly as in k_gen_pick.
+// z' = the row with the repetition penalty applied once to each distinct id of tok[b][first .. pos_out - 1] (theta == 1: none).
+// T == 0 or top_k == 1: the argmax of z' (lowest column; column 0 when no z' is comparable).  Else k_gen_pick's Gumbel-max over
+// z' >= thr, thr the largest of: the top_k-th largest z' (NaN lowest), zmax + T ln(min_p) (min_p > 0), the top-p boundary
+// (0 < top_p < 1).  Dynamic LDS: STAGED, the row, its penalised entries rewritten in place from the global raw values
+// (idempotent, so repeated ids are harmless); else, with a penalty, a presence bitmap of ceil(ncols / 32) words.
+template <bool STAGED>
+__global__ __launch_bounds__(PICK_THREADS) void k_gen_pick_filtered(const float* __restrict__ logits, int ldl, int ncols, float temperature,
+                                                                    int top_k, float top_p, float min_p, float theta, int window,
+                                                                    unsigned seed_lo, unsigned seed_hi, int t, int* __restrict__ tok,
+                                                                    int ldtok, int pos_out, int* __restrict__ out_tok,
+                                                                    float* __restrict__ out_lp, int num) {
+    extern __shared__ float srow[];
+    __shared__ PickShared sh;
+    __shared__ FilterShared fs;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* row = logits + (long long)b * ldl;
+    const int* trow = tok + (long long)b * ldtok;
+    unsigned* bits = (unsigned*)srow;
+    const bool pen = theta != 1.0f;
+    auto penalise = [&](float z) -> float { return z > 0.0f ? z / theta : z * theta; };
+    auto val = [&](int v) -> float {
+        if (STAGED) return srow[v];
+        const float z = row[v];
+        return pen && ((bits[v >> 5] >> (v & 31)) & 1u) ? penalise(z) : z;
+    };
+
+    float mx; int mi;
+    const float lse = row_max_lse<STAGED>(sh, row, srow, ncols, mx, mi);
+
+    if (pen) {      // the context tokens in the window (tok[b][0] is the start word, not part of it)
+        const int first = window > 0 ? max(1, pos_out - window) : 1;
+        if (!STAGED) {
+            for (int i = tid; i < (ncols + 31) >> 5; i += PICK_THREADS) bits[i] = 0u;
+            __syncthreads();
+        }
+        for (int i = first + tid; i < pos_out; i += PICK_THREADS) {
+            const int v = trow[i];
+            if (v < 0 || v >= ncols) continue;
+            if (STAGED) srow[v] = penalise(row[v]);
+            else atomicOr(&bits[v >> 5], 1u << (v & 31));
+        }
+        __syncthreads();
+    }
+    // zmax and its lowest column over the comparable z': the sweep's own (mx, mi) when nothing is penalised and mx > -inf
+    float zm = mx; int zi = mi;
+    if (pen || !(mx > -INFINITY)) {
+        zm = -INFINITY; zi = ncols;
+        for (int v = tid; v < ncols; v += PICK_THREADS) {
+            const float z = val(v);
+            if (z > zm || (z == zm && v < zi)) { zm = z; zi = v; }
+        }
+        block_argmax(sh, zm, zi);
+        if (zi >= ncols) zi = 0;
+    }
+
+    int best = zi;
+    if (temperature > 0.0f && top_k != 1) {
+        float thr = -INFINITY;
+        if (top_k > 1 && top_k < ncols) {
+            const unsigned kk = radix_select_kth_at(sh, ncols, top_k, [&](int v) { return beam_key(val(v)); });
+            if (kk != 0u) thr = key_float(kk);          // (key 0: fewer than top_k comparable columns, all of them stay)
+        }
+        if (min_p > 0.0f) thr = fmaxf(thr, zm + temperature * logf(min_p));
+        if (top_p > 0.0f && top_p < 1.0f) {
+            const unsigned xp = radix_select_mass(fs, ncols, top_p, thr, zm, temperature, val);
+            if (xp != 0u) thr = key_float(xp);          // a survivor's key, so >= the thresholds above
+        }
+        const uint2 key = make_uint2(seed_lo, seed_hi);
+        float bs = -INFINITY; int bi = zi;
+        for (int q = tid; 4 * q < ncols; q += PICK_THREADS) {
+            const uint4 x = philox4x32_10(make_uint4((unsigned)q, (unsigned)t, (unsigned)b, 0u), key);
+            const unsigned xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = 4 * q + j;
+                if (v >= ncols) break;
+                const float l = val(v);
+                if (!(l >= thr)) continue;
+                const float s = l / temperature + gumbel_of(xs[j]);
+                if (s > bs || (s == bs && v < bi)) { bs = s; bi = v; }
+            }
+        }
+        block_argmax(sh, bs, bi);
+        best = bi;
+    }
+    best = min(max(best, 0), ncols - 1);
+    if (tid == 0) {
+        tok[(long long)b * ldtok + pos_out] = best;
+        out_tok[(long long)b * num + t] = best;
+        out_lp[(long long)b * num + t] = row[best] - lse;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_gen_cell(hipStream_t s, const float* Kx, int in_dim, const float* Kh, const float* bias, int Hp, const float* emb, int ldemb,
@@ -555,6 +715,38 @@ hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncol
     else
         hipLaunchKernelGGL((k_gen_pick<false>), dim3(B), dim3(PICK_THREADS), 0, s, logits, ldl, ncols, temperature, top_k, lo, hi, t, tok,
                            ldtok, pos_out, out_tok, out_lp, num);
+    return hipGetLastError();
+}
+
+hipError_t launch_gen_pick_filtered(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, float top_p,
+                                    float min_p, float theta, int window, uint64_t seed, int t, int* tok, int ldtok, int pos_out, int* out_tok,
+                                    float* out_lp, int num) {
+    if (B <= 0) return hipSuccess;
+    if (ncols <= 0 || ncols > ldl || t < 0 || t >= num || pos_out >= ldtok || window < 0) return hipErrorInvalidValue;
+    const bool pen = theta != 1.0f;
+    const size_t bitmap_bytes = pen ? sizeof(unsigned) * (size_t)((ncols + 31) / 32) : 0;
+    if (ncols > PICK_LDS_FLOATS && bitmap_bytes > sizeof(float) * PICK_LDS_FLOATS) return hipErrorInvalidValue;
+    const unsigned lo = (unsigned)(seed & 0xFFFFFFFFull), hi = (unsigned)(seed >> 32);
+    static std::atomic<unsigned long long> attr_set{0};       // as launch_gen_pick: the staged row (or bitmap) may take 128 KiB of LDS
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
+        e = hipFuncSetAttribute((const void*)k_gen_pick_filtered<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)sizeof(float) * PICK_LDS_FLOATS);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)k_gen_pick_filtered<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)sizeof(float) * PICK_LDS_FLOATS);
+        if (e != hipSuccess) return e;
+        attr_set.fetch_or(bit, std::memory_order_release);
+    }
+    if (ncols <= PICK_LDS_FLOATS)
+        hipLaunchKernelGGL((k_gen_pick_filtered<true>), dim3(B), dim3(PICK_THREADS), sizeof(float) * (size_t)ncols, s, logits, ldl, ncols,
+                           temperature, top_k, top_p, min_p, theta, window, lo, hi, t, tok, ldtok, pos_out, out_tok, out_lp, num);
+    else
+        hipLaunchKernelGGL((k_gen_pick_filtered<false>), dim3(B), dim3(PICK_THREADS), bitmap_bytes, s, logits, ldl, ncols, temperature, top_k,
+                           top_p, min_p, theta, window, lo, hi, t, tok, ldtok, pos_out, out_tok, out_lp, num);
     return hipGetLastError();
 }
 

@@ -419,6 +419,12 @@ hipError_t launch_gen_logits(hipStream_t s, const float* W, int ldw, const float
 // out_tok[b * num + t], out_lp[b * num + t] = logit - logsumexp
 hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, uint64_t seed, int t,
                            int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num);
+// launch_gen_pick with the sampling filters (fsmg_generate_filtered): repetition penalty theta (1 = off) over the distinct ids of
+// tok[b][max(1, pos_out - window) .. pos_out - 1] (window 0: from 1), then top_k, min_p (0 = off), top_p (0 or >= 1 = off).
+// ncols above 2^20 with a penalty: hipErrorInvalidValue (the presence bitmap of an unstaged row lives in LDS).
+hipError_t launch_gen_pick_filtered(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, float top_p,
+                                    float min_p, float theta, int window, uint64_t seed, int t, int* tok, int ldtok, int pos_out, int* out_tok,
+                                    float* out_lp, int num);
 // tok rows [start, primer[b / rows_per_primer][0..P-1]]; *err |= 1 for a primer id outside [0, vocab)
 hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err,
                              int rows_per_primer = 1);

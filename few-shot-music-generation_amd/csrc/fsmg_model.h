@@ -612,8 +612,12 @@ void on_softmax_range(fsmg_model* h);
 inline bool is_retry(int rc) { return rc == FSMG_ERR_TIMEOUT || rc == FSMG_ERR_SOFTMAX_RANGE; }
 // ------------------------------------------------------------------ batched generation (api_generate.hip)
 // fsmg_generate's work at the parameters the handle holds now (no BEGIN_CALL: fsmg_maml_generate calls it at theta')
-int generate_core(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens, float* out_logprob);
+// f: the sampling filters (fsmg_generate_filtered; nullptr or neutral: fsmg_generate's pick, unchanged)
+int generate_core(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens, float* out_logprob,
+                  const fsmg_gen_filters* f = nullptr);
 int check_gen_config(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens);
+int check_gen_filters(fsmg_model* h, const fsmg_gen_filters* f);
+bool gen_filters_neutral(const fsmg_gen_filters* f);
 // h->gen holds at least `bytes` (the generation / beam-search scratch; each call lays it out its own way)
 int gen_reserve(fsmg_model* h, size_t bytes);
 // ------------------------------------------------------------------ beam search (api_beam.hip)

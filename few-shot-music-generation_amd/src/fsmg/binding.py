@@ -57,6 +57,14 @@ class FsmgGenConfig(C.Structure):
                 ('reserved', C.c_int32 * 7)]
 
 
+FSMG_GEN_FILTERS_VERSION = 1
+
+
+class FsmgGenFilters(C.Structure):
+    _fields_ = [('version', C.c_int32), ('top_p', C.c_float), ('min_p', C.c_float), ('repetition_penalty', C.c_float),
+                ('repeat_window', C.c_int32), ('reserved', C.c_int32 * 8)]
+
+
 FSMG_BEAM_CONFIG_VERSION = 1
 
 
@@ -110,6 +118,9 @@ SIGNATURES = {
     'fsmg_sample': (C.c_int, [_P, C.c_int32, _I32P]),
     'fsmg_generate': (C.c_int, [_P, C.POINTER(FsmgGenConfig), _P, _I32P, _F32P]),
     'fsmg_maml_generate': (C.c_int, [_P, C.POINTER(FsmgGenConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P, _F32P]),
+    'fsmg_generate_filtered': (C.c_int, [_P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _P, _I32P, _F32P]),
+    'fsmg_maml_generate_filtered': (C.c_int, [_P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _P, C.c_int32, C.c_int32, C.c_float,
+                                              C.c_int32, _P, _I32P, _F32P]),
     'fsmg_beam_search': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, _I32P, _F32P, _F32P]),
     'fsmg_maml_beam_search': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P, _F32P,
                                         _F32P]),
@@ -466,17 +477,32 @@ class FsmgModel(object):
             raise ValueError('primer must be [n_seq, P] (or one [P] row for every sequence), got %r' % (a.shape,))
         return self.gen_config(n_seq, num, temperature, top_k, seed, a.shape[1]), C.c_void_p(a.ctypes.data), a
 
-    def generate(self, n_seq, num, temperature=1.0, top_k=0, seed=0, primer=None, logprobs=False):
+    @staticmethod
+    def gen_filters(top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
+        """the fsmg_gen_filters struct, or None when every filter is off (include/fsmg.h: neutral filters)"""
+        if top_p in (0.0, 1.0) and min_p == 0.0 and repetition_penalty in (0.0, 1.0):
+            return None
+        return FsmgGenFilters(version=FSMG_GEN_FILTERS_VERSION, top_p=float(top_p), min_p=float(min_p),
+                              repetition_penalty=float(repetition_penalty), repeat_window=int(repeat_window))
+
+    def generate(self, n_seq, num, temperature=1.0, top_k=0, seed=0, primer=None, logprobs=False, top_p=0.0, min_p=0.0,
+                 repetition_penalty=1.0, repeat_window=0):
         """n_seq independent samples of num tokens -> int32 [n_seq, num] (, float32 [n_seq, num] log-probs with logprobs=True).
-        primer: int32 [n_seq, P] (or [P] for every row) continued by each row, or (device address, P)."""
+        primer: int32 [n_seq, P] (or [P] for every row) continued by each row, or (device address, P).  top_p, min_p,
+        repetition_penalty, repeat_window: the sampling filters of fsmg_generate_filtered (all off: fsmg_generate)."""
         g, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
+        f = self.gen_filters(top_p, min_p, repetition_penalty, repeat_window)
         toks = np.empty((int(n_seq), int(num)), np.int32)
         lp = np.empty((int(n_seq), int(num)), np.float32) if logprobs else None
-        self._ck(self._lib.fsmg_generate(self._h, C.byref(g), pp, toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None))
+        outs = (pp, toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None)
+        if f is None:
+            self._ck(self._lib.fsmg_generate(self._h, C.byref(g), *outs))
+        else:
+            self._ck(self._lib.fsmg_generate_filtered(self._h, C.byref(g), C.byref(f), *outs))
         return (toks, lp) if logprobs else toks
 
     def maml_generate(self, support, num, inner_steps, inner_lr, n_seq=1, temperature=1.0, top_k=0, seed=0, primer=None,
-                      logprobs=False, n_support_rows=None):
+                      logprobs=False, n_support_rows=None, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
         """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), generate at theta', restore theta"""
         if isinstance(support, (int, np.integer)):
             sp, dev, _k1, rows = C.c_void_p(int(support)), 1, None, int(n_support_rows)
@@ -484,10 +510,14 @@ class FsmgModel(object):
             s = np.ascontiguousarray(support, dtype=np.int32).reshape(-1, self.max_len)
             sp, dev, _k1, rows = C.c_void_p(s.ctypes.data), 0, s, s.shape[0]
         g, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
+        f = self.gen_filters(top_p, min_p, repetition_penalty, repeat_window)
         toks = np.empty((int(n_seq), int(num)), np.int32)
         lp = np.empty((int(n_seq), int(num)), np.float32) if logprobs else None
-        self._ck(self._lib.fsmg_maml_generate(self._h, C.byref(g), sp, rows, int(inner_steps), float(inner_lr), dev, pp,
-                                              toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None))
+        args = (sp, rows, int(inner_steps), float(inner_lr), dev, pp, toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None)
+        if f is None:
+            self._ck(self._lib.fsmg_maml_generate(self._h, C.byref(g), *args))
+        else:
+            self._ck(self._lib.fsmg_maml_generate_filtered(self._h, C.byref(g), C.byref(f), *args))
         return (toks, lp) if logprobs else toks
 
     # -- batched on-device beam search (include/fsmg.h fsmg_beam_search) ----------------------------------------

@@ -125,13 +125,15 @@ class LSTMBaseline(HIPModel):
             raise ValueError('primer_len %d exceeds the song length %d' % (primer_len, songs.shape[1]))
         return np.ascontiguousarray(songs[np.arange(n) % songs.shape[0], :primer_len])
 
-    def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False):
+    def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
         """n independent samples of num tokens (int32 [n, num]), drawn on the device (temperature, top_k, seed; include/fsmg.h
         fsmg_generate).  Each row continues the first primer_len tokens of a support song (dealt round-robin); with
-        primer_len 0 the support set is not used."""
+        primer_len 0 the support set is not used.  top_p, min_p, repetition_penalty, repeat_window: the sampling filters
+        (include/fsmg.h fsmg_generate_filtered; all off by default)."""
         self._require_init()
         return self._model.generate(int(n), int(num), temperature=temperature, top_k=top_k, seed=seed,
-                                    primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs)
+                                    primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs,
+                                    top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window)
 
     def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False):
         """n independent beam searches of width beam_width, num tokens each, on the device (include/fsmg.h fsmg_beam_search):

@@ -59,13 +59,14 @@ class MAMLLSTM(LSTMBaseline):
         self._eval_calls += 1
         return nll
 
-    def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False):
+    def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
         """like LSTMBaseline.generate, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored"""
         self._require_init()
         support = self._tokens(support_set, 2)
         return self._model.maml_generate(support, int(num), self._inner_steps, self._inner_lr, n_seq=int(n),
                                          temperature=temperature, top_k=top_k, seed=seed,
-                                         primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs)
+                                         primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs,
+                                         top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window)
 
     def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False):
         """like LSTMBaseline.beam_search, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored"""

@@ -63,6 +63,16 @@ def sample_seed(base, episode_index):
     return z ^ (z >> 31)
 
 
+# opt-in sampling-filter keys -> model.generate's keyword arguments (include/fsmg.h fsmg_generate_filtered)
+SAMPLE_FILTER_KEYS = (('sample_top_p', 'top_p', float), ('sample_min_p', 'min_p', float),
+                      ('sample_repetition_penalty', 'repetition_penalty', float), ('sample_repeat_window', 'repeat_window', int))
+
+
+def sample_filters(config):
+    """the sampling filters the config sets: only the keys present are passed, so a plugin whose generate lacks them still works"""
+    return {arg: conv(config[key]) for key, arg, conv in SAMPLE_FILTER_KEYS if key in config}
+
+
 def evaluate(model, episode_sampler, n_episodes):
     """Mean of model.eval over n_episodes fresh episodes (train.py:27-33)."""
     total, done = 0.0, 0
@@ -217,7 +227,7 @@ def main(argv=None):
             gen = model.generate(support_set, max_len, n=int(config.get('samples_per_episode', 1)),
                                  temperature=float(config['sample_temperature']), top_k=int(config.get('sample_top_k', 0)),
                                  seed=sample_seed(config.get('sample_seed', 0), i),
-                                 primer_len=int(config.get('sample_primer_len', 0)))
+                                 primer_len=int(config.get('sample_primer_len', 0)), **sample_filters(config))
         for j in range(support_set.shape[0]):
             write_seq(episode_sampler['test'].detokenize(support_set[j]), curr_sample_dir, 'support_%d' % j)
         if 'sample_temperature' not in config:

@@ -280,6 +280,48 @@ int fsmg_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* primer
 int fsmg_maml_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,
                        float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_logprob);
 
+/* ---- sampling filters for fsmg_generate (DESIGN.md "Sampling filters"): nucleus (top-p), min-p and a repetition penalty.
+ * At generated position t of row b, let z be the V1 logits exactly as fsmg_generate computes them and T its temperature.
+ * 1. Penalty (theta = repetition_penalty).  The context is primer[b][0..P-1], g_0 .. g_{t-1}; the start word is not part of it.
+ *    With repeat_window n > 0 take the last min(n, P + t) context tokens, with n = 0 all of them; S = the distinct ids there.
+ *    z'_v = z_v > 0 ? fl(z_v / theta) : fl(z_v * theta) for v in S (once per id, however often it occurs), z'_v = z_v otherwise.
+ *    NaN stays NaN.
+ * 2. Top-k (fsmg_gen_config.top_k, fsmg_generate's rule, on z'): A = the columns with z' >= the top_k-th largest z', ties included
+ *    (NaN columns are never in A; with fewer than top_k comparable columns, every comparable column).
+ * 3. Min-p (min_p = m > 0): keep the v in A with (z'_v - z'_max) / T >= ln m, z'_max the maximum z' over A.
+ * 4. Top-p (0 < top_p = p < 1): for q = softmax(z' / T) renormalised over the survivors of 3, keep v iff the mass of the
+ *    survivors with strictly larger z' is < p.  The top column always stays, and so does every tie at the boundary.
+ * 5. Draw: fsmg_generate's Gumbel-max over the final set, same Philox counter (v >> 2, t, b, 0), same tie rule (lowest index).
+ *    T = 0 or top_k = 1: the argmax of z' (lowest index).  NaN columns are never drawn while any comparable column exists; a row
+ *    without a comparable logit still yields a column in [0, V1).
+ * 6. out_logprob is unchanged: z_tok - logsumexp(all raw z), the untempered, unfiltered model log-probability, with the lse
+ *    bitwise the number fsmg_generate uses.
+ * Neutral filters (f == NULL, or top_p in {0, 1}, min_p = 0 and repetition_penalty in {0, 1}) give fsmg_generate's tokens and
+ * log-probs bitwise.  The rest of fsmg_generate's contract holds with filters on: bitwise deterministic, a row's output bitwise
+ * independent of n_seq and of the other rows, no handle state changed (the MAML variant: fsmg_maml_generate's documented side
+ * effects only).  Top-p sums the masses in fixed point (2^-32 of the top column's weight), exactly and in a fixed order; its
+ * boundary may differ from exact arithmetic only for a column whose mass-ahead is within about V1 * 2^-32 of p.
+ * Errors: FSMG_ERR_INVALID for everything fsmg_generate refuses, a wrong filters version or nonzero reserved fields, top_p or
+ * min_p outside [0, 1] or NaN, repetition_penalty negative or not finite, repeat_window < 0, and a penalty at V1 > 2^20;
+ * FSMG_ERR_TOKEN_RANGE for a primer id outside [0, input_size). */
+#define FSMG_GEN_FILTERS_VERSION 1
+typedef struct fsmg_gen_filters {
+    int32_t version;            /* FSMG_GEN_FILTERS_VERSION                                       */
+    float   top_p;              /* 0 or 1 = off, else (0, 1)                                      */
+    float   min_p;              /* 0 = off, else (0, 1]                                           */
+    float   repetition_penalty; /* 0 or 1 = off, else finite > 0                                 */
+    int32_t repeat_window;      /* >= 0; 0 = the whole context                                    */
+    int32_t reserved[8];        /* must be 0                                                      */
+} fsmg_gen_filters;
+
+/* fsmg_generate with filters f (NULL: none) */
+int fsmg_generate_filtered(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f,
+                           const int32_t* primer, int32_t* out_tokens, float* out_logprob);
+/* fsmg_maml_generate with filters f (NULL: none) */
+int fsmg_maml_generate_filtered(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f,
+                                const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
+                                int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_logprob);
+
 /* ---- batched on-device beam search (DESIGN.md "Beam search").  G independent searches of width W.  Every hypothesis of group g
  * reads [start, primer[g][0..P-1], y_0, y_1, ...] from a zero state, exactly as a row of fsmg_generate does, and the logits are
  * fsmg_generate's (all V1 = input_size + 1 columns).  At generated position t, slot j of a group and column v give
