@@ -1,4 +1,4 @@
-// Handle life cycle (fsmg_create / fsmg_destroy), knobs, statistics, greedy decode.
+// Handle life cycle (fsmg_create / fsmg_destroy), knobs, statistics.
 // Host-side C++ only (part of the C-ABI of libfsmg, include/fsmg.h); every kernel lives in gemm.hip / lstm_*.hip / elementwise.hip.
 #include <mutex>
 #include "fsmg_model.h"
@@ -293,12 +293,6 @@ int fsmg_create(const fsmg_config* cfg, fsmg_handle* out) {
     h->xov_done = h->xov_prog + prog_words;
     if (reset_tok_table(h) != FSMG_OK) return bail(FSMG_ERR_HIP, "fill of the token occurrence table failed");
 
-    // decode scratch: per layer h ping/pong + c, plus x and argmax block scratch
-    {
-        const size_t nblk = (h->V1 + 255) / 256;
-        const size_t fl = (size_t)h->L * 3 * h->Hp + 2 * nblk + 64;
-        if (hipMalloc((void**)&h->dec, sizeof(float) * fl + 256) != hipSuccess) return bail(FSMG_ERR_NOMEM, "hipMalloc(decode) failed");
-    }
     if (hipMalloc((void**)&h->khf, sizeof(float) * (size_t)h->L * 2 * h->Hp * h->G4) != hipSuccess)
         return bail(FSMG_ERR_NOMEM, "hipMalloc(fragment weights) failed");
     if (h->persist && h->xcd && lstm_xcd_supported(1, h->Hp)) {
@@ -352,7 +346,6 @@ int fsmg_destroy(fsmg_handle h) {
     drop_graphs(h);
     if (h->scratch) hipFree(h->scratch);
     if (h->d_step) hipFree(h->d_step);
-    if (h->dec) hipFree(h->dec);
     if (h->gen) hipFree(h->gen);
     if (h->khf) hipFree(h->khf);
     if (h->khx) hipFree(h->khx);
@@ -392,45 +385,6 @@ int fsmg_synchronize(fsmg_handle h) {
     if (!h) return FSMG_ERR_INVALID;
     BEGIN_CALL(h);
     HIPCK(h, hipStreamSynchronize(h->stream));
-    return FSMG_OK;
-}
-
-int fsmg_sample(fsmg_handle h, int32_t num, int32_t* out_tokens) {
-    if (!h || num < 0 || (num > 0 && !out_tokens)) return FSMG_ERR_INVALID;
-    BEGIN_CALL(h);
-    hipStream_t s = h->stream;
-    const int Hp = h->Hp, L = h->L;
-    float* hb = h->dec;                       // [L][2][Hp]
-    float* cb = h->dec + (size_t)L * 2 * Hp;  // [L][Hp]
-    float* arg_scratch = cb + (size_t)L * Hp;
-    HIPCK(h, launch_fill32(s, h->dec, 0u, (long long)((sizeof(float) * (size_t)L * 3 * Hp) / 4)));
-    std::vector<int> toks(num);
-    int word = h->V;                          // start word
-    int* d_hist = nullptr;
-    HIPCK(h, hipMalloc((void**)&d_hist, sizeof(int) * (size_t)(num + 1)));
-    HIPCK(h, hipMemcpyAsync(d_hist, &word, sizeof(int), hipMemcpyHostToDevice, s));
-    // greedy decode is a host loop in the reference too (one sess.run per token, lstm_baseline.py:142-154):
-    // the argmax token is read back each step because it selects the next embedding row.
-    for (int i = 0; i < num; ++i) {
-        const float* x = h->P + h->off_emb + (size_t)word * h->Ep;
-        const int pin = i & 1, pout = pin ^ 1;
-        for (int l = 0; l < L; ++l) {
-            float* h_in = hb + ((size_t)l * 2 + pin) * Hp;
-            float* h_out = hb + ((size_t)l * 2 + pout) * Hp;
-            hipError_t e = launch_decode_cell(s, h->P + h->off_kx[l], h->in_dim[l], h->P + h->off_kh[l],
-                                              h->P + h->off_b[l], x, h_in, h_out, cb + (size_t)l * Hp, Hp);
-            if (e != hipSuccess) { hipFree(d_hist); return fail(h, FSMG_ERR_HIP, hipGetErrorString(e)); }
-            x = h_out;
-        }
-        hipError_t e = launch_decode_argmax(s, h->P + h->off_w, h->V1p, h->P + h->off_d, x, Hp, h->V1,
-                                            d_hist + i + 1, arg_scratch);
-        if (e == hipSuccess) e = hipMemcpyAsync(&word, d_hist + i + 1, sizeof(int), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { hipFree(d_hist); return fail(h, FSMG_ERR_HIP, hipGetErrorString(e)); }
-        toks[i] = word;
-    }
-    hipFree(d_hist);
-    for (int i = 0; i < num; ++i) out_tokens[i] = toks[i];
     return FSMG_OK;
 }
 

@@ -335,7 +335,7 @@ static int adapt_flag(fsmg_handle h) {
 
 namespace fsmg_host {
 // adapt on the support rows like fsmg_maml_eval, run the body at theta', restore theta whatever happened; one repeat on per-step
-// launches when the adaptation ran garbage (skipped) steps.  fsmg_maml_generate and fsmg_maml_beam_search run through here.
+// launches when the adaptation ran garbage (skipped) steps.  The MAML decode entry points (api_decode.hip) run through here.
 int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
                        int32_t support_on_device, const std::function<int()>& at_theta_prime) {
     if (!support || n_support_rows <= 0 || inner_steps < 0 || inner_steps > 64 || !(inner_lr >= 0.f) || !std::isfinite(inner_lr) ||
@@ -358,39 +358,6 @@ int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_
 }  // namespace fsmg_host
 
 extern "C" {
-
-// generate at theta' (api_generate.hip)
-int fsmg_maml_generate(fsmg_handle h, const fsmg_gen_config* g, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,
-                       float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
-    if (!h) return FSMG_ERR_INVALID;
-    const int rc = check_gen_config(h, g, primer, out_tokens);
-    if (rc != FSMG_OK) return rc;
-    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
-                              [&] { return generate_core(h, g, primer, out_tokens, out_logprob); });
-}
-
-// generate with sampling filters at theta' (api_generate.hip)
-int fsmg_maml_generate_filtered(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* support,
-                                int32_t n_support_rows, int32_t inner_steps, float inner_lr, int32_t support_on_device,
-                                const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
-    if (!h) return FSMG_ERR_INVALID;
-    int rc = check_gen_config(h, g, primer, out_tokens);
-    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
-    if (rc != FSMG_OK) return rc;
-    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
-                              [&] { return generate_core(h, g, primer, out_tokens, out_logprob, f); });
-}
-
-// beam search at theta' (api_beam.hip)
-int fsmg_maml_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,
-                          float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_scores,
-                          float* out_logprob) {
-    if (!h) return FSMG_ERR_INVALID;
-    const int rc = check_beam_config(h, b, primer, out_tokens, out_scores);
-    if (rc != FSMG_OK) return rc;
-    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
-                              [&] { return beam_core(h, b, primer, out_tokens, out_scores, out_logprob); });
-}
 
 int fsmg_eval_batch(fsmg_handle h, const int32_t* queries, int32_t n_episodes, int32_t N, int32_t Q,
                     int32_t tokens_on_device, float* nll) {

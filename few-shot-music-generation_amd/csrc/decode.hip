@@ -109,7 +109,7 @@ __global__ __launch_bounds__(GEN_THREADS) void k_gen_cell(const float* __restric
         t += part[3][row][col];
         z[gi] = t + bias[16 * nb + col];
     }
-    // gates i, j, f, o; forget bias 1 (BasicLSTMCell(forget_bias=1.)), exactly as k_decode_cell
+    // gates i, j, f, o; forget bias 1 (BasicLSTMCell(forget_bias=1.))
     const long long u = (long long)r * Hp + 4 * nb + uu;
     const float si = sigmoidf_(z[0]), tj = tanhf(z[1]), sf = sigmoidf_(z[2] + 1.0f), so = sigmoidf_(z[3]);
     const float cn = c[u] * sf + si * tj;
@@ -180,13 +180,19 @@ __device__ __forceinline__ unsigned fkey(float f) {
 }
 __device__ __forceinline__ float key_float(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
+// radix_select's histogram and result: T = int for counts (PickShared), 64-bit fixed point for the top-p masses
+template <class T>
+struct RadixShared {
+    T hist[256];
+    T left;
+    unsigned prefix;
+};
+
 struct PickShared {
     float fv[PICK_THREADS / 64];
     int iv[PICK_THREADS / 64];
     double dv[PICK_THREADS / 64];
-    int hist[256];
-    unsigned prefix;
-    int kleft;
+    RadixShared<int> rs;
 };
 
 // block-wide (max, lowest index) -- every thread gets the result
@@ -222,7 +228,7 @@ template <bool STAGED>
 __device__ __forceinline__ float row_max_lse(PickShared& sh, const float* __restrict__ row, float* srow, int ncols, float& mx, int& mi) {
     const int tid = threadIdx.x;
     // staging and the row maximum in one sweep, 8 loads in flight per thread (the sweep is latency-bound at small B)
-    // the index starts at column 0 (like k_decode_pick), so that a row without a comparable logit (all NaN) still yields a column
+    // the index starts at column 0, so that a row without a comparable logit (all NaN) still yields a column
     mx = -INFINITY; mi = 0;
     for (int v0 = tid; v0 < ncols; v0 += 8 * PICK_THREADS) {
         float l[8];
@@ -243,35 +249,40 @@ __device__ __forceinline__ float row_max_lse(PickShared& sh, const float* __rest
     return mx + (float)log(se);
 }
 
-// The k-th largest of key_at(v) over the columns v < ncols, MSB-first radix select over 8-bit digits.  Returns the key;
-// sh.kleft is then the number of columns with exactly that key that complete the top k (k - the count of larger keys).
-template <class KeyAt>
-__device__ __forceinline__ unsigned radix_select_kth_at(PickShared& sh, int ncols, int k, KeyAt key_at) {
+// MSB-first radix select over the 8-bit digits of key_at(v), v < ncols, each column weighing weight_at(v) (0: not counted): the
+// largest key x such that the columns with key >= x weigh at least target(Z), Z the weight of all of them (seen by the first pass).
+// rs.left is then the weight of the columns with exactly that key that complete the target.  The weights are integers (counts, or
+// the top-p masses in fixed point), so the histograms' sums do not depend on the order the threads arrive in.  Key 0 when no key
+// reaches the target (Z = 0).
+template <class T, class KeyAt, class WeightAt, class Target>
+__device__ __forceinline__ unsigned radix_select(RadixShared<T>& rs, int ncols, KeyAt key_at, WeightAt weight_at, Target target) {
     const int tid = threadIdx.x;
-    if (tid == 0) { sh.prefix = 0u; sh.kleft = k; }
+    if (tid == 0) rs.prefix = 0u;
     unsigned mask = 0u;
     for (int shift = 24; shift >= 0; shift -= 8) {
-        if (tid < 256) sh.hist[tid] = 0;
+        if (tid < 256) rs.hist[tid] = T(0);
         __syncthreads();
-        const unsigned prefix = sh.prefix;
+        const unsigned prefix = rs.prefix;
         for (int v = tid; v < ncols; v += PICK_THREADS) {
             const unsigned key = key_at(v);
-            if ((key & mask) == prefix) atomicAdd(&sh.hist[(key >> shift) & 255u], 1);
+            if ((key & mask) != prefix) continue;
+            const T w = weight_at(v);
+            if (w) atomicAdd(&rs.hist[(key >> shift) & 255u], w);
         }
         __syncthreads();
-        if (tid < 64) {       // wave 0: lane l owns digits 255 - 4l .. 252 - 4l; counts from the top digit down
-            int cnt[4], s = 0;
+        if (tid < 64) {       // wave 0: lane l owns digits 255 - 4l .. 252 - 4l; weights from the top digit down
+            T cnt[4], s = T(0);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { cnt[j] = sh.hist[255 - 4 * tid - j]; s += cnt[j]; }
-            int incl = s;
-            for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o); if (tid >= o) incl += y; }
-            int before = incl - s;
-            const int kl = sh.kleft;
+            for (int j = 0; j < 4; ++j) { cnt[j] = rs.hist[255 - 4 * tid - j]; s += cnt[j]; }
+            T incl = s;
+            for (int o = 1; o < 64; o <<= 1) { const T y = __shfl_up(incl, o); if (tid >= o) incl += y; }
+            T before = incl - s;
+            const T kl = shift == 24 ? target(__shfl(incl, 63)) : rs.left;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (before < kl && kl <= before + cnt[j]) {
-                    sh.prefix = prefix | ((unsigned)(255 - 4 * tid - j) << shift);
-                    sh.kleft = kl - before;
+                    rs.prefix = prefix | ((unsigned)(255 - 4 * tid - j) << shift);
+                    rs.left = kl - before;
                 }
                 before += cnt[j];
             }
@@ -279,14 +290,43 @@ __device__ __forceinline__ unsigned radix_select_kth_at(PickShared& sh, int ncol
         mask |= 255u << shift;
         __syncthreads();
     }
-    return sh.prefix;
+    return rs.prefix;
 }
 
-// radix_select_kth_at over key_of(logit) of the row (staged in srow, or read from global memory)
-template <bool STAGED, class KeyOf>
-__device__ __forceinline__ unsigned radix_select_kth(PickShared& sh, const float* __restrict__ row, const float* srow, int ncols, int k,
-                                                     KeyOf key_of) {
-    return radix_select_kth_at(sh, ncols, k, [&](int v) { return key_of(STAGED ? srow[v] : row[v]); });
+// Gumbel-max over the columns with val(v) >= thr: the argmax of val(v) / temperature + Gumbel(Philox(key = seed, ctr = (v >> 2, t,
+// b, 0))), lowest index on ties; `start` when no column scores above -inf
+template <class ValAt>
+__device__ __forceinline__ int gumbel_max(PickShared& sh, int ncols, float thr, float temperature, unsigned seed_lo, unsigned seed_hi,
+                                          int t, int b, int start, ValAt val) {
+    const uint2 key = make_uint2(seed_lo, seed_hi);
+    float bs = -INFINITY; int bi = start;
+    for (int q = threadIdx.x; 4 * q < ncols; q += PICK_THREADS) {
+        const uint4 x = philox4x32_10(make_uint4((unsigned)q, (unsigned)t, (unsigned)b, 0u), key);
+        const unsigned xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v = 4 * q + j;
+            if (v >= ncols) break;
+            const float l = val(v);
+            if (!(l >= thr)) continue;
+            const float s = l / temperature + gumbel_of(xs[j]);
+            if (s > bs || (s == bs && v < bi)) { bs = s; bi = v; }
+        }
+    }
+    block_argmax(sh, bs, bi);
+    return bi;
+}
+
+// the picked token of row b at generated position t -> the token buffer (the next position's input) and out_tok [b][t]; its raw
+// log-prob row[token] - lse -> out_lp [b][t].  The token gathers an embedding row at the next position: never outside [0, ncols).
+__device__ __forceinline__ void write_pick(int best, const float* __restrict__ row, float lse, int ncols, int b, int t, int* __restrict__ tok,
+                                           int ldtok, int pos_out, int* __restrict__ out_tok, float* __restrict__ out_lp, int num) {
+    best = min(max(best, 0), ncols - 1);
+    if (threadIdx.x == 0) {
+        tok[(long long)b * ldtok + pos_out] = best;
+        out_tok[(long long)b * num + t] = best;
+        out_lp[(long long)b * num + t] = row[best] - lse;
+    }
 }
 
 // One row per workgroup.  Token = argmax over the allowed set of logit / T + Gumbel(Philox(key = seed, ctr = (v >> 2, t, b, 0))),
@@ -299,7 +339,7 @@ __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick(const float* __restri
                                                            int pos_out, int* __restrict__ out_tok, float* __restrict__ out_lp, int num) {
     extern __shared__ float srow[];
     __shared__ PickShared sh;
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     const float* row = logits + (long long)b * ldl;
     auto val = [&](int v) -> float { return STAGED ? srow[v] : row[v]; };
 
@@ -309,31 +349,11 @@ __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick(const float* __restri
     int best = mi;
     if (temperature > 0.0f && top_k != 1) {
         float thr = -INFINITY;
-        if (top_k > 1 && top_k < ncols) thr = key_float(radix_select_kth<STAGED>(sh, row, srow, ncols, top_k, [](float f) { return fkey(f); }));
-        const uint2 key = make_uint2(seed_lo, seed_hi);
-        float bs = -INFINITY; int bi = 0;
-        for (int q = tid; 4 * q < ncols; q += PICK_THREADS) {
-            const uint4 x = philox4x32_10(make_uint4((unsigned)q, (unsigned)t, (unsigned)b, 0u), key);
-            const unsigned xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int v = 4 * q + j;
-                if (v >= ncols) break;
-                const float l = val(v);
-                if (!(l >= thr)) continue;
-                const float s = l / temperature + gumbel_of(xs[j]);
-                if (s > bs || (s == bs && v < bi)) { bs = s; bi = v; }
-            }
-        }
-        block_argmax(sh, bs, bi);
-        best = bi;
+        if (top_k > 1 && top_k < ncols)
+            thr = key_float(radix_select(sh.rs, ncols, [&](int v) { return fkey(val(v)); }, [](int) { return 1; }, [&](int) { return top_k; }));
+        best = gumbel_max(sh, ncols, thr, temperature, seed_lo, seed_hi, t, b, 0, val);
     }
-    best = min(max(best, 0), ncols - 1);      // the token gathers an embedding row at the next position: never outside [0, ncols)
-    if (tid == 0) {
-        tok[(long long)b * ldtok + pos_out] = best;
-        out_tok[(long long)b * num + t] = best;
-        out_lp[(long long)b * num + t] = val(best) - lse;
-    }
+    write_pick(best, row, lse, ncols, b, t, tok, ldtok, pos_out, out_tok, out_lp, num);
 }
 
 // token buffer row b: [start, primer[b / rows_per_primer][0..P-1]]; *err = 1 for a primer id outside [0, vocab)
@@ -386,8 +406,8 @@ __global__ __launch_bounds__(PICK_THREADS) void k_beam_rowtop(const float* __res
         // the sweep's column is the best one already: the largest comparable logit, lowest index on ties
         if (tid == 0) { ck[0] = beam_key(mx); cv[0] = mi; }
     } else {
-        const unsigned kth = radix_select_kth<STAGED>(sh, row, srow, ncols, wr, [](float f) { return beam_key(f); });
-        const int need_eq = sh.kleft, n_above = wr - need_eq;
+        const unsigned kth = radix_select(sh.rs, ncols, [&](int v) { return beam_key(val(v)); }, [](int) { return 1; }, [&](int) { return wr; });
+        const int need_eq = sh.rs.left, n_above = wr - need_eq;
         int eq_base = 0;
         for (int v0 = 0; v0 < ncols; v0 += PICK_THREADS) {
             const int v = v0 + tid;
@@ -519,65 +539,6 @@ __global__ void k_beam_backtrace(int R, int W, int num, const int* __restrict__ 
 }
 
 // ---------------------------------------------------------------- the filtered pick (fsmg_generate_filtered, DESIGN.md "Sampling filters")
-struct FilterShared {
-    unsigned long long hist[256];
-    unsigned long long left;
-    unsigned prefix;
-};
-
-// Top-p boundary over the survivors (z' >= thr1): the largest key x with M(>= x) >= ceil(p * Z), M(>= x) the mass of the survivors
-// with key >= x and Z the mass of all of them.  A survivor's mass is exp((z' - zmax) / T) in fixed point, 2^32 for z' = zmax, so
-// the histograms are integer LDS adds whose sums do not depend on the order the threads arrive in.  MSB-first over 8-bit digits
-// like radix_select_kth_at, with a mass per digit instead of a count.  Returns 0 when no survivor has mass (no comparable column).
-template <class ValAt>
-__device__ __forceinline__ unsigned radix_select_mass(FilterShared& fs, int ncols, float p, float thr1, float zmax, float temperature,
-                                                      ValAt val) {
-    const int tid = threadIdx.x;
-    if (tid == 0) fs.prefix = 0u;
-    unsigned mask = 0u;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        if (tid < 256) fs.hist[tid] = 0ull;
-        __syncthreads();
-        const unsigned prefix = fs.prefix;
-        for (int v = tid; v < ncols; v += PICK_THREADS) {
-            const float z = val(v);
-            const unsigned key = beam_key(z);
-            if ((key & mask) != prefix || !(z >= thr1)) continue;
-            const float d = z == zmax ? 0.0f : (z - zmax) / temperature;
-            const unsigned long long m = (unsigned long long)(expf(d) * 0x1p32f);
-            if (m) atomicAdd(&fs.hist[(key >> shift) & 255u], m);
-        }
-        __syncthreads();
-        if (tid < 64) {       // wave 0: lane l owns digits 255 - 4l .. 252 - 4l; masses from the top digit down
-            unsigned long long cnt[4], s = 0ull;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { cnt[j] = fs.hist[255 - 4 * tid - j]; s += cnt[j]; }
-            unsigned long long incl = s;
-            for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(incl, o); if (tid >= o) incl += y; }
-            unsigned long long before = incl - s, kl;
-            if (shift == 24) {      // the first pass sees every survivor: Z, and the mass the boundary key must reach
-                const unsigned long long Z = __shfl(incl, 63);
-                const double want = ceil((double)p * (double)Z);
-                kl = want < 1.0 ? 1ull : (unsigned long long)want;
-                if (kl > Z) kl = Z;
-            } else {
-                kl = fs.left;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (before < kl && kl <= before + cnt[j]) {
-                    fs.prefix = prefix | ((unsigned)(255 - 4 * tid - j) << shift);
-                    fs.left = kl - before;
-                }
-                before += cnt[j];
-            }
-        }
-        mask |= 255u << shift;
-        __syncthreads();
-    }
-    return fs.prefix;
-}
-
 // k_gen_pick with the sampling filters; one row per workgroup.  lse and out_lp come from the raw row exactly as in k_gen_pick.
 // z' = the row with the repetition penalty applied once to each distinct id of tok[b][first .. pos_out - 1] (theta == 1: none).
 // T == 0 or top_k == 1: the argmax of z' (lowest column; column 0 when no z' is comparable).  Else k_gen_pick's Gumbel-max over
@@ -592,7 +553,7 @@ __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick_filtered(const float*
                                                                     float* __restrict__ out_lp, int num) {
     extern __shared__ float srow[];
     __shared__ PickShared sh;
-    __shared__ FilterShared fs;
+    __shared__ RadixShared<unsigned long long> fs;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* row = logits + (long long)b * ldl;
     const int* trow = tok + (long long)b * ldtok;
@@ -638,38 +599,33 @@ __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick_filtered(const float*
     if (temperature > 0.0f && top_k != 1) {
         float thr = -INFINITY;
         if (top_k > 1 && top_k < ncols) {
-            const unsigned kk = radix_select_kth_at(sh, ncols, top_k, [&](int v) { return beam_key(val(v)); });
+            const unsigned kk = radix_select(sh.rs, ncols, [&](int v) { return beam_key(val(v)); }, [](int) { return 1; }, [&](int) { return top_k; });
             if (kk != 0u) thr = key_float(kk);          // (key 0: fewer than top_k comparable columns, all of them stay)
         }
         if (min_p > 0.0f) thr = fmaxf(thr, zm + temperature * logf(min_p));
         if (top_p > 0.0f && top_p < 1.0f) {
-            const unsigned xp = radix_select_mass(fs, ncols, top_p, thr, zm, temperature, val);
+            // the top-p boundary over the survivors (z' >= thr): the largest key x with M(>= x) >= ceil(p * Z), M(>= x) the mass of
+            // the survivors with key >= x and Z the mass of all of them; a survivor's mass is exp((z' - zmax) / T) in fixed point,
+            // 2^32 for z' = zmax
+            const float thr1 = thr;
+            const unsigned xp = radix_select(
+                fs, ncols, [&](int v) { return beam_key(val(v)); },
+                [&](int v) -> unsigned long long {
+                    const float z = val(v);
+                    if (!(z >= thr1)) return 0ull;
+                    const float d = z == zm ? 0.0f : (z - zm) / temperature;
+                    return (unsigned long long)(expf(d) * 0x1p32f);
+                },
+                [&](unsigned long long Z) {
+                    const double want = ceil((double)top_p * (double)Z);
+                    const unsigned long long kl = want < 1.0 ? 1ull : (unsigned long long)want;
+                    return kl > Z ? Z : kl;
+                });
             if (xp != 0u) thr = key_float(xp);          // a survivor's key, so >= the thresholds above
         }
-        const uint2 key = make_uint2(seed_lo, seed_hi);
-        float bs = -INFINITY; int bi = zi;
-        for (int q = tid; 4 * q < ncols; q += PICK_THREADS) {
-            const uint4 x = philox4x32_10(make_uint4((unsigned)q, (unsigned)t, (unsigned)b, 0u), key);
-            const unsigned xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int v = 4 * q + j;
-                if (v >= ncols) break;
-                const float l = val(v);
-                if (!(l >= thr)) continue;
-                const float s = l / temperature + gumbel_of(xs[j]);
-                if (s > bs || (s == bs && v < bi)) { bs = s; bi = v; }
-            }
-        }
-        block_argmax(sh, bs, bi);
-        best = bi;
+        best = gumbel_max(sh, ncols, thr, temperature, seed_lo, seed_hi, t, b, zi, val);
     }
-    best = min(max(best, 0), ncols - 1);
-    if (tid == 0) {
-        tok[(long long)b * ldtok + pos_out] = best;
-        out_tok[(long long)b * num + t] = best;
-        out_lp[(long long)b * num + t] = row[best] - lse;
-    }
+    write_pick(best, row, lse, ncols, b, t, tok, ldtok, pos_out, out_tok, out_lp, num);
 }
 
 }  // namespace
@@ -692,62 +648,46 @@ hipError_t launch_gen_logits(hipStream_t s, const float* W, int ldw, const float
     return hipGetLastError();
 }
 
-hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, uint64_t seed, int t,
-                           int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num) {
-    if (B <= 0) return hipSuccess;
-    if (ncols <= 0 || ncols > ldl || t < 0 || t >= num || pos_out >= ldtok) return hipErrorInvalidValue;
-    const unsigned lo = (unsigned)(seed & 0xFFFFFFFFull), hi = (unsigned)(seed >> 32);
-    // the staged row may take up to 128 KiB of the 160 KiB LDS: raise the kernel's limit once per device (a second caller racing
-    // the first sets the same value again, harmless)
+namespace {
+// The row-per-workgroup kernels (the picks, k_beam_rowtop), one workgroup per row: the STAGED instantiation holds the row in dynamic
+// LDS up to PICK_LDS_FLOATS columns (128 KiB of the 160 KiB), the other reads it from global memory with `lds` bytes of dynamic LDS.
+// Both instantiations' LDS limit is raised once per device (a second caller racing the first sets the same value again, harmless).
+template <auto* STAGED, auto* UNSTAGED, class... Args>
+hipError_t launch_row_kernel(hipStream_t s, int rows, int ncols, size_t lds, Args... args) {
     static std::atomic<unsigned long long> attr_set{0};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute((const void*)k_gen_pick<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(float) * PICK_LDS_FLOATS);
-        if (e != hipSuccess) return e;
+        for (const void* k : {(const void*)STAGED, (const void*)UNSTAGED}) {
+            e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(float) * PICK_LDS_FLOATS);
+            if (e != hipSuccess) return e;
+        }
         attr_set.fetch_or(bit, std::memory_order_release);
     }
     if (ncols <= PICK_LDS_FLOATS)
-        hipLaunchKernelGGL((k_gen_pick<true>), dim3(B), dim3(PICK_THREADS), sizeof(float) * (size_t)ncols, s, logits, ldl, ncols, temperature,
-                           top_k, lo, hi, t, tok, ldtok, pos_out, out_tok, out_lp, num);
+        hipLaunchKernelGGL(STAGED, dim3(rows), dim3(PICK_THREADS), sizeof(float) * (size_t)ncols, s, args...);
     else
-        hipLaunchKernelGGL((k_gen_pick<false>), dim3(B), dim3(PICK_THREADS), 0, s, logits, ldl, ncols, temperature, top_k, lo, hi, t, tok,
-                           ldtok, pos_out, out_tok, out_lp, num);
+        hipLaunchKernelGGL(UNSTAGED, dim3(rows), dim3(PICK_THREADS), lds, s, args...);
     return hipGetLastError();
 }
+}  // namespace
 
-hipError_t launch_gen_pick_filtered(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, float top_p,
-                                    float min_p, float theta, int window, uint64_t seed, int t, int* tok, int ldtok, int pos_out, int* out_tok,
-                                    float* out_lp, int num) {
+hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, const GenFilters* f,
+                           uint64_t seed, int t, int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num) {
     if (B <= 0) return hipSuccess;
-    if (ncols <= 0 || ncols > ldl || t < 0 || t >= num || pos_out >= ldtok || window < 0) return hipErrorInvalidValue;
-    const bool pen = theta != 1.0f;
-    const size_t bitmap_bytes = pen ? sizeof(unsigned) * (size_t)((ncols + 31) / 32) : 0;
-    if (ncols > PICK_LDS_FLOATS && bitmap_bytes > sizeof(float) * PICK_LDS_FLOATS) return hipErrorInvalidValue;
+    if (ncols <= 0 || ncols > ldl || t < 0 || t >= num || pos_out >= ldtok || (f && f->window < 0)) return hipErrorInvalidValue;
     const unsigned lo = (unsigned)(seed & 0xFFFFFFFFull), hi = (unsigned)(seed >> 32);
-    static std::atomic<unsigned long long> attr_set{0};       // as launch_gen_pick: the staged row (or bitmap) may take 128 KiB of LDS
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute((const void*)k_gen_pick_filtered<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sizeof(float) * PICK_LDS_FLOATS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)k_gen_pick_filtered<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)sizeof(float) * PICK_LDS_FLOATS);
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    if (ncols <= PICK_LDS_FLOATS)
-        hipLaunchKernelGGL((k_gen_pick_filtered<true>), dim3(B), dim3(PICK_THREADS), sizeof(float) * (size_t)ncols, s, logits, ldl, ncols,
-                           temperature, top_k, top_p, min_p, theta, window, lo, hi, t, tok, ldtok, pos_out, out_tok, out_lp, num);
-    else
-        hipLaunchKernelGGL((k_gen_pick_filtered<false>), dim3(B), dim3(PICK_THREADS), bitmap_bytes, s, logits, ldl, ncols, temperature, top_k,
-                           top_p, min_p, theta, window, lo, hi, t, tok, ldtok, pos_out, out_tok, out_lp, num);
-    return hipGetLastError();
+    if (!f)
+        return launch_row_kernel<k_gen_pick<true>, k_gen_pick<false>>(s, B, ncols, 0, logits, ldl, ncols, temperature, top_k, lo, hi, t, tok,
+                                                                      ldtok, pos_out, out_tok, out_lp, num);
+    // an unstaged row with a penalty keeps a presence bitmap of its columns in LDS
+    const size_t bitmap_bytes = f->theta != 1.0f ? sizeof(unsigned) * (size_t)((ncols + 31) / 32) : 0;
+    if (bitmap_bytes > sizeof(float) * PICK_LDS_FLOATS) return hipErrorInvalidValue;
+    return launch_row_kernel<k_gen_pick_filtered<true>, k_gen_pick_filtered<false>>(s, B, ncols, bitmap_bytes, logits, ldl, ncols, temperature,
+                                                                                    top_k, f->top_p, f->min_p, f->theta, f->window, lo, hi, t,
+                                                                                    tok, ldtok, pos_out, out_tok, out_lp, num);
 }
 
 hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err,
@@ -772,22 +712,7 @@ hipError_t launch_beam_rowtop(hipStream_t s, const float* logits, int ldl, int n
                               float* cand_lp, int* cand_v) {
     if (R <= 0) return hipSuccess;
     if (ncols <= 0 || ncols > ldl || W < 1 || W > BEAM_MAX_W) return hipErrorInvalidValue;
-    static std::atomic<unsigned long long> attr_set{0};       // as launch_gen_pick: the staged row may take 128 KiB of LDS
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute((const void*)k_beam_rowtop<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(float) * PICK_LDS_FLOATS);
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    if (ncols <= PICK_LDS_FLOATS)
-        hipLaunchKernelGGL((k_beam_rowtop<true>), dim3(R), dim3(PICK_THREADS), sizeof(float) * (size_t)ncols, s, logits, ldl, ncols, W, cum,
-                           cand_s, cand_lp, cand_v);
-    else
-        hipLaunchKernelGGL((k_beam_rowtop<false>), dim3(R), dim3(PICK_THREADS), 0, s, logits, ldl, ncols, W, cum, cand_s, cand_lp, cand_v);
-    return hipGetLastError();
+    return launch_row_kernel<k_beam_rowtop<true>, k_beam_rowtop<false>>(s, R, ncols, 0, logits, ldl, ncols, W, cum, cand_s, cand_lp, cand_v);
 }
 
 hipError_t launch_beam_select(hipStream_t s, int G, int W, int ncols, const float* cand_s, const float* cand_lp, const int* cand_v,

@@ -1,6 +1,6 @@
 // HBM-bound and small kernels of the step: token staging, softmax cross-entropy rows,
 // deterministic reductions, embedding-gradient segmented sum, global-norm + TF-style Adam,
-// parameter init and the greedy-decode GEMVs.  wave64 everywhere; reductions use
+// parameter init.  wave64 everywhere; reductions use
 // __shfl_xor over 64 lanes.
 #include <algorithm>
 #include "fsmg_kernels.h"
@@ -948,76 +948,6 @@ __global__ __launch_bounds__(1024) void k_unigram_argmax(const unsigned* __restr
     if (tid == 0) *out = si[0];
 }
 
-// ---------------------------------------------------------------- greedy decode (K10)
-// One cell step for one sequence: z = x*Kx + h*Kh + b over packed gate columns; block nb owns
-// units 4nb..4nb+3 (16 packed columns); 256 threads split the (in + Hp) reduction.
-__global__ __launch_bounds__(256) void k_decode_cell(const float* __restrict__ Kx, int in_dim,
-                                                     const float* __restrict__ Kh, const float* __restrict__ bias,
-                                                     const float* __restrict__ x, const float* __restrict__ h_in,
-                                                     float* __restrict__ h_out, float* __restrict__ c, int Hp) {
-    __shared__ float part[16][17];
-    const int nb = blockIdx.x, tid = threadIdx.x;
-    const int col = tid & 15, slice = tid >> 4;         // 16 k-slices x 16 columns
-    const int G4 = 4 * Hp;
-    float s = 0.0f;
-    for (int k = slice; k < in_dim; k += 16) s += x[k] * Kx[(long long)k * G4 + 16 * nb + col];
-    for (int k = slice; k < Hp; k += 16) s += h_in[k] * Kh[(long long)k * G4 + 16 * nb + col];
-    part[slice][col] = s;
-    __syncthreads();
-    if (tid < 4) {
-        float zg[4];
-#pragma unroll
-        for (int gi = 0; gi < 4; ++gi) {
-            const int cc = 4 * gi + tid;
-            float t = bias[16 * nb + cc];
-#pragma unroll
-            for (int sl = 0; sl < 16; ++sl) t += part[sl][cc];
-            zg[gi] = t;
-        }
-        const int u = 4 * nb + tid;
-        const float si = 1.0f / (1.0f + expf(-zg[0])), tj = tanhf(zg[1]);
-        const float sf = 1.0f / (1.0f + expf(-(zg[2] + 1.0f))), so = 1.0f / (1.0f + expf(-zg[3]));
-        const float cn = c[u] * sf + si * tj;
-        c[u] = cn;
-        h_out[u] = tanhf(cn) * so;
-    }
-}
-
-// logits = h*W + b over n_vocab columns, argmax (lowest index on ties, like np.argmax).
-// Stage 1: each block handles 256 columns -> (max, idx) per block; stage 2: one block reduces.
-__global__ __launch_bounds__(256) void k_decode_logits(const float* __restrict__ W, int ldw,
-                                                       const float* __restrict__ bias, const float* __restrict__ h,
-                                                       int Hp, int n_vocab, float* __restrict__ blk_max,
-                                                       int* __restrict__ blk_idx) {
-    __shared__ float smax[256];
-    __shared__ int sidx[256];
-    const int tid = threadIdx.x, v = blockIdx.x * 256 + tid;
-    float s = -INFINITY;
-    if (v < n_vocab) {
-        s = bias[v];
-        for (int k = 0; k < Hp; ++k) s += h[k] * W[(long long)k * ldw + v];
-    }
-    smax[tid] = s; sidx[tid] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-            const float b = smax[tid + o];
-            const int bi = sidx[tid + o];
-            if (b > smax[tid] || (b == smax[tid] && bi < sidx[tid])) { smax[tid] = b; sidx[tid] = bi; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) { blk_max[blockIdx.x] = smax[0]; blk_idx[blockIdx.x] = sidx[0]; }
-}
-__global__ void k_decode_pick(const float* blk_max, const int* blk_idx, int nblk, int* out_token) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        float best = blk_max[0]; int bi = blk_idx[0];
-        for (int i = 1; i < nblk; ++i)
-            if (blk_max[i] > best || (blk_max[i] == best && blk_idx[i] < bi)) { best = blk_max[i]; bi = blk_idx[i]; }
-        *out_token = bi;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_token_prep(hipStream_t s, const int* support, int n_support, const int* query, int n_query,
@@ -1213,23 +1143,6 @@ hipError_t launch_unigram_nll(hipStream_t s, const int* words, long long n, cons
 }
 hipError_t launch_unigram_argmax(hipStream_t s, const unsigned* counts, int vocab, int* out) {
     hipLaunchKernelGGL(k_unigram_argmax, dim3(1), dim3(1024), 0, s, counts, vocab, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_decode_cell(hipStream_t s, const float* Kx, int in_dim, const float* Kh, const float* bias,
-                              const float* x, const float* h_in, float* h_out, float* c, int Hp) {
-    // h_in is read by every block while every block writes its units of h_out: they must differ
-    hipLaunchKernelGGL(k_decode_cell, dim3(Hp / 4), dim3(256), 0, s, Kx, in_dim, Kh, bias, x, h_in, h_out, c, Hp);
-    return hipGetLastError();
-}
-
-hipError_t launch_decode_argmax(hipStream_t s, const float* W, int ldw, const float* bias, const float* h,
-                                int Hp, int n_vocab, int* out_token, float* scratch) {
-    const int nblk = (n_vocab + 255) / 256;
-    float* blk_max = scratch;
-    int* blk_idx = reinterpret_cast<int*>(scratch + nblk);
-    hipLaunchKernelGGL(k_decode_logits, dim3(nblk), dim3(256), 0, s, W, ldw, bias, h, Hp, n_vocab, blk_max, blk_idx);
-    hipLaunchKernelGGL(k_decode_pick, dim3(1), dim3(64), 0, s, blk_max, blk_idx, nblk, out_token);
     return hipGetLastError();
 }
 

@@ -402,11 +402,6 @@ hipError_t launch_clock_probe(hipStream_t s, long long realtime_ticks, unsigned 
 hipError_t launch_unigram_update(hipStream_t s, const int* words, long long n, unsigned* counts, int vocab, int* err_flag);
 hipError_t launch_unigram_nll(hipStream_t s, const int* words, long long n, const unsigned* counts, int vocab, float* out, int* err_flag);
 hipError_t launch_unigram_argmax(hipStream_t s, const unsigned* counts, int vocab, int* out);
-// greedy decode step pieces (sample)
-hipError_t launch_decode_cell(hipStream_t s, const float* Kx, int in_dim, const float* Kh, const float* bias,
-                              const float* x, const float* h_in, float* h_out, float* c, int Hp);
-hipError_t launch_decode_argmax(hipStream_t s, const float* W, int ldw, const float* bias, const float* h,
-                                int Hp, int n_vocab, int* out_token, float* scratch);
 // batched sampling decode (decode.hip, fsmg_generate): no allocation, no synchronisation -- graph-capturable.
 // One LSTM layer at one position for B rows: layer 0 (emb != nullptr) gathers x from the embedding rows tok[r * ldtok + pos];
 // other layers read x [B][Hp].  h_in / h_out / c are [B][Hp]; in_dim and Hp multiples of 16.
@@ -415,16 +410,17 @@ hipError_t launch_gen_cell(hipStream_t s, const float* Kx, int in_dim, const flo
 // logits [B][ldl] = h [B][Hp] . W [Hp][ldw] + bias, the first ncols columns
 hipError_t launch_gen_logits(hipStream_t s, const float* W, int ldw, const float* bias, int ncols, const float* h, int Hp, int B,
                              float* logits, int ldl);
-// per row b: Gumbel-max draw of generated token t (temperature, top_k, Philox key = seed) -> tok[b * ldtok + pos_out],
-// out_tok[b * num + t], out_lp[b * num + t] = logit - logsumexp
-hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, uint64_t seed, int t,
-                           int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num);
-// launch_gen_pick with the sampling filters (fsmg_generate_filtered): repetition penalty theta (1 = off) over the distinct ids of
-// tok[b][max(1, pos_out - window) .. pos_out - 1] (window 0: from 1), then top_k, min_p (0 = off), top_p (0 or >= 1 = off).
-// ncols above 2^20 with a penalty: hipErrorInvalidValue (the presence bitmap of an unstaged row lives in LDS).
-hipError_t launch_gen_pick_filtered(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, float top_p,
-                                    float min_p, float theta, int window, uint64_t seed, int t, int* tok, int ldtok, int pos_out, int* out_tok,
-                                    float* out_lp, int num);
+// the sampling filters of fsmg_generate_filtered: repetition penalty theta (1 = off) over the distinct ids of
+// tok[b][max(1, pos_out - window) .. pos_out - 1] (window 0: from 1), then min_p (0 = off), top_p (0 or >= 1 = off)
+struct GenFilters {
+    float top_p, min_p, theta;
+    int window;
+};
+// per row b: Gumbel-max draw of generated token t (temperature, top_k, filters f, Philox key = seed) -> tok[b * ldtok + pos_out],
+// out_tok[b * num + t], out_lp[b * num + t] = logit - logsumexp.  f == nullptr: no filters (k_gen_pick).  ncols above 2^20 with a
+// penalty: hipErrorInvalidValue (the presence bitmap of an unstaged row lives in LDS).
+hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, const GenFilters* f,
+                           uint64_t seed, int t, int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num);
 // tok rows [start, primer[b / rows_per_primer][0..P-1]]; *err |= 1 for a primer id outside [0, vocab)
 hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err,
                              int rows_per_primer = 1);

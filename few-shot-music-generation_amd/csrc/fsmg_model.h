@@ -1,6 +1,6 @@
 // Host-side internals of libfsmg shared by the api_*.hip translation units: the model handle, its HBM layout, the helpers every
 // C entry point uses.  Nothing here is exported; include/fsmg.h is the public surface, fsmg_kernels.h the launcher interface.
-//   api_handle.hip    fsmg_create / fsmg_destroy, knobs, statistics, greedy decode
+//   api_handle.hip    fsmg_create / fsmg_destroy, knobs, statistics
 //   api_layout.hip    padded parameter layout, host <-> device tensor transfers, parameter / optimizer-state entry points
 //   api_scratch.hip   activation scratch sizing, split-K policy
 //   api_schedule.hip  which kernel and which order a pass takes (choose_schedule, the XCD-partitioned gate / queue), gemm()
@@ -8,6 +8,7 @@
 //   api_update.hip    clip + Adam, inner-loop SGD, time-out bookkeeping, loss read-back
 //   api_step.hip      train / eval / MAML-style entry points          api_comm.hip  RCCL glue (fsmg_comm_*)
 //   api_unigram.hip   unigram baseline                                 api_debug.hip debug reads, timers, clock probe
+//   api_decode.hip    decoding: fsmg_generate(_filtered), fsmg_beam_search, their MAML twins, fsmg_sample (one driver)
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
@@ -206,9 +207,7 @@ struct fsmg_model {
     std::map<std::string, hipGraphExec_t> graphs;
     struct LaunchCounts { int64_t xcd = 0, persist = 0, step = 0; bool bwd_xcd = false; };   // bwd_xcd: what last_bwd_xcd was when the capture ended
     std::map<std::string, LaunchCounts> graph_counts;   // recurrent launches one replay of a graph stands for (fsmg_get_stats)
-    // decode
-    float* dec = nullptr;
-    // batched generation (fsmg_generate): its own scratch, grown between calls after a stream sync
+    // decoding (api_decode.hip): its own scratch, grown between calls after a stream sync
     char* gen = nullptr;
     size_t gen_bytes = 0;
 
@@ -610,20 +609,8 @@ int restore_theta(fsmg_model* h);
 void on_timeout(fsmg_model* h);
 void on_softmax_range(fsmg_model* h);
 inline bool is_retry(int rc) { return rc == FSMG_ERR_TIMEOUT || rc == FSMG_ERR_SOFTMAX_RANGE; }
-// ------------------------------------------------------------------ batched generation (api_generate.hip)
-// fsmg_generate's work at the parameters the handle holds now (no BEGIN_CALL: fsmg_maml_generate calls it at theta')
-// f: the sampling filters (fsmg_generate_filtered; nullptr or neutral: fsmg_generate's pick, unchanged)
-int generate_core(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens, float* out_logprob,
-                  const fsmg_gen_filters* f = nullptr);
-int check_gen_config(fsmg_model* h, const fsmg_gen_config* g, const int32_t* primer, int32_t* out_tokens);
-int check_gen_filters(fsmg_model* h, const fsmg_gen_filters* f);
-bool gen_filters_neutral(const fsmg_gen_filters* f);
-// h->gen holds at least `bytes` (the generation / beam-search scratch; each call lays it out its own way)
-int gen_reserve(fsmg_model* h, size_t bytes);
-// ------------------------------------------------------------------ beam search (api_beam.hip)
-int beam_core(fsmg_model* h, const fsmg_beam_config* b, const int32_t* primer, int32_t* out_tokens, float* out_scores, float* out_logprob);
-int check_beam_config(fsmg_model* h, const fsmg_beam_config* b, const int32_t* primer, int32_t* out_tokens, float* out_scores);
-// adapt on the support rows like fsmg_maml_eval, run `at_theta_prime` there, restore theta whatever happened (api_step.hip)
+// adapt on the support rows like fsmg_maml_eval, run `at_theta_prime` there, restore theta whatever happened (api_step.hip; the MAML
+// decode entry points in api_decode.hip)
 int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
                        int32_t support_on_device, const std::function<int()>& at_theta_prime);
 int poll_skipped(fsmg_model* h);

@@ -465,17 +465,30 @@ class FsmgModel(object):
                              temperature=float(temperature), top_k=int(top_k), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
                              primer_on_device=int(primer_on_device))
 
-    def _gen_args(self, n_seq, num, temperature, top_k, seed, primer):
+    @staticmethod
+    def _primer(primer, rows, what):
+        """primer [rows, P] (or one [P] row for all), or (device address, P) -> (P, on_device, pointer, keepalive)"""
         if primer is None:
-            return self.gen_config(n_seq, num, temperature, top_k, seed), None, None
+            return 0, 0, None, None
         if isinstance(primer, tuple):                 # (device address, primer_len)
-            return self.gen_config(n_seq, num, temperature, top_k, seed, int(primer[1]), 1), C.c_void_p(int(primer[0])), None
+            return int(primer[1]), 1, C.c_void_p(int(primer[0])), None
         a = np.ascontiguousarray(primer, dtype=np.int32)
         if a.ndim == 1:
-            a = np.ascontiguousarray(np.broadcast_to(a, (int(n_seq), a.size)))
-        if a.ndim != 2 or a.shape[0] != int(n_seq):
-            raise ValueError('primer must be [n_seq, P] (or one [P] row for every sequence), got %r' % (a.shape,))
-        return self.gen_config(n_seq, num, temperature, top_k, seed, a.shape[1]), C.c_void_p(a.ctypes.data), a
+            a = np.ascontiguousarray(np.broadcast_to(a, (int(rows), a.size)))
+        if a.ndim != 2 or a.shape[0] != int(rows):
+            raise ValueError('primer must be [%s, P] (or one [P] row for every %s), got %r' % (what[0], what[1], a.shape))
+        return a.shape[1], 0, C.c_void_p(a.ctypes.data), a
+
+    def _support(self, support, n_support_rows):
+        """support [rows, max_len] (numpy), or a device address with n_support_rows -> (pointer, rows, on_device, keepalive)"""
+        if isinstance(support, (int, np.integer)):
+            return C.c_void_p(int(support)), int(n_support_rows), 1, None
+        s = np.ascontiguousarray(support, dtype=np.int32).reshape(-1, self.max_len)
+        return C.c_void_p(s.ctypes.data), s.shape[0], 0, s
+
+    def _gen_args(self, n_seq, num, temperature, top_k, seed, primer):
+        P, on_device, pp, keep = self._primer(primer, n_seq, ('n_seq', 'sequence'))
+        return self.gen_config(n_seq, num, temperature, top_k, seed, P, on_device), pp, keep
 
     @staticmethod
     def gen_filters(top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
@@ -485,40 +498,32 @@ class FsmgModel(object):
         return FsmgGenFilters(version=FSMG_GEN_FILTERS_VERSION, top_p=float(top_p), min_p=float(min_p),
                               repetition_penalty=float(repetition_penalty), repeat_window=int(repeat_window))
 
+    def _generate(self, adapt, n_seq, num, temperature, top_k, seed, primer, logprobs, filters):
+        """fsmg_generate (adapt = ()) or fsmg_maml_generate (adapt = its support arguments), the _filtered entry point when a
+        filter is on"""
+        g, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
+        f = self.gen_filters(*filters)
+        toks = np.empty((int(n_seq), int(num)), np.int32)
+        lp = np.empty((int(n_seq), int(num)), np.float32) if logprobs else None
+        name = ('fsmg_maml_generate' if adapt else 'fsmg_generate') + ('' if f is None else '_filtered')
+        head = (C.byref(g),) if f is None else (C.byref(g), C.byref(f))
+        self._ck(getattr(self._lib, name)(self._h, *head, *adapt, pp, toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None))
+        return (toks, lp) if logprobs else toks
+
     def generate(self, n_seq, num, temperature=1.0, top_k=0, seed=0, primer=None, logprobs=False, top_p=0.0, min_p=0.0,
                  repetition_penalty=1.0, repeat_window=0):
         """n_seq independent samples of num tokens -> int32 [n_seq, num] (, float32 [n_seq, num] log-probs with logprobs=True).
         primer: int32 [n_seq, P] (or [P] for every row) continued by each row, or (device address, P).  top_p, min_p,
         repetition_penalty, repeat_window: the sampling filters of fsmg_generate_filtered (all off: fsmg_generate)."""
-        g, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
-        f = self.gen_filters(top_p, min_p, repetition_penalty, repeat_window)
-        toks = np.empty((int(n_seq), int(num)), np.int32)
-        lp = np.empty((int(n_seq), int(num)), np.float32) if logprobs else None
-        outs = (pp, toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None)
-        if f is None:
-            self._ck(self._lib.fsmg_generate(self._h, C.byref(g), *outs))
-        else:
-            self._ck(self._lib.fsmg_generate_filtered(self._h, C.byref(g), C.byref(f), *outs))
-        return (toks, lp) if logprobs else toks
+        return self._generate((), n_seq, num, temperature, top_k, seed, primer, logprobs,
+                              (top_p, min_p, repetition_penalty, repeat_window))
 
     def maml_generate(self, support, num, inner_steps, inner_lr, n_seq=1, temperature=1.0, top_k=0, seed=0, primer=None,
                       logprobs=False, n_support_rows=None, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
         """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), generate at theta', restore theta"""
-        if isinstance(support, (int, np.integer)):
-            sp, dev, _k1, rows = C.c_void_p(int(support)), 1, None, int(n_support_rows)
-        else:
-            s = np.ascontiguousarray(support, dtype=np.int32).reshape(-1, self.max_len)
-            sp, dev, _k1, rows = C.c_void_p(s.ctypes.data), 0, s, s.shape[0]
-        g, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
-        f = self.gen_filters(top_p, min_p, repetition_penalty, repeat_window)
-        toks = np.empty((int(n_seq), int(num)), np.int32)
-        lp = np.empty((int(n_seq), int(num)), np.float32) if logprobs else None
-        args = (sp, rows, int(inner_steps), float(inner_lr), dev, pp, toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None)
-        if f is None:
-            self._ck(self._lib.fsmg_maml_generate(self._h, C.byref(g), *args))
-        else:
-            self._ck(self._lib.fsmg_maml_generate_filtered(self._h, C.byref(g), C.byref(f), *args))
-        return (toks, lp) if logprobs else toks
+        sp, rows, dev, _keep = self._support(support, n_support_rows)
+        return self._generate((sp, rows, int(inner_steps), float(inner_lr), dev), n_seq, num, temperature, top_k, seed, primer,
+                              logprobs, (top_p, min_p, repetition_penalty, repeat_window))
 
     # -- batched on-device beam search (include/fsmg.h fsmg_beam_search) ----------------------------------------
     @staticmethod
@@ -526,48 +531,29 @@ class FsmgModel(object):
         return FsmgBeamConfig(version=FSMG_BEAM_CONFIG_VERSION, n_groups=int(n_groups), beam_width=int(beam_width), num=int(num),
                               primer_len=int(primer_len), primer_on_device=int(primer_on_device))
 
-    def _beam_args(self, n_groups, beam_width, num, primer):
-        if primer is None:
-            return self.beam_config(n_groups, beam_width, num), None, None
-        if isinstance(primer, tuple):                 # (device address, primer_len)
-            return self.beam_config(n_groups, beam_width, num, int(primer[1]), 1), C.c_void_p(int(primer[0])), None
-        a = np.ascontiguousarray(primer, dtype=np.int32)
-        if a.ndim == 1:
-            a = np.ascontiguousarray(np.broadcast_to(a, (int(n_groups), a.size)))
-        if a.ndim != 2 or a.shape[0] != int(n_groups):
-            raise ValueError('primer must be [n_groups, P] (or one [P] row for every group), got %r' % (a.shape,))
-        return self.beam_config(n_groups, beam_width, num, a.shape[1]), C.c_void_p(a.ctypes.data), a
-
-    def _beam_outputs(self, n_groups, beam_width, num, logprobs):
+    def _beam_search(self, adapt, num, beam_width, n_groups, primer, logprobs):
+        """fsmg_beam_search (adapt = ()) or fsmg_maml_beam_search (adapt = its support arguments)"""
+        P, on_device, pp, _keep = self._primer(primer, n_groups, ('n_groups', 'group'))
+        b = self.beam_config(n_groups, beam_width, num, P, on_device)
         G, W, num = int(n_groups), int(beam_width), int(num)
         toks = np.empty((G, W, num), np.int32)
         scores = np.empty((G, W), np.float32)
         lp = np.empty((G, W, num), np.float32) if logprobs else None
-        return toks, scores, lp
+        fn = self._lib.fsmg_maml_beam_search if adapt else self._lib.fsmg_beam_search
+        self._ck(fn(self._h, C.byref(b), *adapt, pp, toks.ctypes.data_as(_I32P), _f32p(scores), _f32p(lp) if logprobs else None))
+        return (toks, scores, lp) if logprobs else (toks, scores)
 
     def beam_search(self, num, beam_width, n_groups=1, primer=None, logprobs=False):
         """n_groups independent beam searches of width beam_width, num tokens each -> tokens int32 [G, W, num], scores float32
         [G, W] (, log-probs float32 [G, W, num] with logprobs=True), each group's hypotheses best first.  primer: int32 [G, P]
         (or [P] for every group) continued by every hypothesis of its group, or (device address, P)."""
-        b, pp, _keep = self._beam_args(n_groups, beam_width, num, primer)
-        toks, scores, lp = self._beam_outputs(n_groups, beam_width, num, logprobs)
-        self._ck(self._lib.fsmg_beam_search(self._h, C.byref(b), pp, toks.ctypes.data_as(_I32P), _f32p(scores),
-                                            _f32p(lp) if logprobs else None))
-        return (toks, scores, lp) if logprobs else (toks, scores)
+        return self._beam_search((), num, beam_width, n_groups, primer, logprobs)
 
     def maml_beam_search(self, support, num, inner_steps, inner_lr, beam_width, n_groups=1, primer=None, logprobs=False,
                          n_support_rows=None):
         """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), beam search at theta', restore theta"""
-        if isinstance(support, (int, np.integer)):
-            sp, dev, _k1, rows = C.c_void_p(int(support)), 1, None, int(n_support_rows)
-        else:
-            s = np.ascontiguousarray(support, dtype=np.int32).reshape(-1, self.max_len)
-            sp, dev, _k1, rows = C.c_void_p(s.ctypes.data), 0, s, s.shape[0]
-        b, pp, _keep = self._beam_args(n_groups, beam_width, num, primer)
-        toks, scores, lp = self._beam_outputs(n_groups, beam_width, num, logprobs)
-        self._ck(self._lib.fsmg_maml_beam_search(self._h, C.byref(b), sp, rows, int(inner_steps), float(inner_lr), dev, pp,
-                                                 toks.ctypes.data_as(_I32P), _f32p(scores), _f32p(lp) if logprobs else None))
-        return (toks, scores, lp) if logprobs else (toks, scores)
+        sp, rows, dev, _keep = self._support(support, n_support_rows)
+        return self._beam_search((sp, rows, int(inner_steps), float(inner_lr), dev), num, beam_width, n_groups, primer, logprobs)
 
     def read_losses(self, n):
         out = np.empty(n, np.float32)

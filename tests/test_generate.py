@@ -92,9 +92,11 @@ def test_greedy_rows_equal_fsmg_sample():
     cfg = small_config(input_size=97, max_len=12, embedding_size=12, hidden_size=48, n_layers=2)
     m = _trained(cfg)
     want = m.sample(24)
-    toks = m.generate(5, 24, temperature=0.0)
+    toks, lps = m.generate(5, 24, temperature=0.0, logprobs=True)
     for b in range(5):
         assert list(toks[b]) == want
+    # fsmg_sample is the driver's one-row greedy case: the greedy rows also stand against the fp64 decoder
+    R.check_margins(f64_params(m), cfg, toks, lps, temperature=0.0, top_k=0, seed=0)
 
 
 def test_determinism_and_row_independence():

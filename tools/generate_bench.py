@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Tokens/s of fsmg_generate (batched on-device sampling) at cfg-B and cfg-C dims against fsmg_sample (the greedy host loop)
-on the same handle.  Prints one line per case and one JSON line per case (--json FILE also writes them to a file).
+"""Tokens/s of fsmg_generate (batched on-device sampling) at cfg-B and cfg-C dims against fsmg_sample (the same driver at one
+greedy row) on the same handle.  Prints one line per case and one JSON line per case (--json FILE also writes them to a file).
 
   python tools/generate_bench.py [--num 256] [--reps 5] [--configs cfg-B,cfg-C] [--json profiles/generate_bench.jsonl]
 
