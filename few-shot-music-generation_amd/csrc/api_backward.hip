@@ -60,9 +60,9 @@ int backward(fsmg_model* h, int B, int part) {
     const Lane mainl = main_lane(h);
     hipStream_t s = h->stream;
     const bool ov = use_overlap(h);
-    const bool xcd = use_xcd(h, B, true) && h->persist_bwd;
-    const bool rs = !xcd && h->persist && h->persist_bwd && h->inbox != nullptr && lstm_bwd_rs_supported(B, Hp) && lstm_bwd_rs_inbox_floats(B, Hp) <= h->inbox_floats;
-    const bool chain = xcd || rs || (h->persist && h->persist_bwd && h->dzF_all != nullptr && lstm_bwd_chain_supported(B, Hp) &&
+    const bool xcd = use_xcd(h, B, true);
+    const bool rs = !xcd && h->persist && h->inbox != nullptr && lstm_bwd_rs_supported(B, Hp) && lstm_bwd_rs_inbox_floats(B, Hp) <= h->inbox_floats;
+    const bool chain = xcd || rs || (h->persist && h->dzF_all != nullptr && lstm_bwd_chain_supported(B, Hp) &&
                               (int64_t)T * ((B + 15) / 16 * 16) * G4 <= h->dzfa_floats);
     if (!xcd && h->cs_stale) return fail(h, FSMG_ERR_STATE, "internal: backward pass on the column-split kernels with stale fragment copies of K_h (ensure_cs not called)");
     const int nch = ov ? (chain ? h->nchunk_persist : h->nchunk) : 1;
@@ -85,7 +85,6 @@ int backward(fsmg_model* h, int B, int part) {
     // weight- / input-gradient GEMMs of the bottom layer, the embedding gradient and the norm
     const bool cut_late = cut && h->dp_split == 2 && part != 0;
     bool dx_sq_done = false, top_fills_done = false;
-    PHASE(3);
     // Slab sums of the split-K GEMMs ride in two launches per pass instead of one each: `fills` (issued right in front of a
     // recurrent chain: what the chain reads -- dH -- plus the fills) and `late` (in front of the embedding gradient: every
     // weight gradient + dx with its squared-norm partials).  Only the order that runs start to end on one stream in one call
@@ -127,7 +126,7 @@ int backward(fsmg_model* h, int B, int part) {
         HIPCK(h, hipEventRecord(h->ev_join, h->aux));
     } else {
         GEMMCK(dhout_chunk(h, mainl, B, 0, T, d_now));
-        if (defer_ok && !h->fills_late) {     // dH's slab sum + the top chain's fills go out in front of dW: the chain starts right behind a GEMM
+        if (defer_ok) {     // dH's slab sum + the top chain's fills go out in front of dW: the chain starts right behind a GEMM
             GEMMCK(bptt_fills(h, fills, B, xcd, rs, chain, 0));
             GEMMCK(fills.flush());
             top_fills_done = true;
@@ -178,7 +177,6 @@ int backward(fsmg_model* h, int B, int part) {
         const bool skip_chain = part == 2 && cut_late;                      // layer 0: its chain ran in part 1
         if (!skip_chain) {
         if (top && ov) HIPCK(h, hipStreamWaitEvent(s, h->ev_chunk[nch - 1], 0));
-        PHASE(4);
         const bool packed = xov && (top || pend_on);      // this layer's chain sits on the first XCDs only
         if (!(top && top_fills_done)) {
             GEMMCK(bptt_fills(h, fills, B, xcd, rs, chain, packed ? rpx : 0));
@@ -257,7 +255,6 @@ int backward(fsmg_model* h, int B, int part) {
         }   // !skip_chain
         if (part == 1 && cut_late && l == 0) return FSMG_OK;                // bucket 0 travels beside what follows
         const int in_p = h->in_dim[l];
-        PHASE(5);
         // dK_l (weight gradient) and dx_l (input gradient) contract the same dZ and do not depend on each other.  Layer 0 with the tail
         // moved aside: dx first, so that its slab sum, the embedding gradient and the other deferred sums run on the auxiliary stream
         // beside the dK GEMM (below); everywhere else dK first (the layer below waits for dx only).
@@ -358,7 +355,6 @@ int backward(fsmg_model* h, int B, int part) {
     }
     if (!aside) GEMMCK(tail_kernels(s));
     if (ov) HIPCK(h, hipStreamWaitEvent(s, h->ev_join, 0));     // dW / dd landed
-    PHASE(6);
     h->have_grads = true;
     return FSMG_OK;
 }

@@ -118,23 +118,6 @@ int xov_selfcheck(fsmg_model* h, int B) {
     return FSMG_OK;
 }
 
-// FSMG_FILL_EARLY=1 (A/B): the hand-off fills of a layer's forward chain in front of its x-part GEMM instead of right in front of
-// the chain, so that the chain does not start on an L2 full of fill lines
-int chain_fills_early(fsmg_model* h, OpBatch& fills, int l, int B, bool chain, bool xcd, int xov_words) {
-    const int T = h->T, Hp = h->Hp;
-    const size_t Bp16 = (size_t)(B + 15) / 16 * 16;
-    if (chain) GEMMCK(fills.add(h->HF[l] + Bp16 * Hp, 0xFFFFFFFFu, (long long)T * Bp16 * Hp));
-    if (xcd) {
-        GEMMCK(fills.add(h->tickets, 0u, (long long)8 * fsmg_model::TICKET_LAUNCHES));
-        h->ticket_next = 0;
-        const long long step_f = lstm_xcd_hx_floats(B, 0, Hp, h->xcd_bx3);
-        GEMMCK(fills.add(h->HX, 0u, step_f));
-        GEMMCK(fills.add(h->HX + step_f, 0xFFFFFFFFu, step_f * T));
-        if (xov_words > 0) GEMMCK(fills.add(h->xov_ctl, 0u, xov_words));
-    }
-    return fills.flush();
-}
-
 int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_out, bool want_dlogits) {
     ScopedRange rng_(want_dlogits ? "fsmg.forward(train)" : "fsmg.forward(eval)");
     const int T = h->T, Hp = h->Hp, G4 = h->G4;
@@ -142,43 +125,28 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
     const Lane mainl = main_lane(h);
     hipStream_t s = h->stream;
     const bool ov = use_overlap(h);
-    const bool xcd = use_xcd(h, B) && h->persist_fwd;
-    const bool chain1 = !xcd && h->persist && h->persist_fwd && !h->force_fwd_rt && lstm_fwd_chain_supported(B, Hp);
-    const bool chain_rt = !xcd && h->persist && h->persist_fwd && !chain1 && lstm_fwd_chain_rt_supported(B, Hp);   // all row tiles per block
+    const bool xcd = use_xcd(h, B);
+    const bool chain1 = !xcd && h->persist && !h->force_fwd_rt && lstm_fwd_chain_supported(B, Hp);
+    const bool chain_rt = !xcd && h->persist && !chain1 && lstm_fwd_chain_rt_supported(B, Hp);   // all row tiles per block
     const bool chain = chain1 || chain_rt;
     if (!xcd && h->cs_stale) return fail(h, FSMG_ERR_STATE, "internal: forward pass on the column-split kernels with stale fragment copies of K_h (ensure_cs not called)");
     const int nch_ov = ov ? ((chain || xcd) ? h->nchunk_persist : h->nchunk) : 1;
     // XCD-partitioned schedule: the chain packed on the first XCDs publishes the time steps it has finished, the projection's
     // row tiles are drawn by the other XCDs as their rows arrive (and by the whole chip once the chain is over)
-    // The queue takes the rows of the time steps [0, t_cut); the last few steps' rows (complete only when the chain is) go to a
-    // chip-wide launch of the 128-tile kernel behind it: a 256 x 256 tile is 85 us of latency with 1/6 of the CUs busy, the same
-    // rows as 128 x 128 tiles are one under-full round of ~40 us (same bits: the kernels share k order and term order, K = H is never split)
-    // (t_cut is a multiple of the publishing period: the queue's last row tile then waits for a step that IS published)
-    const int t_cut = (T >= 4 * h->xov_tail && h->xov_tail > 0) ? (T - h->xov_tail) / h->xov_pub * h->xov_pub : T;
-    GemmArgs ghead = logits_args(h, B, 0, t_cut);
+    GemmArgs ghead = logits_args(h, B, 0, T);
     // Fused softmax: where dlogits would be written in place, nothing overlaps on a second stream chunk by chunk, and the weight
     // gradient of the projection runs on the 256 x 256-tile kernel (the one with weighted column sums).  The projection itself may be
     // any of the bf16-split kernels: they share the epilogue (store_tile_at) and the layout of the partials.
     h->fs_call = false;
-    if (want_dlogits && h->fused_softmax && !ov && h->bx3 && h->inplace_dlogits && h->Hsc != nullptr && t_cut == T && mainl.lds_pad == 0) {
+    if (want_dlogits && h->fused_softmax && !ov && h->bx3 && h->inplace_dlogits && h->Hsc != nullptr && mainl.lds_pad == 0) {
         h->fs_call = true;                   // (dw_args reads it)
         h->fs_call = use_h_gemm(h, OP_XC, OP_XC, dw_args(h, B), mainl);
     }
     if (h->fs_call) fused_softmax_args(h, ghead);
     const bool xov = h->xov_call && (h->xov_parts & 1) && xcd && want_dlogits && !ov && xov_fits(ghead);
-#ifdef FSMG_EXPERIMENTS
-    // the cross entropy under the pair's tail (fsmg_model::ce_tail, measured and rejected): not in a pass that self-checks the logits first
-    const int tiles_m = (int)((rows + 255) / 256);
-    const bool ce_tail = xov && !h->fs_call && h->ce_tail && h->aux2 != nullptr && h->xov_selfcheck_left <= 0 && t_cut == T && !h->timing &&
-                         h->V1p <= 12 * 1024 && tiles_m < fsmg_model::XOV_DONE;      // (the last word of xov_done is the row counter)
-    if (ce_tail) ghead.done = h->xov_done;
-#else
-    constexpr bool ce_tail = false;
-#endif
     const int xfree = xov_first_free(B, Hp);
     const int rpx = xov ? lstm_xcd16_packed_rows(B, Hp) : 0;
     if (xov) xov_gate(h, ghead, B);
-    PHASE(0);
     for (int l = 0; l < h->L; ++l) {
         const size_t Bp16 = (size_t)(B + 15) / 16 * 16;
         const bool top = l == h->L - 1;
@@ -186,7 +154,6 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
         GEMMCK(fills.add(h->Hs[l], 0u, (long long)B * Hp));
         GEMMCK(fills.add(h->Cs[l], 0u, (long long)B * Hp));
         if (!xcd) GEMMCK(fills.add(h->HF[l], 0u, (long long)Bp16 * Hp));
-        if (h->fill_early && !xov) GEMMCK(chain_fills_early(h, fills, l, B, chain, xcd, 0));
         {
             ScopedTimer tm(h, "gemm_zx");
             GemmArgs g{};
@@ -197,7 +164,6 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
             g.bias = h->P + h->off_b[l]; g.ksplit = 1;
             GEMMCK(gemm(h, mainl, OP_KC, OP_XC, g));
         }
-        PHASE(1);
         auto chain_fills = [&]() -> int {
             if (chain)       // "not written yet" fill pattern of the h fragments of time indices 1..T (index 0 is the zero state)
                 GEMMCK(fills.add(h->HF[l] + Bp16 * Hp, 0xFFFFFFFFu, (long long)T * Bp16 * Hp));
@@ -210,12 +176,11 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
                 if (xov && top) {
                     GEMMCK(fills.add(h->xov_ctl, 0u, 4 + gemm_items(ghead)));
                     GEMMCK(fills.add(h->xov_prog, 0u, T));
-                    if (ce_tail) GEMMCK(fills.add(h->xov_done, 0u, fsmg_model::XOV_DONE));
                 }
             }
             return fills.flush();
         };
-        if (!h->fill_early || xov) GEMMCK(chain_fills());
+        GEMMCK(chain_fills());
         // the softmax half of the previous update may still be running on the auxiliary stream (apply_update): what has been issued
         // so far -- token_prep, the bottom layer's x-part GEMM, the fills -- reads none of it; everything from here on may
         if (l == 0) GEMMCK(settle_pending(h));
@@ -233,9 +198,6 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
                 ScopedTimer tm(h, "lstm_fwd");
                 LstmFwdXcdArgs a{};
                 a.rpx = (xov && top) ? rpx : 0; a.progress = (xov && top) ? h->xov_prog : nullptr; a.Hp = Hp;
-#ifdef FSMG_EXPERIMENTS
-                { const int dbg = xov_debug(); a.progress_lag = ((dbg & 2) ? 2 : 0) | ((dbg & 256) ? 256 : 0); if ((dbg & 128) && (dbg & 1)) a.progress = nullptr; }
-#endif
                 a.progress_every = h->xov_pub; a.bx3 = h->xcd_bx3 ? 1 : 0;
                 a.variant = h->xcd_variant >= 0 ? h->xcd_variant : lstm_xcd_default_variant(B, true, Hp, a.rpx, h->xcd_bx3);
                 a.KhX = h->khx + (size_t)(2 * l) * lstm_xcd_weight_floats((int)Hp, h->xcd_bx3); a.HX = h->HX; a.Z = h->Z[l]; a.Cs = h->Cs[l]; a.Hs = h->Hs[l];
@@ -272,35 +234,13 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
             }
         }
     }
-    PHASE(2);
     if (ov) {
         HIPCK(h, hipEventRecord(h->ev_join, h->aux));
         HIPCK(h, hipStreamWaitEvent(s, h->ev_join, 0));
     } else if (xov) {
         {
             ScopedTimer tm(h, "gemm_logits");      // (what is left of the queue when the chain is over, on the whole chip)
-            if (t_cut < T) {       // the last steps' rows as 128 x 128 tiles (three blocks per CU): they fit the XCDs the chain has just left,
-                GemmArgs gt = logits_args(h, B, t_cut, T);      // beside the queue's tiles still in flight on the others
-                gt.bx3 = 1; gt.ksplit = 1;
-                HIPCK(h, launch_gemm(s, OP_KC, OP_XC, gt, 0));
-            }
-#ifdef FSMG_EXPERIMENTS
-            if (ce_tail) {         // the gated cross entropy starts when the chain is over, beside what is left of the queue
-                HIPCK(h, hipEventRecord(h->ev_ce_fork, s));
-                HIPCK(h, hipStreamWaitEvent(h->aux2, h->ev_ce_fork, 0));
-            }
-#endif
             GEMMCK(gemm_cleanup(h, s, OP_KC, OP_XC, ghead, h->xov_ctl));
-#ifdef FSMG_EXPERIMENTS
-            if (ce_tail) {
-                const int tiles_n = (h->V1p + 255) / 256;
-                HIPCK(h, launch_ce_rows_gated(h->aux2, h->logits, h->V1p, (int)rows, h->V1, h->Y, h->lse, h->ce, dlogits_buf(h),
-                                              (float)(1.0 / ((double)rows + 1e-12)), h->xov_done, tiles_n, 256, h->d_err,
-                                              h->chain_spin_limit > 0 ? 200000 : 0, h->ce_tail_blocks, h->xov_done + fsmg_model::XOV_DONE - 1));
-                HIPCK(h, hipEventRecord(h->ev_ce, h->aux2));
-                HIPCK(h, hipStreamWaitEvent(s, h->ev_ce, 0));
-            }
-#endif
             HIPCK(h, hipStreamWaitEvent(s, h->ev_join, 0));    // the restricted launch and its tiles in flight
         }
         // ... and one pass in every `xov_selfcheck_every` (1000: ~0.4 ms per 1.6 s of training, 0.03 %) for the handle's whole life: the
@@ -310,7 +250,7 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
         if (h->xov_selfcheck_every > 0 && h->xov_selfcheck_left <= 0 && h->xov_passes % h->xov_selfcheck_every == 0) h->xov_selfcheck_left = 1;
         if (h->xov_selfcheck_left > 0) GEMMCK(xov_selfcheck(h, B));
         if (h->fs_call) GEMMCK(ce_finish(h, s, B, rows));
-        else if (!ce_tail) GEMMCK(ce_rows(h, s, B, 0, T, rows));
+        else GEMMCK(ce_rows(h, s, B, 0, T, rows));
     } else if (h->fs_call) {
         {
             ScopedTimer tm(h, "gemm_logits");                                  // the kernel the shape would get anyway (K = Hp: never split)

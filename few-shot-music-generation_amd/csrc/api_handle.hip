@@ -199,30 +199,6 @@ int fsmg_create(const fsmg_config* cfg, fsmg_handle* out) {
         if (const char* e = std::getenv("FSMG_CHAIN_SPIN_LIMIT")) h->chain_spin_limit = std::max(0, std::atoi(e));
         if (const char* e = std::getenv("FSMG_XCD_VARIANT")) h->xcd_variant = std::atoi(e);      // XCD_* bits, both directions (tests: the non-default paths)
         if (const char* e = std::getenv("FSMG_XCD_VARIANT_BWD")) h->xcd_variant_bwd = std::atoi(e);
-#ifdef FSMG_EXPERIMENTS         // settled A/Bs: tuning values and rejected alternatives, experiment builds only
-        if (const char* e = std::getenv("FSMG_CE_TAIL")) h->ce_tail = (e[0] != '0');
-        if (const char* e = std::getenv("FSMG_CE_TAIL_BLOCKS")) h->ce_tail_blocks = std::max(1, std::min(4096, std::atoi(e)));
-        if (const char* e = std::getenv("FSMG_XOV_DW_SPLIT")) h->xov_dw_split = std::max(1, std::atoi(e));
-        if (const char* e = std::getenv("FSMG_XOV_PUB")) h->xov_pub = std::max(1, std::min(64, std::atoi(e)));
-        if (const char* e = std::getenv("FSMG_FILL_EARLY")) h->fill_early = (e[0] != '0');
-        if (const char* e = std::getenv("FSMG_FILLS_LATE")) h->fills_late = (e[0] != '0');
-        if (const char* e = std::getenv("FSMG_XOV_TAIL")) h->xov_tail = std::max(0, std::min(64, std::atoi(e)));
-        if (const char* e = std::getenv("FSMG_BWD_RS")) h->bwd_rs = (e[0] != '0');
-        if (const char* e = std::getenv("FSMG_DP_SPLIT")) h->dp_split = std::max(0, std::min(2, std::atoi(e)));
-        if (const char* e = std::getenv("FSMG_XCD_MAX_ROWS")) h->xcd_max_rows = std::max(1, std::min(128, std::atoi(e)));
-        if (const char* e = std::getenv("FSMG_PERSIST_FWD")) h->persist_fwd = (e[0] != '0');
-        if (const char* e = std::getenv("FSMG_PERSIST_BWD")) h->persist_bwd = (e[0] != '0');
-        if (const char* e = std::getenv("FSMG_NCHUNK")) h->nchunk = h->nchunk_persist = std::max(1, std::min((int)fsmg_model::NCHUNK, std::atoi(e)));
-        if (const char* e = std::getenv("FSMG_CHUNK_STEPS")) {      // e.g. "12,36,34,34,12": must add up to max_len
-            std::vector<int> edges{0};
-            for (const char* p = e; *p;) { edges.push_back(edges.back() + std::max(1, std::atoi(p))); while (*p && *p != ',') ++p; if (*p) ++p; }
-            if (edges.back() == h->T && (int)edges.size() - 1 <= (int)fsmg_model::NCHUNK) {
-                h->chunk_edges = edges;
-                h->nchunk = h->nchunk_persist = (int)edges.size() - 1;
-            }
-        }
-        if (const char* e = std::getenv("FSMG_AUX_BLOCKS")) { h->aux_blocks_per_cu = h->aux_blocks_persist = std::max(1, std::min(4, std::atoi(e))); h->aux_blocks_from_env = true; }
-#endif
         if (hipEventCreateWithFlags(&h->ev_turn, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&h->ev_turn_aux, hipEventDisableTiming) != hipSuccess) return bail(FSMG_ERR_HIP, "event create failed");
         if (turnstile_on()) {      // the probe below asks whether two streams of this handle run side by side: not while another handle's pass has the chip
@@ -240,11 +216,6 @@ int fsmg_create(const fsmg_config* cfg, fsmg_handle* out) {
                 h->overlap = false; h->overlap_forced = true; h->tail_aside = false; h->upd_split = false;
             }
         }
-#ifdef FSMG_EXPERIMENTS
-        if (h->ce_tail && (hipStreamCreateWithPriority(&h->aux2, hipStreamNonBlocking, 0) != hipSuccess ||
-                           hipEventCreateWithFlags(&h->ev_ce_fork, hipEventDisableTiming) != hipSuccess ||
-                           hipEventCreateWithFlags(&h->ev_ce, hipEventDisableTiming) != hipSuccess)) return bail(FSMG_ERR_HIP, "aux2 stream create failed");
-#endif
         for (int c = 0; c < fsmg_model::NCHUNK; ++c)
             if (hipEventCreateWithFlags(&h->ev_chunk[c], hipEventDisableTiming) != hipSuccess) return bail(FSMG_ERR_HIP, "event create failed");
         if (hipEventCreateWithFlags(&h->ev_bucket[0], hipEventDisableTiming) != hipSuccess ||
@@ -274,7 +245,7 @@ int fsmg_create(const fsmg_config* cfg, fsmg_handle* out) {
     const size_t tok_words = (size_t)round_up(h->V1, 64);
     const size_t prog_words = (size_t)round_up(h->T + 8, 64);
     const size_t small_bytes = 256 * 4 + sizeof(float) * RING_CAP + sizeof(int) * 8 * fsmg_model::TICKET_LAUNCHES + sizeof(int) * 2 * fsmg_model::XOV_CTL +
-                               sizeof(int) * 2 * tok_words + sizeof(int) * prog_words + sizeof(int) * fsmg_model::XOV_DONE;
+                               sizeof(int) * 2 * tok_words + sizeof(int) * prog_words;
     if (hipMalloc((void**)&small, small_bytes) != hipSuccess) return bail(FSMG_ERR_NOMEM, "hipMalloc(scalars) failed");
     hipMemsetAsync(small, 0, small_bytes, h->stream);
     h->d_step = (long long*)small; h->d_err = (int*)(small + 256); h->d_gnorm = (float*)(small + 512);
@@ -290,7 +261,6 @@ int fsmg_create(const fsmg_config* cfg, fsmg_handle* out) {
     h->xov_ctl = h->tickets + 8 * fsmg_model::TICKET_LAUNCHES;
     h->tok_first = h->xov_ctl + 2 * fsmg_model::XOV_CTL; h->tok_count = h->tok_first + tok_words;
     h->xov_prog = h->tok_count + tok_words;
-    h->xov_done = h->xov_prog + prog_words;
     if (reset_tok_table(h) != FSMG_OK) return bail(FSMG_ERR_HIP, "fill of the token occurrence table failed");
 
     if (hipMalloc((void**)&h->khf, sizeof(float) * (size_t)h->L * 2 * h->Hp * h->G4) != hipSuccess)
@@ -367,11 +337,6 @@ int fsmg_destroy(fsmg_handle h) {
     if (h->ev_side) hipEventDestroy(h->ev_side);
     if (h->ev_turn) hipEventDestroy(h->ev_turn);
     if (h->ev_turn_aux) hipEventDestroy(h->ev_turn_aux);
-#ifdef FSMG_EXPERIMENTS
-    if (h->ev_ce_fork) hipEventDestroy(h->ev_ce_fork);
-    if (h->ev_ce) hipEventDestroy(h->ev_ce);
-    if (h->aux2) { hipStreamSynchronize(h->aux2); hipStreamDestroy(h->aux2); }
-#endif
     comm_destroy(h);
     if (h->probe) { hipStreamSynchronize(h->probe); hipStreamDestroy(h->probe); }
     if (h->d_probe) hipFree(h->d_probe);

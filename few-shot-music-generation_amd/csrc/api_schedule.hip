@@ -130,13 +130,13 @@ void choose_schedule(fsmg_model* h, int B, bool train) {
     h->xov_call = false;
     // a pass whose recurrence is one persistent launch per direction is short enough to issue eagerly; per-step kernels (big
     // validation batches, the fallback after a time-out) keep the graph
-    h->eager_call = h->eager && !h->ov_call && h->persist && h->persist_fwd && h->persist_bwd &&
+    h->eager_call = h->eager && !h->ov_call && h->persist &&
                     (use_xcd(h, B) || lstm_fwd_chain_supported(B, h->Hp) || lstm_fwd_chain_rt_supported(B, h->Hp));
     // XCD-partitioned schedule (round 4 form): the bf16-split chains packed on ceil(B / 16) XCDs, the 256-tile work-queue GEMMs of
     // the projection / its weight gradient on the others
     // hidden 1024 (round 6): the TOP layer's pair on three XCD pairs (the bf16-split pair kernels take 16 rows per pair at one MFMA
     // phase's cost), the projection / its weight gradient on the fourth
-    if (train && h->xov && ((h->Hp == 512 && h->L == 1) || h->Hp == 1024) && h->xcd_bx3 && h->bx3 && !h->ov_call && h->aux != nullptr && use_xcd(h, B) && h->persist_fwd && h->persist_bwd &&
+    if (train && h->xov && ((h->Hp == 512 && h->L == 1) || h->Hp == 1024) && h->xcd_bx3 && h->bx3 && !h->ov_call && h->aux != nullptr && use_xcd(h, B) &&
         (!h->timing || h->timing_only == "lstm_fwd" || h->timing_only == "lstm_bwd")) {
         const int rpx = lstm_xcd16_packed_rows(B, h->Hp);
         h->xov_call = rpx > 0 && xov_first_free(B, h->Hp) <= (h->Hp == 1024 ? 6 : 5);          // at least three XCDs (hidden 1024: a pair) for the GEMMs
@@ -153,14 +153,6 @@ void xov_gate(fsmg_model* h, GemmArgs& g, int B) {     // the projection's A row
 }
 int gemm_restricted(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs g, int first, int* ctl) {
     g.bx3 = 3; g.xcd_first = first; g.work = ctl; g.stop = ctl + 2; g.claim = ctl + 4; g.work_limit = gemm_items(g);
-#ifdef FSMG_EXPERIMENTS         // FSMG_XOV_DEBUG (make experiments): the A/B runs of DESIGN.md 9.2
-    const int dbg = xov_debug();
-    if (dbg & 1) g.work_limit = 0;                 // nothing for the restricted launch: the serial order on the packed kernels
-    if ((dbg & 1) && (dbg & (128 | 256))) g.gate = nullptr;
-    if (dbg & 16) g.dbg |= 32;                     // agent-scope loads of the gated operand
-    if (dbg & 8) g.dbg |= 128;                     // agent-scope acquire behind the gate
-    if (dbg & 32) g.dbg |= 64;                     // blocks below xcd_first never join
-#endif
     HIPCK(h, launch_gemm(s, amode, bmode, g, 0));
     return FSMG_OK;
 }
@@ -186,9 +178,6 @@ int gemm_prepare_queue(fsmg_model* h, GemmArgs& g, int split, OpBatch* defer, bo
 }
 int gemm_cleanup(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs g, int* ctl) {
     g.bx3 = 3; g.xcd_first = -1; g.work = ctl; g.claim = ctl + 4;
-#ifdef FSMG_EXPERIMENTS
-    if ((xov_debug() & 1) && (xov_debug() & (128 | 256))) g.gate = nullptr;
-#endif
     HIPCK(h, launch_gemm(s, amode, bmode, g, 0));
     return FSMG_OK;
 }

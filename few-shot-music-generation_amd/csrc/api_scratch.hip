@@ -58,7 +58,7 @@ int ensure_scratch(fsmg_model* h, int B) {
         if (lstm_bwd_rs_supported(r, (int)Hp)) rows_rs = r;
         if (lstm_bwd_chain_supported(r, (int)Hp)) rows_ag = r;
     }
-    const bool want_inbox = h->persist && h->bwd_rs && rows_rs > 0;
+    const bool want_inbox = h->persist && rows_rs > 0;
     const bool want_dzfa = h->persist && !want_inbox && rows_ag > 0;
     const int64_t n_dzfa = want_dzfa ? T * (int64_t)rows_ag * G4 : 0;
     const int64_t o_dzfa = place(want_dzfa ? 4 * n_dzfa : 256);

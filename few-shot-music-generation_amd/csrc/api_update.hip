@@ -109,10 +109,6 @@ int apply_update(fsmg_model* h, float grad_scale) {
     bool inc_done = false;
     GEMMCK(repack_recurrent_weights(h, s, &inc, &inc_done));
     if (!inc_done) HIPCK(h, launch_step_increment(s, inc));
-    PHASE(7);
-#ifdef FSMG_PHASE_DEBUG
-    phase_report(h);
-#endif
     h->have_grads = false;
     return FSMG_OK;
 }

@@ -62,27 +62,13 @@ struct GemmArgs {
                             // 2: k_gemm_bx3w, its wave-specialised variant (same bits; two 512-thread blocks per CU)
     int group_m;                // bf16-split kernels: tile order, see tile_coords (gemm.hip); 0 = row tiles fastest
     unsigned long long* prof;   // diagnostics (tools/gemm_bench PROF=1, bx3 only): [blocks][waves][8] stamps, see k_gemm_bx3
-    int dbg;                    // diagnostics, stamped instantiation only (k_gemm_bx3w): ablation bits, results are wrong
+    int dbg;                    // diagnostics, stamped instantiations only: ablation bits (k_gemm_bx3w: 1, 2, 4; k_gemm_bx3h: 8), results are wrong
     // Two-part op(A) of an XC x XC product on the 256 x 256-tile kernel (the merged weight gradient [x | h_prev]^T dZ of a layer: one
     // launch, one K split, one set of slabs for what were two GEMMs over the same dZ).  m_split > 0: rows [0, m_split) of op(A) are
     // the columns of A -- K rows gathered through `gather` when it is set (the caller guarantees the gathered table < 4 GiB) --,
     // rows [m_split, M) the columns of A2 (never gathered).  m_split is a multiple of 256.
     const float* A2; int lda2; int m_split;
-    // Work-queue launches of the 256 x 256-tile kernel: done != nullptr -> the tile is stored write-through (sc1), and a block whose stores
-    // have all been acknowledged adds 1 to done[row tile] (zeroed by the caller): what a consumer on other CUs gates the rows of that row tile on
-    // (launch_ce_rows_gated: the cross entropy under the forward pair's tail)
-    int* done;              // (experiment builds: measured and rejected, profiles/r05_ce_under_tail_*)
-    // Operands that arrive PRE-SPLIT (256 x 256-tile kernel only; round 6): the "plane image" launch_split_planes writes -- the three
-    // bf16 planes of op(A) / op(B) as [plane][k / 8][x][8 bf16], k padded with zeros to a multiple of 16, x = the M (N) index -- i.e.
-    // the kernel's LDS image per k group, so a tile is 24 LDS-DMA instructions of 1 KiB and no split work in the k loop.  Same six
-    // products in the same order as the in-loop split: the same bits.  A / B (fp32) are then not read (B's column sums: not with Bpl).
-    const void* Apl; const void* Bpl;
 };
-// Plane images (GemmArgs::Apl / Bpl).  src is op(X) stored k-contiguous (mode OP_KC: src[x][k], ld >= K) or x-contiguous (OP_XC:
-// src[k][x], ld >= X); planes holds plane_image_bytes(K, X) bytes.  Exact: piece1 + piece2 + piece3 == value for every finite fp32.
-inline long long plane_image_k8(int K) { return 2LL * ((K + 15) / 16); }
-inline long long plane_image_bytes(int K, int X) { return 3LL * plane_image_k8(K) * X * 16; }
-hipError_t launch_split_planes(hipStream_t s, int mode, const float* src, int ld, int K, int X, void* planes);
 // amode/bmode in {OP_KC, OP_XC}. Supported combinations: (KC,XC) (XC,XC) (KC,KC)
 hipError_t launch_gemm(hipStream_t s, int amode, int bmode, const GemmArgs& g, int lds_pad = 0);
 // dynamic-LDS padding that caps a GEMM at `blocks_per_cu` resident blocks per CU
@@ -224,7 +210,7 @@ struct LstmFwdXcdArgs {
     int* progress;              // bf16-split kernels only, nullptr = off: [T] counters, ZERO before the launch; progress[t] reaches
                                 // lstm_xcd_active_blocks(B, rpx) when the row-major h of step t (Hs index t + 1) is in memory
                                 // (write-through stores) -- what a GEMM on the other XCDs gates its row tiles on
-    int progress_lag;           // diagnostics: publish this many steps later than the stores' completion requires
+    int progress_lag;           // diagnostics: publish this many steps later than the stores' completion requires (always 0: nothing sets it)
     int progress_every;         // publish every this many steps (0 = 1): only progress[t] with t % every == every - 1, and progress[T - 1],
                                 // are counted up -- a publish is a memory operation in front of the next poll of the publishing wave
 };
@@ -299,11 +285,6 @@ hipError_t launch_token_prep(hipStream_t s, const int* support, int n_support, c
 // (softmax - onehot) * inv_n (pad columns zero) for the backward projection GEMMs
 hipError_t launch_ce_rows(hipStream_t s, const float* logits, int ld, int rows, int n_vocab, const int* tgt,
                           float* lse, float* ce, float* dlogits, float inv_n);
-// the same rows (register-resident kernels only: ld <= 12288) by a persistent grid of `blocks` blocks, each row behind the completion
-// counter of its row tile: done[row / tile_rows] >= done_expect (GemmArgs::done of the work-queue projection that is still running)
-hipError_t launch_ce_rows_gated(hipStream_t s, const float* logits, int ld, int rows, int n_vocab, const int* tgt, float* lse, float* ce,
-                                float* dlogits, float inv_n, const int* done, int done_expect, int tile_rows, int* err_flag, int spin_cap, int blocks,
-                                int* next_row /* one int, zero before the launch: the rows are drawn from it */);
 // what the shift-free softmax of GemmArgs::ce_store is used for: e^-60 <= S = sum_v exp(x_v) <= 1e30 (the largest logit of a row within
 // about [-60, 69 - log(vocabulary)]) and exp(target logit) >= 1e-30 (its log is taken) -- E, S and c = 1 / (n S) stay normal fp32 numbers
 constexpr float CE_SUM_MIN = 8.0e-27f, CE_SUM_MAX = 1.0e30f, CE_TGT_MIN = 1.0e-30f;

@@ -91,11 +91,10 @@ struct fsmg_model {
     int partials_cap = 0;
     std::vector<float*> HF;             // fragment-ordered h per layer: [T+1][ceil(B/16)*16][Hp]
     float* dzF = nullptr;               // fragment-ordered dz ping-pong: [2][ceil(B/16)*16][4Hp]
-    float* dzF_all = nullptr;           // persistent backward chain, all-gather form (FSMG_BWD_RS=0): fragment-ordered dz of every time step
+    float* dzF_all = nullptr;           // persistent backward chain, all-gather form (where the reduce-scatter form does not apply): fragment-ordered dz of every time step
     int64_t dzfa_floats = 0;
     float* inbox = nullptr;             // persistent backward chain, reduce-scatter form: dh partial tiles [2][row tiles][P][P][64][4]
     int64_t inbox_floats = 0;
-    bool bwd_rs = true;                 // FSMG_BWD_RS=0 selects the all-gather form
     int chain_spin_limit = 1 << 18;     // FSMG_CHAIN_SPIN_LIMIT (0 forces the timeout + fallback path: tests)
     bool retry_armed = false;           // a train step was skipped on the device and the handle has changed its schedule for the repeat: a persistent kernel
                                         // gave up (per-step launches now) or a row left the fused softmax's range (cross-entropy pass now)
@@ -106,7 +105,6 @@ struct fsmg_model {
     long long* d_counters = nullptr;    // the same memory as the device sees it
     long long seen_timeouts = 0, seen_token_errors = 0, seen_peer_failures = 0, seen_range_skips = 0;
     bool force_fwd_rt = false;          // FSMG_FWD_RT=1: take the all-row-tiles forward kernel wherever it applies (tests)
-    bool persist_fwd = true, persist_bwd = true;   // FSMG_PERSIST_FWD / FSMG_PERSIST_BWD = 0: that direction launches per step
     bool persist = true;                // FSMG_PERSISTENT=0: one launch per time step instead of one persistent launch per chain chunk
     float* khf = nullptr;               // fragment-ordered recurrent weights: per layer fwd copy, bwd copy
     float* P_saved = nullptr;           // cfg-E: theta while the handle computes at the adapted theta'
@@ -118,8 +116,8 @@ struct fsmg_model {
     // XCD-local recurrence (lstm_xcd.hip; hidden size 512): per layer the forward and backward register images of K_h,
     // the h hand-off buffer, the dh-partial inboxes and the per-launch ticket counters
     bool xcd = true;                    // FSMG_XCD=0: keep the column-split persistent kernels
-    int xcd_max_rows = 128;             // FSMG_XCD_MAX_ROWS: largest sequence count that takes the XCD-local kernels
-    int dp_split = 0;                   // FSMG_DP_SPLIT=1 / 2: fsmg_forward_backward replays TWO graphs (forward + projection gradients | BPTT + the rest) and
+    static constexpr int xcd_max_rows = 128;   // largest sequence count that takes the XCD-local kernels
+    int dp_split = 0;                   // fsmg_config.dp_split_backward = 1 / 2: fsmg_forward_backward replays TWO graphs (forward + projection gradients | BPTT + the rest) and
                                         // records bucket 0's readiness between them, so its all-reduce runs under the second one
     int pair_mode = 2;                  // hidden size 1024 (one copy of K_h per XCD pair): 0 = column-split kernels, 1 = pair kernel forward only
                                         // (6.4 against 7.0 us per step; the backward pair kernel ties with the column-split one), 2 = both directions
@@ -156,8 +154,6 @@ struct fsmg_model {
     // captured token_prep cannot take the caller's pointers.  FSMG_EAGER=0: graphs wherever fsmg_config.use_graph allows.
     bool eager = true, eager_call = false;
     const int* cur_sup = nullptr; const int* cur_qry = nullptr;     // what token_prep reads: the caller's device buffers (eager) or the staging buffer
-    bool fills_late = false;            // FSMG_FILLS_LATE=1: dH's slab sum + the BPTT fills behind the dW GEMM instead of in front of it (A/B)
-    bool fill_early = false;            // FSMG_FILL_EARLY=1: the forward hand-off fills in front of the zx GEMM instead of behind it (A/B)
     float* colsum_slabs = nullptr;
     float* slabs2 = nullptr;            // ... and of the GEMMs on the auxiliary stream
     float* colsum_slabs2 = nullptr;
@@ -170,12 +166,10 @@ struct fsmg_model {
     // switched off for the handle), else the number of streams it drew
     int aux_tries = 0;
     static constexpr int NCHUNK = 16;   // max time chunks of the overlap schedule
-    std::vector<int> chunk_edges;       // explicit chunk boundaries (FSMG_CHUNK_STEPS), empty = uniform
-    int nchunk = 8;                     // chunks in use with one launch per step (FSMG_NCHUNK)
-    int nchunk_persist = 4;             // ... and with the persistent step kernels (swept at cfg-B: 3-4 chunks x 2 blocks/CU)
-    int aux_blocks_persist = 2;
-    bool aux_blocks_from_env = false;
-    int aux_blocks_per_cu = 2;          // occupancy cap of the overlapped GEMMs (FSMG_AUX_BLOCKS); swept: 8 x 2 is best at cfg-B
+    static constexpr int nchunk = 8;    // chunks in use with one launch per step
+    static constexpr int nchunk_persist = 4;   // ... and with the persistent step kernels (swept at cfg-B: 3-4 chunks x 2 blocks/CU)
+    static constexpr int aux_blocks_persist = 2;
+    static constexpr int aux_blocks_per_cu = 2;   // occupancy cap of the overlapped GEMMs; swept: 8 x 2 is best at cfg-B
     hipEvent_t ev_chunk[NCHUNK] = {};   // main -> aux (forward) / aux -> main (backward): chunk ready
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool merge_dk = true;               // dKx and dKh of a layer as one GEMM with a two-part A (FSMG_MERGE_DK=0: two GEMMs)
@@ -190,9 +184,8 @@ struct fsmg_model {
     bool xov = false, xov_call = false;
     bool xov_eligible = false;          // what `xov` was decided to be at creation before the second-stream probe had its say (fsmg_debug_set("reprobe_aux"))
     bool bucket0_recorded = false;      // backward() recorded ev_bucket[0] itself (two-stream / XCD-partitioned order)
-    int xov_dw_split = 4;               // K split of dW under this schedule: an item must be short against the chain it runs beside
-    int xov_tail = 0;                   // FSMG_XOV_TAIL: time steps whose projection rows are left to a chip-wide launch behind the chain (0: none)
-    int xov_pub = 6;                    // FSMG_XOV_PUB: the forward chain publishes every this many steps (a 256-row tile is 5.7 steps of 45 rows)
+    static constexpr int xov_dw_split = 4;   // K split of dW under this schedule: an item must be short against the chain it runs beside
+    static constexpr int xov_pub = 6;   // the forward chain publishes every this many steps (a 256-row tile is 5.7 steps of 45 rows)
     int xov_strikes = 0;                // time-outs of passes in the XCD-partitioned order: the second one parks the schedule for this handle
     bool xov_last = false;              // the pass in flight took the XCD-partitioned order
     int xov_parts = 3;                  // FSMG_XOV_PARTS: 1 = forward pair, 2 = backward pair (dW beside the top chain), 4 = stacked layers: dK of layer l + 1
@@ -211,9 +204,6 @@ struct fsmg_model {
     char* gen = nullptr;
     size_t gen_bytes = 0;
 
-#ifdef FSMG_PHASE_DEBUG
-    hipEvent_t ph[8] = {}; bool ph_init = false; int ph_step = 0;      // per handle (was file scope: shared by all handles)
-#endif
     // gradient exchange inside the library (fsmg_comm_*): RCCL communicator, its stream, the event the compute stream waits on
     void* comm = nullptr; bool own_comm = false; int world = 1, rank = 0;
     hipStream_t comm_stream = nullptr;
@@ -264,20 +254,6 @@ struct fsmg_model {
     // loss, k_embed_grad, the embedding-slice norm -- on the auxiliary stream BESIDE the bottom layer's weight-gradient GEMM, which is
     // issued behind dx instead of in front of it (the two do not depend on each other); the main stream waits for it right behind that
     // GEMM.  Same kernels on the same operands: same bits.  FSMG_TAIL_ASIDE=0 / fsmg_debug_set("tail_aside", 0): everything in line.
-#ifdef FSMG_EXPERIMENTS
-    // MEASURED AND REJECTED (round 5, experiment builds only: profiles/r05_ce_under_tail_*): the cross entropy UNDER the forward pair's
-    // tail.  Every work-queue tile of the projection is stored write-through and counts itself in xov_done[row tile]; the cross entropy
-    // is a persistent grid on a third stream that starts when the chain is over and takes each row behind its row tile's counter.
-    // Bit-identical -- and 7-25 % SLOWER: the persistent blocks hold CUs the last tiles need (136 VGPRs: no co-residency with a GEMM
-    // block), the tail grows from 105 to 225 us and the cross entropy itself takes 330 us instead of 92; the idle CU-time of the tail
-    // (~12 k CU-us) is half of what the pass needs in the first place.  FSMG_CE_TAIL=1, FSMG_CE_TAIL_BLOCKS.
-    bool ce_tail = false;
-    int ce_tail_blocks = 256;
-    hipStream_t aux2 = nullptr;
-    hipEvent_t ev_ce_fork = nullptr, ev_ce = nullptr;
-#endif
-    int* xov_done = nullptr;            // [XOV_DONE] completion counters of the projection's row tiles (GemmArgs::done; experiment builds)
-    static constexpr int XOV_DONE = 256;
     bool tail_aside = true;
     bool side_pending = false;          // the auxiliary stream may still be reading the main lane's slabs (gemm() waits before it reuses them)
     hipEvent_t ev_side_fork = nullptr, ev_side = nullptr;
@@ -404,7 +380,7 @@ inline Lane main_lane(fsmg_model* h) { return Lane{h->stream, h->slabs, h->colsu
 // forward-only passes (validation: many rows per step, patch step kernel) tolerate one more overlapped GEMM block
 // per CU than training steps do (measured at cfg-B: eval 2862 vs 2690 episodes/s, train 290 vs 303)
 inline Lane aux_lane(fsmg_model* h, bool forward_only = false, bool persistent_chain = false) {
-    const int cap = std::min(4, (persistent_chain ? h->aux_blocks_persist : h->aux_blocks_per_cu) + (forward_only && !h->aux_blocks_from_env ? 1 : 0));
+    const int cap = std::min(4, (persistent_chain ? h->aux_blocks_persist : h->aux_blocks_per_cu) + (forward_only ? 1 : 0));
     return Lane{h->aux, h->slabs2, h->colsum_slabs2, gemm_lds_pad_for(cap), 256 * cap};
 }
 
@@ -519,32 +495,9 @@ int run_graphed(fsmg_model* h, const std::string& key, F&& body) {
 // so the projection work runs on a low-priority auxiliary stream, forked / joined with events (inside
 // the captured graph these become parallel branches).  Event timing (eager, one class at a time)
 // and FSMG_OVERLAP=0 use the single-stream order.
-// time-chunk boundaries of the overlap schedule: uniform, or the explicit step counts of FSMG_CHUNK_STEPS ("12,36,34,34,12")
-inline int chunk_begin(const fsmg_model* h, int c, int nch) {
-    if (!h->chunk_edges.empty() && (int)h->chunk_edges.size() == nch + 1) return h->chunk_edges[c];
-    return (int)((int64_t)c * h->T / nch);
-}
+// time-chunk boundaries of the overlap schedule: the uniform split
+inline int chunk_begin(const fsmg_model* h, int c, int nch) { return (int)((int64_t)c * h->T / nch); }
 inline bool use_overlap(const fsmg_model* h) { return h->ov_call && !h->timing && h->aux != nullptr && h->T >= std::max(h->nchunk, h->nchunk_persist); }
-
-#ifdef FSMG_PHASE_DEBUG
-// compile-time debugging aid (make EXTRA=-DFSMG_PHASE_DEBUG): GPU time of the phases of the eager overlap
-// schedule, from events on the main stream; printed every 20th step
-inline void phase_mark(fsmg_model* h, int i) {
-    if (!h->ph_init) { for (auto& e : h->ph) hipEventCreate(&e); h->ph_init = true; }
-    hipEventRecord(h->ph[i], h->stream);
-}
-inline void phase_report(fsmg_model* h) {
-    if (++h->ph_step % 20) return;
-    hipStreamSynchronize(h->stream);
-    const char* nm[] = {"zx+memsets", "fwd chain", "fwd join+loss", "to bwd chain", "bwd chain", "dk/dx/embed + dW join", "update"};
-    float tot = 0;
-    for (int i = 0; i < 7; ++i) { float ms = 0; hipEventElapsedTime(&ms, h->ph[i], h->ph[i + 1]); tot += ms; fprintf(stderr, "[phase] %-24s %7.1f us\n", nm[i], ms * 1000); }
-    fprintf(stderr, "[phase] total %.1f us\n", tot * 1000);
-}
-#define PHASE(i) phase_mark(h, i)
-#else
-#define PHASE(i) ((void)0)
-#endif
 
 // the XCD-local kernels take this row count at this hidden size (and their buffers exist)
 inline bool use_xcd(const fsmg_model* h, int B, bool backward = false) {
@@ -568,9 +521,6 @@ inline int* next_tickets(fsmg_model* h) {
     return t;
 }
 
-#ifdef FSMG_EXPERIMENTS
-inline int xov_debug() { static const int dbg = std::getenv("FSMG_XOV_DEBUG") ? std::atoi(std::getenv("FSMG_XOV_DEBUG")) : 0; return dbg; }
-#endif
 // Work-queue GEMM in two launches of k_gemm_bx3h<..., QUEUE> (GemmArgs::xcd_first): the restricted one lets the XCDs >= first
 // draw items (all of them: the two launches drain one queue); the clean-up one, ordered behind the kernel that owned the other
 // XCDs, lets the whole chip take what is left.  work / claim words are zeroed on the main stream before the fork.
@@ -600,7 +550,7 @@ int ensure_khf(fsmg_model* h);
 int ensure_cs(fsmg_model* h);           // the column-split copies of K_h are current (call OUTSIDE a graph capture, before a pass that reads them)
 // a pass over B sequences reads the column-split copies: its recurrence does not take the XCD-local kernels in some direction
 inline bool pass_reads_cs(const fsmg_model* h, int B, bool train) {
-    return !(use_xcd(h, B) && h->persist_fwd) || (train && !(use_xcd(h, B, true) && h->persist_bwd));
+    return !use_xcd(h, B) || (train && !use_xcd(h, B, true));
 }
 int apply_update(fsmg_model* h, float grad_scale);
 int sgd_update(fsmg_model* h, float lr);
