@@ -125,6 +125,7 @@ int ensure_scratch(fsmg_model* h, int B) {
     const int64_t o_slab2 = place(4 * std::max<int64_t>(slab_need, 64));
     const int64_t o_cslab2 = place(4 * (int64_t)MAX_SPLIT * std::max<int64_t>(h->V1p, G4));
     const int64_t o_arena = place(4 * std::max<int64_t>(arena_need, 64));
+    const int64_t o_score = place(4 * 4 * rows);        // fsmg_score's four per-position outputs (last: nothing else moves)
     hipError_t e = hipMalloc((void**)&h->scratch, off);
     if (e != hipSuccess) {
         h->Bcap = 0;
@@ -156,6 +157,7 @@ int ensure_scratch(fsmg_model* h, int B) {
     h->ce_part = (float2*)(s + o_cep); h->tgt_logit = (float*)(s + o_tl); h->ce_nparts = nparts;
     h->slabs = (float*)(s + o_slab); h->colsum_slabs = (float*)(s + o_cslab); h->slab_cap = slab_need;
     h->slabs2 = (float*)(s + o_slab2); h->colsum_slabs2 = (float*)(s + o_cslab2);
+    h->score_out = (float*)(s + o_score);
     h->arena = (float*)(s + o_arena); h->arena_cap = arena_need; h->arena_off = 0;
     h->Bcap = B;
     return FSMG_OK;

@@ -421,4 +421,15 @@ hipError_t launch_beam_reorder(hipStream_t s, int L, int R, int W, int Hp, const
 hipError_t launch_beam_backtrace(hipStream_t s, int R, int W, int num, const int* par, const int* htok, const float* hlp, const float* cum,
                                  int* out_tok, float* out_lp, float* out_score);
 
+// ---------------------------------------------------------------- scoring (score.hip, fsmg_score)
+// Per row r = t * B + b of the time-major logits [rows = T * B][ld] (the first n_vocab columns count; ld % 4 == 0) against the target
+// column tgt[r], written TRANSPOSED at [b * T + t]:
+//   out_lp = z_y - (m + log(sum_v exp(z_v - m))), m the row maximum;  out_rank = #{v : z_v > z_y} + #{v < y : z_v == z_y};
+//   out_ent = log S - sum_v exp(z_v - m) (z_v - m) / S, a -inf column contributing 0;  out_arg = the lowest column holding m.
+// A null output is not stored.  A row with a NaN logit: NaN out_lp / out_ent, rank and argmax some column in [0, n_vocab).
+// Rows of up to SCORE_REG_COLS floats are read once into registers, wider ones twice; no allocation, no synchronisation, no atomics.
+constexpr int SCORE_REG_COLS = 10 * 1024;
+hipError_t launch_score_rows(hipStream_t s, const float* logits, int ld, int rows, int n_vocab, const int* tgt, int B, int T,
+                             float* out_lp, int* out_rank, float* out_ent, int* out_arg);
+
 }  // namespace fsmg

@@ -9,6 +9,7 @@
 //   api_step.hip      train / eval / MAML-style entry points          api_comm.hip  RCCL glue (fsmg_comm_*)
 //   api_unigram.hip   unigram baseline                                 api_debug.hip debug reads, timers, clock probe
 //   api_decode.hip    decoding: fsmg_generate(_filtered), fsmg_beam_search, their MAML twins, fsmg_sample (one driver)
+//   api_score.hip     scoring of given songs: fsmg_score, fsmg_maml_score
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
@@ -86,6 +87,7 @@ struct fsmg_model {
     int* d_tok = nullptr; int *X = nullptr, *Y = nullptr;
     std::vector<float*> Z, Hs, Cs;
     float2* ce_part = nullptr; float* tgt_logit = nullptr; int ce_nparts = 0;
+    float* score_out = nullptr;         // fsmg_score: [4][T * Bcap] words -- log-prob, entropy (float), rank, argmax (int), each [b][t]
     float *dC = nullptr, *dH = nullptr, *logits = nullptr, *dlogits = nullptr, *lse = nullptr, *ce = nullptr, *dXemb = nullptr, *dXpart = nullptr;
     double* partials = nullptr;
     int partials_cap = 0;
@@ -538,7 +540,8 @@ int gemm_cleanup(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs g,
 int stage_tokens(fsmg_model* h, const int32_t* support, int n_sup, const int32_t* query, int n_qry, int on_device);
 int reset_tok_table(fsmg_model* h);
 int token_prep(fsmg_model* h, int n_sup, int n_qry, bool train = false);
-int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_out, bool want_dlogits);
+enum { HEAD_LOSS = 0, HEAD_LOGITS = 1 };     // what a forward pass ends in: projection + cross entropy + loss, or the bare logits (fsmg_score)
+int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_out, bool want_dlogits, int head = HEAD_LOSS);
 GemmArgs dw_args(fsmg_model* h, int B);        // api_backward.hip: dW = Hout^T dlogits, dd = colsum(dlogits) (forward() asks which kernel it will take)
 // api_backward.hip
 // part 0: the whole pass; part 1: up to and including the projection gradients; part 2: the rest (see backward())

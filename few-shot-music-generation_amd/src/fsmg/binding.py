@@ -73,6 +73,15 @@ class FsmgBeamConfig(C.Structure):
                 ('primer_len', C.c_int32), ('primer_on_device', C.c_int32), ('reserved', C.c_int32 * 8)]
 
 
+FSMG_SCORE_CONFIG_VERSION = 1
+FSMG_SCORE_PASS_ROWS = 128
+
+
+class FsmgScoreConfig(C.Structure):
+    _fields_ = [('version', C.c_int32), ('n_rows', C.c_int32), ('tokens_on_device', C.c_int32), ('nll_first', C.c_int32),
+                ('nll_count', C.c_int32), ('pass_rows', C.c_int32), ('reserved', C.c_int32 * 10)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -124,6 +133,9 @@ SIGNATURES = {
     'fsmg_beam_search': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, _I32P, _F32P, _F32P]),
     'fsmg_maml_beam_search': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P, _F32P,
                                         _F32P]),
+    'fsmg_score': (C.c_int, [_P, C.POINTER(FsmgScoreConfig), _P, _F32P, _I32P, _F32P, _I32P, _F32P]),
+    'fsmg_maml_score': (C.c_int, [_P, C.POINTER(FsmgScoreConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _F32P, _I32P,
+                                  _F32P, _I32P, _F32P]),
     'fsmg_read_losses': (C.c_int, [_P, _F32P, C.c_int32]),
     'fsmg_get_stats': (C.c_int, [_P, C.POINTER(FsmgStats)]),
     'fsmg_debug_read': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
@@ -554,6 +566,57 @@ class FsmgModel(object):
         """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), beam search at theta', restore theta"""
         sp, rows, dev, _keep = self._support(support, n_support_rows)
         return self._beam_search((sp, rows, int(inner_steps), float(inner_lr), dev), num, beam_width, n_groups, primer, logprobs)
+
+    # -- scoring of given songs (include/fsmg.h fsmg_score) -----------------------------------------------------
+    @staticmethod
+    def score_config(n_rows, nll_first=0, nll_count=0, pass_rows=0, tokens_on_device=0):
+        return FsmgScoreConfig(version=FSMG_SCORE_CONFIG_VERSION, n_rows=int(n_rows), tokens_on_device=int(tokens_on_device),
+                               nll_first=int(nll_first), nll_count=int(nll_count), pass_rows=int(pass_rows))
+
+    def _score(self, adapt, tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows):
+        """fsmg_score (adapt = ()) or fsmg_maml_score (adapt = its support arguments)"""
+        if isinstance(tokens, (int, np.integer)):
+            tp, dev, _keep, R = C.c_void_p(int(tokens)), 1, None, int(n_rows)
+        else:
+            a = np.ascontiguousarray(tokens, dtype=np.int32)
+            if a.ndim == 0 or a.shape[-1] != self.max_len:
+                raise ValueError('tokens %r do not match max_len=%d' % (a.shape, self.max_len))
+            a = a.reshape(-1, self.max_len)
+            tp, dev, _keep, R = C.c_void_p(a.ctypes.data), 0, a, a.shape[0]
+        c = self.score_config(R, nll_first, nll_count, pass_rows, dev)
+        T = self.max_len
+        out = {}
+        if logprob:
+            out['logprob'] = np.empty((R, T), np.float32)
+        if rank:
+            out['rank'] = np.empty((R, T), np.int32)
+        if entropy:
+            out['entropy'] = np.empty((R, T), np.float32)
+        if argmax:
+            out['argmax'] = np.empty((R, T), np.int32)
+        if row_nll:
+            out['row_nll'] = np.empty(R, np.float32)
+        f = lambda k: _f32p(out[k]) if k in out else None
+        i = lambda k: out[k].ctypes.data_as(_I32P) if k in out else None
+        fn = self._lib.fsmg_maml_score if adapt else self._lib.fsmg_score
+        self._ck(fn(self._h, C.byref(c), *adapt, tp, f('logprob'), i('rank'), f('entropy'), i('argmax'), f('row_nll')))
+        return out
+
+    def score(self, tokens, logprob=True, rank=False, entropy=False, argmax=False, row_nll=True, nll_first=0, nll_count=0,
+              pass_rows=0, n_rows=None):
+        """Per-token statistics of given songs: tokens int32 [R, max_len] (or a device address with n_rows) -> a dict with the
+        requested arrays: 'logprob' float32 [R, T] (model log-probability of each token), 'rank' int32 [R, T] (0-based rank of the
+        true token, lower index first on ties), 'entropy' float32 [R, T] (predictive entropy), 'argmax' int32 [R, T], 'row_nll'
+        float32 [R] (mean NLL of positions nll_first .. nll_first + nll_count - 1; nll_count 0 = to the end).  pass_rows: rows
+        per device pass (0 = 128)."""
+        return self._score((), tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows)
+
+    def maml_score(self, support, tokens, inner_steps, inner_lr, logprob=True, rank=False, entropy=False, argmax=False, row_nll=True,
+                   nll_first=0, nll_count=0, pass_rows=0, n_rows=None, n_support_rows=None):
+        """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), score at theta', restore theta"""
+        sp, rows, dev, _keep = self._support(support, n_support_rows)
+        return self._score((sp, rows, int(inner_steps), float(inner_lr), dev), tokens, n_rows, logprob, rank, entropy, argmax,
+                           row_nll, nll_first, nll_count, pass_rows)
 
     def read_losses(self, n):
         out = np.empty(n, np.float32)

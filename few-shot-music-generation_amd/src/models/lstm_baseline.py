@@ -13,7 +13,9 @@ are replaced by libfsmg (hand-written gfx950 kernels behind include/fsmg.h):
 
 Beyond the reference: generate(s, num, n, temperature, top_k, seed, primer_len) draws n samples at once on the device,
 optionally continuing the first primer_len tokens of the support songs; beam_search(s, num, beam_width, n, primer_len) returns
-the beam_width highest-scoring continuations of each of n groups, searched on the device.
+the beam_width highest-scoring continuations of each of n groups, searched on the device; score(s, songs, ...) reads given songs
+and returns per-token log-probabilities, ranks of the true token, predictive entropies, argmaxes and per-song NLLs (the support set
+is ignored, as in sample).
 
 Optional config keys beyond the reference's: device, clip_norm_mode ('tf1_slices' | 'dense'),
 max_sequences, use_graph, gemm / schedule / recurrence / dp_split_backward (fsmg_config), dp_exchange ('torch': the
@@ -142,3 +144,10 @@ class LSTMBaseline(HIPModel):
         self._require_init()
         return self._model.beam_search(int(num), int(beam_width), n_groups=int(n),
                                        primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs)
+
+    def score(self, support_set, songs, **kw):
+        """Per-token statistics of the given songs (int32 [R, max_len]) under the model (include/fsmg.h fsmg_score): a dict of
+        'logprob' / 'row_nll' and, on request (rank=True, entropy=True, argmax=True), 'rank', 'entropy', 'argmax'.  The support
+        set is ignored, as in sample.  Keywords: FsmgModel.score's."""
+        self._require_init()
+        return self._model.score(songs, **kw)

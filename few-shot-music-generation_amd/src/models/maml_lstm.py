@@ -14,6 +14,8 @@ adaptation of deep networks") as the direction the project was heading.  This pl
   generate(s, num, n, ...)  n samples drawn at theta' adapted on the support set s (fsmg_maml_generate): generation AS the
                   episode's artist.
   beam_search(s, num, beam_width, n, ...)  the same at theta' (fsmg_maml_beam_search).
+  score(s, songs, ...)  per-token log-probabilities, ranks, entropies and per-song NLLs of given songs at theta' adapted on the
+                  support set s (fsmg_maml_score); theta is restored.
 
 Extra config keys: inner_steps (default 1), inner_lr (default 0.1).
 """
@@ -74,6 +76,11 @@ class MAMLLSTM(LSTMBaseline):
         support = self._tokens(support_set, 2)
         return self._model.maml_beam_search(support, int(num), self._inner_steps, self._inner_lr, int(beam_width), n_groups=int(n),
                                             primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs)
+
+    def score(self, support_set, songs, **kw):
+        """like LSTMBaseline.score, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored"""
+        self._require_init()
+        return self._model.maml_score(self._tokens(support_set, 2), songs, self._inner_steps, self._inner_lr, **kw)
 
     def eval_many(self, episodes):
         """adaptation is per episode, so there is nothing to batch: one maml_eval per episode"""

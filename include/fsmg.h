@@ -358,6 +358,51 @@ int fsmg_maml_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_
                           int32_t inner_steps, float inner_lr, int32_t support_on_device, const int32_t* primer,
                           int32_t* out_tokens, float* out_scores, float* out_logprob);
 
+/* ---- scoring of given songs (DESIGN.md "Scoring").  Row r of tokens [R, max_len] is read exactly as an eval row: the inputs are
+ * [start, x_0 .. x_{T-2}] (start = input_size, T = max_len) from a zero state, z the V1 = input_size + 1 logits after input t -- the
+ * numbers a training forward pass puts in row t * B + b of its logits -- and y = x_t the target.  Per position:
+ *   out_logprob[r][t] = fl(z_y - lse), lse = m + log(sum_v exp(z_v - m)), m the row maximum: the untempered model log-probability,
+ *                       the quantity fsmg_generate reports for its own tokens;
+ *   out_rank[r][t]    = #{v : z_v > z_y} + #{v < y : z_v == z_y}: 0-based, the lower index first on ties (the decode driver's rule);
+ *   out_entropy[r][t] = lse - sum_v p_v z_v, p_v = exp(z_v - lse); a column with z_v = -inf contributes 0, not NaN;
+ *   out_argmax[r][t]  = the lowest index holding the row maximum;
+ * and per row, with t0 = nll_first and t1 = nll_count ? t0 + nll_count : T (a continuation scored without its primer):
+ *   out_row_nll[r]    = -(sum of out_logprob[r][t], t0 <= t < t1) / (t1 - t0), accumulated in fp64 in increasing t and rounded once
+ *                       to fp32: bitwise recomputable from out_logprob.
+ * A row with a NaN logit gives NaN log-prob and entropy; its rank and argmax are unspecified but in [0, V1); the call succeeds.
+ * Passes: the R rows are processed pass_rows at a time, the last pass shorter.  The outputs are bitwise those of scoring each pass's
+ * rows in a call of their own; the pass size is a function of the config alone, never of what the handle ran before; two identical
+ * calls give identical bits.  A row's bits are NOT promised independent of its pass's row count (the recurrent kernel family and
+ * the projection's kernel follow the rows).  Any output may be NULL (not all): the others keep their bits.
+ * State: parameters, Adam moments, global_step, the loss ring and the gradient buffer are untouched by fsmg_score; activations
+ * (fsmg_debug_read) are overwritten -- "logits" then holds the last pass's logits, time-major --; the recurrent-launch counters of
+ * fsmg_stats advance as in fsmg_eval_batch, and a time-out of a persistent recurrent kernel is handled as there (the pass is
+ * repeated on per-step launches).  fsmg_maml_score adapts like fsmg_maml_eval, scores at theta' and restores theta whatever
+ * happens: exactly fsmg_maml_generate's documented side effects (the gradient buffer, the recurrent-launch counters).
+ * Errors: FSMG_ERR_INVALID for a wrong version, nonzero reserved fields, n_rows < 1 (or > 2^20), tokens_on_device not 0 / 1,
+ * nll_first outside [0, T) or nll_first + nll_count > T or nll_count < 0, pass_rows outside {0} u [1, 1024], every output NULL, NULL
+ * tokens; FSMG_ERR_TOKEN_RANGE for a token outside [0, input_size).  After an error the contents of the outputs are unspecified. */
+#define FSMG_SCORE_CONFIG_VERSION 1
+#define FSMG_SCORE_PASS_ROWS 128          /* default rows per device pass */
+typedef struct fsmg_score_config {
+    int32_t version;          /* FSMG_SCORE_CONFIG_VERSION                                   */
+    int32_t n_rows;           /* R >= 1 songs of max_len tokens each                         */
+    int32_t tokens_on_device; /* 0 host, 1 device                                            */
+    int32_t nll_first;        /* t0 in [0, T): first position counted in out_row_nll         */
+    int32_t nll_count;        /* 0 = up to T, else t0 + nll_count <= T                       */
+    int32_t pass_rows;        /* 0 = FSMG_SCORE_PASS_ROWS, else 1..1024                      */
+    int32_t reserved[10];     /* must be 0                                                   */
+} fsmg_score_config;
+
+/* tokens [R,T]; host outputs, any may be NULL but not all:
+   out_logprob [R,T], out_rank [R,T], out_entropy [R,T], out_argmax [R,T], out_row_nll [R] */
+int fsmg_score(fsmg_handle h, const fsmg_score_config* c, const int32_t* tokens,
+               float* out_logprob, int32_t* out_rank, float* out_entropy, int32_t* out_argmax, float* out_row_nll);
+/* adapt on support [n_support_rows, max_len] like fsmg_maml_generate, score at theta', restore theta */
+int fsmg_maml_score(fsmg_handle h, const fsmg_score_config* c, const int32_t* support, int32_t n_support_rows,
+                    int32_t inner_steps, float inner_lr, int32_t support_on_device, const int32_t* tokens,
+                    float* out_logprob, int32_t* out_rank, float* out_entropy, int32_t* out_argmax, float* out_row_nll);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
