@@ -81,7 +81,7 @@ int logits_and_ce(fsmg_model* h, const Lane& ln, int B, int t0, int t1, int64_t 
         g.ce_nvocab = h->V1; g.bx3 = h->bx3;
         if (use_h_gemm(h, OP_KC, OP_XC, g, ln)) g.bx3 = 3;                  // (the softmax partials are per 64-column half of a 128-column tile in every kernel)
         else if (use_ws_gemm(h, OP_KC, OP_XC, g, ln)) { g.bx3 = 2; g.group_m = 4; }
-        HIPCK(h, launch_gemm(ln.s, OP_KC, OP_XC, g, ln.lds_pad));          // K = Hp: never split
+        HIPCK(h, launch_gemm(h, ln.s, OP_KC, OP_XC, g, ln.lds_pad));          // K = Hp: never split
         HIPCK(h, launch_ce_combine(ln.s, h->ce_part + (size_t)r0 * h->ce_nparts, h->ce_nparts,
                                    h->tgt_logit + r0, (int)m, h->ce + r0));
         return FSMG_OK;
@@ -112,7 +112,7 @@ int xov_selfcheck(fsmg_model* h, int B) {
         GemmArgs g = logits_args(h, B, 0, h->T);
         if (h->fs_call) fused_softmax_args(h, g);        // (the same epilogue as the queue launch: E values; the partials it rewrites are the same numbers)
         g.C = h->dlogits; g.bx3 = 3; g.ksplit = 1;
-        HIPCK(h, launch_gemm(h->stream, OP_KC, OP_XC, g, 0));
+        HIPCK(h, launch_gemm(h, h->stream, OP_KC, OP_XC, g, 0));
     }
     HIPCK(h, launch_compare_words(h->stream, h->logits, h->dlogits, rows * h->V1p, h->d_err, h->d_counters + 3));
     return FSMG_OK;
@@ -241,7 +241,7 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
         ghead.bx3 = h->bx3;
         if (use_h_gemm(h, OP_KC, OP_XC, ghead, mainl)) ghead.bx3 = 3;
         else if (use_ws_gemm(h, OP_KC, OP_XC, ghead, mainl)) { ghead.bx3 = 2; ghead.group_m = 4; }
-        HIPCK(h, launch_gemm(s, OP_KC, OP_XC, ghead, 0));
+        HIPCK(h, launch_gemm(h, s, OP_KC, OP_XC, ghead, 0));
     } else if (ov) {
         HIPCK(h, hipEventRecord(h->ev_join, h->aux));
         HIPCK(h, hipStreamWaitEvent(s, h->ev_join, 0));
@@ -265,7 +265,7 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
             ghead.bx3 = h->bx3;
             if (use_h_gemm(h, OP_KC, OP_XC, ghead, mainl)) ghead.bx3 = 3;
             else if (use_ws_gemm(h, OP_KC, OP_XC, ghead, mainl)) { ghead.bx3 = 2; ghead.group_m = 4; }
-            HIPCK(h, launch_gemm(s, OP_KC, OP_XC, ghead, 0));
+            HIPCK(h, launch_gemm(h, s, OP_KC, OP_XC, ghead, 0));
         }
         GEMMCK(ce_finish(h, s, B, rows));
     } else {

@@ -178,6 +178,9 @@ int fsmg_create(const fsmg_config* cfg, fsmg_handle* out) {
         const char* env = std::getenv("FSMG_OVERLAP");
         if (env) { h->overlap = env[0] != '0'; h->overlap_forced = true; }
         if (const char* e = std::getenv("FSMG_GEMM")) h->bx3 = std::strcmp(e, "f32") != 0;
+        if (const char* e = std::getenv("FSMG_GEMM_H")) h->gemm_h = std::atoi(e);
+        if (const char* e = std::getenv("FSMG_GEMM_WS")) h->gemm_ws = std::atoi(e);
+        if (const char* e = std::getenv("FSMG_MAX_SPLIT")) h->max_split = std::max(1, std::atoi(e));     // debugging knob
         if (const char* e = std::getenv("FSMG_XCD_OVERLAP")) h->xov = std::atoi(e) != 0;
         if (const char* e = std::getenv("FSMG_XOV_PARTS")) h->xov_parts = std::max(1, std::min(7, std::atoi(e)));
         if (const char* e = std::getenv("FSMG_EAGER")) h->eager = (e[0] != '0');

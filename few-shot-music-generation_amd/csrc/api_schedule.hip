@@ -13,9 +13,9 @@ namespace fsmg_host {
 // blocks per CU) pays where blocks are short-lived or few -- the projection (K = hidden size: 32 k tiles per block, +5-9 %)
 // and the weight-gradient GEMMs whose M x N is only a few dozen tiles (dKh, dKx, dx: +15-20 %, a block alone on its CU
 // needs 1700 cycles per k tile instead of 2470) -- and is a wash on the two large contractions over the vocabulary / the
-// rows (tools/gemm_bench BX3=1 vs 2, profiles/r03_gemm_prof*.log).  FSMG_GEMM_WS=0 / 2: never / always (A/B runs).
+// rows (tools/gemm_bench BX3=1 vs 2, profiles/r03_gemm_prof*.log).  FSMG_GEMM_WS=0 / 2: never / always (A/B runs; read at fsmg_create).
 bool use_ws_gemm(fsmg_model* h, int amode, int bmode, const GemmArgs& g, const Lane& ln) {
-    static const int mode = std::getenv("FSMG_GEMM_WS") ? std::atoi(std::getenv("FSMG_GEMM_WS")) : 1;
+    const int mode = h->gemm_ws;
     if (!h->bx3 || mode == 0 || ln.lds_pad != 0 || g.xcd_first != 0) return false;
     if (mode == 2) return true;
     // measured in the cfg-B step (profiles/r03b_bench_ws*.json, ms per launch without / with): projection 0.328 / 0.312,
@@ -30,9 +30,9 @@ bool use_ws_gemm(fsmg_model* h, int amode, int bmode, const GemmArgs& g, const L
 
 // The 256 x 256-tile kernel k_gemm_bx3h (one 8-wave block per CU; half the loads, split work and fragment reads per MFMA; same
 // bits for the same K split): where the output has enough 256-tiles x K slabs to fill the 256 CUs about once.
-// FSMG_GEMM_H=0 / 2: never / wherever it can run (A/B runs).
+// FSMG_GEMM_H=0 / 2: never / wherever it can run (A/B runs; read at fsmg_create).
 bool use_h_gemm(fsmg_model* h, int amode, int bmode, const GemmArgs& g, const Lane& ln) {
-    static const int mode = std::getenv("FSMG_GEMM_H") ? std::atoi(std::getenv("FSMG_GEMM_H")) : 1;
+    const int mode = h->gemm_h;
     if (!h->bx3 || mode == 0 || ln.lds_pad != 0 || g.xcd_first != 0) return false;
     if (amode == OP_XC && g.gather != nullptr && g.m_split == 0) return false;
     if (mode == 2) return true;
@@ -60,7 +60,7 @@ int gemm(fsmg_model* h, const Lane& ln, int amode, int bmode, GemmArgs g, OpBatc
         g.bx3 = 2; slots = 512 * 4 / 3;             // pick_split takes 3/4 of `slots` for the bf16-split kernels: 512 here
         if (amode == OP_KC && bmode == OP_XC) g.group_m = 4;
     }
-    const int S = (g.ldc == g.N) ? pick_split(g.M, g.N, g.K, slots, g.bx3 != 0, tile_mn) : 1;
+    const int S = (g.ldc == g.N) ? pick_split(h->max_split, g.M, g.N, g.K, slots, g.bx3 != 0, tile_mn) : 1;
     const int64_t mn = (int64_t)g.M * g.N;
     float* slabs = ln.slabs; float* cslabs = ln.colsum_slabs;
     bool deferred = false;
@@ -78,7 +78,7 @@ int gemm(fsmg_model* h, const Lane& ln, int amode, int bmode, GemmArgs g, OpBatc
             fprintf(stderr, "[fsmg] split-K of a %d x %d x %d GEMM dropped: %d slabs do not fit the slab buffer (%lld floats)\n", g.M, g.N, g.K, S, (long long)h->slab_cap);
         }
         g.ksplit = 1;
-        HIPCK(h, launch_gemm(s, amode, bmode, g, ln.lds_pad));
+        HIPCK(h, launch_gemm(h, s, amode, bmode, g, ln.lds_pad));
         if (g.row_scale != nullptr) HIPCK(h, launch_scale_rows(s, g.C, g.row_scale, g.M, g.N));
         return FSMG_OK;
     }
@@ -93,7 +93,7 @@ int gemm(fsmg_model* h, const Lane& ln, int amode, int bmode, GemmArgs g, OpBatc
     float* C = g.C; float* colsum = g.colsum;
     g.C = slabs; g.c_slab = mn; g.ksplit = S;
     if (colsum) { g.colsum = cslabs; g.colsum_slab = g.N; }
-    HIPCK(h, launch_gemm(s, amode, bmode, g, ln.lds_pad));
+    HIPCK(h, launch_gemm(h, s, amode, bmode, g, ln.lds_pad));
     if (deferred) {
         if (sq != nullptr && g.row_scale != nullptr) return fail(h, FSMG_ERR_STATE, "internal: row-scaled GEMM with squared-norm partials");
         GEMMCK(defer->room(colsum ? 2 : 1));
@@ -153,7 +153,7 @@ void xov_gate(fsmg_model* h, GemmArgs& g, int B) {     // the projection's A row
 }
 int gemm_restricted(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs g, int first, int* ctl) {
     g.bx3 = 3; g.xcd_first = first; g.work = ctl; g.stop = ctl + 2; g.claim = ctl + 4; g.work_limit = gemm_items(g);
-    HIPCK(h, launch_gemm(s, amode, bmode, g, 0));
+    HIPCK(h, launch_gemm(h, s, amode, bmode, g, 0));
     return FSMG_OK;
 }
 // A split-K GEMM for the work queue: slabs in the pass arena, the fixed-order slab sums (same order as gemm()'s) queued in `defer`;
@@ -178,7 +178,7 @@ int gemm_prepare_queue(fsmg_model* h, GemmArgs& g, int split, OpBatch* defer, bo
 }
 int gemm_cleanup(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs g, int* ctl) {
     g.bx3 = 3; g.xcd_first = -1; g.work = ctl; g.claim = ctl + 4;
-    HIPCK(h, launch_gemm(s, amode, bmode, g, 0));
+    HIPCK(h, launch_gemm(h, s, amode, bmode, g, 0));
     return FSMG_OK;
 }
 

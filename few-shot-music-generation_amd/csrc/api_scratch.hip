@@ -11,9 +11,8 @@ namespace fsmg_host {
 // A 128x128-tile GEMM with few output tiles leaves most of the 256 CUs (2 resident blocks each)
 // idle; splitting K multiplies the block count.  Cost model: MFMA time at ~100 TF/s divided by the
 // slot efficiency of tiles*S blocks over the resident-block slots, plus S slabs of C written and read back.
-int pick_split(int64_t M, int64_t N, int64_t K, int64_t slots, bool bx3, int tile_mn) {
-    static const int max_split_env = std::getenv("FSMG_MAX_SPLIT") ? std::max(1, std::atoi(std::getenv("FSMG_MAX_SPLIT"))) : MAX_SPLIT;   // debugging knob
-    if (max_split_env <= 1) return 1;
+int pick_split(int max_split, int64_t M, int64_t N, int64_t K, int64_t slots, bool bx3, int tile_mn) {
+    if (max_split <= 1) return 1;          // the handle's FSMG_MAX_SPLIT (debugging knob: 1 = one K range per GEMM; any other value leaves the policy alone)
     if (slots <= 0) slots = gemm_block_slots();
     if (bx3 && tile_mn == 0) slots = slots * 3 / 4;     // k_gemm_bx3: three resident blocks per CU where k_gemm has four
     const int64_t tm = tile_mn ? tile_mn : gemm_tile_m(), tn = tile_mn ? tile_mn : 128;   // tile_mn = 256: k_gemm_bx3h, `slots` as given
@@ -79,18 +78,20 @@ int ensure_scratch(fsmg_model* h, int B) {
     h->partials_cap = sqnorm_blocks(h->n_flat) + sqnorm_blocks(rows * h->Ep) + 8;
     const int64_t o_part = place(8 * (int64_t)h->partials_cap);
     // split-K slabs: the largest S*M*N over the backward GEMMs of this shape, over every (kernel, slot count) gemm() may pick
-    // -- the 128-tile kernels on 256 .. 1024 slots, the wave-specialised one (682) and the 256 x 256-tile one (256 slots)
+    // -- the 128-tile kernels on 256 .. 1024 slots, the wave-specialised one (682) and the 256 x 256-tile one (256 slots).
+    // Sized with this handle's own cap (max_split), the one its gemm() calls pass: slabs and arena belong to the handle, so another
+    // handle's cap never meets them
     int64_t slab_need = 0, arena_need = 0;
     {
         auto worst = [&](int64_t M, int64_t N, int64_t K) {
             int64_t w = 0;
             for (int64_t slots : {(int64_t)256, (int64_t)512, (int64_t)682, (int64_t)768, (int64_t)gemm_block_slots()}) {
                 for (bool bx : {false, true}) {
-                    const int S = pick_split(M, N, K, slots, bx);
+                    const int S = pick_split(h->max_split, M, N, K, slots, bx);
                     if (S > 1) w = std::max(w, (int64_t)S * M * N);
                 }
             }
-            const int Sh = pick_split(M, N, K, 256, true, 256);
+            const int Sh = pick_split(h->max_split, M, N, K, 256, true, 256);
             if (Sh > 1) w = std::max(w, (int64_t)Sh * M * N);
             return w;
         };
@@ -108,9 +109,9 @@ int ensure_scratch(fsmg_model* h, int B) {
         const int64_t m = ((int64_t)(c + 1) * T / nc - (int64_t)c * T / nc) * B;
         for (int64_t slots : {(int64_t)256, (int64_t)512, (int64_t)768, (int64_t)gemm_block_slots()}) {
             for (bool bx : {false, true}) {
-                const int S = pick_split(m, Hp, h->V1p, slots, bx);
+                const int S = pick_split(h->max_split, m, Hp, h->V1p, slots, bx);
                 if (S > 1) slab_need = std::max(slab_need, (int64_t)S * m * Hp);
-                const int S2 = pick_split(m, h->V1p, Hp, slots, bx);
+                const int S2 = pick_split(h->max_split, m, h->V1p, Hp, slots, bx);
                 if (S2 > 1) slab_need = std::max(slab_need, (int64_t)S2 * m * h->V1p);
             }
         }

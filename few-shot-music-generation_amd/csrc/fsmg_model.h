@@ -183,6 +183,15 @@ struct fsmg_model {
     // section 4): the recurrence packs its rows on the first XCDs and work-queue GEMMs on the auxiliary stream take the XCDs
     // it leaves free
     int bx3 = 1;                        // FSMG_GEMM=f32 selects the fp32-MFMA GEMM, default: bf16-split (k_gemm_bx3)
+    // which bf16-split kernel / how many K slabs a GEMM of this handle may take: read from the environment at creation like every
+    // other knob (a process that sets them before it starts sees what it always saw; two handles of a process may differ)
+    int gemm_h = 1;                     // FSMG_GEMM_H=0 / 2: the 256 x 256-tile kernel never / wherever it can run (use_h_gemm)
+    int gemm_ws = 1;                    // FSMG_GEMM_WS=0 / 2: the wave-specialised kernel never / always (use_ws_gemm)
+    int max_split = fsmg_host::MAX_SPLIT;   // FSMG_MAX_SPLIT=1: one K range per GEMM (pick_split)
+    // GEMM launches the HOST enqueued through this handle, by kernel: [0] fp32 MFMA (k_gemm / k_gemm_staged / k_gemm_queue),
+    // [1] k_gemm_bx3, [2] k_gemm_bx3w, [3] k_gemm_bx3h -- a launch captured into a hipGraph counts once, its replays do not
+    // (fsmg_debug_read("gemm_kinds"))
+    long long gemm_kinds[4] = {};
     bool xov = false, xov_call = false;
     bool xov_eligible = false;          // what `xov` was decided to be at creation before the second-stream probe had its say (fsmg_debug_set("reprobe_aux"))
     bool bucket0_recorded = false;      // backward() recorded ev_bucket[0] itself (two-stream / XCD-partitioned order)
@@ -372,7 +381,7 @@ int upload_tensor(fsmg_model* h, float* flat, const char* name, const float* hos
 int download_tensor(fsmg_model* h, const float* flat, const char* name, float* host, int64_t count);
 
 // ------------------------------------------------------------------ scratch + split-K policy (api_scratch.hip)
-int pick_split(int64_t M, int64_t N, int64_t K, int64_t slots = 0, bool bx3 = false, int tile_mn = 0);
+int pick_split(int max_split, int64_t M, int64_t N, int64_t K, int64_t slots = 0, bool bx3 = false, int tile_mn = 0);    // max_split: the handle's cap (fsmg_model::max_split)
 int ensure_scratch(fsmg_model* h, int B);
 void drop_graphs(fsmg_model* h);
 
@@ -389,6 +398,14 @@ inline Lane aux_lane(fsmg_model* h, bool forward_only = false, bool persistent_c
 // ------------------------------------------------------------------ kernel / order selection (api_schedule.hip)
 bool use_ws_gemm(fsmg_model* h, int amode, int bmode, const GemmArgs& g, const Lane& ln);
 bool use_h_gemm(fsmg_model* h, int amode, int bmode, const GemmArgs& g, const Lane& ln);
+// every GEMM launch of a handle goes through here: tallies the kernel the arguments select (fsmg_model::gemm_kinds) and launches it
+inline hipError_t launch_gemm(fsmg_model* h, hipStream_t s, int amode, int bmode, const GemmArgs& g, int lds_pad = 0) {
+    if (g.M <= 0 || g.N <= 0) return hipSuccess;
+    const hipError_t e = fsmg::launch_gemm(s, amode, bmode, g, lds_pad);
+    // (a work-queue launch that is not the 256 x 256-tile kernel's is k_gemm_queue, fp32 MFMA whatever g.bx3 says)
+    if (e == hipSuccess) ++h->gemm_kinds[(g.bx3 >= 1 && g.bx3 <= 3 && !(g.xcd_first != 0 && g.bx3 != 3)) ? g.bx3 : 0];
+    return e;
+}
 
 // defer != nullptr: a split-K GEMM writes its slabs into the handle's slab ARENA (bump-allocated, reset per backward pass) and
 // leaves their sum as REDUCE ops in *defer instead of launching it -- the caller flushes the batch before the first reader of C

@@ -463,7 +463,11 @@ int fsmg_get_stats(fsmg_handle h, fsmg_stats* out);
  *   rows are TIME-major (row = t*B + b).  count = elements to copy (<= buffer size).
  *   "xcd_bx3" [1]: 1.0 when the handle runs the bf16-split XCD-local recurrent kernels (hidden 512: created for > 64 rows, or for
  *   the XCD-partitioned schedule); "aux_tries" [1]: second streams fsmg_create drew until one ran BESIDE the handle's stream (a process's
- *   streams share GPU_MAX_HW_QUEUES hardware queues; -1: none did and the handle keeps the serial order); "xcd_partitioned" [3]: 1.0 when train passes take the XCD-partitioned order, XCDs the chains occupy, whether the LAST pass took it */
+ *   streams share GPU_MAX_HW_QUEUES hardware queues; -1: none did and the handle keeps the serial order); "xcd_partitioned" [3]: 1.0 when train passes take the XCD-partitioned order, XCDs the chains occupy, whether the LAST pass took it;
+ *   "gemm_kinds" [4]: GEMM launches the host has enqueued through this handle since fsmg_create, by kernel: [0] fp32 MFMA (k_gemm,
+ *   k_gemm_staged, k_gemm_queue), [1] k_gemm_bx3, [2] k_gemm_bx3w (wave-specialised), [3] k_gemm_bx3h (256 x 256 tile).  A launch
+ *   captured into a hipGraph counts once, when it is captured; a replay of the graph does not count again.  Which kernel a GEMM takes
+ *   follows FSMG_GEMM_H / FSMG_GEMM_WS, how many K slabs FSMG_MAX_SPLIT: all three are read by fsmg_create, per handle */
 int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count);
 /* run-time knobs of a handle that used to be create-time environment variables (tests, diagnostics):
  *   "chain_spin_limit"  polls before a persistent recurrent kernel gives up (0 forces the time-out path)

@@ -4,7 +4,8 @@ csrc/api_schedule.hip) and, in all of them, operand loads as buffer loads or thr
 x-contiguous operands through LDS-DMA as well, FSMG_GEMM_DMA).  DESIGN.md claims they produce THE SAME BITS for the same K split -- same LDS image, k order and term order --
 which is what lets the choice be made per shape by measured speed alone.  ("For the same K split": the variants keep a different
 number of blocks per CU, so the split policy may cut K differently for them and the slabs are then summed in a different
-association; FSMG_MAX_SPLIT=1 takes that out of the comparison.)  The knobs are read once per process, so every variant
+association; FSMG_MAX_SPLIT=1 takes that out of the comparison.)  FSMG_GEMM_BUF and FSMG_GEMM_DMA are read once per process (the kernel
+choice, FSMG_GEMM_H / FSMG_GEMM_WS, and FSMG_MAX_SPLIT by fsmg_create, per handle: tests/test_gemm_forced.py), so every variant
 runs in its own interpreter on the same seeded episodes at a production-shaped problem (hidden 512, vocabulary 10001, 45 rows,
 so that every GEMM class of the step takes part) and reports a digest of the losses and of every parameter after three updates."""
 import hashlib

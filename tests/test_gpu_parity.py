@@ -1133,7 +1133,9 @@ def test_forced_kernel_families_on_a_reduced_shape_list(env, idx, monkeypatch):
     """The kernel families a default run only picks at some shapes, forced at a reduced list of SHAPES (B = 45 rows, two stacked
     layers, hidden 512 with 1 / 2 / 4 row groups and stacked): the bf16-split XCD-local recurrence (FSMG_XCD_BX3=1), the
     256 x 256-tile GEMM wherever it can run (FSMG_GEMM_H=2), the serial order where AUTO would take the XCD-partitioned one
-    (FSMG_XCD_OVERLAP=0) -- loss, h, c and every gradient against the fp64 oracle, same bounds as the default families."""
+    (FSMG_XCD_OVERLAP=0) -- loss, h, c and every gradient against the fp64 oracle, same bounds as the default families.
+    Every knob here is read by fsmg_create and stays with the handle, and the handle reports what it then ran: a case whose
+    family did not run fails, however good its numbers are (tests/test_gemm_forced.py takes FSMG_GEMM_H=2 to the tile edges)."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     over, N, K, Q = SHAPES[idx]
@@ -1144,6 +1146,35 @@ def test_forced_kernel_families_on_a_reduced_shape_list(env, idx, monkeypatch):
     loss, cache, grads, aux = cached_oracle_step(('shape', repr(sorted(over.items())), N, K, Q), params, sup, qry, cfg)
     B = N * (K + Q)
     model.forward_backward(sup, qry)
+    d, L = model.debug_dims(), cfg['n_layers']
+    if env.get('FSMG_GEMM_H') == '2':
+        # [fp32 MFMA, k_gemm_bx3, k_gemm_bx3w, k_gemm_bx3h] launches of this first pass.  use_h_gemm (api_schedule.hip) declines by rule a
+        # lane with lds_pad (the two-stream order's auxiliary lane: no shape here takes that order, V1 < 8 H L), a work-queue launch
+        # (xcd_first: the XCD-partitioned order, off here) and an x-contiguous A that is gathered and not the first part of a merged
+        # dK.  Of the 3 + 4 L GEMMs of a pass -- projection, dH, dW and per layer zx, dKh, dKx, dx -- the last rule meets exactly
+        # one: dKx of layer 0 (embedding rows by token id), which falls to k_gemm_bx3 (use_ws_gemm's default rule wants 256 128-tiles),
+        # unless Ep % 256 == 0 makes it the first part of the merged dKx + dKh GEMM (api_backward.hip dk_gemm).  zx of layer 0 gathers
+        # K-contiguous rows, which the 256-tile kernel takes.  A layer above 0 with Hp % 256 == 0 merges its pair too.
+        merged = [(d['Ep'] if l == 0 else d['Hp']) % 256 == 0 for l in range(L)]
+        kinds = [int(x) for x in model.debug_read('gemm_kinds', 4)]
+        assert kinds[3] > 0
+        assert kinds == [0, 0 if merged[0] else 1, 0, 3 + 4 * L - sum(merged) - (0 if merged[0] else 1)]
+        assert model.debug_read('fused_softmax', 2)[1] == 1          # dW on the 256-tile kernel: the pass took the fused softmax
+        if idx == 20:
+            # the merged dK ran (in_p = Ep = 256): with FSMG_MERGE_DK=0 on a second handle the same pass has one launch more, and it
+            # is the gathered dKx on k_gemm_bx3
+            assert merged == [True] and kinds == [0, 0, 0, 6]
+            monkeypatch.setenv('FSMG_MERGE_DK', '0')
+            pair = new_model(cfg, max_sequences=B)
+            pair.forward_backward(sup, qry)
+            assert [int(x) for x in pair.debug_read('gemm_kinds', 4)] == [0, 1, 0, 6]
+    if 'FSMG_XCD_BX3' in env:        # (a no-op at hidden 48 / 32, shapes 2 and 4: only the XCD-local kernels of hidden 512 / 1024 have the format)
+        assert bool(model.debug_read('xcd_bx3', 1)[0]) == (d['Hp'] in (512, 1024))
+    if 'FSMG_XCD_OVERLAP' in env:    # whether this pass took the XCD-partitioned order
+        assert model.debug_read('xcd_partitioned', 3)[2] == float(env['FSMG_XCD_OVERLAP'] == '1')
+    if env.get('FSMG_XCD') == '0':
+        st = model.stats()
+        assert st['xcd_launches'] == 0 and st['persistent_launches'] > 0
     tail = model.debug_read('tail', 16)
     assert abs(tail[1] - loss) <= NLL_RTOL * abs(loss)
     for l in range(cfg['n_layers']):
