@@ -1,6 +1,7 @@
 // Batched on-device decoding: fsmg_generate / fsmg_generate_filtered, fsmg_beam_search, their MAML twins (at theta', through
-// with_adapted_theta in api_step.hip) and fsmg_sample, the one-row greedy case of the generate driver.
-// Host-side C++ only (part of the C-ABI of libfsmg, include/fsmg.h); the kernels live in decode.hip.  DESIGN.md 12-14.
+// with_adapted_theta in api_step.hip) and fsmg_sample, the one-row greedy case of the generate driver; and the decode states
+// (fsmg_dstate_*): the same driver started from a carried LSTM state and committed back to it.
+// Host-side C++ only (part of the C-ABI of libfsmg, include/fsmg.h); the kernels live in decode.hip.  DESIGN.md 12-14, 16.
 #include "fsmg_model.h"
 
 using namespace fsmg;
@@ -33,18 +34,26 @@ struct Decode {
     float* hlp = nullptr;
     int* out_tok = nullptr;                                   // the packed output block, one D2H copy: tokens [R][num], log-probs
     float *out_lp = nullptr, *out_score = nullptr;            // [R][num], beam scores [R]
+    int* flag = nullptr;                                      // one word behind the output block: fsmg_dstate_feed's token-range flag
 };
 
 // The prologue of generate (W = 0) and beam search (W > 0: W rows per primer row): a host primer is range-checked before any device
 // work; the scratch is laid out (h->gen grown if need be); the token buffer rows get [start word, primer row]; a device primer is
 // checked once, before the token loop; the LSTM state is zeroed.
-int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool primer_on_device, const int32_t* primer) {
+// From a decode state (st != nullptr; P = st->kept()) the three differences of a stateful call: the primer region of the token rows
+// is the state's history tail, so that the pending token sits at position P, where the caller's loop starts; h and c are copied
+// from the state (row r from state row r / W); and `primer` is nullptr, or with `feed` the call's [R][num] given tokens (ids in
+// [0, input_size]), which go behind the tail -- a device array's range flag is d.flag, read back with the outputs.
+int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool primer_on_device, const int32_t* primer,
+                 const fsmg_dstate_s* st = nullptr, bool feed = false) {
     const bool beam = W > 0;
     const int rows_per_primer = beam ? W : 1;
-    const size_t n_primer = (size_t)(R / rows_per_primer) * P;
-    if (P > 0 && !primer_on_device) {
+    const size_t n_primer = st ? (feed ? (size_t)R * num : 0) : (size_t)(R / rows_per_primer) * P;
+    if (n_primer > 0 && !primer_on_device) {
+        const int hi = st ? h->V1 : h->V;           // fed tokens may be the start word
         for (size_t i = 0; i < n_primer; ++i)
-            if (primer[i] < 0 || primer[i] >= h->V) return fail(h, FSMG_ERR_TOKEN_RANGE, "primer id outside [0, input_size)");
+            if (primer[i] < 0 || primer[i] >= hi)
+                return fail(h, FSMG_ERR_TOKEN_RANGE, st ? "fed id outside [0, input_size]" : "primer id outside [0, input_size)");
     }
     d.R = R; d.P = P; d.num = num;
     d.ldl = (int)round_up(h->V1, 64);
@@ -56,7 +65,7 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
     const size_t o_logits = place(sizeof(float) * R * d.ldl);
     const size_t o_tok = place(sizeof(int) * R * d.ldtok);
     const size_t o_beam = place(beam ? sizeof(float) * (R + 3 * cands + 3 * n) : 0);
-    const size_t o_out = place(sizeof(float) * (2 * n + (beam ? R : 0)));
+    const size_t o_out = place(sizeof(float) * (2 * n + (beam ? R : 0) + 1));
     const size_t o_primer = place(sizeof(int) * n_primer);
     const size_t o_err = place(sizeof(int));
     int rc = gen_reserve(h, off);
@@ -80,13 +89,23 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
     d.out_tok = (int*)(base + o_out);
     d.out_lp = (float*)(d.out_tok + n);
     d.out_score = d.out_lp + n;
+    d.flag = (int*)(d.out_score + (beam ? R : 0));
     int* err = (int*)(base + o_err);
 
     hipStream_t s = h->stream;
     const int32_t* d_primer = primer;
-    if (P > 0 && !primer_on_device) {
+    if (n_primer > 0 && !primer_on_device) {
         d_primer = (const int32_t*)(base + o_primer);
         HIPCK(h, hipMemcpyAsync((void*)d_primer, primer, sizeof(int) * n_primer, hipMemcpyHostToDevice, s));
+    }
+    if (st) {
+        HIPCK(h, launch_dstate_rows(s, h->L, R, st->R, h->Hp, nullptr, rows_per_primer, st->h, d.h_in, st->c, d.c, st->ctx, st->history + 1, 0,
+                                    d.tok, d.ldtok, 0, P + 1));
+        if (feed) {
+            HIPCK(h, hipMemsetAsync(d.flag, 0, sizeof(int), s));
+            HIPCK(h, launch_dstate_tokens(s, d_primer, R, num, h->V1, h->V, d.tok, d.ldtok, P + 1, d.flag));
+        }
+        return FSMG_OK;
     }
     HIPCK(h, hipMemsetAsync(err, 0, sizeof(int), s));
     HIPCK(h, launch_gen_primer(s, d_primer, R, P, h->V, h->V, d.tok, d.ldtok, err, rows_per_primer));
@@ -101,9 +120,21 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
     return FSMG_OK;
 }
 
+// The end of a stateful call that read `n` tokens behind the state's tail: h (the cells' last output, in d.h_in after the loop's
+// swap), c and the new history tail go back to the state; the counters move on the host.
+int commit_state(fsmg_model* h, const Decode& d, fsmg_dstate_s* st, int n, bool generated) {
+    const int keep = (int)std::min<long long>(st->n_ctx + n, st->history);
+    HIPCK(h, launch_dstate_rows(h->stream, h->L, d.R, d.R, h->Hp, nullptr, 1, d.h_in, st->h, d.c, st->c, d.tok, d.ldtok, d.P + n - keep + 1,
+                                st->ctx, st->history + 1, 1, keep));
+    st->n_ctx += n;
+    if (generated) st->n_gen += n;
+    return FSMG_OK;
+}
+
 // Every layer one position p (it reads tok[:, p]): layer l reads h_in[l] and the new h of the layer below, writes h_out[l] and
-// updates c[l].  At a generated position (p >= P) the top layer's h_out then gives the logits.
-int advance(fsmg_model* h, const Decode& d, int p) {
+// updates c[l].  At a generated position (p >= P), or wherever fsmg_dstate_feed wants a log-prob, the top layer's h_out then gives
+// the logits.
+int advance(fsmg_model* h, const Decode& d, int p, bool logits) {
     const size_t layer = (size_t)d.R * h->Hp;
     const float* x = nullptr;
     for (int l = 0; l < h->L; ++l) {
@@ -112,7 +143,7 @@ int advance(fsmg_model* h, const Decode& d, int p) {
                                  d.c + l * layer, d.R));
         x = d.h_out + l * layer;
     }
-    if (p >= d.P) HIPCK(h, launch_gen_logits(h->stream, h->P + h->off_w, h->V1p, h->P + h->off_d, h->V1, x, h->Hp, d.R, d.logits, d.ldl));
+    if (logits) HIPCK(h, launch_gen_logits(h->stream, h->P + h->off_w, h->V1p, h->P + h->off_d, h->V1, x, h->Hp, d.R, d.logits, d.ldl));
     return FSMG_OK;
 }
 
@@ -188,40 +219,45 @@ int check_beam_config(fsmg_model* h, const fsmg_beam_config* b, const int32_t* p
 }
 
 // fsmg_generate_filtered's work at the parameters the handle holds now (no BEGIN_CALL: the MAML variants call it at theta').
-// f == nullptr or neutral: fsmg_generate's pick.
+// f == nullptr or neutral: fsmg_generate's pick.  st != nullptr: from that decode state (the token loop starts at the pending token,
+// the Philox position runs on from n_gen) and back into it.
 int generate_core(fsmg_model* h, const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* primer, int32_t* out_tokens,
-                  float* out_logprob) {
+                  float* out_logprob, fsmg_dstate_s* st = nullptr) {
     const bool neutral = !f || ((f->top_p == 0.f || f->top_p == 1.f) && f->min_p == 0.f &&
                                 (f->repetition_penalty == 0.f || f->repetition_penalty == 1.f));
     GenFilters pf{};
     if (!neutral) pf = GenFilters{f->top_p, f->min_p, f->repetition_penalty == 0.f ? 1.f : f->repetition_penalty, f->repeat_window};
     const GenFilters* pick_f = neutral ? nullptr : &pf;      // neutral filters: exactly fsmg_generate's pick
     Decode d;
-    int rc = begin_decode(h, d, g->n_seq, 0, g->primer_len, g->num, g->primer_on_device, primer);
+    int rc = begin_decode(h, d, g->n_seq, 0, st ? st->kept() : g->primer_len, g->num, g->primer_on_device, primer, st);
     if (rc != FSMG_OK || d.num == 0) return rc;
+    const int p0 = st ? d.P : 0, ctr0 = st ? (int)st->n_gen : 0;
     // position p reads tok[:, p]; primer positions (p < P) run the cells only, generated position t = p - P writes tok[:, p + 1]
-    for (int p = 0; p < d.P + d.num; ++p) {
-        if ((rc = advance(h, d, p)) != FSMG_OK) return rc;
+    for (int p = p0; p < d.P + d.num; ++p) {
+        if ((rc = advance(h, d, p, p >= d.P)) != FSMG_OK) return rc;
         if (p >= d.P)
-            HIPCK(h, launch_gen_pick(h->stream, d.logits, d.ldl, h->V1, d.R, g->temperature, g->top_k, pick_f, g->seed, p - d.P, d.tok,
-                                     d.ldtok, p + 1, d.out_tok, d.out_lp, d.num));
+            HIPCK(h, launch_gen_pick(h->stream, d.logits, d.ldl, h->V1, d.R, g->temperature, g->top_k, pick_f, g->seed, p - d.P,
+                                     ctr0 + p - d.P, d.tok, d.ldtok, p + 1, d.out_tok, d.out_lp, d.num));
         std::swap(d.h_in, d.h_out);                 // the new state is every row's own
     }
+    if (st && (rc = commit_state(h, d, st, d.num, true)) != FSMG_OK) return rc;
     return read_outputs(h, d, out_tokens, out_logprob);
 }
 
-// fsmg_beam_search's work at the parameters the handle holds now (no BEGIN_CALL, as generate_core)
-int beam_core(fsmg_model* h, const fsmg_beam_config* b, const int32_t* primer, int32_t* out_tokens, float* out_scores, float* out_logprob) {
+// fsmg_beam_search's work at the parameters the handle holds now (no BEGIN_CALL, as generate_core).  st != nullptr: group g starts
+// from row g of that decode state, which is only read.
+int beam_core(fsmg_model* h, const fsmg_beam_config* b, const int32_t* primer, int32_t* out_tokens, float* out_scores, float* out_logprob,
+              const fsmg_dstate_s* st = nullptr) {
     const int G = b->n_groups, W = b->beam_width, L = h->L, Hp = h->Hp;
     hipStream_t s = h->stream;
     Decode d;
     // the primer runs on all G * W rows (row r reads primer[r / W]): the slots of a group stay identical until the first pick
-    int rc = begin_decode(h, d, G * W, W, b->primer_len, b->num, b->primer_on_device, primer);
+    int rc = begin_decode(h, d, G * W, W, st ? st->kept() : b->primer_len, b->num, b->primer_on_device, primer, st);
     if (rc != FSMG_OK) return rc;
     HIPCK(h, launch_beam_init(s, d.cum, d.R, W));
     // position p reads tok[:, p]; generated position t = p - P writes tok[:, p + 1] and par / htok / hlp [t]
-    for (int p = 0; p < d.P + d.num; ++p) {
-        if ((rc = advance(h, d, p)) != FSMG_OK) return rc;
+    for (int p = st ? d.P : 0; p < d.P + d.num; ++p) {
+        if ((rc = advance(h, d, p, p >= d.P)) != FSMG_OK) return rc;
         if (p < d.P) {                              // no choice yet: the new state is every row's own
             std::swap(d.h_in, d.h_out);
             continue;
@@ -238,6 +274,55 @@ int beam_core(fsmg_model* h, const fsmg_beam_config* b, const int32_t* primer, i
     HIPCK(h, launch_beam_backtrace(s, d.R, W, d.num, d.par, d.htok, d.hlp, d.cum, d.out_tok, d.out_lp, d.out_score));
     return read_outputs(h, d, out_tokens, out_logprob, out_scores);
 }
+
+// fsmg_dstate_feed's work: the n given tokens behind the state's tail; position p reads tok[:, p] (the pending token first) and, with
+// log-probs, scores tok[:, p + 1] from its output.  One D2H copy: the log-probs and the device tokens' range flag.
+int feed_core(fsmg_model* h, fsmg_dstate_s* st, const int32_t* tokens, int n, bool on_device, float* out_logprob) {
+    Decode d;
+    int rc = begin_decode(h, d, st->R, 0, st->kept(), n, on_device, tokens, st, true);
+    if (rc != FSMG_OK) return rc;
+    for (int p = d.P; p < d.P + n; ++p) {
+        if ((rc = advance(h, d, p, out_logprob != nullptr)) != FSMG_OK) return rc;
+        if (out_logprob)
+            HIPCK(h, launch_feed_logprob(h->stream, d.logits, d.ldl, h->V1, d.R, d.tok, d.ldtok, p + 1, d.out_lp, n, p - d.P));
+        std::swap(d.h_in, d.h_out);
+    }
+    if ((rc = commit_state(h, d, st, n, false)) != FSMG_OK) return rc;
+    if (!out_logprob && !on_device) {               // host tokens were checked up front: nothing to read back, but the caller's
+        HIPCK(h, hipStreamSynchronize(h->stream));  // array must have been consumed before the call returns
+        return FSMG_OK;
+    }
+    const size_t nlp = out_logprob ? (size_t)d.R * n : 0;
+    std::vector<float> host(nlp + 1);
+    if (out_logprob) {              // [out_lp | flag] are contiguous (generate's layout with no beam scores)
+        HIPCK(h, hipMemcpyAsync(host.data(), d.out_lp, sizeof(float) * (nlp + 1), hipMemcpyDeviceToHost, h->stream));
+    } else {
+        HIPCK(h, hipMemcpyAsync(host.data(), d.flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    int bad = 0;
+    std::memcpy(&bad, host.data() + nlp, sizeof(int));
+    if (on_device && bad) return fail(h, FSMG_ERR_TOKEN_RANGE, "fed id outside [0, input_size] (the state's contents are unspecified now)");
+    if (out_logprob) std::memcpy(out_logprob, host.data(), sizeof(float) * nlp);
+    return FSMG_OK;
+}
+
+// the decode state `st` if this handle owns it (the registry: a destroyed or foreign pointer is never dereferenced)
+fsmg_dstate_s* find_state(fsmg_model* h, fsmg_dstate st) {
+    for (fsmg_dstate_s* s : h->dstates)
+        if (s == st && st != nullptr) return s;
+    fail(h, FSMG_ERR_INVALID, "not a decode state of this handle (never created here, or already destroyed)");
+    return nullptr;
+}
+
+int reset_state(fsmg_model* h, fsmg_dstate_s* st) {
+    HIPCK(h, launch_dstate_reset(h->stream, (long long)h->L * st->R * h->Hp, st->h, st->c, (long long)st->R * (st->history + 1), st->ctx, h->V));
+    st->n_ctx = st->n_gen = 0;
+    return FSMG_OK;
+}
+
+// rows * (history + n + 1) token slots of a stateful call over n tokens: the one-shot calls' bound
+bool state_call_fits(const fsmg_dstate_s* st, int64_t rows, int64_t n) { return rows * ((int64_t)st->history + n + 1) <= (1LL << 30); }
 }  // namespace
 
 }  // namespace fsmg_host
@@ -303,6 +388,185 @@ int fsmg_maml_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_
     if (rc != FSMG_OK) return rc;
     return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
                               [&] { return beam_core(h, b, primer, out_tokens, out_scores, out_logprob); });
+}
+
+// ---- decode states
+int fsmg_dstate_create(fsmg_handle h, const fsmg_dstate_config* c, fsmg_dstate* out) {
+    if (!h) return FSMG_ERR_INVALID;
+    if (!c || !out) return fail(h, FSMG_ERR_INVALID, "null fsmg_dstate_config / out");
+    if (c->version != FSMG_DSTATE_CONFIG_VERSION)
+        return fail(h, FSMG_ERR_INVALID, "fsmg_dstate_config.version is " + std::to_string(c->version) + ", this library expects " +
+                                             std::to_string(FSMG_DSTATE_CONFIG_VERSION));
+    for (int32_t r : c->reserved)
+        if (r != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_dstate_config.reserved must be zero");
+    if (c->n_rows < 1 || c->n_rows > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n_rows must be in [1, 2^20]");
+    if (c->history < 1 || (int64_t)c->n_rows * ((int64_t)c->history + 1) > (1LL << 30))
+        return fail(h, FSMG_ERR_INVALID, "history must be >= 1 and n_rows * (history + 1) <= 2^30");
+    BEGIN_CALL(h);
+    fsmg_dstate_s* st = new (std::nothrow) fsmg_dstate_s;
+    if (!st) return fail(h, FSMG_ERR_NOMEM, "out of host memory");
+    st->R = c->n_rows; st->history = c->history;
+    const size_t layer = (size_t)round_up((int64_t)sizeof(float) * h->L * st->R * h->Hp, 256);
+    const size_t bytes = 2 * layer + sizeof(int) * (size_t)st->R * (st->history + 1);
+    if (hipMalloc((void**)&st->mem, bytes) != hipSuccess) { delete st; return fail(h, FSMG_ERR_NOMEM, "hipMalloc(decode state) failed"); }
+    st->h = (float*)st->mem;
+    st->c = (float*)(st->mem + layer);
+    st->ctx = (int*)(st->mem + 2 * layer);
+    const int rc = reset_state(h, st);
+    if (rc != FSMG_OK) { hipFree(st->mem); delete st; return rc; }
+    h->dstates.push_back(st);
+    *out = st;
+    return FSMG_OK;
+}
+
+int fsmg_dstate_destroy(fsmg_handle h, fsmg_dstate st) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h);
+    HIPCK(h, hipStreamSynchronize(h->stream));      // nothing in flight reads it
+    h->dstates.erase(std::find(h->dstates.begin(), h->dstates.end(), s));
+    hipFree(s->mem);
+    delete s;
+    return FSMG_OK;
+}
+
+int fsmg_dstate_reset(fsmg_handle h, fsmg_dstate st) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h);
+    return reset_state(h, s);
+}
+
+int fsmg_dstate_info(fsmg_handle h, fsmg_dstate st, int64_t out[4]) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    if (!out) return fail(h, FSMG_ERR_INVALID, "null out");
+    out[0] = s->R; out[1] = s->history; out[2] = s->n_ctx; out[3] = s->n_gen;
+    return FSMG_OK;
+}
+
+int fsmg_dstate_get(fsmg_handle h, fsmg_dstate st, float* h_out, float* c_out, int32_t* ctx_out) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h);
+    const size_t rows = (size_t)h->L * s->R, ld = (size_t)s->history + 1;
+    const int keep = s->kept();
+    std::vector<float> hp(rows * h->Hp), cp(rows * h->Hp);
+    std::vector<int> ctx((size_t)s->R * ld);
+    HIPCK(h, hipMemcpyAsync(hp.data(), s->h, sizeof(float) * hp.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipMemcpyAsync(cp.data(), s->c, sizeof(float) * cp.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipMemcpyAsync(ctx.data(), s->ctx, sizeof(int) * ctx.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    for (size_t r = 0; r < rows; ++r) {             // the padded units stay inside
+        if (h_out) std::memcpy(h_out + r * h->H, hp.data() + r * h->Hp, sizeof(float) * h->H);
+        if (c_out) std::memcpy(c_out + r * h->H, cp.data() + r * h->Hp, sizeof(float) * h->H);
+    }
+    if (ctx_out)
+        for (int r = 0; r < s->R; ++r) std::memcpy(ctx_out + (size_t)r * keep, ctx.data() + r * ld + 1, sizeof(int) * keep);
+    return FSMG_OK;
+}
+
+int fsmg_dstate_set(fsmg_handle h, fsmg_dstate st, const float* h_in, const float* c_in, const int32_t* ctx_in, int64_t n_ctx,
+                    int64_t n_gen) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    if (!h_in || !c_in) return fail(h, FSMG_ERR_INVALID, "null h_in / c_in");
+    if (n_ctx < 0 || n_gen < 0 || n_gen > n_ctx || n_gen > INT32_MAX) return fail(h, FSMG_ERR_INVALID, "0 <= n_gen <= n_ctx, n_gen < 2^31");
+    const int keep = (int)std::min<int64_t>(n_ctx, s->history);
+    if (keep > 0 && !ctx_in) return fail(h, FSMG_ERR_INVALID, "n_ctx > 0 needs ctx_in");
+    for (size_t i = 0; i < (size_t)s->R * keep; ++i)
+        if (ctx_in[i] < 0 || ctx_in[i] >= h->V1) return fail(h, FSMG_ERR_TOKEN_RANGE, "ctx_in id outside [0, input_size]");
+    BEGIN_CALL(h);
+    const size_t rows = (size_t)h->L * s->R, ld = (size_t)s->history + 1;
+    std::vector<float> hp(rows * h->Hp, 0.0f), cp(rows * h->Hp, 0.0f);
+    std::vector<int> ctx((size_t)s->R * ld, h->V);
+    for (size_t r = 0; r < rows; ++r) {
+        std::memcpy(hp.data() + r * h->Hp, h_in + r * h->H, sizeof(float) * h->H);
+        std::memcpy(cp.data() + r * h->Hp, c_in + r * h->H, sizeof(float) * h->H);
+    }
+    for (int r = 0; r < s->R; ++r)
+        if (keep > 0) std::memcpy(ctx.data() + r * ld + 1, ctx_in + (size_t)r * keep, sizeof(int) * keep);
+    HIPCK(h, hipMemcpyAsync(s->h, hp.data(), sizeof(float) * hp.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCK(h, hipMemcpyAsync(s->c, cp.data(), sizeof(float) * cp.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCK(h, hipMemcpyAsync(s->ctx, ctx.data(), sizeof(int) * ctx.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));      // the host vectors go out of scope
+    s->n_ctx = n_ctx; s->n_gen = n_gen;
+    return FSMG_OK;
+}
+
+int fsmg_dstate_gather(fsmg_handle h, fsmg_dstate dst, fsmg_dstate src, const int32_t* rows) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* d = find_state(h, dst);
+    fsmg_dstate_s* s = d ? find_state(h, src) : nullptr;
+    if (!d || !s) return FSMG_ERR_INVALID;
+    if (d == s) return fail(h, FSMG_ERR_INVALID, "gather needs dst != src");
+    if (d->history != s->history) return fail(h, FSMG_ERR_INVALID, "gather needs states of equal history");
+    if (!rows) return fail(h, FSMG_ERR_INVALID, "null rows");
+    for (int i = 0; i < d->R; ++i)
+        if (rows[i] < 0 || rows[i] >= s->R) return fail(h, FSMG_ERR_INVALID, "gather index outside [0, src rows)");
+    BEGIN_CALL(h);
+    int rc = gen_reserve(h, sizeof(int) * (size_t)d->R);
+    if (rc != FSMG_OK) return rc;
+    int* d_rows = (int*)h->gen;
+    HIPCK(h, hipMemcpyAsync(d_rows, rows, sizeof(int) * (size_t)d->R, hipMemcpyHostToDevice, h->stream));
+    HIPCK(h, launch_dstate_rows(h->stream, h->L, d->R, s->R, h->Hp, d_rows, 1, s->h, d->h, s->c, d->c, s->ctx, s->history + 1, 0, d->ctx,
+                                d->history + 1, 0, d->history + 1));
+    HIPCK(h, hipStreamSynchronize(h->stream));      // the caller's index array has been consumed
+    d->n_ctx = s->n_ctx; d->n_gen = s->n_gen;
+    return FSMG_OK;
+}
+
+int fsmg_dstate_feed(fsmg_handle h, fsmg_dstate st, const int32_t* tokens, int32_t n, int32_t tokens_on_device, float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    if (n < 0) return fail(h, FSMG_ERR_INVALID, "n must be >= 0");
+    if (tokens_on_device != 0 && tokens_on_device != 1) return fail(h, FSMG_ERR_INVALID, "tokens_on_device must be 0 or 1");
+    if (n > 0 && !tokens) return fail(h, FSMG_ERR_INVALID, "null tokens");
+    if (!state_call_fits(s, s->R, n)) return fail(h, FSMG_ERR_INVALID, "rows * (history + n + 1) too large");
+    if (n == 0) return FSMG_OK;
+    BEGIN_CALL(h);
+    return feed_core(h, s, tokens, n, tokens_on_device != 0, out_logprob);
+}
+
+int fsmg_dstate_generate(fsmg_handle h, fsmg_dstate st, const fsmg_gen_config* g, const fsmg_gen_filters* f, int32_t* out_tokens,
+                         float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    int rc = check_gen_config(h, g, nullptr, out_tokens);
+    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    if (rc != FSMG_OK) return rc;
+    if (g->n_seq != s->R) return fail(h, FSMG_ERR_INVALID, "n_seq must be the state's row count");
+    if (g->primer_len != 0) return fail(h, FSMG_ERR_INVALID, "primer_len must be 0 with a decode state (feed the primer)");
+    if (!state_call_fits(s, s->R, g->num)) return fail(h, FSMG_ERR_INVALID, "rows * (history + num + 1) too large");
+    if (s->n_gen + g->num > INT32_MAX) return fail(h, FSMG_ERR_INVALID, "n_gen + num exceeds 2^31 - 1");
+    if (f && f->repetition_penalty != 0.f && f->repetition_penalty != 1.f) {      // the penalty must find its whole window in the history
+        if (f->repeat_window > s->history) return fail(h, FSMG_ERR_INVALID, "repeat_window must be in [1, history]");
+        if (f->repeat_window == 0 && s->n_ctx + g->num > s->history)
+            return fail(h, FSMG_ERR_INVALID, "repeat_window 0 (the whole context) needs n_ctx + num <= history");
+    }
+    BEGIN_CALL(h);
+    return generate_core(h, g, f, nullptr, out_tokens, out_logprob, s);
+}
+
+int fsmg_dstate_beam_search(fsmg_handle h, fsmg_dstate st, const fsmg_beam_config* b, int32_t* out_tokens, float* out_scores,
+                            float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    const int rc = check_beam_config(h, b, nullptr, out_tokens, out_scores);
+    if (rc != FSMG_OK) return rc;
+    if (b->n_groups != s->R) return fail(h, FSMG_ERR_INVALID, "n_groups must be the state's row count");
+    if (b->primer_len != 0) return fail(h, FSMG_ERR_INVALID, "primer_len must be 0 with a decode state (feed the primer)");
+    if (!state_call_fits(s, (int64_t)s->R * b->beam_width, b->num)) return fail(h, FSMG_ERR_INVALID, "rows * beam_width * (history + num + 1) too large");
+    BEGIN_CALL(h);
+    return beam_core(h, b, nullptr, out_tokens, out_scores, out_logprob, s);
 }
 
 }  // extern "C"

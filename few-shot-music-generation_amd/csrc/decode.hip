@@ -329,14 +329,16 @@ __device__ __forceinline__ void write_pick(int best, const float* __restrict__ r
     }
 }
 
-// One row per workgroup.  Token = argmax over the allowed set of logit / T + Gumbel(Philox(key = seed, ctr = (v >> 2, t, b, 0))),
-// lowest index on ties; T == 0 or top_k == 1: argmax of the logits.  Allowed set: logit >= the top_k-th largest logit (radix
+// One row per workgroup.  Token = argmax over the allowed set of logit / T + Gumbel(Philox(key = seed, ctr = (v >> 2, ctr_t, b, 0))),
+// lowest index on ties; T == 0 or top_k == 1: argmax of the logits.  ctr_t is the Philox position, t the output index: equal in a
+// one-shot call, ctr_t = n_gen + t when the call continues a decode state.  Allowed set: logit >= the top_k-th largest logit (radix
 // select on order-preserving keys), every column when top_k is 0 or ncols.  Writes the token into the token buffer (the next
 // position's input), out_tok / out_lp [b][t], lp = logit_tok - logsumexp(all ncols logits).
 template <bool STAGED>
 __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick(const float* __restrict__ logits, int ldl, int ncols, float temperature, int top_k,
-                                                           unsigned seed_lo, unsigned seed_hi, int t, int* __restrict__ tok, int ldtok,
-                                                           int pos_out, int* __restrict__ out_tok, float* __restrict__ out_lp, int num) {
+                                                           unsigned seed_lo, unsigned seed_hi, int t, int ctr_t, int* __restrict__ tok,
+                                                           int ldtok, int pos_out, int* __restrict__ out_tok, float* __restrict__ out_lp,
+                                                           int num) {
     extern __shared__ float srow[];
     __shared__ PickShared sh;
     const int b = blockIdx.x;
@@ -351,7 +353,7 @@ __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick(const float* __restri
         float thr = -INFINITY;
         if (top_k > 1 && top_k < ncols)
             thr = key_float(radix_select(sh.rs, ncols, [&](int v) { return fkey(val(v)); }, [](int) { return 1; }, [&](int) { return top_k; }));
-        best = gumbel_max(sh, ncols, thr, temperature, seed_lo, seed_hi, t, b, 0, val);
+        best = gumbel_max(sh, ncols, thr, temperature, seed_lo, seed_hi, ctr_t, b, 0, val);
     }
     write_pick(best, row, lse, ncols, b, t, tok, ldtok, pos_out, out_tok, out_lp, num);
 }
@@ -548,9 +550,9 @@ __global__ void k_beam_backtrace(int R, int W, int num, const int* __restrict__ 
 template <bool STAGED>
 __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick_filtered(const float* __restrict__ logits, int ldl, int ncols, float temperature,
                                                                     int top_k, float top_p, float min_p, float theta, int window,
-                                                                    unsigned seed_lo, unsigned seed_hi, int t, int* __restrict__ tok,
-                                                                    int ldtok, int pos_out, int* __restrict__ out_tok,
-                                                                    float* __restrict__ out_lp, int num) {
+                                                                    unsigned seed_lo, unsigned seed_hi, int t, int ctr_t,
+                                                                    int* __restrict__ tok, int ldtok, int pos_out,
+                                                                    int* __restrict__ out_tok, float* __restrict__ out_lp, int num) {
     extern __shared__ float srow[];
     __shared__ PickShared sh;
     __shared__ RadixShared<unsigned long long> fs;
@@ -623,9 +625,80 @@ __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick_filtered(const float*
                 });
             if (xp != 0u) thr = key_float(xp);          // a survivor's key, so >= the thresholds above
         }
-        best = gumbel_max(sh, ncols, thr, temperature, seed_lo, seed_hi, t, b, zi, val);
+        best = gumbel_max(sh, ncols, thr, temperature, seed_lo, seed_hi, ctr_t, b, zi, val);
     }
     write_pick(best, row, lse, ncols, b, t, tok, ldtok, pos_out, out_tok, out_lp, num);
+}
+
+// ---------------------------------------------------------------- decode states (fsmg_dstate_*, DESIGN.md "Decode states")
+// The teacher-forced log-prob of fsmg_dstate_feed; one row per workgroup.  lse is the picks' (row_max_lse), so that the log-prob feed
+// returns for a token is bitwise the number a pick that chose it reports: out_lp[b][i] = logit[target] - lse, the target the token
+// the row reads next, tok[b][pos_tgt] (clamped into [0, ncols): it indexes the row).
+template <bool STAGED>
+__global__ __launch_bounds__(PICK_THREADS) void k_feed_logprob(const float* __restrict__ logits, int ldl, int ncols,
+                                                               const int* __restrict__ tok, int ldtok, int pos_tgt,
+                                                               float* __restrict__ out_lp, int n, int i) {
+    extern __shared__ float srow[];
+    __shared__ PickShared sh;
+    const int b = blockIdx.x;
+    const float* row = logits + (long long)b * ldl;
+    float mx; int mi;
+    const float lse = row_max_lse<STAGED>(sh, row, srow, ncols, mx, mi);
+    if (threadIdx.x == 0) {
+        const int y = min(max(tok[(long long)b * ldtok + pos_tgt], 0), ncols - 1);
+        out_lp[(long long)b * n + i] = row[y] - lse;
+    }
+}
+
+// Rows of a decode state: dst row i takes src row (rows != nullptr ? rows[i] : i / div), h and c of every layer ([L][R][Hp], float4
+// per thread) and ntok tokens, tok_src[row][off_src ..] -> tok_dst[i][off_dst ..].  The load of a stateful call (div = W for beam
+// search), its commit (div = 1) and fsmg_dstate_gather (rows) are this kernel.  A row index outside [0, Rs) copies nothing.
+__global__ void k_dstate_rows(int L, int Rd, int Rs, int Hp, const int* __restrict__ rows, int div, const float* __restrict__ h_src,
+                              float* __restrict__ h_dst, const float* __restrict__ c_src, float* __restrict__ c_dst,
+                              const int* __restrict__ tok_src, int ld_src, int off_src, int* __restrict__ tok_dst, int ld_dst, int off_dst,
+                              int ntok) {
+    const int q4 = Hp >> 2;
+    const long long n_state = (long long)L * Rd * q4, n = n_state + (long long)Rd * ntok;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        if (i < n_state) {
+            const int u = (int)(i % q4);
+            const long long lr = i / q4;
+            const int r = (int)(lr % Rd), l = (int)(lr / Rd);
+            const int sr = rows != nullptr ? rows[r] : r / div;
+            if (sr < 0 || sr >= Rs) continue;
+            const long long src = ((long long)l * Rs + sr) * Hp + 4 * u, dst = lr * Hp + 4 * u;
+            *(float4*)(h_dst + dst) = *(const float4*)(h_src + src);
+            *(float4*)(c_dst + dst) = *(const float4*)(c_src + src);
+        } else {
+            const long long j = i - n_state;
+            const int r = (int)(j / ntok), p = (int)(j % ntok);
+            const int sr = rows != nullptr ? rows[r] : r / div;
+            if (sr < 0 || sr >= Rs) continue;
+            tok_dst[(long long)r * ld_dst + off_dst + p] = tok_src[(long long)sr * ld_src + off_src + p];
+        }
+    }
+}
+
+// a fresh state: zero h and c ([L][R][Hp]), every token slot the start word
+__global__ void k_dstate_reset(long long n_state, float* __restrict__ hh, float* __restrict__ cc, long long n_tok, int* __restrict__ tok,
+                               int start) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n_state + n_tok; i += (long long)gridDim.x * blockDim.x) {
+        if (i < n_state) { hh[i] = 0.0f; cc[i] = 0.0f; }
+        else tok[i - n_state] = start;
+    }
+}
+
+// the fed tokens of a call, tokens [R][n] -> tok[r][off + i]; *err = 1 for an id outside [0, ncols) (the start word is allowed), which
+// is stored as the start word: the cells gather an embedding row by it
+__global__ void k_dstate_tokens(const int* __restrict__ tokens, int R, int n, int ncols, int start, int* __restrict__ tok, int ldtok, int off,
+                                int* __restrict__ err) {
+    const long long total = (long long)R * n;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int r = (int)(i / n), p = (int)(i % n);
+        int w = tokens[i];
+        if (w < 0 || w >= ncols) { atomicOr(err, 1); w = start; }
+        tok[(long long)r * ldtok + off + p] = w;
+    }
 }
 
 }  // namespace
@@ -675,19 +748,19 @@ hipError_t launch_row_kernel(hipStream_t s, int rows, int ncols, size_t lds, Arg
 }  // namespace
 
 hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, const GenFilters* f,
-                           uint64_t seed, int t, int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num) {
+                           uint64_t seed, int t, int ctr_t, int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num) {
     if (B <= 0) return hipSuccess;
-    if (ncols <= 0 || ncols > ldl || t < 0 || t >= num || pos_out >= ldtok || (f && f->window < 0)) return hipErrorInvalidValue;
+    if (ncols <= 0 || ncols > ldl || t < 0 || t >= num || ctr_t < t || pos_out >= ldtok || (f && f->window < 0)) return hipErrorInvalidValue;
     const unsigned lo = (unsigned)(seed & 0xFFFFFFFFull), hi = (unsigned)(seed >> 32);
     if (!f)
-        return launch_row_kernel<k_gen_pick<true>, k_gen_pick<false>>(s, B, ncols, 0, logits, ldl, ncols, temperature, top_k, lo, hi, t, tok,
-                                                                      ldtok, pos_out, out_tok, out_lp, num);
+        return launch_row_kernel<k_gen_pick<true>, k_gen_pick<false>>(s, B, ncols, 0, logits, ldl, ncols, temperature, top_k, lo, hi, t, ctr_t,
+                                                                      tok, ldtok, pos_out, out_tok, out_lp, num);
     // an unstaged row with a penalty keeps a presence bitmap of its columns in LDS
     const size_t bitmap_bytes = f->theta != 1.0f ? sizeof(unsigned) * (size_t)((ncols + 31) / 32) : 0;
     if (bitmap_bytes > sizeof(float) * PICK_LDS_FLOATS) return hipErrorInvalidValue;
     return launch_row_kernel<k_gen_pick_filtered<true>, k_gen_pick_filtered<false>>(s, B, ncols, bitmap_bytes, logits, ldl, ncols, temperature,
                                                                                     top_k, f->top_p, f->min_p, f->theta, f->window, lo, hi, t,
-                                                                                    tok, ldtok, pos_out, out_tok, out_lp, num);
+                                                                                    ctr_t, tok, ldtok, pos_out, out_tok, out_lp, num);
 }
 
 hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err,
@@ -739,6 +812,43 @@ hipError_t launch_beam_backtrace(hipStream_t s, int R, int W, int num, const int
     if (R <= 0) return hipSuccess;
     if (W < 1 || R % W || num < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_beam_backtrace, dim3((R + 255) / 256), dim3(256), 0, s, R, W, num, par, htok, hlp, cum, out_tok, out_lp, out_score);
+    return hipGetLastError();
+}
+
+hipError_t launch_feed_logprob(hipStream_t s, const float* logits, int ldl, int ncols, int R, const int* tok, int ldtok, int pos_tgt,
+                               float* out_lp, int n, int i) {
+    if (R <= 0) return hipSuccess;
+    if (ncols <= 0 || ncols > ldl || i < 0 || i >= n || pos_tgt < 0 || pos_tgt >= ldtok) return hipErrorInvalidValue;
+    return launch_row_kernel<k_feed_logprob<true>, k_feed_logprob<false>>(s, R, ncols, 0, logits, ldl, ncols, tok, ldtok, pos_tgt, out_lp, n, i);
+}
+
+hipError_t launch_dstate_rows(hipStream_t s, int L, int Rd, int Rs, int Hp, const int* rows, int div, const float* h_src, float* h_dst,
+                              const float* c_src, float* c_dst, const int* tok_src, int ld_src, int off_src, int* tok_dst, int ld_dst,
+                              int off_dst, int ntok) {
+    if (Rd <= 0) return hipSuccess;
+    if ((Hp & 3) || Rs <= 0 || div < 1 || ntok < 0 || off_src < 0 || off_dst < 0 || off_src + ntok > ld_src || off_dst + ntok > ld_dst ||
+        (rows == nullptr && (long long)(Rd - 1) / div >= Rs))
+        return hipErrorInvalidValue;
+    const long long n = (long long)L * Rd * (Hp / 4) + (long long)Rd * ntok;
+    const int blocks = (int)std::min<long long>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_dstate_rows, dim3(blocks), dim3(256), 0, s, L, Rd, Rs, Hp, rows, div, h_src, h_dst, c_src, c_dst, tok_src, ld_src,
+                       off_src, tok_dst, ld_dst, off_dst, ntok);
+    return hipGetLastError();
+}
+
+hipError_t launch_dstate_reset(hipStream_t s, long long n_state, float* hh, float* cc, long long n_tok, int* tok, int start) {
+    if (n_state + n_tok <= 0) return hipSuccess;
+    const int blocks = (int)std::min<long long>((n_state + n_tok + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_dstate_reset, dim3(blocks), dim3(256), 0, s, n_state, hh, cc, n_tok, tok, start);
+    return hipGetLastError();
+}
+
+hipError_t launch_dstate_tokens(hipStream_t s, const int* tokens, int R, int n, int ncols, int start, int* tok, int ldtok, int off, int* err) {
+    if (R <= 0 || n <= 0) return hipSuccess;
+    if (tokens == nullptr || off < 0 || off + n > ldtok || start < 0 || start >= ncols) return hipErrorInvalidValue;
+    const long long total = (long long)R * n;
+    const int blocks = (int)std::min<long long>((total + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_dstate_tokens, dim3(blocks), dim3(256), 0, s, tokens, R, n, ncols, start, tok, ldtok, off, err);
     return hipGetLastError();
 }
 

@@ -397,11 +397,12 @@ struct GenFilters {
     float top_p, min_p, theta;
     int window;
 };
-// per row b: Gumbel-max draw of generated token t (temperature, top_k, filters f, Philox key = seed) -> tok[b * ldtok + pos_out],
-// out_tok[b * num + t], out_lp[b * num + t] = logit - logsumexp.  f == nullptr: no filters (k_gen_pick).  ncols above 2^20 with a
-// penalty: hipErrorInvalidValue (the presence bitmap of an unstaged row lives in LDS).
+// per row b: Gumbel-max draw of generated token t (temperature, top_k, filters f, Philox key = seed, Philox position ctr_t >= t: t in
+// a one-shot call, n_gen + t in a call that continues a decode state) -> tok[b * ldtok + pos_out], out_tok[b * num + t],
+// out_lp[b * num + t] = logit - logsumexp.  f == nullptr: no filters (k_gen_pick).  ncols above 2^20 with a penalty:
+// hipErrorInvalidValue (the presence bitmap of an unstaged row lives in LDS).
 hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, const GenFilters* f,
-                           uint64_t seed, int t, int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num);
+                           uint64_t seed, int t, int ctr_t, int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num);
 // tok rows [start, primer[b / rows_per_primer][0..P-1]]; *err |= 1 for a primer id outside [0, vocab)
 hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err,
                              int rows_per_primer = 1);
@@ -420,6 +421,19 @@ hipError_t launch_beam_reorder(hipStream_t s, int L, int R, int W, int Hp, const
 // par / htok / hlp [num][R] -> out_tok / out_lp [R][num], out_score [R] = cum
 hipError_t launch_beam_backtrace(hipStream_t s, int R, int W, int num, const int* par, const int* htok, const float* hlp, const float* cum,
                                  int* out_tok, float* out_lp, float* out_score);
+// decode states (decode.hip, fsmg_dstate_*): no allocation, no synchronisation.
+// per row b: out_lp[b * n + i] = logits[b][tok[b * ldtok + pos_tgt]] - logsumexp (the picks' lse, bitwise)
+hipError_t launch_feed_logprob(hipStream_t s, const float* logits, int ldl, int ncols, int R, const int* tok, int ldtok, int pos_tgt,
+                               float* out_lp, int n, int i);
+// dst row i takes src row (rows ? rows[i] : i / div; rows a DEVICE array of Rd indices, one outside [0, Rs) copies nothing): h / c
+// [L][R][Hp] and ntok tokens tok_src[row * ld_src + off_src ..] -> tok_dst[i * ld_dst + off_dst ..]
+hipError_t launch_dstate_rows(hipStream_t s, int L, int Rd, int Rs, int Hp, const int* rows, int div, const float* h_src, float* h_dst,
+                              const float* c_src, float* c_dst, const int* tok_src, int ld_src, int off_src, int* tok_dst, int ld_dst,
+                              int off_dst, int ntok);
+// hh / cc [n_state] = 0, tok [n_tok] = start
+hipError_t launch_dstate_reset(hipStream_t s, long long n_state, float* hh, float* cc, long long n_tok, int* tok, int start);
+// tokens [R][n] -> tok[r * ldtok + off + i]; *err |= 1 for an id outside [0, ncols) (stored as `start`)
+hipError_t launch_dstate_tokens(hipStream_t s, const int* tokens, int R, int n, int ncols, int start, int* tok, int ldtok, int off, int* err);
 
 // ---------------------------------------------------------------- scoring (score.hip, fsmg_score)
 // Per row r = t * B + b of the time-major logits [rows = T * B][ld] (the first n_vocab columns count; ld % 4 == 0) against the target

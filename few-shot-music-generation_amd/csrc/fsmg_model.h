@@ -8,7 +8,7 @@
 //   api_update.hip    clip + Adam, inner-loop SGD, time-out bookkeeping, loss read-back
 //   api_step.hip      train / eval / MAML-style entry points          api_comm.hip  RCCL glue (fsmg_comm_*)
 //   api_unigram.hip   unigram baseline                                 api_debug.hip debug reads, timers, clock probe
-//   api_decode.hip    decoding: fsmg_generate(_filtered), fsmg_beam_search, their MAML twins, fsmg_sample (one driver)
+//   api_decode.hip    decoding: fsmg_generate(_filtered), fsmg_beam_search, their MAML twins, fsmg_sample (one driver); decode states (fsmg_dstate_*)
 //   api_score.hip     scoring of given songs: fsmg_score, fsmg_maml_score
 #pragma once
 #include <atomic>
@@ -55,6 +55,17 @@ struct TimerClass {
 };
 
 }  // namespace fsmg_host
+
+// A decode state (fsmg_dstate_*, api_decode.hip): its own allocation, [h | c | ctx].  ctx rows are laid out as the head of a decode
+// call's token rows: [start word, the last min(n_ctx, history) context tokens oldest first], the pending token the last of them.
+struct fsmg_dstate_s {
+    int R = 0, history = 0;
+    long long n_ctx = 0, n_gen = 0;
+    char* mem = nullptr;
+    float *h = nullptr, *c = nullptr;   // [L][R][Hp]
+    int* ctx = nullptr;                 // [R][history + 1]
+    int kept() const { return (int)std::min<long long>(n_ctx, history); }
+};
 
 struct fsmg_model {
     fsmg_config cfg{};
@@ -214,6 +225,7 @@ struct fsmg_model {
     // decoding (api_decode.hip): its own scratch, grown between calls after a stream sync
     char* gen = nullptr;
     size_t gen_bytes = 0;
+    std::vector<fsmg_dstate_s*> dstates;   // the decode states this handle owns (fsmg_dstate_create): every entry point looks its state up here
 
     // gradient exchange inside the library (fsmg_comm_*): RCCL communicator, its stream, the event the compute stream waits on
     void* comm = nullptr; bool own_comm = false; int world = 1, rank = 0;

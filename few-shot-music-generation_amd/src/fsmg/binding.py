@@ -82,6 +82,13 @@ class FsmgScoreConfig(C.Structure):
                 ('nll_count', C.c_int32), ('pass_rows', C.c_int32), ('reserved', C.c_int32 * 10)]
 
 
+FSMG_DSTATE_CONFIG_VERSION = 1
+
+
+class FsmgDstateConfig(C.Structure):
+    _fields_ = [('version', C.c_int32), ('n_rows', C.c_int32), ('history', C.c_int32), ('reserved', C.c_int32 * 9)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -136,6 +143,16 @@ SIGNATURES = {
     'fsmg_score': (C.c_int, [_P, C.POINTER(FsmgScoreConfig), _P, _F32P, _I32P, _F32P, _I32P, _F32P]),
     'fsmg_maml_score': (C.c_int, [_P, C.POINTER(FsmgScoreConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _F32P, _I32P,
                                   _F32P, _I32P, _F32P]),
+    'fsmg_dstate_create': (C.c_int, [_P, C.POINTER(FsmgDstateConfig), C.POINTER(_P)]),
+    'fsmg_dstate_destroy': (C.c_int, [_P, _P]),
+    'fsmg_dstate_reset': (C.c_int, [_P, _P]),
+    'fsmg_dstate_info': (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
+    'fsmg_dstate_get': (C.c_int, [_P, _P, _F32P, _F32P, _I32P]),
+    'fsmg_dstate_set': (C.c_int, [_P, _P, _F32P, _F32P, _I32P, C.c_int64, C.c_int64]),
+    'fsmg_dstate_gather': (C.c_int, [_P, _P, _P, _I32P]),
+    'fsmg_dstate_feed': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _F32P]),
+    'fsmg_dstate_generate': (C.c_int, [_P, _P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _I32P, _F32P]),
+    'fsmg_dstate_beam_search': (C.c_int, [_P, _P, C.POINTER(FsmgBeamConfig), _I32P, _F32P, _F32P]),
     'fsmg_read_losses': (C.c_int, [_P, _F32P, C.c_int32]),
     'fsmg_get_stats': (C.c_int, [_P, C.POINTER(FsmgStats)]),
     'fsmg_debug_read': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
@@ -197,6 +214,82 @@ def _tok_ptr(tokens):
         return C.c_void_p(int(tokens)), 1, None
     a = np.ascontiguousarray(tokens, dtype=np.int32)
     return C.c_void_p(a.ctypes.data), 0, a
+
+
+class DecodeState(object):
+    """A decode state of an FsmgModel (include/fsmg.h fsmg_dstate_*): h and c of every layer, the pending token and the last
+    `history` context tokens of `rows` decode rows, resident on the device.  Made by FsmgModel.new_state; FsmgModel.feed and the
+    state= keyword of FsmgModel.generate / beam_search start from it (feed and generate leave it advanced)."""
+
+    def __init__(self, model, rows, history):
+        self._model = model
+        self.rows, self.history = int(rows), int(history)
+        c = FsmgDstateConfig(version=FSMG_DSTATE_CONFIG_VERSION, n_rows=self.rows, history=self.history)
+        st = _P()
+        model._ck(model._lib.fsmg_dstate_create(model._h, C.byref(c), C.byref(st)))
+        self._st = st
+
+    def close(self):
+        # (a state whose model is closed already went with it: fsmg_destroy frees what is left)
+        if getattr(self, '_st', None) and getattr(self._model, '_h', None):
+            self._model._lib.fsmg_dstate_destroy(self._model._h, self._st)
+        self._st = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _call(self, fn, *args):
+        if not getattr(self, '_st', None):
+            raise FsmgError(-1, 'the decode state is closed')
+        self._model._ck(fn(self._model._h, self._st, *args))
+
+    def reset(self):
+        """back to the fresh state: zero h and c, no context, the start word pending"""
+        self._call(self._model._lib.fsmg_dstate_reset)
+
+    def info(self):
+        out = (C.c_int64 * 4)()
+        self._call(self._model._lib.fsmg_dstate_info, out)
+        return dict(rows=int(out[0]), history=int(out[1]), n_ctx=int(out[2]), n_gen=int(out[3]))
+
+    def _layers(self):
+        return int(self._model.cfg.n_layers), int(self._model.cfg.hidden_size)
+
+    def get(self):
+        """-> dict: 'h', 'c' float32 [L, rows, H], 'ctx' int32 [rows, min(n_ctx, history)] (oldest first), 'n_ctx', 'n_gen'"""
+        L, H = self._layers()
+        info = self.info()
+        hh, cc = np.empty((L, self.rows, H), np.float32), np.empty((L, self.rows, H), np.float32)
+        ctx = np.empty((self.rows, min(info['n_ctx'], self.history)), np.int32)
+        self._call(self._model._lib.fsmg_dstate_get, _f32p(hh), _f32p(cc), ctx.ctypes.data_as(_I32P))
+        return dict(h=hh, c=cc, ctx=ctx, n_ctx=info['n_ctx'], n_gen=info['n_gen'])
+
+    def set(self, h, c, ctx=None, n_ctx=0, n_gen=0):
+        """the reverse of get: h, c [L, rows, H]; ctx [rows, min(n_ctx, history)] (None when n_ctx is 0)"""
+        L, H = self._layers()
+        hh, cc = np.ascontiguousarray(h, dtype=np.float32), np.ascontiguousarray(c, dtype=np.float32)
+        if hh.shape != (L, self.rows, H) or cc.shape != (L, self.rows, H):
+            raise ValueError('h and c must be [%d, %d, %d], got %r and %r' % (L, self.rows, H, hh.shape, cc.shape))
+        keep = min(int(n_ctx), self.history)
+        a = None
+        if keep > 0:
+            a = np.ascontiguousarray(ctx, dtype=np.int32)
+            if a.shape != (self.rows, keep):
+                raise ValueError('ctx must be [%d, %d], got %r' % (self.rows, keep, a.shape))
+        self._call(self._model._lib.fsmg_dstate_set, _f32p(hh), _f32p(cc), a.ctypes.data_as(_I32P) if a is not None else None,
+                   int(n_ctx), int(n_gen))
+
+    def gather(self, src, rows):
+        """this state's row i = row rows[i] of src (another state of the same model and history); the counters are copied"""
+        idx = np.ascontiguousarray(rows, dtype=np.int32)
+        if idx.shape != (self.rows,):
+            raise ValueError('rows must be [%d] indices, got %r' % (self.rows, idx.shape))
+        if not isinstance(src, DecodeState) or not getattr(src, '_st', None):
+            raise ValueError('src must be an open DecodeState')
+        self._call(self._model._lib.fsmg_dstate_gather, src._st, idx.ctypes.data_as(_I32P))
 
 
 class FsmgModel(object):
@@ -523,12 +616,47 @@ class FsmgModel(object):
         return (toks, lp) if logprobs else toks
 
     def generate(self, n_seq, num, temperature=1.0, top_k=0, seed=0, primer=None, logprobs=False, top_p=0.0, min_p=0.0,
-                 repetition_penalty=1.0, repeat_window=0):
+                 repetition_penalty=1.0, repeat_window=0, state=None):
         """n_seq independent samples of num tokens -> int32 [n_seq, num] (, float32 [n_seq, num] log-probs with logprobs=True).
         primer: int32 [n_seq, P] (or [P] for every row) continued by each row, or (device address, P).  top_p, min_p,
-        repetition_penalty, repeat_window: the sampling filters of fsmg_generate_filtered (all off: fsmg_generate)."""
-        return self._generate((), n_seq, num, temperature, top_k, seed, primer, logprobs,
-                              (top_p, min_p, repetition_penalty, repeat_window))
+        repetition_penalty, repeat_window: the sampling filters of fsmg_generate_filtered (all off: fsmg_generate).
+        state: a DecodeState of n_seq rows to continue and leave advanced (fsmg_dstate_generate; no primer then: feed it)."""
+        filters = (top_p, min_p, repetition_penalty, repeat_window)
+        if state is None:
+            return self._generate((), n_seq, num, temperature, top_k, seed, primer, logprobs, filters)
+        if primer is not None:
+            raise ValueError('a state takes no primer: feed it first')
+        if int(n_seq) != state.rows:
+            raise ValueError('n_seq %d is not the row count of the state (%d)' % (int(n_seq), state.rows))
+        g = self.gen_config(n_seq, num, temperature, top_k, seed)
+        f = self.gen_filters(*filters)
+        toks = np.empty((int(n_seq), int(num)), np.int32)
+        lp = np.empty((int(n_seq), int(num)), np.float32) if logprobs else None
+        state._call(self._lib.fsmg_dstate_generate, C.byref(g), C.byref(f) if f is not None else None, toks.ctypes.data_as(_I32P),
+                    _f32p(lp) if logprobs else None)
+        return (toks, lp) if logprobs else toks
+
+    # -- decode states (include/fsmg.h fsmg_dstate_*) ---------------------------------------------------------
+    def new_state(self, rows, history=1024):
+        """a fresh DecodeState of `rows` rows that keeps the last `history` context tokens (the repetition penalty's reach)"""
+        return DecodeState(self, rows, history)
+
+    def feed(self, state, tokens, logprobs=False):
+        """read given tokens int32 [rows, n] (one [n] row: for every row; or (device address, n)) into the state; ids in
+        [0, input_size], the start word included.  logprobs=True -> float32 [rows, n], the model log-probability of each token
+        given everything the row has read; else None, and no logits are computed."""
+        if isinstance(tokens, tuple):                 # (device address, n)
+            tp, n, dev, _keep = C.c_void_p(int(tokens[0])), int(tokens[1]), 1, None
+        else:
+            a = np.ascontiguousarray(tokens, dtype=np.int32)
+            if a.ndim == 1:
+                a = np.ascontiguousarray(np.broadcast_to(a, (state.rows, a.size)))
+            if a.ndim != 2 or a.shape[0] != state.rows:
+                raise ValueError('tokens must be [%d, n] (or one [n] row for every row), got %r' % (state.rows, a.shape))
+            tp, n, dev, _keep = C.c_void_p(a.ctypes.data), a.shape[1], 0, a
+        lp = np.empty((state.rows, n), np.float32) if logprobs else None
+        state._call(self._lib.fsmg_dstate_feed, tp, n, dev, _f32p(lp) if logprobs else None)
+        return lp
 
     def maml_generate(self, support, num, inner_steps, inner_lr, n_seq=1, temperature=1.0, top_k=0, seed=0, primer=None,
                       logprobs=False, n_support_rows=None, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
@@ -555,11 +683,25 @@ class FsmgModel(object):
         self._ck(fn(self._h, C.byref(b), *adapt, pp, toks.ctypes.data_as(_I32P), _f32p(scores), _f32p(lp) if logprobs else None))
         return (toks, scores, lp) if logprobs else (toks, scores)
 
-    def beam_search(self, num, beam_width, n_groups=1, primer=None, logprobs=False):
+    def beam_search(self, num, beam_width, n_groups=1, primer=None, logprobs=False, state=None):
         """n_groups independent beam searches of width beam_width, num tokens each -> tokens int32 [G, W, num], scores float32
         [G, W] (, log-probs float32 [G, W, num] with logprobs=True), each group's hypotheses best first.  primer: int32 [G, P]
-        (or [P] for every group) continued by every hypothesis of its group, or (device address, P)."""
-        return self._beam_search((), num, beam_width, n_groups, primer, logprobs)
+        (or [P] for every group) continued by every hypothesis of its group, or (device address, P).
+        state: a DecodeState of n_groups rows, group g searching on from its row g (fsmg_dstate_beam_search; the state is only read)."""
+        if state is None:
+            return self._beam_search((), num, beam_width, n_groups, primer, logprobs)
+        if primer is not None:
+            raise ValueError('a state takes no primer: feed it first')
+        if int(n_groups) != state.rows:
+            raise ValueError('n_groups %d is not the row count of the state (%d)' % (int(n_groups), state.rows))
+        b = self.beam_config(n_groups, beam_width, num)
+        G, W, num = int(n_groups), int(beam_width), int(num)
+        toks = np.empty((G, W, num), np.int32)
+        scores = np.empty((G, W), np.float32)
+        lp = np.empty((G, W, num), np.float32) if logprobs else None
+        state._call(self._lib.fsmg_dstate_beam_search, C.byref(b), toks.ctypes.data_as(_I32P), _f32p(scores),
+                    _f32p(lp) if logprobs else None)
+        return (toks, scores, lp) if logprobs else (toks, scores)
 
     def maml_beam_search(self, support, num, inner_steps, inner_lr, beam_width, n_groups=1, primer=None, logprobs=False,
                          n_support_rows=None):

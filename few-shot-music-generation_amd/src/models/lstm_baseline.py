@@ -15,7 +15,9 @@ Beyond the reference: generate(s, num, n, temperature, top_k, seed, primer_len) 
 optionally continuing the first primer_len tokens of the support songs; beam_search(s, num, beam_width, n, primer_len) returns
 the beam_width highest-scoring continuations of each of n groups, searched on the device; score(s, songs, ...) reads given songs
 and returns per-token log-probabilities, ranks of the true token, predictive entropies, argmaxes and per-song NLLs (the support set
-is ignored, as in sample).
+is ignored, as in sample).  condition(s) reads the support songs into a decode state, one row per artist (include/fsmg.h
+fsmg_dstate_*); generate(..., condition_on_support=True) continues from it, and eval_conditioned(episode) is the few-shot baseline
+that reads the support set before it scores the query songs.
 
 Optional config keys beyond the reference's: device, clip_norm_mode ('tf1_slices' | 'dense'),
 max_sequences, use_graph, gemm / schedule / recurrence / dp_split_backward (fsmg_config), dp_exchange ('torch': the
@@ -127,12 +129,76 @@ class LSTMBaseline(HIPModel):
             raise ValueError('primer_len %d exceeds the song length %d' % (primer_len, songs.shape[1]))
         return np.ascontiguousarray(songs[np.arange(n) % songs.shape[0], :primer_len])
 
-    def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
+    def condition(self, support_set, history=None):
+        """Read the support songs into a decode state (fsmg.binding.DecodeState): support_set int32 [A, K, max_len] (or
+        [K, max_len]: one artist) -> a state of A rows, row a having read song_1, then [start] + song_k for k = 2..K of artist a.
+        Every song has max_len tokens, so the rows stay in lockstep.  history: context tokens the state keeps (the repetition
+        penalty's reach); default: everything condition reads plus 2 * max_len.  The caller closes the state."""
+        self._require_init()
+        s = np.ascontiguousarray(support_set, dtype=np.int32)
+        if s.ndim == 2:
+            s = s[None]
+        if s.ndim != 3 or s.shape[2] != self._time_steps:
+            raise ValueError('support_set must be [A, K, %d] or [K, %d], got %r' % (self._time_steps, self._time_steps, s.shape))
+        A, K, T = s.shape
+        state = self._model.new_state(A, history=int(history) if history else K * (T + 1) + 2 * T)
+        start = np.full((A, 1), self._start_word, np.int32)
+        for k in range(K):
+            self._model.feed(state, s[:, k] if k == 0 else np.concatenate([start, s[:, k]], axis=1))
+        return state
+
+    def eval_conditioned(self, episode):
+        """The few-shot baseline that reads the support set: artist a's support songs are read into a decode state (condition), the
+        state is copied to the artist's Q query rows, and each row is fed [start] + its query song with log-probs.  -> the mean NLL
+        of the N * Q * max_len query-song tokens (the start word's own log-prob is dropped): eval's number, with every query song
+        scored behind its artist's support songs instead of from a zero state.  No backward pass, no state change of the model."""
+        self._require_init()
+        query = self._tokens(episode.query, 3)
+        N, Q, T = query.shape
+        support = self._tokens(episode.support, 3)
+        if support.shape[0] != N or T != self._time_steps:
+            raise ValueError('support %r / query %r do not match max_len=%d' % (support.shape, query.shape, self._time_steps))
+        state = self.condition(support)
+        rows = self._model.new_state(N * Q, history=state.history)
+        try:
+            rows.gather(state, np.repeat(np.arange(N), Q))
+            start = np.full((N * Q, 1), self._start_word, np.int32)
+            lp = self._model.feed(rows, np.concatenate([start, query.reshape(N * Q, T)], axis=1), logprobs=True)
+        finally:
+            rows.close()
+            state.close()
+        return float(-np.mean(lp[:, 1:].astype(np.float64)))
+
+    def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0,
+                 condition_on_support=False):
         """n independent samples of num tokens (int32 [n, num]), drawn on the device (temperature, top_k, seed; include/fsmg.h
         fsmg_generate).  Each row continues the first primer_len tokens of a support song (dealt round-robin); with
         primer_len 0 the support set is not used.  top_p, min_p, repetition_penalty, repeat_window: the sampling filters
-        (include/fsmg.h fsmg_generate_filtered; all off by default)."""
+        (include/fsmg.h fsmg_generate_filtered; all off by default).
+        condition_on_support=True: the support songs are read first (condition: one state row per artist, dealt round-robin over the
+        n rows), then [start] and the first primer_len tokens of one of that artist's support songs, and the rows continue from
+        there."""
         self._require_init()
+        if condition_on_support:
+            n, num = int(n), int(num)
+            K, T = np.shape(support_set)[-2:]
+            # room for everything the rows will have read, so that a whole-context penalty (repeat_window 0) reaches all of it
+            state = self.condition(support_set, history=K * (T + 1) + 1 + int(primer_len) + num)
+            rows = self._model.new_state(n, history=state.history)
+            try:
+                rows.gather(state, np.arange(n) % state.rows)
+                # row i continues artist i % A: [start], then the first primer_len tokens of one of that artist's own songs
+                songs = np.ascontiguousarray(support_set, dtype=np.int32).reshape(state.rows, K, T)
+                i = np.arange(n)
+                if int(primer_len) > T:
+                    raise ValueError('primer_len %d exceeds the song length %d' % (primer_len, T))
+                head = np.full((n, 1), self._start_word, np.int32)
+                self._model.feed(rows, np.concatenate([head, songs[i % state.rows, (i // state.rows) % K, :max(int(primer_len), 0)]], axis=1))
+                return self._model.generate(n, num, temperature=temperature, top_k=top_k, seed=seed, logprobs=logprobs, top_p=top_p,
+                                            min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window, state=rows)
+            finally:
+                rows.close()
+                state.close()
         return self._model.generate(int(n), int(num), temperature=temperature, top_k=top_k, seed=seed,
                                     primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs,
                                     top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window)

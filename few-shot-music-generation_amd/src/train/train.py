@@ -223,11 +223,13 @@ def main(argv=None):
         support_set = episode.support[0]
         if 'sample_temperature' not in config:
             sample = model.sample(support_set, max_len)
-        else:        # opt-in: samples_per_episode draws from model.generate, conditioned on the episode's support set
+        else:        # opt-in: samples_per_episode draws from model.generate, conditioned on the episode's support set (its primer;
+            # with sample_condition_on_support the whole support set is read first, into a decode state)
             gen = model.generate(support_set, max_len, n=int(config.get('samples_per_episode', 1)),
                                  temperature=float(config['sample_temperature']), top_k=int(config.get('sample_top_k', 0)),
                                  seed=sample_seed(config.get('sample_seed', 0), i),
-                                 primer_len=int(config.get('sample_primer_len', 0)), **sample_filters(config))
+                                 primer_len=int(config.get('sample_primer_len', 0)), **sample_filters(config),
+                                 **({'condition_on_support': True} if config.get('sample_condition_on_support') else {}))
         for j in range(support_set.shape[0]):
             write_seq(episode_sampler['test'].detokenize(support_set[j]), curr_sample_dir, 'support_%d' % j)
         if 'sample_temperature' not in config:

@@ -240,7 +240,7 @@ int fsmg_maml_step_indexed(fsmg_handle h, int32_t table_id, const int32_t* suppo
                            int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, float* loss);
 
 /* replaces LSTMBaseline.sample (src/models/lstm_baseline.py:135-156): greedy argmax decode of
- * `num` tokens from the start word and a zero state (the support set is ignored there). */
+ * `num` tokens from the start word and a zero state (the support set is ignored there; a carried state: fsmg_dstate_*). */
 int fsmg_sample(fsmg_handle h, int32_t num, int32_t* out_tokens);
 
 /* ---- batched on-device generation (DESIGN.md "Batched generation").  n_seq independent rows, each the input sequence
@@ -402,6 +402,79 @@ int fsmg_score(fsmg_handle h, const fsmg_score_config* c, const int32_t* tokens,
 int fsmg_maml_score(fsmg_handle h, const fsmg_score_config* c, const int32_t* support, int32_t n_support_rows,
                     int32_t inner_steps, float inner_lr, int32_t support_on_device, const int32_t* tokens,
                     float* out_logprob, int32_t* out_rank, float* out_entropy, int32_t* out_argmax, float* out_row_nll);
+
+/* ---- decode states (DESIGN.md "Decode states"): the LSTM state of R decode rows as a device-resident object the handle owns, so
+ * that every decode entry point can start from it and leave it advanced -- continue a piece, read something longer than max_len in
+ * chunks, read an artist's support songs and go on from there.  The one-shot entry points above start every row from a zero state
+ * and throw the state away; they are unchanged.
+ * A state holds, per row: h and c of every layer; a PENDING token, the next input the cells read; the last `history` context tokens.
+ * And for all rows together (the rows of a state advance in lockstep): n_ctx, the number of context tokens so far, and n_gen, how
+ * many of them were generated.  A fresh (created or reset) state has zero h and c, n_ctx = n_gen = 0 and the start word
+ * (input_size) pending; that implicit start word is not context, as in fsmg_generate_filtered.
+ *   fsmg_dstate_feed      given tokens x_0 .. x_{n-1} per row ([R][n]; ids in [0, input_size]: the start word may be fed explicitly,
+ *                         which is how a new song is begun on a carried state, and an explicitly fed start word IS context).  For each
+ *                         x_i in order: the pending token is read through the cells; with out_logprob != NULL,
+ *                         out_logprob[r][i] = fl(z[x_i] - lse) from that output, z the V1 logits fsmg_generate computes and lse
+ *                         bitwise the number its log-probs use; then x_i becomes pending and joins the context.  Without
+ *                         out_logprob no logits are computed (the cells-only primer path).  n_ctx += n.
+ *   fsmg_dstate_generate  at local position t the pending token is read and a token picked exactly as fsmg_generate_filtered picks
+ *                         it (g->n_seq == rows, g->primer_len == 0), with Philox counter (v >> 2, n_gen + t, b, 0), b the row index in
+ *                         the state; the token becomes pending and joins the context; n_ctx += num, n_gen += num.  The repetition
+ *                         penalty's context is the last min(repeat_window, n_ctx + t) tokens of (the history followed by this
+ *                         call's tokens): with a penalty on, repeat_window must be in [1, history], and repeat_window = 0 (the
+ *                         whole context) is allowed only while n_ctx + num <= history.
+ *   fsmg_dstate_beam_search  group g starts from state row g with beam_width copies of it (b->n_groups == rows, b->primer_len == 0);
+ *                         the state is read and not modified.
+ * What follows from it, all bitwise: a fresh state, feed(primer) without log-probs, generate(num) gives
+ * fsmg_generate_filtered(primer, num) with the same config, seed and filters, tokens and log-probs (with a penalty: while its window
+ * fits the history); generate(a) then generate(b) gives generate(a + b); feed(x[:a]) then feed(x[a:]) gives feed(x); the log-probs
+ * feed returns for tokens generate produced are the ones generate reported; a row's outputs depend neither on the row count nor on
+ * the other rows; fresh state, feed(primer), beam_search gives fsmg_beam_search(primer); get followed by set into a fresh state of
+ * the same shape continues with the same bits.  No other handle state changes (fsmg_generate's list), and the one-shot entry points
+ * return the bits they returned before states existed.
+ *   fsmg_dstate_create / _destroy  a state of n_rows rows keeping `history` context tokens; its storage is its own allocation.
+ *                         fsmg_destroy frees the states still alive.
+ *   fsmg_dstate_reset     back to the fresh state.
+ *   fsmg_dstate_info      out = {rows, history, n_ctx, n_gen}.
+ *   fsmg_dstate_get       h_out / c_out host [L][R][H] (the reference's layout: H, not the padded width), ctx_out host
+ *                         [R][min(n_ctx, history)] oldest first (its last token is the pending one); any may be NULL.
+ *   fsmg_dstate_set       the reverse (pad units are written as zero; n_gen <= n_ctx; ctx_in may be NULL when n_ctx = 0, and then
+ *                         the start word is pending).
+ *   fsmg_dstate_gather    dst row i = src row rows[i] (host indices, repeats allowed; dst->rows of them), equal history, dst != src;
+ *                         the counters are copied.
+ * Errors: FSMG_ERR_INVALID for a state this handle does not own or one already destroyed (the handle keeps a registry: an error,
+ * not a crash), a wrong version or nonzero reserved fields, n_rows < 1 (or > 2^20), history < 1, a row-count mismatch, a primer_len
+ * other than 0, a gather index out of range, the window rules above, n < 0, tokens_on_device not 0 / 1, rows * (history + n + 1) >
+ * 2^30 (n = the call's tokens), n_gen + num > 2^31 - 1, and everything fsmg_generate_filtered / fsmg_beam_search refuse;
+ * FSMG_ERR_TOKEN_RANGE for a fed id or a ctx_in id outside [0, input_size].  Host tokens are checked before any device work; device
+ * tokens by a flag read back with the outputs.  An argument error leaves the state untouched; after a token-range error on DEVICE
+ * tokens the state's contents are unspecified (reset it or set it).
+ * States at MAML's theta' do not exist: a state would outlive the restored parameters. */
+#define FSMG_DSTATE_CONFIG_VERSION 1
+typedef struct fsmg_dstate_s* fsmg_dstate;
+typedef struct fsmg_dstate_config {
+    int32_t version;          /* FSMG_DSTATE_CONFIG_VERSION                                  */
+    int32_t n_rows;           /* R >= 1 rows advancing in lockstep                           */
+    int32_t history;          /* >= 1 context tokens kept per row (the penalty's reach)      */
+    int32_t reserved[9];      /* must be 0                                                   */
+} fsmg_dstate_config;
+
+int fsmg_dstate_create(fsmg_handle h, const fsmg_dstate_config* c, fsmg_dstate* out);
+int fsmg_dstate_destroy(fsmg_handle h, fsmg_dstate st);
+int fsmg_dstate_reset(fsmg_handle h, fsmg_dstate st);
+int fsmg_dstate_info(fsmg_handle h, fsmg_dstate st, int64_t out[4]);
+int fsmg_dstate_get(fsmg_handle h, fsmg_dstate st, float* h_out, float* c_out, int32_t* ctx_out);
+int fsmg_dstate_set(fsmg_handle h, fsmg_dstate st, const float* h_in, const float* c_in, const int32_t* ctx_in, int64_t n_ctx,
+                    int64_t n_gen);
+int fsmg_dstate_gather(fsmg_handle h, fsmg_dstate dst, fsmg_dstate src, const int32_t* rows);
+/* tokens [R,n] host, or device when tokens_on_device; out_logprob host [R,n] or NULL */
+int fsmg_dstate_feed(fsmg_handle h, fsmg_dstate st, const int32_t* tokens, int32_t n, int32_t tokens_on_device, float* out_logprob);
+/* out_tokens host [R,num], out_logprob host [R,num] or NULL; f may be NULL */
+int fsmg_dstate_generate(fsmg_handle h, fsmg_dstate st, const fsmg_gen_config* g, const fsmg_gen_filters* f, int32_t* out_tokens,
+                         float* out_logprob);
+/* out_tokens host [R,W,num]; out_scores host [R,W]; out_logprob host [R,W,num] or NULL */
+int fsmg_dstate_beam_search(fsmg_handle h, fsmg_dstate st, const fsmg_beam_config* b, int32_t* out_tokens, float* out_scores,
+                            float* out_logprob);
 
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
