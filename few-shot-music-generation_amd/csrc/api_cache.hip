@@ -1,0 +1,476 @@
+// Support-set neural cache: fsmg_cache_build / _create_from / _get / _info / _destroy, fsmg_cache_attend, fsmg_cache_score,
+// fsmg_cache_eval_step.  Host-side C++ only (part of the C-ABI of libfsmg, include/fsmg.h); the kernels live in cache.hip (attention,
+// cache fill) and score.hip (the model log-prob).  DESIGN.md 17.
+#include "fsmg_model.h"
+
+using namespace fsmg;
+using namespace fsmg_host;
+
+namespace fsmg_host {
+
+namespace {
+
+constexpr int64_t CACHE_MAX_ENTRIES = 1LL << 22;
+constexpr int64_t CACHE_MAX_KEY_BYTES = 1LL << 31;
+
+// the cache `c` if this handle owns it (the registry: a destroyed or foreign pointer is never dereferenced)
+fsmg_cache_s* find_cache(fsmg_model* h, fsmg_cache c) {
+    for (fsmg_cache_s* s : h->caches)
+        if (s == c && c != nullptr) return s;
+    fail(h, FSMG_ERR_INVALID, "not a cache of this handle (never created here, or already destroyed)");
+    return nullptr;
+}
+
+int check_cache_size(fsmg_model* h, int64_t G, int64_t Mg) {
+    if (G < 1 || Mg < 1) return fail(h, FSMG_ERR_INVALID, "a cache needs n_groups >= 1 and entries_per_group >= 1");
+    if (G > CACHE_MAX_ENTRIES || Mg > CACHE_MAX_ENTRIES || G * Mg > CACHE_MAX_ENTRIES)
+        return fail(h, FSMG_ERR_INVALID, "n_groups * entries_per_group must be <= 2^22");
+    if (G * Mg * h->Hp * 4 > CACHE_MAX_KEY_BYTES) return fail(h, FSMG_ERR_INVALID, "the keys of a cache must fit 2^31 bytes");
+    return FSMG_OK;
+}
+
+// an empty cache of G x Mg entries on the device, not yet registered
+int alloc_cache(fsmg_model* h, int G, int Mg, fsmg_cache_s** out) {
+    fsmg_cache_s* c = new (std::nothrow) fsmg_cache_s;
+    if (!c) return fail(h, FSMG_ERR_NOMEM, "out of host memory");
+    c->G = G; c->Mg = Mg; c->H = h->H; c->Hp = h->Hp;
+    const size_t kbytes = (size_t)round_up((int64_t)sizeof(float) * G * Mg * h->Hp, 256);
+    c->bytes = kbytes + sizeof(int) * (size_t)G * Mg;
+    if (hipMalloc((void**)&c->mem, c->bytes) != hipSuccess) { delete c; return fail(h, FSMG_ERR_NOMEM, "hipMalloc(cache) failed"); }
+    c->keys = (float*)c->mem;
+    c->vals = (int*)(c->mem + kbytes);
+    *out = c;
+    return FSMG_OK;
+}
+
+void free_cache(fsmg_cache_s* c) {
+    if (c->mem) hipFree(c->mem);
+    delete c;
+}
+
+// h->cat holds at least `bytes`: grown between calls, after a stream sync
+int cat_reserve(fsmg_model* h, size_t bytes) {
+    if (bytes <= h->cat_bytes) return FSMG_OK;
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (h->cat) hipFree(h->cat);
+    h->cat = nullptr; h->cat_bytes = 0;
+    if (hipMalloc((void**)&h->cat, bytes) != hipSuccess) return fail(h, FSMG_ERR_NOMEM, "hipMalloc(cache attention scratch) failed");
+    h->cat_bytes = bytes;
+    return FSMG_OK;
+}
+
+// The queries of an attention call sorted by group into tiles of CACHE_ATTEND_QT slots (one workgroup each): groups in increasing
+// order, a group's queries in increasing id, the last tile of a group padded with -1.
+struct Tiles {
+    std::vector<int> slot_query, tile_group;
+    int n_tiles() const { return (int)tile_group.size(); }
+};
+template <class GroupOf>
+Tiles make_tiles(int n, int G, GroupOf&& group_of) {
+    std::vector<int> count(G, 0), first(G + 1, 0);
+    for (int q = 0; q < n; ++q) ++count[group_of(q)];
+    for (int g = 0; g < G; ++g) first[g + 1] = first[g] + (count[g] + CACHE_ATTEND_QT - 1) / CACHE_ATTEND_QT;
+    Tiles t;
+    t.tile_group.resize(first[G]);
+    t.slot_query.assign((size_t)first[G] * CACHE_ATTEND_QT, -1);
+    std::vector<int> next(G);
+    for (int g = 0; g < G; ++g) {
+        next[g] = first[g] * CACHE_ATTEND_QT;
+        for (int j = first[g]; j < first[g + 1]; ++j) t.tile_group[j] = g;
+    }
+    for (int q = 0; q < n; ++q) t.slot_query[next[group_of(q)]++] = q;
+    return t;
+}
+
+// The layout of an attention call in h->cat: [out n_theta x n floats | tiles | (raw form) targets n ints | queries n x Hp floats]
+struct AttendScratch {
+    float* out = nullptr; int* slot_query = nullptr; int* tile_group = nullptr; int* tgt = nullptr; float* Q = nullptr;
+};
+int attend_scratch(fsmg_model* h, int n, int n_theta, const Tiles& t, bool raw, AttendScratch* s) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (size_t)round_up((int64_t)(off + bytes), 256); return o; };
+    const size_t o_out = take(sizeof(float) * (size_t)n_theta * n);
+    const size_t o_slot = take(sizeof(int) * t.slot_query.size());
+    const size_t o_grp = take(sizeof(int) * t.tile_group.size());
+    const size_t o_tgt = take(raw ? sizeof(int) * (size_t)n : 0);
+    const size_t o_q = take(raw ? sizeof(float) * (size_t)n * h->Hp : 0);
+    const int rc = cat_reserve(h, off);
+    if (rc != FSMG_OK) return rc;
+    s->out = (float*)(h->cat + o_out); s->slot_query = (int*)(h->cat + o_slot); s->tile_group = (int*)(h->cat + o_grp);
+    s->tgt = (int*)(h->cat + o_tgt); s->Q = (float*)(h->cat + o_q);
+    return FSMG_OK;
+}
+
+// uploads the tiles and launches the attention kernel; the caller keeps `t` alive until the stream has been synchronised
+int attend_launch(fsmg_model* h, const fsmg_cache_s* c, const Tiles& t, const AttendScratch& s, int n, const float* Q, int B,
+                  const int* tgt, const float* thetas, int n_theta) {
+    HIPCK(h, hipMemcpyAsync(s.slot_query, t.slot_query.data(), sizeof(int) * t.slot_query.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCK(h, hipMemcpyAsync(s.tile_group, t.tile_group.data(), sizeof(int) * t.tile_group.size(), hipMemcpyHostToDevice, h->stream));
+    CacheAttendArgs a{};
+    a.keys = c->keys; a.vals = c->vals; a.Mg = c->Mg; a.Hp = c->Hp;
+    a.Q = Q; a.ldq = c->Hp; a.B = B; a.T = h->T; a.tgt = tgt;
+    a.slot_query = s.slot_query; a.tile_group = s.tile_group; a.n_tiles = t.n_tiles(); a.n = n;
+    for (int k = 0; k < n_theta; ++k) a.theta[k] = thetas[k];
+    a.n_theta = n_theta; a.out = s.out;
+    ScopedTimer tm(h, "cache_attend");
+    HIPCK(h, launch_cache_attend(h->stream, a));
+    return FSMG_OK;
+}
+
+bool thetas_ok(const float* thetas, int n) {
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(thetas[k]) || thetas[k] < 0.0f) return false;
+    return true;
+}
+
+int check_host_tokens(fsmg_model* h, const int32_t* tokens, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (tokens[i] < 0 || tokens[i] >= h->V) return fail(h, FSMG_ERR_TOKEN_RANGE, "token id outside [0, input_size)");
+    return FSMG_OK;
+}
+
+int check_build_config(fsmg_model* h, const fsmg_cache_config* c, const int32_t* tokens, fsmg_cache* out) {
+    if (!c || !out) return fail(h, FSMG_ERR_INVALID, "null fsmg_cache_config / out");
+    if (c->version != FSMG_CACHE_CONFIG_VERSION)
+        return fail(h, FSMG_ERR_INVALID, "fsmg_cache_config.version is " + std::to_string(c->version) + ", this library expects " +
+                                             std::to_string(FSMG_CACHE_CONFIG_VERSION));
+    for (int32_t r : c->reserved)
+        if (r != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_cache_config.reserved must be zero");
+    if (c->n_rows < 1 || c->n_rows > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n_rows must be in [1, 2^20]");
+    if (c->n_groups < 1 || c->n_rows % c->n_groups != 0) return fail(h, FSMG_ERR_INVALID, "n_groups must be >= 1 and divide n_rows");
+    if (c->tokens_on_device != 0 && c->tokens_on_device != 1) return fail(h, FSMG_ERR_INVALID, "tokens_on_device must be 0 or 1");
+    if (c->pass_rows < 0 || c->pass_rows > 1024) return fail(h, FSMG_ERR_INVALID, "pass_rows must be 0 or in [1, 1024]");
+    if (!tokens) return fail(h, FSMG_ERR_INVALID, "null tokens");
+    return check_cache_size(h, c->n_groups, (int64_t)(c->n_rows / c->n_groups) * h->T);
+}
+
+// one pass's read-back of the error word, fsmg_score's way: *again = repeat this pass on per-step launches
+int pass_status(fsmg_model* h, int err, bool* retried, bool* again) {
+    *again = false;
+    if (!err) { *retried = false; return FSMG_OK; }
+    HIPCK(h, hipMemsetAsync(h->d_err, 0, sizeof(int), h->stream));
+    if (err == 2) on_timeout(h);
+    const int rc = report(h, err);
+    if (is_retry(rc) && h->retry_armed && !*retried) {
+        h->retry_armed = false;
+        *retried = true;
+        *again = true;
+        return FSMG_OK;
+    }
+    return rc;
+}
+
+// what a scoring-style pass over B rows needs before its launches (score_core's prologue)
+int prepare_pass(fsmg_model* h, int B, const int32_t* rows, int on_device) {
+    choose_schedule(h, B);
+    h->ov_call = false;
+    int rc;
+    if (pass_reads_cs(h, B, false) && (rc = ensure_cs(h)) != FSMG_OK) return rc;
+    return stage_tokens(h, rows, 0, rows, B, on_device);
+}
+
+// fsmg_cache_build's work behind the argument checks
+int build_core(fsmg_model* h, const fsmg_cache_config* c, const int32_t* tokens, fsmg_cache_s** out) {
+    const int R = c->n_rows, T = h->T;
+    const int P = c->pass_rows > 0 ? c->pass_rows : FSMG_SCORE_PASS_ROWS;
+    int rc;
+    if (!c->tokens_on_device && (rc = check_host_tokens(h, tokens, (size_t)R * T)) != FSMG_OK) return rc;
+    if ((rc = ensure_scratch(h, std::min(R, P))) != FSMG_OK) return rc;
+    if ((rc = ensure_khf(h)) != FSMG_OK) return rc;
+    fsmg_cache_s* cache = nullptr;
+    if ((rc = alloc_cache(h, c->n_groups, R / c->n_groups * T, &cache)) != FSMG_OK) return rc;
+    auto passes = [&]() -> int {
+        bool retried = false;
+        for (int r0 = 0; r0 < R; r0 += P) {
+            const int B = std::min(P, R - r0);
+            int r = prepare_pass(h, B, tokens + (size_t)r0 * T, c->tokens_on_device);
+            if (r != FSMG_OK) return r;
+            r = run_graphed(h, "cb:" + std::to_string(B), [&]() -> int {
+                const int rr = token_prep(h, 0, B);
+                return rr == FSMG_OK ? forward(h, B, B, 1, nullptr, false, HEAD_NONE) : rr;
+            });
+            if (r != FSMG_OK) return r;
+            h->lastB = B;
+            // rows r0 .. r0 + B - 1 of the cache's [rows][T] entries: a pass repeated after a time-out overwrites what it wrote
+            HIPCK(h, launch_cache_fill(h->stream, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Y, B, T, h->H, h->Hp, r0, cache->keys, cache->vals));
+            int err = 0;
+            HIPCK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            HIPCK(h, hipStreamSynchronize(h->stream));
+            bool again = false;
+            if ((r = pass_status(h, err, &retried, &again)) != FSMG_OK) return r;
+            if (again) r0 -= P;
+        }
+        return FSMG_OK;
+    };
+    if ((rc = passes()) != FSMG_OK) { hipStreamSynchronize(h->stream); free_cache(cache); return rc; }
+    *out = cache;
+    return FSMG_OK;
+}
+
+int check_score_config(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_config* c, const int32_t* tokens,
+                       const int32_t* group, const void* const outs[4]) {
+    if (!c) return fail(h, FSMG_ERR_INVALID, "null fsmg_cache_score_config");
+    if (c->version != FSMG_CACHE_SCORE_CONFIG_VERSION)
+        return fail(h, FSMG_ERR_INVALID, "fsmg_cache_score_config.version is " + std::to_string(c->version) + ", this library expects " +
+                                             std::to_string(FSMG_CACHE_SCORE_CONFIG_VERSION));
+    for (int32_t r : c->reserved)
+        if (r != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_cache_score_config.reserved must be zero");
+    if (c->n_rows < 1 || c->n_rows > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n_rows must be in [1, 2^20]");
+    if (c->tokens_on_device != 0 && c->tokens_on_device != 1) return fail(h, FSMG_ERR_INVALID, "tokens_on_device must be 0 or 1");
+    if (c->nll_first < 0 || c->nll_first >= h->T || c->nll_count < 0 || (int64_t)c->nll_first + c->nll_count > h->T)
+        return fail(h, FSMG_ERR_INVALID, "nll_first must be in [0, max_len) and nll_first + nll_count <= max_len");
+    if (c->pass_rows < 0 || c->pass_rows > 1024) return fail(h, FSMG_ERR_INVALID, "pass_rows must be 0 or in [1, 1024]");
+    if (c->n_theta < 1 || c->n_theta > FSMG_CACHE_MAX_THETA) return fail(h, FSMG_ERR_INVALID, "n_theta must be in [1, 8]");
+    if (!thetas_ok(c->thetas, c->n_theta)) return fail(h, FSMG_ERR_INVALID, "every theta must be finite and >= 0");
+    if (c->n_lambda < 1 || c->n_lambda > FSMG_CACHE_MAX_LAMBDA) return fail(h, FSMG_ERR_INVALID, "n_lambda must be in [1, 16]");
+    for (int j = 0; j < c->n_lambda; ++j)
+        if (!(c->lambdas[j] >= 0.0f && c->lambdas[j] <= 1.0f)) return fail(h, FSMG_ERR_INVALID, "every lambda must lie in [0, 1]");
+    if (!tokens) return fail(h, FSMG_ERR_INVALID, "null tokens");
+    if (!outs[0] && !outs[1] && !outs[2] && !outs[3]) return fail(h, FSMG_ERR_INVALID, "every output is null");
+    if (cache->H != h->H || cache->Hp != h->Hp) return fail(h, FSMG_ERR_INVALID, "the cache's hidden size is not the handle's");
+    if (group)
+        for (int r = 0; r < c->n_rows; ++r)
+            if (group[r] < 0 || group[r] >= cache->G) return fail(h, FSMG_ERR_INVALID, "group id outside [0, groups of the cache)");
+    return FSMG_OK;
+}
+
+// log((1 - lambda) exp(lp) + lambda pc) in fp64, rounded once
+inline float mix_logprob(float lp, float pc, double log1m_lambda, double log_lambda) {
+    const double a = log1m_lambda + (double)lp;                         // lambda = 0: 0 + lp
+    const double b = log_lambda + std::log((double)pc);                 // -inf at pc = 0 (and at lambda = 0)
+    if (std::isnan(a) || std::isnan(b)) return (float)(a + b);
+    const double hi = std::max(a, b), lo = std::min(a, b);
+    if (hi == -INFINITY) return -INFINITY;
+    return (float)(hi + std::log1p(std::exp(lo - hi)));
+}
+
+// fsmg_cache_score's work behind the argument checks
+int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_config* c, const int32_t* tokens, const int32_t* group,
+               float* out_logprob, float* out_cache_prob, float* out_lstm_logprob, float* out_row_nll) {
+    const int R = c->n_rows, T = h->T, NT = c->n_theta, NL = c->n_lambda;
+    const int P = c->pass_rows > 0 ? c->pass_rows : FSMG_SCORE_PASS_ROWS;
+    const size_t RT = (size_t)R * T;
+    int rc;
+    if (!c->tokens_on_device && (rc = check_host_tokens(h, tokens, RT)) != FSMG_OK) return rc;
+    if ((rc = ensure_scratch(h, std::min(R, P))) != FSMG_OK) return rc;
+    if ((rc = ensure_khf(h)) != FSMG_OK) return rc;
+    // the mixture and the row NLL are host work over the two device outputs: those come to the host whether asked for or not
+    const bool want_mix = out_logprob != nullptr || out_row_nll != nullptr;
+    const bool want_pc = want_mix || out_cache_prob != nullptr, want_lp = want_mix || out_lstm_logprob != nullptr;
+    std::vector<float> lp_own, pc_own, mix_own;
+    float* lp_host = out_lstm_logprob;
+    float* pc_host = out_cache_prob;
+    if (want_lp && !lp_host) { lp_own.resize(RT); lp_host = lp_own.data(); }
+    if (want_pc && !pc_host) { pc_own.resize(RT * NT); pc_host = pc_own.data(); }
+    bool retried = false;
+    for (int r0 = 0; r0 < R; r0 += P) {
+        const int B = std::min(P, R - r0);
+        const int n = B * T;
+        if ((rc = prepare_pass(h, B, tokens + (size_t)r0 * T, c->tokens_on_device)) != FSMG_OK) return rc;
+        Tiles tiles;
+        AttendScratch as;
+        if (want_pc) {              // query q = b * T + t of the pass, in its row's group
+            tiles = make_tiles(n, cache->G, [&](int q) { return group ? group[r0 + q / T] : 0; });
+            if ((rc = attend_scratch(h, n, NT, tiles, false, &as)) != FSMG_OK) return rc;
+        }
+        float* d_lp = h->score_out;
+        // fsmg_score's pass with the log-prob as its one output (the same graph key: the same launches)
+        rc = run_graphed(h, "sc:" + std::to_string(B) + ":1", [&]() -> int {
+            int r = token_prep(h, 0, B);
+            if (r == FSMG_OK) r = forward(h, B, B, 1, nullptr, false, HEAD_LOGITS);
+            if (r != FSMG_OK) return r;
+            ScopedTimer tm(h, "ce");
+            HIPCK(h, launch_score_rows(h->stream, h->logits, h->V1p, n, h->V1, h->Y, B, T, d_lp, nullptr, nullptr, nullptr));
+            return FSMG_OK;
+        });
+        if (rc != FSMG_OK) return rc;
+        h->lastB = B;
+        if (want_pc && (rc = attend_launch(h, cache, tiles, as, n, h->Hs[h->L - 1], B, h->Y, c->thetas, NT)) != FSMG_OK) return rc;
+        const size_t o = (size_t)r0 * T;
+        int err = 0;
+        if (want_lp) HIPCK(h, hipMemcpyAsync(lp_host + o, d_lp, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
+        if (want_pc)
+            for (int k = 0; k < NT; ++k)
+                HIPCK(h, hipMemcpyAsync(pc_host + k * RT + o, as.out + (size_t)k * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
+        HIPCK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        bool again = false;
+        if ((rc = pass_status(h, err, &retried, &again)) != FSMG_OK) return rc;
+        if (again) r0 -= P;
+    }
+    if (!want_mix) return FSMG_OK;
+    float* mix = out_logprob;
+    if (!mix) { mix_own.resize(RT); mix = mix_own.data(); }            // (row NLL alone: one (theta, lambda) plane at a time)
+    const int t0 = c->nll_first, t1 = c->nll_count > 0 ? t0 + c->nll_count : T;
+    for (int k = 0; k < NT; ++k)
+        for (int j = 0; j < NL; ++j) {
+            const double lam = (double)c->lambdas[j];
+            const double l1m = std::log1p(-lam), ll = std::log(lam);
+            float* plane = out_logprob ? mix + ((size_t)k * NL + j) * RT : mix;
+            const float* pc = pc_host + k * RT;
+            for (size_t i = 0; i < RT; ++i) plane[i] = mix_logprob(lp_host[i], pc[i], l1m, ll);
+            if (!out_row_nll) continue;
+            for (int r = 0; r < R; ++r) {
+                double s = 0.0;         // fp64, increasing t, rounded once: bitwise recomputable from out_logprob
+                for (int t = t0; t < t1; ++t) s += (double)plane[(size_t)r * T + t];
+                out_row_nll[((size_t)k * NL + j) * R + r] = (float)(-s / (double)(t1 - t0));
+            }
+        }
+    return FSMG_OK;
+}
+
+}  // namespace
+
+}  // namespace fsmg_host
+
+// =========================================================================== C ABI
+extern "C" {
+
+int fsmg_cache_build(fsmg_handle h, const fsmg_cache_config* c, const int32_t* tokens, fsmg_cache* out) {
+    if (!h) return FSMG_ERR_INVALID;
+    const int rc0 = check_build_config(h, c, tokens, out);
+    if (rc0 != FSMG_OK) return rc0;
+    BEGIN_CALL(h);
+    fsmg_cache_s* cache = nullptr;
+    const int rc = build_core(h, c, tokens, &cache);
+    if (rc != FSMG_OK) return rc;
+    h->caches.push_back(cache);
+    *out = cache;
+    return FSMG_OK;
+}
+
+int fsmg_cache_create_from(fsmg_handle h, int32_t n_groups, int32_t entries_per_group, const float* keys, const int32_t* values,
+                           fsmg_cache* out) {
+    if (!h) return FSMG_ERR_INVALID;
+    if (!keys || !values || !out) return fail(h, FSMG_ERR_INVALID, "null keys / values / out");
+    int rc = check_cache_size(h, n_groups, entries_per_group);
+    if (rc != FSMG_OK) return rc;
+    const size_t n = (size_t)n_groups * entries_per_group;
+    for (size_t i = 0; i < n; ++i)
+        if (values[i] < 0 || values[i] >= h->V1) return fail(h, FSMG_ERR_TOKEN_RANGE, "cache value outside [0, input_size]");
+    BEGIN_CALL(h);
+    fsmg_cache_s* c = nullptr;
+    if ((rc = alloc_cache(h, n_groups, entries_per_group, &c)) != FSMG_OK) return rc;
+    std::vector<float> kp(n * h->Hp, 0.0f);             // the pad units are exact zeros
+    for (size_t i = 0; i < n; ++i) std::memcpy(kp.data() + i * h->Hp, keys + i * h->H, sizeof(float) * h->H);
+    hipError_t e = hipMemcpyAsync(c->keys, kp.data(), sizeof(float) * kp.size(), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->vals, values, sizeof(int) * n, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);           // the host vector goes out of scope
+    if (e != hipSuccess) { free_cache(c); return fail(h, FSMG_ERR_HIP, std::string("cache upload: ") + hipGetErrorString(e)); }
+    h->caches.push_back(c);
+    *out = c;
+    return FSMG_OK;
+}
+
+int fsmg_cache_get(fsmg_handle h, fsmg_cache cache, float* keys, int32_t* values) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_cache_s* c = find_cache(h, cache);
+    if (!c) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h);
+    const size_t n = (size_t)c->G * c->Mg;
+    std::vector<float> kp(keys ? n * c->Hp : 0);
+    if (keys) HIPCK(h, hipMemcpyAsync(kp.data(), c->keys, sizeof(float) * kp.size(), hipMemcpyDeviceToHost, h->stream));
+    if (values) HIPCK(h, hipMemcpyAsync(values, c->vals, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (keys)
+        for (size_t i = 0; i < n; ++i) std::memcpy(keys + i * c->H, kp.data() + i * c->Hp, sizeof(float) * c->H);   // the padded units stay inside
+    return FSMG_OK;
+}
+
+int fsmg_cache_info(fsmg_handle h, fsmg_cache cache, int64_t out[4]) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_cache_s* c = find_cache(h, cache);
+    if (!c) return FSMG_ERR_INVALID;
+    if (!out) return fail(h, FSMG_ERR_INVALID, "null out");
+    out[0] = c->G; out[1] = c->Mg; out[2] = c->H; out[3] = (int64_t)c->bytes;
+    return FSMG_OK;
+}
+
+int fsmg_cache_destroy(fsmg_handle h, fsmg_cache cache) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_cache_s* c = find_cache(h, cache);
+    if (!c) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h);
+    HIPCK(h, hipStreamSynchronize(h->stream));      // nothing in flight reads it
+    h->caches.erase(std::find(h->caches.begin(), h->caches.end(), c));
+    free_cache(c);
+    return FSMG_OK;
+}
+
+int fsmg_cache_attend(fsmg_handle h, fsmg_cache cache, int32_t n, const float* queries, const int32_t* targets, const int32_t* group,
+                      const float* thetas, int32_t n_theta, float* out_prob) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_cache_s* c = find_cache(h, cache);
+    if (!c) return FSMG_ERR_INVALID;
+    if (n < 1 || n > (1 << 22)) return fail(h, FSMG_ERR_INVALID, "n must be in [1, 2^22]");
+    if (!queries || !targets || !thetas || !out_prob) return fail(h, FSMG_ERR_INVALID, "null queries / targets / thetas / out_prob");
+    if (n_theta < 1 || n_theta > FSMG_CACHE_MAX_THETA) return fail(h, FSMG_ERR_INVALID, "n_theta must be in [1, 8]");
+    if (!thetas_ok(thetas, n_theta)) return fail(h, FSMG_ERR_INVALID, "every theta must be finite and >= 0");
+    if (c->H != h->H || c->Hp != h->Hp) return fail(h, FSMG_ERR_INVALID, "the cache's hidden size is not the handle's");
+    if (group)
+        for (int q = 0; q < n; ++q)
+            if (group[q] < 0 || group[q] >= c->G) return fail(h, FSMG_ERR_INVALID, "group id outside [0, groups of the cache)");
+    BEGIN_CALL(h);
+    const Tiles tiles = make_tiles(n, c->G, [&](int q) { return group ? group[q] : 0; });
+    AttendScratch as;
+    int rc = attend_scratch(h, n, n_theta, tiles, true, &as);
+    if (rc != FSMG_OK) return rc;
+    std::vector<float> qp((size_t)n * h->Hp, 0.0f);
+    for (int q = 0; q < n; ++q) std::memcpy(qp.data() + (size_t)q * h->Hp, queries + (size_t)q * h->H, sizeof(float) * h->H);
+    HIPCK(h, hipMemcpyAsync(as.Q, qp.data(), sizeof(float) * qp.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCK(h, hipMemcpyAsync(as.tgt, targets, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if ((rc = attend_launch(h, c, tiles, as, n, as.Q, 0, as.tgt, thetas, n_theta)) != FSMG_OK) return rc;
+    HIPCK(h, hipMemcpyAsync(out_prob, as.out, sizeof(float) * (size_t)n_theta * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return FSMG_OK;
+}
+
+int fsmg_cache_score(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const int32_t* tokens, const int32_t* group,
+                     float* out_logprob, float* out_cache_prob, float* out_lstm_logprob, float* out_row_nll) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_cache_s* s = find_cache(h, cache);
+    if (!s) return FSMG_ERR_INVALID;
+    const void* outs[4] = {out_logprob, out_cache_prob, out_lstm_logprob, out_row_nll};
+    const int rc = check_score_config(h, s, c, tokens, group, outs);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return score_core(h, s, c, tokens, group, out_logprob, out_cache_prob, out_lstm_logprob, out_row_nll);
+}
+
+int fsmg_cache_eval_step(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q, float theta,
+                         float lambda, float* nll) {
+    if (!h) return FSMG_ERR_INVALID;
+    if (!support || !query || !nll) return fail(h, FSMG_ERR_INVALID, "null support / query / nll");
+    if (N < 1 || K < 1 || Q < 1 || (int64_t)N * K > (1 << 20) || (int64_t)N * Q > (1 << 20))
+        return fail(h, FSMG_ERR_INVALID, "N, K, Q must be >= 1 and N * K, N * Q <= 2^20");
+    fsmg_cache_config bc{};
+    bc.version = FSMG_CACHE_CONFIG_VERSION; bc.n_rows = N * K; bc.n_groups = N;
+    fsmg_cache_score_config sc{};
+    sc.version = FSMG_CACHE_SCORE_CONFIG_VERSION; sc.n_rows = N * Q; sc.n_theta = 1; sc.n_lambda = 1;
+    sc.thetas[0] = theta; sc.lambdas[0] = lambda;
+    fsmg_cache_s shape;                 // the argument checks of both halves before any device work (check_score_config reads G and H)
+    shape.G = N; shape.H = h->H; shape.Hp = h->Hp;
+    fsmg_cache dummy = nullptr;
+    std::vector<int32_t> group((size_t)N * Q);
+    for (int r = 0; r < N * Q; ++r) group[r] = r / Q;
+    std::vector<float> lp((size_t)N * Q * h->T);
+    const void* outs[4] = {lp.data(), nullptr, nullptr, nullptr};
+    int rc = check_build_config(h, &bc, support, &dummy);
+    if (rc == FSMG_OK) rc = check_score_config(h, &shape, &sc, query, group.data(), outs);
+    if (rc == FSMG_OK) rc = check_host_tokens(h, support, (size_t)N * K * h->T);
+    if (rc == FSMG_OK) rc = check_host_tokens(h, query, (size_t)N * Q * h->T);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    fsmg_cache_s* cache = nullptr;
+    if ((rc = build_core(h, &bc, support, &cache)) != FSMG_OK) return rc;
+    rc = score_core(h, cache, &sc, query, group.data(), lp.data(), nullptr, nullptr, nullptr);
+    hipStreamSynchronize(h->stream);
+    free_cache(cache);                  // never registered: nobody else has seen it
+    if (rc != FSMG_OK) return rc;
+    double s = 0.0;
+    for (float v : lp) s += (double)v;
+    *nll = (float)(-s / (double)lp.size());
+    return FSMG_OK;
+}
+
+}  // extern "C"

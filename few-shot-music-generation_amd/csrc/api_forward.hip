@@ -120,13 +120,14 @@ int xov_selfcheck(fsmg_model* h, int B) {
 
 // head == HEAD_LOGITS (fsmg_score; want_dlogits false): the chains as an eval pass runs them, then the projection as ONE plain launch
 // over all T * B rows into h->logits behind the last chain -- no softmax epilogue, no cross entropy, no loss
+// head == HEAD_NONE (fsmg_cache_build; want_dlogits false): the same chains and nothing behind them
 int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_out, bool want_dlogits, int head) {
-    ScopedRange rng_(want_dlogits ? "fsmg.forward(train)" : head == HEAD_LOGITS ? "fsmg.forward(score)" : "fsmg.forward(eval)");
+    ScopedRange rng_(want_dlogits ? "fsmg.forward(train)" : head == HEAD_LOGITS ? "fsmg.forward(score)" : head == HEAD_NONE ? "fsmg.forward(cache)" : "fsmg.forward(eval)");
     const int T = h->T, Hp = h->Hp, G4 = h->G4;
     const int64_t rows = (int64_t)T * B;
     const Lane mainl = main_lane(h);
     hipStream_t s = h->stream;
-    const bool ov = head != HEAD_LOGITS && use_overlap(h);
+    const bool ov = head == HEAD_LOSS && use_overlap(h);
     const bool xcd = use_xcd(h, B);
     const bool chain1 = !xcd && h->persist && !h->force_fwd_rt && lstm_fwd_chain_supported(B, Hp);
     const bool chain_rt = !xcd && h->persist && !chain1 && lstm_fwd_chain_rt_supported(B, Hp);   // all row tiles per block
@@ -236,7 +237,9 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
             }
         }
     }
-    if (head == HEAD_LOGITS) {
+    if (head == HEAD_NONE) {
+        // the hidden states are the product
+    } else if (head == HEAD_LOGITS) {
         ScopedTimer tm(h, "gemm_logits");                                      // the kernel the shape would get anyway (K = Hp: never split)
         ghead.bx3 = h->bx3;
         if (use_h_gemm(h, OP_KC, OP_XC, ghead, mainl)) ghead.bx3 = 3;
@@ -271,7 +274,7 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
     } else {
         GEMMCK(logits_and_ce(h, mainl, B, 0, T, rows, want_dlogits));
     }
-    if (!want_dlogits && head != HEAD_LOGITS) {         // (a train pass reduces its loss in backward(): k_sum_partials, no launch of its own)
+    if (!want_dlogits && head == HEAD_LOSS) {        // (a train pass reduces its loss in backward(): k_sum_partials, no launch of its own)
         ScopedTimer tm(h, "ce");
         HIPCK(h, launch_loss_reduce(s, h->ce, T, B, rows_per_group, ngroups, loss_out));
     }

@@ -1,0 +1,283 @@
+// Support-set neural cache (include/fsmg.h fsmg_cache_*): the fused attention kernel and the kernel that files a pass's
+// top-layer hidden states into a cache.
+//
+// k_cache_attend: p_cache(y) = sum_{i : v_i = y} exp(theta (d_i - d_max)) / sum_i exp(theta (d_i - d_max)), d_i = q . k_i over the
+// Mg keys of the query's group, for up to 8 values of theta in one pass over the keys.  One 256-thread workgroup owns a tile of 32
+// queries of ONE group (the host sorts the queries by group: CacheAttendArgs::slot_query / tile_group) and keeps them in LDS; its four
+// waves walk the group's 16-key tiles round robin (wave w takes tiles w, w + 4, ...: a function of Mg alone).  Keys are the A operand
+// and queries the B operand, so that lane l ends up with the scores of query l % 16 against keys l / 16 + {0, 4, 8, 12} of the tile: every
+// lane runs an online softmax of ITS OWN (query, key subset) pair in registers -- one running maximum for all theta (theta >= 0), a
+// denominator and a numerator per theta -- and nothing crosses lanes inside the key loop.  The score matrix never leaves the
+// registers.  The partial (max, sums) are merged in a fixed order: lanes 16 / 32 apart by shuffles, then the four waves through LDS by
+// one thread per query.  A key index >= Mg is skipped (masked, not scored as zero).  No atomics.  A query's bits depend on its vector,
+// its group's entries and theta alone: each score is an accumulator element of its own, and the merge tree does not depend on the slot
+// a query got.
+//
+// Precision.  theta d reaches tens of units, and an error of e in theta (d_i - d_max) is a relative error of e in that entry's mass.
+// With scores accumulated in fp32 over 512 units p_cache was measured 5.6e-6 off fp64 at theta (d_max - d_min) = 40, and even a
+// correctly rounded fp32 score of magnitude 8 is up to 5e-7 off.  So the products run on v_mfma_f64_16x16x4_f64 -- the fp32 inputs
+// widened exactly, every product exact, fp64 accumulation: half the fp32 pipe's rate, and the one way to scores that are not the
+// error budget -- and the exponent stays in fp64 up to the last step:
+//   u = theta log2(e);  S = ceil(u m), m the running maximum (an integer shift: changing it rescales the sums by an exact power of two);
+//   t = u d - S in fp64 (<= 0),  hi = fl32(t),  lo = fl32(t - hi);   mass = exp2f(hi) (1 + lo ln 2), summed in fp64.
+// What is left is exp2f's own rounding, ~1e-7 per entry.
+#include "fsmg_kernels.h"
+
+namespace fsmg {
+namespace {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int CA_QT = CACHE_ATTEND_QT;      // queries per workgroup: two 16-column B operands, so a key load feeds two MFMAs
+constexpr int CA_WAVES = 4;
+constexpr int CA_PAD = 4;                   // floats behind a query row in LDS: rows 16 B apart in the banks
+constexpr double CA_LOG2E = 1.4426950408889634;
+constexpr float CA_LN2 = 0.693147180559945f;
+
+// a partial softmax over some of a group's keys: the sums are sum_i 2^(u_k d_i - ceil(u_k m)), m the largest d among them
+struct CaState {
+    double m = -INFINITY;
+    double den[CACHE_MAX_THETA] = {}, num[CACHE_MAX_THETA] = {};
+};
+
+// 2^(ceil(u m_from) - ceil(u m_to)), m_to >= m_from: exact; an empty partial (m_from = -inf, sums 0) scales by 0, u = 0 included
+__device__ __forceinline__ double ca_scale(double u, double m_from, double m_to) {
+    if (m_from == -INFINITY) return 0.0;
+    return ldexp(1.0, (int)fmax(ceil(u * m_from) - ceil(u * m_to), -4000.0));
+}
+
+// 2^t, t <= 0 in fp64: the fp32 exponential of the rounded exponent, corrected to first order for what the rounding dropped
+__device__ __forceinline__ double ca_exp2(double t) {
+    const float hi = (float)t;
+    const float lo = (float)(t - (double)hi);
+    const float e = exp2f(hi);
+    return (double)fmaf(e, lo * CA_LN2, e);
+}
+
+// the four scores of a lane (keys kbase, kbase + 4, kbase + 8, kbase + 12 of the group, values v) into its running state
+__device__ __forceinline__ void ca_update(CaState& st, const f64x4& d, int kbase, int Mg, const int v[4], int y, const double* u,
+                                          int n_theta) {
+    double mt = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (kbase + 4 * i < Mg) mt = fmax(mt, d[i]);
+    if (mt > st.m) {
+#pragma unroll
+        for (int k = 0; k < CACHE_MAX_THETA; ++k)
+            if (k < n_theta) {
+                const double sc = ca_scale(u[k], st.m, mt);
+                st.den[k] *= sc; st.num[k] *= sc;
+            }
+        st.m = mt;
+    }
+#pragma unroll
+    for (int k = 0; k < CACHE_MAX_THETA; ++k) {
+        if (k >= n_theta) continue;
+        const double S = ceil(u[k] * st.m);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (kbase + 4 * i >= Mg) continue;          // a tail key has no mass
+            const double e = ca_exp2(fma(u[k], d[i], -S));
+            st.den[k] += e;
+            if (v[i] == y) st.num[k] += e;
+        }
+    }
+}
+
+// (st) <- (st) merged with the partial (mo, deno, numo), in this order
+__device__ __forceinline__ void ca_merge(CaState& st, double mo, const double* deno, const double* numo, const double* u, int n_theta) {
+    const double m = fmax(st.m, mo);
+#pragma unroll
+    for (int k = 0; k < CACHE_MAX_THETA; ++k)
+        if (k < n_theta) {
+            const double sa = ca_scale(u[k], st.m, m), sb = ca_scale(u[k], mo, m);
+            st.den[k] = st.den[k] * sa + deno[k] * sb;
+            st.num[k] = st.num[k] * sa + numo[k] * sb;
+        }
+    st.m = m;
+}
+
+__device__ __forceinline__ double ca_shfl(double x, int off) {
+    int lo = __double2loint(x), hi = __double2hiint(x);
+    lo = __shfl_xor(lo, off, 64); hi = __shfl_xor(hi, off, 64);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ void ca_merge_lanes(CaState& st, int off, const double* u, int n_theta) {
+    const double mo = ca_shfl(st.m, off);
+    double deno[CACHE_MAX_THETA], numo[CACHE_MAX_THETA];
+#pragma unroll
+    for (int k = 0; k < CACHE_MAX_THETA; ++k) {
+        deno[k] = ca_shfl(st.den[k], off);
+        numo[k] = ca_shfl(st.num[k], off);
+    }
+    ca_merge(st, mo, deno, numo, u, n_theta);
+}
+
+// 16 keys x 32 queries x 16 k: the key fragment feeds both query halves; k order x, y, z, w
+__device__ __forceinline__ void ca_mfma4(f64x4& acc0, f64x4& acc1, const float4& kv, const float4& b0, const float4& b1) {
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.x, (double)b0.x, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.x, (double)b1.x, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.y, (double)b0.y, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.y, (double)b1.y, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.z, (double)b0.z, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.z, (double)b1.z, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.w, (double)b0.w, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.w, (double)b1.w, acc1, 0, 0, 0);
+}
+
+// what the four waves of a workgroup hand to the threads that merge them
+struct CaMerge {
+    double m[CA_WAVES][CA_QT];
+    double den[CA_WAVES][CACHE_MAX_THETA][CA_QT], num[CA_WAVES][CACHE_MAX_THETA][CA_QT];
+};
+
+// where query id q lives and what its target is (CacheAttendArgs)
+__device__ __forceinline__ long long ca_query_row(const CacheAttendArgs& a, int q) {
+    return a.B > 0 ? (long long)(q % a.T + 1) * a.B + q / a.T : (long long)q;
+}
+__device__ __forceinline__ int ca_target(const CacheAttendArgs& a, int q) {
+    return a.B > 0 ? a.tgt[(long long)(q % a.T) * a.B + q / a.T] : a.tgt[q];
+}
+
+__global__ __launch_bounds__(256) void k_cache_attend(CacheAttendArgs a) {
+    // the query tile [CA_QT][Hp + CA_PAD] floats; once the key loop is over the same bytes hold the waves' partials (CaMerge): at
+    // hidden 512 a workgroup then needs 66 KiB, and two of them share a CU's 160 KiB
+    extern __shared__ double ca_lds[];
+    float* ca_q = reinterpret_cast<float*>(ca_lds);
+    CaMerge& mg = *reinterpret_cast<CaMerge*>(ca_lds);
+    const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int Hp = a.Hp, Mg = a.Mg, ldl = Hp + CA_PAD, n_theta = a.n_theta;
+    const int g = a.tile_group[tile];
+    const int* slots = a.slot_query + (long long)tile * CA_QT;
+    double theta[CACHE_MAX_THETA];                  // u = theta log2(e)
+#pragma unroll
+    for (int k = 0; k < CACHE_MAX_THETA; ++k) theta[k] = (double)a.theta[k] * CA_LOG2E;
+
+    // the tile's queries into LDS, an empty slot as zeros
+    const int c4n = Hp >> 2;
+    for (int idx = tid; idx < CA_QT * c4n; idx += 256) {
+        const int s = idx / c4n, c4 = idx - s * c4n;
+        const int q = slots[s];
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (q >= 0) v = *reinterpret_cast<const float4*>(a.Q + ca_query_row(a, q) * a.ldq + 4 * c4);
+        *reinterpret_cast<float4*>(ca_q + s * ldl + 4 * c4) = v;
+    }
+    __syncthreads();
+
+    const int kq = lane & 15, ks = lane >> 4;
+    const float* kg = a.keys + (long long)g * Mg * Hp;
+    const int* vg = a.vals + (long long)g * Mg;
+    const int q0 = slots[kq], q1 = slots[16 + kq];
+    const int y0 = q0 >= 0 ? ca_target(a, q0) : -1, y1 = q1 >= 0 ? ca_target(a, q1) : -1;       // (values are >= 0: -1 never hits)
+    CaState st0, st1;
+    const float* qp0 = ca_q + kq * ldl + 4 * ks;
+    const float* qp1 = qp0 + 16 * ldl;
+    const int n_kt = (Mg + 15) >> 4;
+    for (int kt = wave; kt < n_kt; kt += CA_WAVES) {
+        // lane l loads key row l % 16 of the tile (a tail row: the group's last key, in bounds, masked below), k = 16 j + 4 (l / 16) .. + 3
+        const int krow = min(kt * 16 + kq, Mg - 1);
+        const float* kp = kg + (long long)krow * Hp + 4 * ks;
+        f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+        // (two k groups per trip by hand: the loads of the second go out before the first one's products; a requested unroll of this
+        // loop is refused by the compiler)
+        int k = 0;
+        for (; k + 32 <= Hp; k += 32) {
+            const float4 kv = *reinterpret_cast<const float4*>(kp + k), kw = *reinterpret_cast<const float4*>(kp + k + 16);
+            const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k), c0 = *reinterpret_cast<const float4*>(qp0 + k + 16);
+            const float4 b1 = *reinterpret_cast<const float4*>(qp1 + k), c1 = *reinterpret_cast<const float4*>(qp1 + k + 16);
+            ca_mfma4(acc0, acc1, kv, b0, b1);
+            ca_mfma4(acc0, acc1, kw, c0, c1);
+        }
+        if (k < Hp) {
+            const float4 kv = *reinterpret_cast<const float4*>(kp + k);
+            const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k);
+            const float4 b1 = *reinterpret_cast<const float4*>(qp1 + k);
+            ca_mfma4(acc0, acc1, kv, b0, b1);
+        }
+        // accumulator register i of lane l (the fp64 instruction's layout): key 4 i + l / 16 of the tile against query l % 16
+        const int kbase = kt * 16 + ks;
+        int v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = vg[min(kbase + 4 * i, Mg - 1)];
+        ca_update(st0, acc0, kbase, Mg, v, y0, theta, n_theta);
+        ca_update(st1, acc1, kbase, Mg, v, y1, theta, n_theta);
+    }
+    // the four key subsets of a wave: (0 + 1) + (2 + 3), read from the lanes with l / 16 == 0
+    ca_merge_lanes(st0, 16, theta, n_theta); ca_merge_lanes(st0, 32, theta, n_theta);
+    ca_merge_lanes(st1, 16, theta, n_theta); ca_merge_lanes(st1, 32, theta, n_theta);
+    __syncthreads();                                 // every wave is done with the query tile
+    if (ks == 0) {
+        mg.m[wave][kq] = st0.m; mg.m[wave][16 + kq] = st1.m;
+#pragma unroll
+        for (int k = 0; k < CACHE_MAX_THETA; ++k) {
+            mg.den[wave][k][kq] = st0.den[k]; mg.den[wave][k][16 + kq] = st1.den[k];
+            mg.num[wave][k][kq] = st0.num[k]; mg.num[wave][k][16 + kq] = st1.num[k];
+        }
+    }
+    __syncthreads();
+    if (tid >= CA_QT) return;
+    const int q = slots[tid];
+    if (q < 0) return;
+    CaState st;                                      // waves 0, 1, 2, 3 in this order
+    for (int w = 0; w < CA_WAVES; ++w) {
+        double deno[CACHE_MAX_THETA], numo[CACHE_MAX_THETA];
+#pragma unroll
+        for (int k = 0; k < CACHE_MAX_THETA; ++k) { deno[k] = mg.den[w][k][tid]; numo[k] = mg.num[w][k][tid]; }
+        ca_merge(st, mg.m[w][tid], deno, numo, theta, n_theta);
+    }
+#pragma unroll
+    for (int k = 0; k < CACHE_MAX_THETA; ++k)
+        if (k < n_theta) a.out[(long long)k * a.n + q] = st.num[k] == 0.0 ? 0.0f : (float)(st.num[k] / st.den[k]);
+}
+
+// Hs1: slot 1 of the pass's top-layer hidden states, time-major [T][B][Hp]; Y [T][B].  Pass row b is row r0 + b of the cache's
+// [rows][T] entries (group-major: group = row / rows_per_group, entry = (row % rows_per_group) * T + t).  Pad units are written as zeros.
+__global__ __launch_bounds__(256) void k_cache_fill(const float* __restrict__ Hs1, const int* __restrict__ Y, int B, int T, int H, int Hp,
+                                                    long long r0, float* __restrict__ keys, int* __restrict__ vals) {
+    const int c4n = Hp >> 2;
+    const long long total = (long long)T * B * c4n;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const long long row = idx / c4n;                // t * B + b
+        const int c4 = (int)(idx - row * c4n);
+        const int t = (int)(row / B), b = (int)(row - (long long)t * B);
+        float4 v = *reinterpret_cast<const float4*>(Hs1 + row * Hp + 4 * c4);
+        const int c = 4 * c4;
+        if (c + 0 >= H) v.x = 0.0f;
+        if (c + 1 >= H) v.y = 0.0f;
+        if (c + 2 >= H) v.z = 0.0f;
+        if (c + 3 >= H) v.w = 0.0f;
+        const long long e = (r0 + b) * T + t;
+        *reinterpret_cast<float4*>(keys + e * Hp + c) = v;
+        if (c4 == 0) vals[e] = Y[row];
+    }
+}
+
+}  // namespace
+
+size_t cache_attend_lds_bytes(int Hp) { return std::max(sizeof(float) * (size_t)CA_QT * (Hp + CA_PAD), sizeof(CaMerge)); }
+
+hipError_t launch_cache_attend(hipStream_t s, const CacheAttendArgs& a) {
+    if (a.n_tiles <= 0) return hipSuccess;
+    if (a.Mg < 1 || a.Hp < 16 || (a.Hp & 15) != 0 || a.n_theta < 1 || a.n_theta > CACHE_MAX_THETA || (a.ldq & 3) != 0 || a.n < 1)
+        return hipErrorInvalidValue;
+    const size_t lds = cache_attend_lds_bytes(a.Hp);
+    if (lds > 64 * 1024) {                  // hidden sizes above 508: more dynamic LDS than a launch gets by default (160 KiB per CU)
+        const hipError_t e = hipFuncSetAttribute((const void*)k_cache_attend, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_cache_attend, dim3(a.n_tiles), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cache_fill(hipStream_t s, const float* Hs1, const int* Y, int B, int T, int H, int Hp, long long r0, float* keys,
+                             int* vals) {
+    if (B <= 0 || T <= 0) return hipSuccess;
+    if ((Hp & 3) != 0) return hipErrorInvalidValue;
+    const long long total = (long long)T * B * (Hp >> 2);
+    const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_cache_fill, dim3(blocks), dim3(256), 0, s, Hs1, Y, B, T, H, Hp, r0, keys, vals);
+    return hipGetLastError();
+}
+
+}  // namespace fsmg

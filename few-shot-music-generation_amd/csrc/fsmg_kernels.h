@@ -446,4 +446,34 @@ constexpr int SCORE_REG_COLS = 10 * 1024;
 hipError_t launch_score_rows(hipStream_t s, const float* logits, int ld, int rows, int n_vocab, const int* tgt, int B, int T,
                              float* out_lp, int* out_rank, float* out_ent, int* out_arg);
 
+// ---------------------------------------------------------------- support-set neural cache (cache.hip, fsmg_cache_*)
+// out[k * n + q] = sum_{i : vals[g][i] == y_q} exp(theta_k (d_i - d_max)) / sum_i exp(theta_k (d_i - d_max)), d_i = Q_q . keys[g][i]
+// over the Mg keys of q's group g; exactly 0 when no entry holds y_q.  The host sorts the queries by group: tile j (one workgroup) holds
+// up to CACHE_ATTEND_QT query ids of group tile_group[j] in slot_query[j * CACHE_ATTEND_QT ..], -1 in an empty slot.
+// B == 0: query q is row q of Q (ldq floats apart) and its target tgt[q].  B > 0: q = b * T + t is row (t + 1) * B + b of Q (a pass's
+// top-layer hidden states [T + 1][B][Hp], ldq = Hp) and its target tgt[t * B + b] (the pass's Y).
+// Fused (no score matrix in memory), scores on the fp64 MFMA (exact products of the fp32 inputs), tail keys masked, no atomics, fixed merge order; a query's bits depend on
+// its vector, its group's entries and theta alone.  No allocation, no synchronisation.
+constexpr int CACHE_ATTEND_QT = 32;
+constexpr int CACHE_MAX_THETA = 8;
+struct CacheAttendArgs {
+    const float* keys;          // [G][Mg][Hp], pad units exact zeros
+    const int* vals;            // [G][Mg]
+    int Mg, Hp;
+    const float* Q; long long ldq;
+    int B, T;
+    const int* tgt;
+    const int* slot_query;      // [n_tiles][CACHE_ATTEND_QT]
+    const int* tile_group;      // [n_tiles]
+    int n_tiles, n;
+    float theta[CACHE_MAX_THETA]; int n_theta;      // theta >= 0
+    float* out;                 // [n_theta][n]
+};
+size_t cache_attend_lds_bytes(int Hp);
+hipError_t launch_cache_attend(hipStream_t s, const CacheAttendArgs& a);
+// a pass's top-layer hidden states (Hs1: slot 1, time-major [T][B][Hp]) and targets Y [T][B] into rows r0 .. r0 + B - 1 of a cache's
+// [rows][T] entries; units >= H are written as zeros
+hipError_t launch_cache_fill(hipStream_t s, const float* Hs1, const int* Y, int B, int T, int H, int Hp, long long r0, float* keys,
+                             int* vals);
+
 }  // namespace fsmg

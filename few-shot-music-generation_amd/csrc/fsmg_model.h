@@ -10,6 +10,7 @@
 //   api_unigram.hip   unigram baseline                                 api_debug.hip debug reads, timers, clock probe
 //   api_decode.hip    decoding: fsmg_generate(_filtered), fsmg_beam_search, their MAML twins, fsmg_sample (one driver); decode states (fsmg_dstate_*)
 //   api_score.hip     scoring of given songs: fsmg_score, fsmg_maml_score
+//   api_cache.hip     support-set neural cache: fsmg_cache_* (build, attend, score and eval against a cache)
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
@@ -65,6 +66,16 @@ struct fsmg_dstate_s {
     float *h = nullptr, *c = nullptr;   // [L][R][Hp]
     int* ctx = nullptr;                 // [R][history + 1]
     int kept() const { return (int)std::min<long long>(n_ctx, history); }
+};
+
+// A support-set cache (fsmg_cache_*, api_cache.hip): its own allocation, [keys | values].  Data only: it holds vectors and tokens and
+// does not refer to the parameters that produced them.
+struct fsmg_cache_s {
+    int G = 0, Mg = 0, H = 0, Hp = 0;
+    size_t bytes = 0;
+    char* mem = nullptr;
+    float* keys = nullptr;              // [G][Mg][Hp], pad units exact zeros
+    int* vals = nullptr;                // [G][Mg]
 };
 
 struct fsmg_model {
@@ -226,6 +237,10 @@ struct fsmg_model {
     char* gen = nullptr;
     size_t gen_bytes = 0;
     std::vector<fsmg_dstate_s*> dstates;   // the decode states this handle owns (fsmg_dstate_create): every entry point looks its state up here
+    // support-set caches (api_cache.hip): the registry, and the attention calls' scratch (grown between calls after a stream sync)
+    std::vector<fsmg_cache_s*> caches;
+    char* cat = nullptr;
+    size_t cat_bytes = 0;
 
     // gradient exchange inside the library (fsmg_comm_*): RCCL communicator, its stream, the event the compute stream waits on
     void* comm = nullptr; bool own_comm = false; int world = 1, rank = 0;
@@ -569,7 +584,8 @@ int gemm_cleanup(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs g,
 int stage_tokens(fsmg_model* h, const int32_t* support, int n_sup, const int32_t* query, int n_qry, int on_device);
 int reset_tok_table(fsmg_model* h);
 int token_prep(fsmg_model* h, int n_sup, int n_qry, bool train = false);
-enum { HEAD_LOSS = 0, HEAD_LOGITS = 1 };     // what a forward pass ends in: projection + cross entropy + loss, or the bare logits (fsmg_score)
+// what a forward pass ends in: projection + cross entropy + loss, the bare logits (fsmg_score), or the hidden states alone (fsmg_cache_build)
+enum { HEAD_LOSS = 0, HEAD_LOGITS = 1, HEAD_NONE = 2 };
 int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_out, bool want_dlogits, int head = HEAD_LOSS);
 GemmArgs dw_args(fsmg_model* h, int B);        // api_backward.hip: dW = Hout^T dlogits, dd = colsum(dlogits) (forward() asks which kernel it will take)
 // api_backward.hip

@@ -89,6 +89,23 @@ class FsmgDstateConfig(C.Structure):
     _fields_ = [('version', C.c_int32), ('n_rows', C.c_int32), ('history', C.c_int32), ('reserved', C.c_int32 * 9)]
 
 
+FSMG_CACHE_CONFIG_VERSION = 1
+FSMG_CACHE_SCORE_CONFIG_VERSION = 1
+FSMG_CACHE_MAX_THETA = 8
+FSMG_CACHE_MAX_LAMBDA = 16
+
+
+class FsmgCacheConfig(C.Structure):
+    _fields_ = [('version', C.c_int32), ('n_rows', C.c_int32), ('n_groups', C.c_int32), ('tokens_on_device', C.c_int32),
+                ('pass_rows', C.c_int32), ('reserved', C.c_int32 * 11)]
+
+
+class FsmgCacheScoreConfig(C.Structure):
+    _fields_ = [('version', C.c_int32), ('n_rows', C.c_int32), ('tokens_on_device', C.c_int32), ('nll_first', C.c_int32),
+                ('nll_count', C.c_int32), ('pass_rows', C.c_int32), ('n_theta', C.c_int32), ('n_lambda', C.c_int32),
+                ('thetas', C.c_float * 8), ('lambdas', C.c_float * 16), ('reserved', C.c_int32 * 8)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -153,6 +170,14 @@ SIGNATURES = {
     'fsmg_dstate_feed': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _F32P]),
     'fsmg_dstate_generate': (C.c_int, [_P, _P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _I32P, _F32P]),
     'fsmg_dstate_beam_search': (C.c_int, [_P, _P, C.POINTER(FsmgBeamConfig), _I32P, _F32P, _F32P]),
+    'fsmg_cache_build': (C.c_int, [_P, C.POINTER(FsmgCacheConfig), _P, C.POINTER(_P)]),
+    'fsmg_cache_create_from': (C.c_int, [_P, C.c_int32, C.c_int32, _F32P, _I32P, C.POINTER(_P)]),
+    'fsmg_cache_get': (C.c_int, [_P, _P, _F32P, _I32P]),
+    'fsmg_cache_info': (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
+    'fsmg_cache_destroy': (C.c_int, [_P, _P]),
+    'fsmg_cache_attend': (C.c_int, [_P, _P, C.c_int32, _F32P, _I32P, _I32P, _F32P, C.c_int32, _F32P]),
+    'fsmg_cache_score': (C.c_int, [_P, _P, C.POINTER(FsmgCacheScoreConfig), _P, _I32P, _F32P, _F32P, _F32P, _F32P]),
+    'fsmg_cache_eval_step': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _F32P]),
     'fsmg_read_losses': (C.c_int, [_P, _F32P, C.c_int32]),
     'fsmg_get_stats': (C.c_int, [_P, C.POINTER(FsmgStats)]),
     'fsmg_debug_read': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
@@ -290,6 +315,51 @@ class DecodeState(object):
         if not isinstance(src, DecodeState) or not getattr(src, '_st', None):
             raise ValueError('src must be an open DecodeState')
         self._call(self._model._lib.fsmg_dstate_gather, src._st, idx.ctypes.data_as(_I32P))
+
+
+class FsmgCache(object):
+    """A support-set cache of an FsmgModel (include/fsmg.h fsmg_cache_*): `groups` groups (one per artist) of `entries` (key, value)
+    pairs each, resident on the device -- a key is a top-layer hidden state, a value the token that followed it.  Made by
+    FsmgModel.cache_build / cache_from; FsmgModel.cache_attend / cache_score read it.  A cache is data: it stays valid, and stale,
+    when the parameters change."""
+
+    def __init__(self, model, handle):
+        self._model = model
+        self._c = handle
+        i = self.info()
+        self.groups, self.entries, self.hidden = i['groups'], i['entries'], i['hidden']
+
+    def close(self):
+        # (a cache whose model is closed already went with it: fsmg_destroy frees what is left)
+        if getattr(self, '_c', None) and getattr(self._model, '_h', None):
+            self._model._lib.fsmg_cache_destroy(self._model._h, self._c)
+        self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ptr(self):
+        if not getattr(self, '_c', None):
+            raise FsmgError(-1, 'the cache is closed')
+        return self._c
+
+    def _call(self, fn, *args):
+        self._model._ck(fn(self._model._h, self._ptr(), *args))
+
+    def info(self):
+        out = (C.c_int64 * 4)()
+        self._call(self._model._lib.fsmg_cache_info, out)
+        return dict(groups=int(out[0]), entries=int(out[1]), hidden=int(out[2]), bytes=int(out[3]))
+
+    def get(self):
+        """-> (keys float32 [groups, entries, H], values int32 [groups, entries])"""
+        keys = np.empty((self.groups, self.entries, self.hidden), np.float32)
+        vals = np.empty((self.groups, self.entries), np.int32)
+        self._call(self._model._lib.fsmg_cache_get, _f32p(keys), vals.ctypes.data_as(_I32P))
+        return keys, vals
 
 
 class FsmgModel(object):
@@ -759,6 +829,115 @@ class FsmgModel(object):
         sp, rows, dev, _keep = self._support(support, n_support_rows)
         return self._score((sp, rows, int(inner_steps), float(inner_lr), dev), tokens, n_rows, logprob, rank, entropy, argmax,
                            row_nll, nll_first, nll_count, pass_rows)
+
+    # -- support-set neural cache (include/fsmg.h fsmg_cache_*) ---------------------------------------------------
+    @staticmethod
+    def cache_score_config(n_rows, thetas, lambdas, nll_first=0, nll_count=0, pass_rows=0, tokens_on_device=0):
+        """FsmgCacheScoreConfig for thetas (1..8 finite values >= 0) and lambdas (1..16 values in [0, 1]); ValueError otherwise"""
+        th = np.atleast_1d(np.asarray(thetas, np.float32))
+        la = np.atleast_1d(np.asarray(lambdas, np.float32))
+        if th.ndim != 1 or not 1 <= th.size <= FSMG_CACHE_MAX_THETA or not np.all(np.isfinite(th)) or np.any(th < 0):
+            raise ValueError('thetas must be 1..%d finite values >= 0, got %r' % (FSMG_CACHE_MAX_THETA, thetas))
+        if la.ndim != 1 or not 1 <= la.size <= FSMG_CACHE_MAX_LAMBDA or not np.all((la >= 0) & (la <= 1)):
+            raise ValueError('lambdas must be 1..%d values in [0, 1], got %r' % (FSMG_CACHE_MAX_LAMBDA, lambdas))
+        c = FsmgCacheScoreConfig(version=FSMG_CACHE_SCORE_CONFIG_VERSION, n_rows=int(n_rows), tokens_on_device=int(tokens_on_device),
+                                 nll_first=int(nll_first), nll_count=int(nll_count), pass_rows=int(pass_rows), n_theta=th.size,
+                                 n_lambda=la.size)
+        c.thetas[:th.size] = th.tolist()
+        c.lambdas[:la.size] = la.tolist()
+        return c
+
+    def _rows(self, tokens, n_rows):
+        """host [.., max_len] tokens or a device address with n_rows -> (void*, on_device, keepalive, rows)"""
+        if isinstance(tokens, (int, np.integer)):
+            return C.c_void_p(int(tokens)), 1, None, int(n_rows)
+        a = np.ascontiguousarray(tokens, dtype=np.int32)
+        if a.ndim == 0 or a.shape[-1] != self.max_len:
+            raise ValueError('tokens %r do not match max_len=%d' % (a.shape, self.max_len))
+        a = a.reshape(-1, self.max_len)
+        return C.c_void_p(a.ctypes.data), 0, a, a.shape[0]
+
+    def cache_build(self, tokens, n_groups=1, pass_rows=0, n_rows=None):
+        """Read support songs int32 [rows, max_len] ([groups, K, max_len] works too; or a device address with n_rows) into a new
+        FsmgCache of n_groups groups: row r belongs to group r // (rows // n_groups), and entry (r % rows_per_group) * T + t holds
+        the top-layer hidden state that predicts token t of the row, with that token as its value."""
+        tp, dev, _keep, R = self._rows(tokens, n_rows)
+        c = FsmgCacheConfig(version=FSMG_CACHE_CONFIG_VERSION, n_rows=R, n_groups=int(n_groups), tokens_on_device=dev,
+                            pass_rows=int(pass_rows))
+        out = _P()
+        self._ck(self._lib.fsmg_cache_build(self._h, C.byref(c), tp, C.byref(out)))
+        return FsmgCache(self, out)
+
+    def cache_from(self, keys, values):
+        """a new FsmgCache from host arrays: keys float32 [groups, entries, H], values int32 [groups, entries]"""
+        k = np.ascontiguousarray(keys, dtype=np.float32)
+        v = np.ascontiguousarray(values, dtype=np.int32)
+        if k.ndim != 3 or k.shape[2] != int(self.cfg.hidden_size) or v.shape != k.shape[:2]:
+            raise ValueError('keys must be [groups, entries, %d] and values [groups, entries], got %r and %r'
+                             % (int(self.cfg.hidden_size), k.shape, v.shape))
+        out = _P()
+        self._ck(self._lib.fsmg_cache_create_from(self._h, k.shape[0], k.shape[1], _f32p(k), v.ctypes.data_as(_I32P), C.byref(out)))
+        return FsmgCache(self, out)
+
+    def cache_attend(self, cache, queries, targets, thetas, group=None):
+        """p_cache of raw query vectors: queries float32 [n, H], targets int32 [n], group int32 [n] (None: all in group 0), thetas
+        1..8 values >= 0 -> float32 [n_theta, n]: the softmax(theta q . k) mass of the entries of the query's group that hold its
+        target, exactly 0 when none does."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        y = np.ascontiguousarray(targets, dtype=np.int32)
+        th = np.atleast_1d(np.ascontiguousarray(thetas, dtype=np.float32))
+        if q.ndim != 2 or q.shape[1] != int(self.cfg.hidden_size) or y.shape != (q.shape[0],):
+            raise ValueError('queries must be [n, %d] and targets [n], got %r and %r' % (int(self.cfg.hidden_size), q.shape, y.shape))
+        g = None
+        if group is not None:
+            g = np.ascontiguousarray(group, dtype=np.int32)
+            if g.shape != y.shape:
+                raise ValueError('group must be [%d], got %r' % (y.size, g.shape))
+        out = np.empty((th.size, q.shape[0]), np.float32)
+        self._ck(self._lib.fsmg_cache_attend(self._h, cache._ptr(), q.shape[0], _f32p(q), y.ctypes.data_as(_I32P),
+                    g.ctypes.data_as(_I32P) if g is not None else None, _f32p(th), th.size, _f32p(out)))
+        return out
+
+    def cache_score(self, cache, tokens, thetas, lambdas, group=None, logprob=True, cache_prob=False, lstm_logprob=False, row_nll=True,
+                    nll_first=0, nll_count=0, pass_rows=0, n_rows=None):
+        """score() with a cache beside the model: tokens int32 [R, max_len] (or a device address with n_rows), row r attending
+        over group group[r] of the cache (None: group 0) -> a dict with the requested arrays: 'logprob' float32 [n_theta, n_lambda, R,
+        T] (log of the (1 - lambda, lambda) mixture of the model's and the cache's probability of each token), 'cache_prob' float32
+        [n_theta, R, T], 'lstm_logprob' float32 [R, T] (score()'s 'logprob'), 'row_nll' float32 [n_theta, n_lambda, R].  The whole
+        (theta, lambda) grid costs one device pass."""
+        tp, dev, _keep, R = self._rows(tokens, n_rows)
+        c = self.cache_score_config(R, thetas, lambdas, nll_first, nll_count, pass_rows, dev)
+        g = None
+        if group is not None:
+            g = np.ascontiguousarray(group, dtype=np.int32)
+            if g.shape != (R,):
+                raise ValueError('group must be [%d], got %r' % (R, g.shape))
+        T, NT, NL = self.max_len, c.n_theta, c.n_lambda
+        out = {}
+        if logprob:
+            out['logprob'] = np.empty((NT, NL, R, T), np.float32)
+        if cache_prob:
+            out['cache_prob'] = np.empty((NT, R, T), np.float32)
+        if lstm_logprob:
+            out['lstm_logprob'] = np.empty((R, T), np.float32)
+        if row_nll:
+            out['row_nll'] = np.empty((NT, NL, R), np.float32)
+        f = lambda k: _f32p(out[k]) if k in out else None
+        self._ck(self._lib.fsmg_cache_score(self._h, cache._ptr(), C.byref(c), tp, g.ctypes.data_as(_I32P) if g is not None else None,
+                                            f('logprob'), f('cache_prob'), f('lstm_logprob'), f('row_nll')))
+        return out
+
+    def cache_eval_step(self, support, query, theta, lam):
+        """support int32 [N, K, max_len], query int32 [N, Q, max_len] -> the mean NLL of the query tokens under the mixture, artist
+        a's query songs attending over a cache built from artist a's support songs (eval_step with the support set used)"""
+        s = np.ascontiguousarray(support, dtype=np.int32)
+        q = np.ascontiguousarray(query, dtype=np.int32)
+        if s.ndim != 3 or q.ndim != 3 or s.shape[0] != q.shape[0] or s.shape[2] != self.max_len or q.shape[2] != self.max_len:
+            raise ValueError('support %r / query %r must be [N, K, %d] and [N, Q, %d]' % (s.shape, q.shape, self.max_len, self.max_len))
+        nll = C.c_float()
+        self._ck(self._lib.fsmg_cache_eval_step(self._h, C.c_void_p(s.ctypes.data), C.c_void_p(q.ctypes.data), s.shape[0], s.shape[1],
+                                                q.shape[1], float(theta), float(lam), C.byref(nll)))
+        return nll.value
 
     def read_losses(self, n):
         out = np.empty(n, np.float32)

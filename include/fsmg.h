@@ -476,6 +476,101 @@ int fsmg_dstate_generate(fsmg_handle h, fsmg_dstate st, const fsmg_gen_config* g
 int fsmg_dstate_beam_search(fsmg_handle h, fsmg_dstate st, const fsmg_beam_config* b, int32_t* out_tokens, float* out_scores,
                             float* out_logprob);
 
+/* ---- support-set neural cache (DESIGN.md "Support-set cache"; Grave, Joulin, Usunier: Improving neural language models with a
+ * continuous cache).  The few-shot route that needs no gradient: keep the top-layer hidden states the model produced while reading an
+ * artist's support songs, each with the token that followed it; at a query position attend over them with the query's own hidden
+ * state; mix the resulting distribution with the model's.
+ * A cache is a device-resident object the handle owns: G groups (one per artist) of Mg entries each; an entry is a key of H floats
+ * (stored padded, the pad units exact zeros) and an int32 value, the token that followed.  A cache is DATA: it holds vectors and does
+ * not refer to the parameters.  It stays valid -- and STALE -- after a train step, fsmg_set_param or fsmg_init_params: it still holds
+ * the vectors of the parameters it was built with, and scoring against it is defined and deterministic.  Caches at MAML's theta' do
+ * not exist.
+ *   fsmg_cache_build      rows tokens [n_rows, max_len], read exactly as fsmg_score reads a row; row r belongs to group
+ *                         r / (n_rows / n_groups).  Entry e = (r mod rows_per_group) * T + t of that group: the key is the top-layer h
+ *                         after the inputs [start, x_0 .. x_{t-1}] -- the vector whose projection is the logits row fsmg_score scores
+ *                         at (r, t) -- and the value is x_t.  Mg = (n_rows / n_groups) * T.  No logits are computed.  The rows are
+ *                         processed pass_rows at a time, the last pass shorter; the keys are bitwise the top-layer hidden states an
+ *                         fsmg_score pass over the same rows with the same pass_rows computes; the cache is bitwise what building each
+ *                         pass's rows in a call of their own gives; the pass size is a function of the config alone; two identical
+ *                         calls give identical bits.  A row's bits are NOT promised independent of its pass's row count.
+ *                         State: exactly fsmg_score's -- parameters, Adam moments, global_step, the loss ring and the gradient buffer
+ *                         untouched, activations overwritten, the recurrent-launch counters advance, a time-out of a persistent
+ *                         recurrent kernel repeats the pass on per-step launches.
+ *   fsmg_cache_create_from  a cache from host arrays: keys [G][Mg][H], values [G][Mg] (ids in [0, input_size]).
+ *   fsmg_cache_get        the reverse; either output may be NULL.
+ *   fsmg_cache_info       out = {groups, entries per group, H, device bytes}.
+ *   fsmg_cache_destroy    frees it; fsmg_destroy frees the caches still alive.
+ *   fsmg_cache_attend     for query vector q (host [n][H]) in group g (host [n], NULL = all 0) with target y and sharpness theta >= 0:
+ *                           d_i = q . k_i over the group's Mg keys (exact products of the fp32 inputs, fp64 accumulation),
+ *                           p_cache(y) = sum_{i : v_i = y} exp(theta (d_i - d_max)) / sum_i exp(theta (d_i - d_max)),
+ *                         exactly 0 when no entry holds y; out_prob host [n_theta][n].  Deterministic (no atomics); a query's bits
+ *                         depend on its vector, its group's entries and theta alone -- not on the other queries of the call, their
+ *                         number or the query's place among them.
+ *   fsmg_cache_score      fsmg_score's rows with the cache beside the model: per pass the model log-prob lp (fsmg_score's kernel) and
+ *                         p_cache(y) for the pass's own top-layer hidden states as queries (no host round trip), row r in group
+ *                         group[r] (host [R], NULL = all 0).  Outputs, any may be NULL but not all:
+ *                           out_lstm_logprob [R][T]                  bitwise fsmg_score's out_logprob for the same rows and pass_rows;
+ *                           out_cache_prob   [n_theta][R][T]         p_cache(y), bitwise fsmg_cache_attend on the pass's hidden states;
+ *                           out_logprob      [n_theta][n_lambda][R][T]  log((1 - lambda) exp(lp) + lambda p_cache), evaluated on the
+ *                                            host in fp64 from the two fp32 numbers and rounded once: a = log1p(-lambda) + lp,
+ *                                            b = log(lambda) + log(p_cache) (-inf at p_cache = 0), out = logaddexp(a, b); lambda = 0
+ *                                            gives lp bitwise, lambda = 1 gives log(p_cache);
+ *                           out_row_nll      [n_theta][n_lambda][R]  fsmg_score's definition over out_logprob (nll_first / nll_count):
+ *                                            an fp64 sum in increasing t, rounded once; bitwise recomputable from out_logprob.
+ *                         The whole (theta, lambda) grid costs one device pass.  Passes, state and time-outs as fsmg_score.
+ *   fsmg_cache_eval_step  support [N,K,T] and query [N,Q,T] on the host: builds a cache of N groups of K rows, scores the N * Q query
+ *                         rows with group = artist, *nll = -(fp64 mean of out_logprob), destroys the cache.  fsmg_eval_step's number
+ *                         with the support set used instead of ignored; lambda = 0 gives the model's own NLL.
+ * Errors: FSMG_ERR_INVALID for a cache this handle does not own or one already destroyed (a registry: an error, not a crash), a wrong
+ * version, nonzero reserved fields, n_rows < 1 (or > 2^20), n_groups < 1, n_rows not a multiple of n_groups, tokens_on_device not
+ * 0 / 1, pass_rows outside {0} u [1, 1024], the nll window rules of fsmg_score, n_theta outside [1, 8], a theta that is negative or not
+ * finite, n_lambda outside [1, 16], a lambda outside [0, 1], n < 1 (or > 2^22), a group id outside [0, G), a cache whose H is not the
+ * handle's, every output NULL, NULL arguments, G < 1, Mg < 1, G * Mg > 2^22, G * Mg * Hp * 4 > 2^31 (Hp the padded hidden size);
+ * FSMG_ERR_TOKEN_RANGE for a token outside [0, input_size) or a value outside [0, input_size].  Host tokens are checked before any
+ * device work. */
+#define FSMG_CACHE_CONFIG_VERSION 1
+#define FSMG_CACHE_SCORE_CONFIG_VERSION 1
+#define FSMG_CACHE_MAX_THETA 8
+#define FSMG_CACHE_MAX_LAMBDA 16
+typedef struct fsmg_cache_s* fsmg_cache;
+typedef struct fsmg_cache_config {
+    int32_t version;          /* FSMG_CACHE_CONFIG_VERSION                                   */
+    int32_t n_rows;           /* support rows of max_len tokens each                         */
+    int32_t n_groups;         /* G >= 1; n_rows % n_groups == 0                              */
+    int32_t tokens_on_device; /* 0 host, 1 device                                            */
+    int32_t pass_rows;        /* 0 = FSMG_SCORE_PASS_ROWS, else 1..1024                      */
+    int32_t reserved[11];     /* must be 0                                                   */
+} fsmg_cache_config;
+typedef struct fsmg_cache_score_config {
+    int32_t version;          /* FSMG_CACHE_SCORE_CONFIG_VERSION                             */
+    int32_t n_rows;           /* R >= 1 songs of max_len tokens each                         */
+    int32_t tokens_on_device; /* 0 host, 1 device                                            */
+    int32_t nll_first;        /* as fsmg_score_config                                        */
+    int32_t nll_count;        /* as fsmg_score_config                                        */
+    int32_t pass_rows;        /* 0 = FSMG_SCORE_PASS_ROWS, else 1..1024                      */
+    int32_t n_theta;          /* 1..8                                                        */
+    int32_t n_lambda;         /* 1..16                                                       */
+    float thetas[8];          /* finite, >= 0; the first n_theta count                       */
+    float lambdas[16];        /* in [0, 1]; the first n_lambda count                         */
+    int32_t reserved[8];      /* must be 0                                                   */
+} fsmg_cache_score_config;
+
+int fsmg_cache_build(fsmg_handle h, const fsmg_cache_config* c, const int32_t* tokens, fsmg_cache* out);
+/* keys host [G][Mg][H], values host [G][Mg] */
+int fsmg_cache_create_from(fsmg_handle h, int32_t n_groups, int32_t entries_per_group, const float* keys, const int32_t* values,
+                           fsmg_cache* out);
+int fsmg_cache_get(fsmg_handle h, fsmg_cache cache, float* keys, int32_t* values);
+int fsmg_cache_info(fsmg_handle h, fsmg_cache cache, int64_t out[4]);
+int fsmg_cache_destroy(fsmg_handle h, fsmg_cache cache);
+/* queries host [n][H], targets host [n], group host [n] or NULL, thetas host [n_theta], out_prob host [n_theta][n] */
+int fsmg_cache_attend(fsmg_handle h, fsmg_cache cache, int32_t n, const float* queries, const int32_t* targets, const int32_t* group,
+                      const float* thetas, int32_t n_theta, float* out_prob);
+/* tokens [R,T]; group host [R] or NULL; host outputs, any may be NULL but not all */
+int fsmg_cache_score(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const int32_t* tokens, const int32_t* group,
+                     float* out_logprob, float* out_cache_prob, float* out_lstm_logprob, float* out_row_nll);
+int fsmg_cache_eval_step(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q, float theta,
+                         float lambda, float* nll);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
