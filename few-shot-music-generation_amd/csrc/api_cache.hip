@@ -8,11 +8,6 @@ using namespace fsmg_host;
 
 namespace fsmg_host {
 
-namespace {
-
-constexpr int64_t CACHE_MAX_ENTRIES = 1LL << 22;
-constexpr int64_t CACHE_MAX_KEY_BYTES = 1LL << 31;
-
 // the cache `c` if this handle owns it (the registry: a destroyed or foreign pointer is never dereferenced)
 fsmg_cache_s* find_cache(fsmg_model* h, fsmg_cache c) {
     for (fsmg_cache_s* s : h->caches)
@@ -20,6 +15,19 @@ fsmg_cache_s* find_cache(fsmg_model* h, fsmg_cache c) {
     fail(h, FSMG_ERR_INVALID, "not a cache of this handle (never created here, or already destroyed)");
     return nullptr;
 }
+
+void free_cache(fsmg_cache_s* c) {
+    if (c->mem) hipFree(c->mem);
+    if (c->idx_mem) hipFree(c->idx_mem);
+    delete c;
+}
+
+namespace {
+
+constexpr int64_t CACHE_MAX_ENTRIES = 1LL << 22;
+constexpr int64_t CACHE_MAX_KEY_BYTES = 1LL << 31;
+constexpr int64_t CACHE_GEN_MAX_SCORES = 1LL << 26;     // R * Mg of one cache-conditioned call (fp64 scores: 512 MiB)
+static_assert(CACHE_GEN_CHUNK == FSMG_CACHE_GEN_CHUNK, "include/fsmg.h states the key chunk of k_cache_scores");
 
 int check_cache_size(fsmg_model* h, int64_t G, int64_t Mg) {
     if (G < 1 || Mg < 1) return fail(h, FSMG_ERR_INVALID, "a cache needs n_groups >= 1 and entries_per_group >= 1");
@@ -41,11 +49,6 @@ int alloc_cache(fsmg_model* h, int G, int Mg, fsmg_cache_s** out) {
     c->vals = (int*)(c->mem + kbytes);
     *out = c;
     return FSMG_OK;
-}
-
-void free_cache(fsmg_cache_s* c) {
-    if (c->mem) hipFree(c->mem);
-    delete c;
 }
 
 // h->cat holds at least `bytes`: grown between calls, after a stream sync
@@ -321,6 +324,137 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
 
 }  // namespace
 
+// ---- cache-conditioned generation: the cache side (the decode driver in api_decode.hip calls these)
+int cache_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const int32_t* group, int64_t R, CacheGen* cg) {
+    fsmg_cache_s* c = find_cache(h, cache);
+    if (!c) return FSMG_ERR_INVALID;
+    if (!cc) return fail(h, FSMG_ERR_INVALID, "null fsmg_cache_gen_config");
+    if (cc->version != FSMG_CACHE_GEN_CONFIG_VERSION)
+        return fail(h, FSMG_ERR_INVALID, "fsmg_cache_gen_config.version is " + std::to_string(cc->version) + ", this library expects " +
+                                             std::to_string(FSMG_CACHE_GEN_CONFIG_VERSION));
+    for (int32_t r : cc->reserved)
+        if (r != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_cache_gen_config.reserved must be zero");
+    if (!thetas_ok(&cc->theta, 1)) return fail(h, FSMG_ERR_INVALID, "theta must be finite and >= 0");
+    if (!(cc->lambda >= 0.0f && cc->lambda <= 1.0f)) return fail(h, FSMG_ERR_INVALID, "lambda must lie in [0, 1]");
+    if (R < 1 || R > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "the row count must be in [1, 2^20]");
+    if (c->H != h->H || c->Hp != h->Hp) return fail(h, FSMG_ERR_INVALID, "the cache's hidden size is not the handle's");
+    if (R * c->Mg > CACHE_GEN_MAX_SCORES) return fail(h, FSMG_ERR_INVALID, "rows * entries_per_group must be <= 2^26");
+    if (group)
+        for (int64_t r = 0; r < R; ++r)
+            if (group[r] < 0 || group[r] >= c->G) return fail(h, FSMG_ERR_INVALID, "group id outside [0, groups of the cache)");
+    cg->c = c; cg->theta = cc->theta; cg->lambda = cc->lambda;
+    cg->R = (int)R; cg->ldl = (int)round_up(h->V1, 64);
+    Tiles t = make_tiles((int)R, c->G, [&](int q) { return group ? group[q] : 0; });
+    cg->slot_query = std::move(t.slot_query);
+    cg->tile_group = std::move(t.tile_group);
+    cg->row_group.resize((size_t)R);
+    for (int64_t r = 0; r < R; ++r) cg->row_group[r] = group ? group[r] : 0;
+    return FSMG_OK;
+}
+
+int ensure_value_index(fsmg_model* h, fsmg_cache_s* c) {
+    if (c->idx_mem) return FSMG_OK;
+    const size_t G = c->G, Mg = c->Mg, n = G * Mg;
+    std::vector<int> vals(n);
+    HIPCK(h, hipMemcpyAsync(vals.data(), c->vals, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    // one host block [order | seg_beg | seg_end | seg_val (G * Mg each) | n_seg | n_long (G each)], the device layout
+    std::vector<int> idx(4 * n + 2 * G, 0);
+    int* order = idx.data();
+    int* seg_beg = order + n;
+    int* seg_end = seg_beg + n;
+    int* seg_val = seg_end + n;
+    int* n_seg = seg_val + n;
+    int* n_long = n_seg + G;
+    std::vector<int> beg;                               // a group's segment starts in value order
+    for (size_t g = 0; g < G; ++g) {
+        const int* v = vals.data() + g * Mg;
+        int* o = order + g * Mg;
+        for (size_t i = 0; i < Mg; ++i) o[i] = (int)i;
+        std::stable_sort(o, o + Mg, [&](int x, int y) { return v[x] < v[y]; });
+        beg.clear();
+        for (size_t j = 0; j < Mg; ++j)
+            if (j == 0 || v[o[j]] != v[o[j - 1]]) beg.push_back((int)j);
+        beg.push_back((int)Mg);
+        // the segments longer than CACHE_MIX_SHORT first (a wave each), then the others (a thread each), value order inside both
+        int ns = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            for (size_t s = 0; s + 1 < beg.size(); ++s) {
+                if ((beg[s + 1] - beg[s] > CACHE_MIX_SHORT) != (pass == 0)) continue;
+                seg_beg[g * Mg + ns] = beg[s]; seg_end[g * Mg + ns] = beg[s + 1]; seg_val[g * Mg + ns] = v[o[beg[s]]];
+                ++ns;
+            }
+            if (pass == 0) n_long[g] = ns;
+        }
+        n_seg[g] = ns;
+    }
+    const size_t bytes = sizeof(int) * idx.size();
+    char* mem = nullptr;
+    if (hipMalloc((void**)&mem, bytes) != hipSuccess) return fail(h, FSMG_ERR_NOMEM, "hipMalloc(cache value index) failed");
+    hipError_t e = hipMemcpyAsync(mem, idx.data(), bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);           // the host vector goes out of scope
+    if (e != hipSuccess) { hipFree(mem); return fail(h, FSMG_ERR_HIP, std::string("value index upload: ") + hipGetErrorString(e)); }
+    c->idx_mem = mem;
+    c->order = (int*)mem;
+    c->seg_beg = c->order + n;
+    c->seg_end = c->seg_beg + n;
+    c->seg_val = c->seg_end + n;
+    c->n_seg = c->seg_val + n;
+    c->n_long = c->n_seg + G;
+    c->bytes += bytes;
+    return FSMG_OK;
+}
+
+namespace {
+// [D R * Mg doubles | pc R * ldl floats | slot_query | tile_group | row_group], each 256-byte aligned
+struct CacheGenLayout { size_t o_D, o_pc, o_slot, o_tile, o_row, total; };
+CacheGenLayout cache_gen_layout(const CacheGen& cg) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (size_t)round_up((int64_t)(off + bytes), 256); return o; };
+    CacheGenLayout l{};
+    l.o_D = take(sizeof(double) * (size_t)cg.R * cg.c->Mg);
+    l.o_pc = take(sizeof(float) * (size_t)cg.R * cg.ldl);
+    l.o_slot = take(sizeof(int) * cg.slot_query.size());
+    l.o_tile = take(sizeof(int) * cg.tile_group.size());
+    l.o_row = take(sizeof(int) * cg.row_group.size());
+    l.total = off;
+    return l;
+}
+}  // namespace
+
+size_t cache_gen_bytes(const fsmg_model*, const CacheGen& cg) { return cache_gen_layout(cg).total; }
+
+int cache_gen_place(fsmg_model* h, CacheGen& cg, char* base) {
+    const CacheGenLayout l = cache_gen_layout(cg);
+    cg.D = (double*)(base + l.o_D); cg.pc = (float*)(base + l.o_pc);
+    cg.d_slot_query = (int*)(base + l.o_slot); cg.d_tile_group = (int*)(base + l.o_tile); cg.d_row_group = (int*)(base + l.o_row);
+    HIPCK(h, hipMemcpyAsync(cg.d_slot_query, cg.slot_query.data(), sizeof(int) * cg.slot_query.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCK(h, hipMemcpyAsync(cg.d_tile_group, cg.tile_group.data(), sizeof(int) * cg.tile_group.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCK(h, hipMemcpyAsync(cg.d_row_group, cg.row_group.data(), sizeof(int) * cg.row_group.size(), hipMemcpyHostToDevice, h->stream));
+    return FSMG_OK;
+}
+
+int cache_gen_step(fsmg_model* h, const CacheGen& cg, const float* Q, float* logits, float* out_lse) {
+    const fsmg_cache_s* c = cg.c;
+    CacheScoresArgs sa{};
+    sa.keys = c->keys; sa.Mg = c->Mg; sa.Hp = c->Hp; sa.Q = Q; sa.ldq = c->Hp;
+    sa.slot_query = cg.d_slot_query; sa.tile_group = cg.d_tile_group; sa.n_tiles = (int)cg.tile_group.size(); sa.D = cg.D;
+    {
+        ScopedTimer tm(h, "cache_scores");
+        HIPCK(h, launch_cache_scores(h->stream, sa));
+    }
+    const double lam = (double)cg.lambda;
+    CacheMixArgs ma{};
+    ma.logits = logits; ma.ldl = cg.ldl; ma.ncols = h->V1; ma.D = cg.D; ma.Mg = c->Mg; ma.row_group = cg.d_row_group;
+    ma.order = c->order; ma.seg_beg = c->seg_beg; ma.seg_end = c->seg_end; ma.seg_val = c->seg_val;
+    ma.n_seg = c->n_seg; ma.n_long = c->n_long;
+    ma.pc = cg.pc; ma.out_lse = out_lse;
+    ma.u = (double)cg.theta * CA_LOG2E; ma.log1m_lambda = std::log1p(-lam); ma.log_lambda = std::log(lam); ma.mix = cg.lambda > 0.0f;
+    ScopedTimer tm(h, "cache_mix");
+    HIPCK(h, launch_cache_mix(h->stream, cg.R, ma));
+    return FSMG_OK;
+}
+
 }  // namespace fsmg_host
 
 // =========================================================================== C ABI
@@ -423,6 +557,48 @@ int fsmg_cache_attend(fsmg_handle h, fsmg_cache cache, int32_t n, const float* q
     HIPCK(h, hipMemcpyAsync(out_prob, as.out, sizeof(float) * (size_t)n_theta * n, hipMemcpyDeviceToHost, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));
     return FSMG_OK;
+}
+
+int fsmg_cache_distribution(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, int32_t n, const float* queries,
+                            const float* logits, const int32_t* group, float* out_cache_prob, float* out_logprob, float* out_lse) {
+    if (!h) return FSMG_ERR_INVALID;
+    if (!find_cache(h, cache)) return FSMG_ERR_INVALID;
+    if (n < 1 || n > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n must be in [1, 2^20]");
+    if (!queries || !logits) return fail(h, FSMG_ERR_INVALID, "null queries / logits");
+    if (!out_cache_prob && !out_logprob && !out_lse) return fail(h, FSMG_ERR_INVALID, "every output is null");
+    CacheGen cg;
+    int rc = cache_gen_check(h, cache, cc, group, n, &cg);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    if ((rc = ensure_value_index(h, const_cast<fsmg_cache_s*>(cg.c))) != FSMG_OK) return rc;
+    // [cache_gen's block | queries n x Hp | logits n x ldl | lse n]
+    const int Hp = h->Hp, ldl = cg.ldl, V1 = h->V1;
+    const size_t o_q = (size_t)round_up((int64_t)cache_gen_bytes(h, cg), 256);
+    const size_t o_z = (size_t)round_up((int64_t)(o_q + sizeof(float) * (size_t)n * Hp), 256);
+    const size_t o_lse = (size_t)round_up((int64_t)(o_z + sizeof(float) * (size_t)n * ldl), 256);
+    if ((rc = gen_reserve(h, o_lse + sizeof(float) * (size_t)n)) != FSMG_OK) return rc;
+    float* d_q = (float*)(h->gen + o_q);
+    float* d_z = (float*)(h->gen + o_z);
+    float* d_lse = (float*)(h->gen + o_lse);
+    std::vector<float> qp((size_t)n * Hp, 0.0f);
+    for (int q = 0; q < n; ++q) std::memcpy(qp.data() + (size_t)q * Hp, queries + (size_t)q * h->H, sizeof(float) * h->H);
+    auto run = [&]() -> int {
+        int r = cache_gen_place(h, cg, h->gen);
+        if (r != FSMG_OK) return r;
+        HIPCK(h, hipMemcpyAsync(d_q, qp.data(), sizeof(float) * qp.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCK(h, hipMemcpy2DAsync(d_z, sizeof(float) * ldl, logits, sizeof(float) * V1, sizeof(float) * V1, n, hipMemcpyHostToDevice, h->stream));
+        if ((r = cache_gen_step(h, cg, d_q, d_z, d_lse)) != FSMG_OK) return r;
+        if (out_cache_prob)
+            HIPCK(h, hipMemcpy2DAsync(out_cache_prob, sizeof(float) * V1, cg.pc, sizeof(float) * ldl, sizeof(float) * V1, n, hipMemcpyDeviceToHost, h->stream));
+        if (out_logprob)
+            HIPCK(h, hipMemcpy2DAsync(out_logprob, sizeof(float) * V1, d_z, sizeof(float) * ldl, sizeof(float) * V1, n, hipMemcpyDeviceToHost, h->stream));
+        if (out_lse) HIPCK(h, hipMemcpyAsync(out_lse, d_lse, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        return FSMG_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(h->stream);       // the host vectors go out of scope
+    if (rc == FSMG_OK && e != hipSuccess) return fail(h, FSMG_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
 }
 
 int fsmg_cache_score(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const int32_t* tokens, const int32_t* group,

@@ -9,7 +9,6 @@ using namespace fsmg_host;
 
 namespace fsmg_host {
 
-namespace {
 // h->gen holds at least `bytes`: grown between calls, after a stream sync
 int gen_reserve(fsmg_model* h, size_t bytes) {
     if (bytes <= h->gen_bytes) return FSMG_OK;
@@ -21,6 +20,7 @@ int gen_reserve(fsmg_model* h, size_t bytes) {
     return FSMG_OK;
 }
 
+namespace {
 // One call's buffers in h->gen for R rows (generate: one per sequence; beam search: W per group).
 struct Decode {
     int R = 0, P = 0, num = 0, ldl = 0, ldtok = 0;
@@ -35,6 +35,8 @@ struct Decode {
     int* out_tok = nullptr;                                   // the packed output block, one D2H copy: tokens [R][num], log-probs
     float *out_lp = nullptr, *out_score = nullptr;            // [R][num], beam scores [R]
     int* flag = nullptr;                                      // one word behind the output block: fsmg_dstate_feed's token-range flag
+    size_t extra_bytes = 0;                                   // set by the caller: a block of its own behind everything else
+    char* extra = nullptr;                                    // (cache-conditioned generation: the cache kernels' scratch)
 };
 
 // The prologue of generate (W = 0) and beam search (W > 0: W rows per primer row): a host primer is range-checked before any device
@@ -68,6 +70,7 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
     const size_t o_out = place(sizeof(float) * (2 * n + (beam ? R : 0) + 1));
     const size_t o_primer = place(sizeof(int) * n_primer);
     const size_t o_err = place(sizeof(int));
+    const size_t o_extra = place(d.extra_bytes);
     int rc = gen_reserve(h, off);
     if (rc != FSMG_OK) return rc;
     char* base = h->gen;
@@ -91,6 +94,7 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
     d.out_score = d.out_lp + n;
     d.flag = (int*)(d.out_score + (beam ? R : 0));
     int* err = (int*)(base + o_err);
+    d.extra = base + o_extra;
 
     hipStream_t s = h->stream;
     const int32_t* d_primer = primer;
@@ -220,21 +224,26 @@ int check_beam_config(fsmg_model* h, const fsmg_beam_config* b, const int32_t* p
 
 // fsmg_generate_filtered's work at the parameters the handle holds now (no BEGIN_CALL: the MAML variants call it at theta').
 // f == nullptr or neutral: fsmg_generate's pick.  st != nullptr: from that decode state (the token loop starts at the pending token,
-// the Philox position runs on from n_gen) and back into it.
+// the Philox position runs on from n_gen) and back into it.  cg != nullptr (fsmg_cache_generate with lambda > 0): at every generated
+// position the logits rows are overwritten with the mixed log-probabilities z'' before the unchanged pick reads them.
 int generate_core(fsmg_model* h, const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* primer, int32_t* out_tokens,
-                  float* out_logprob, fsmg_dstate_s* st = nullptr) {
+                  float* out_logprob, fsmg_dstate_s* st = nullptr, CacheGen* cg = nullptr) {
     const bool neutral = !f || ((f->top_p == 0.f || f->top_p == 1.f) && f->min_p == 0.f &&
                                 (f->repetition_penalty == 0.f || f->repetition_penalty == 1.f));
     GenFilters pf{};
     if (!neutral) pf = GenFilters{f->top_p, f->min_p, f->repetition_penalty == 0.f ? 1.f : f->repetition_penalty, f->repeat_window};
     const GenFilters* pick_f = neutral ? nullptr : &pf;      // neutral filters: exactly fsmg_generate's pick
     Decode d;
+    if (cg && g->num > 0) d.extra_bytes = cache_gen_bytes(h, *cg);        // the scratch grows here, never inside the token loop
     int rc = begin_decode(h, d, g->n_seq, 0, st ? st->kept() : g->primer_len, g->num, g->primer_on_device, primer, st);
     if (rc != FSMG_OK || d.num == 0) return rc;
+    if (cg && (rc = cache_gen_place(h, *cg, d.extra)) != FSMG_OK) return rc;
     const int p0 = st ? d.P : 0, ctr0 = st ? (int)st->n_gen : 0;
     // position p reads tok[:, p]; primer positions (p < P) run the cells only, generated position t = p - P writes tok[:, p + 1]
     for (int p = p0; p < d.P + d.num; ++p) {
         if ((rc = advance(h, d, p, p >= d.P)) != FSMG_OK) return rc;
+        // the rows' queries: the top layer's h_out of this position, whose projection the logits are
+        if (p >= d.P && cg && (rc = cache_gen_step(h, *cg, d.h_out + (size_t)(h->L - 1) * d.R * h->Hp, d.logits, nullptr)) != FSMG_OK) return rc;
         if (p >= d.P)
             HIPCK(h, launch_gen_pick(h->stream, d.logits, d.ldl, h->V1, d.R, g->temperature, g->top_k, pick_f, g->seed, p - d.P,
                                      ctr0 + p - d.P, d.tok, d.ldtok, p + 1, d.out_tok, d.out_lp, d.num));
@@ -323,6 +332,35 @@ int reset_state(fsmg_model* h, fsmg_dstate_s* st) {
 
 // rows * (history + n + 1) token slots of a stateful call over n tokens: the one-shot calls' bound
 bool state_call_fits(const fsmg_dstate_s* st, int64_t rows, int64_t n) { return rows * ((int64_t)st->history + n + 1) <= (1LL << 30); }
+
+// what fsmg_dstate_generate refuses, before any device work
+int check_state_generate(fsmg_model* h, const fsmg_dstate_s* s, const fsmg_gen_config* g, const fsmg_gen_filters* f, int32_t* out_tokens) {
+    int rc = check_gen_config(h, g, nullptr, out_tokens);
+    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    if (rc != FSMG_OK) return rc;
+    if (g->n_seq != s->R) return fail(h, FSMG_ERR_INVALID, "n_seq must be the state's row count");
+    if (g->primer_len != 0) return fail(h, FSMG_ERR_INVALID, "primer_len must be 0 with a decode state (feed the primer)");
+    if (!state_call_fits(s, s->R, g->num)) return fail(h, FSMG_ERR_INVALID, "rows * (history + num + 1) too large");
+    if (s->n_gen + g->num > INT32_MAX) return fail(h, FSMG_ERR_INVALID, "n_gen + num exceeds 2^31 - 1");
+    if (f && f->repetition_penalty != 0.f && f->repetition_penalty != 1.f) {      // the penalty must find its whole window in the history
+        if (f->repeat_window > s->history) return fail(h, FSMG_ERR_INVALID, "repeat_window must be in [1, history]");
+        if (f->repeat_window == 0 && s->n_ctx + g->num > s->history)
+            return fail(h, FSMG_ERR_INVALID, "repeat_window 0 (the whole context) needs n_ctx + num <= history");
+    }
+    return FSMG_OK;
+}
+
+// fsmg_cache_generate / fsmg_dstate_cache_generate behind the argument checks.  lambda = 0: the plain driver, the cache not read
+// (and its value index not built).  The tiles' host arrays in cg must outlive the uploads: a failed call is synchronised too.
+int cache_generate_core(fsmg_model* h, CacheGen& cg, const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* primer,
+                        int32_t* out_tokens, float* out_logprob, fsmg_dstate_s* st) {
+    if (cg.lambda == 0.0f) return generate_core(h, g, f, primer, out_tokens, out_logprob, st);
+    int rc = ensure_value_index(h, const_cast<fsmg_cache_s*>(cg.c));
+    if (rc != FSMG_OK) return rc;
+    rc = generate_core(h, g, f, primer, out_tokens, out_logprob, st, &cg);
+    if (rc != FSMG_OK) hipStreamSynchronize(h->stream);
+    return rc;
+}
 }  // namespace
 
 }  // namespace fsmg_host
@@ -539,20 +577,38 @@ int fsmg_dstate_generate(fsmg_handle h, fsmg_dstate st, const fsmg_gen_config* g
     if (!h) return FSMG_ERR_INVALID;
     fsmg_dstate_s* s = find_state(h, st);
     if (!s) return FSMG_ERR_INVALID;
-    int rc = check_gen_config(h, g, nullptr, out_tokens);
-    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    const int rc = check_state_generate(h, s, g, f, out_tokens);
     if (rc != FSMG_OK) return rc;
-    if (g->n_seq != s->R) return fail(h, FSMG_ERR_INVALID, "n_seq must be the state's row count");
-    if (g->primer_len != 0) return fail(h, FSMG_ERR_INVALID, "primer_len must be 0 with a decode state (feed the primer)");
-    if (!state_call_fits(s, s->R, g->num)) return fail(h, FSMG_ERR_INVALID, "rows * (history + num + 1) too large");
-    if (s->n_gen + g->num > INT32_MAX) return fail(h, FSMG_ERR_INVALID, "n_gen + num exceeds 2^31 - 1");
-    if (f && f->repetition_penalty != 0.f && f->repetition_penalty != 1.f) {      // the penalty must find its whole window in the history
-        if (f->repeat_window > s->history) return fail(h, FSMG_ERR_INVALID, "repeat_window must be in [1, history]");
-        if (f->repeat_window == 0 && s->n_ctx + g->num > s->history)
-            return fail(h, FSMG_ERR_INVALID, "repeat_window 0 (the whole context) needs n_ctx + num <= history");
-    }
     BEGIN_CALL(h);
     return generate_core(h, g, f, nullptr, out_tokens, out_logprob, s);
+}
+
+// ---- cache-conditioned generation: the generate calls with a support-set cache beside the model
+int fsmg_cache_generate(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_gen_config* g,
+                        const fsmg_gen_filters* f, const int32_t* group, const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    if (!find_cache(h, cache)) return FSMG_ERR_INVALID;
+    int rc = check_gen_config(h, g, primer, out_tokens);
+    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    CacheGen cg;
+    if (rc == FSMG_OK) rc = cache_gen_check(h, cache, cc, group, g->n_seq, &cg);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return cache_generate_core(h, cg, g, f, primer, out_tokens, out_logprob, nullptr);
+}
+
+int fsmg_dstate_cache_generate(fsmg_handle h, fsmg_dstate st, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_gen_config* g,
+                               const fsmg_gen_filters* f, const int32_t* group, int32_t* out_tokens, float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    if (!find_cache(h, cache)) return FSMG_ERR_INVALID;
+    int rc = check_state_generate(h, s, g, f, out_tokens);
+    CacheGen cg;
+    if (rc == FSMG_OK) rc = cache_gen_check(h, cache, cc, group, g->n_seq, &cg);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return cache_generate_core(h, cg, g, f, nullptr, out_tokens, out_logprob, s);
 }
 
 int fsmg_dstate_beam_search(fsmg_handle h, fsmg_dstate st, const fsmg_beam_config* b, int32_t* out_tokens, float* out_scores,

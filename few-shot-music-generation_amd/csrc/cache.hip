@@ -31,8 +31,6 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int CA_QT = CACHE_ATTEND_QT;      // queries per workgroup: two 16-column B operands, so a key load feeds two MFMAs
 constexpr int CA_WAVES = 4;
 constexpr int CA_PAD = 4;                   // floats behind a query row in LDS: rows 16 B apart in the banks
-constexpr double CA_LOG2E = 1.4426950408889634;
-constexpr float CA_LN2 = 0.693147180559945f;
 
 // a partial softmax over some of a group's keys: the sums are sum_i 2^(u_k d_i - ceil(u_k m)), m the largest d among them
 struct CaState {
@@ -44,14 +42,6 @@ struct CaState {
 __device__ __forceinline__ double ca_scale(double u, double m_from, double m_to) {
     if (m_from == -INFINITY) return 0.0;
     return ldexp(1.0, (int)fmax(ceil(u * m_from) - ceil(u * m_to), -4000.0));
-}
-
-// 2^t, t <= 0 in fp64: the fp32 exponential of the rounded exponent, corrected to first order for what the rounding dropped
-__device__ __forceinline__ double ca_exp2(double t) {
-    const float hi = (float)t;
-    const float lo = (float)(t - (double)hi);
-    const float e = exp2f(hi);
-    return (double)fmaf(e, lo * CA_LN2, e);
 }
 
 // the four scores of a lane (keys kbase, kbase + 4, kbase + 8, kbase + 12 of the group, values v) into its running state
@@ -253,6 +243,73 @@ __global__ __launch_bounds__(256) void k_cache_fill(const float* __restrict__ Hs
     }
 }
 
+// ---------------------------------------------------------------- cache-conditioned generation, stage one (fsmg_kernels.h)
+// One wave: 16 keys of a chunk against the 16 (or 32) queries of a tile, operands straight from global memory -- a wave's key
+// fragment is read once, and the tile's queries are a few KiB that every wave of the group reads and the caches keep.  Four k groups
+// per trip so that eight (twelve) 16-byte loads are in flight: at a decode step one wave per SIMD is all the occupancy there is.
+// The k order is k_cache_attend's: groups of 16 in increasing k, x, y, z, w inside a group.
+template <bool TWO>
+__device__ __forceinline__ void cs_mfma4(f64x4& acc0, f64x4& acc1, const float4& kv, const float4& b0, const float4& b1) {
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.x, (double)b0.x, acc0, 0, 0, 0);
+    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.x, (double)b1.x, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.y, (double)b0.y, acc0, 0, 0, 0);
+    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.y, (double)b1.y, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.z, (double)b0.z, acc0, 0, 0, 0);
+    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.z, (double)b1.z, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.w, (double)b0.w, acc0, 0, 0, 0);
+    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.w, (double)b1.w, acc1, 0, 0, 0);
+}
+
+template <bool TWO>
+__device__ __forceinline__ void cs_tile(const float* __restrict__ kp, const float* __restrict__ qp0, const float* __restrict__ qp1, int Hp,
+                                        f64x4& acc0, f64x4& acc1) {
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int k = 0;
+    for (; k + 64 <= Hp; k += 64) {
+        float4 kv[4], b0[4], b1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            kv[j] = *reinterpret_cast<const float4*>(kp + k + 16 * j);
+            b0[j] = *reinterpret_cast<const float4*>(qp0 + k + 16 * j);
+            b1[j] = TWO ? *reinterpret_cast<const float4*>(qp1 + k + 16 * j) : zero;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cs_mfma4<TWO>(acc0, acc1, kv[j], b0[j], b1[j]);
+    }
+    for (; k < Hp; k += 16) {
+        const float4 kv = *reinterpret_cast<const float4*>(kp + k);
+        const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k);
+        const float4 b1 = TWO ? *reinterpret_cast<const float4*>(qp1 + k) : zero;
+        cs_mfma4<TWO>(acc0, acc1, kv, b0, b1);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_cache_scores(CacheScoresArgs a, int n_chunks) {
+    const int tile = blockIdx.x / n_chunks, chunk = blockIdx.x - tile * n_chunks;
+    const int lane = threadIdx.x, kq = lane & 15, ks = lane >> 4;
+    const int Hp = a.Hp, Mg = a.Mg;
+    const int* slots = a.slot_query + (long long)tile * CACHE_ATTEND_QT;
+    const int q0 = slots[kq], q1 = slots[16 + kq];
+    const bool two = slots[16] >= 0;                // the slots fill in order: a wave-uniform choice
+    const int qa = slots[0];                        // (never empty) an empty slot reads this row, in bounds, and stores nothing
+    // lane l loads key row l % 16 of the chunk (a tail row: the group's last key, in bounds, not stored), k = 16 j + 4 (l / 16) .. + 3
+    const int krow = min(chunk * CACHE_GEN_CHUNK + kq, Mg - 1);
+    const float* kp = a.keys + ((long long)a.tile_group[tile] * Mg + krow) * Hp + 4 * ks;
+    const float* qp0 = a.Q + (long long)(q0 >= 0 ? q0 : qa) * a.ldq + 4 * ks;
+    const float* qp1 = a.Q + (long long)(q1 >= 0 ? q1 : qa) * a.ldq + 4 * ks;
+    f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+    if (two) cs_tile<true>(kp, qp0, qp1, Hp, acc0, acc1);
+    else cs_tile<false>(kp, qp0, qp1, Hp, acc0, acc1);
+    // accumulator register i of lane l: key 4 i + l / 16 of the chunk against query l % 16
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int key = chunk * CACHE_GEN_CHUNK + 4 * i + ks;
+        if (key >= Mg) continue;                    // a tail key has no score
+        if (q0 >= 0) a.D[(long long)q0 * Mg + key] = acc0[i];
+        if (two && q1 >= 0) a.D[(long long)q1 * Mg + key] = acc1[i];
+    }
+}
+
 }  // namespace
 
 size_t cache_attend_lds_bytes(int Hp) { return std::max(sizeof(float) * (size_t)CA_QT * (Hp + CA_PAD), sizeof(CaMerge)); }
@@ -267,6 +324,14 @@ hipError_t launch_cache_attend(hipStream_t s, const CacheAttendArgs& a) {
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_cache_attend, dim3(a.n_tiles), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cache_scores(hipStream_t s, const CacheScoresArgs& a) {
+    if (a.n_tiles <= 0) return hipSuccess;
+    const long long n_chunks = ((long long)a.Mg + CACHE_GEN_CHUNK - 1) / CACHE_GEN_CHUNK;
+    if (a.Mg < 1 || a.Hp < 16 || (a.Hp & 15) != 0 || (a.ldq & 3) != 0 || n_chunks * a.n_tiles > 0x7FFFFFFFLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_cache_scores, dim3((unsigned)(n_chunks * a.n_tiles)), dim3(64), 0, s, a, (int)n_chunks);
     return hipGetLastError();
 }
 

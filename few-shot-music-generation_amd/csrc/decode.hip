@@ -701,7 +701,94 @@ __global__ void k_dstate_tokens(const int* __restrict__ tokens, int R, int n, in
     }
 }
 
+// ---------------------------------------------------------------- cache-conditioned generation, stage two (fsmg_kernels.h)
+// block-wide maximum of doubles -- every thread gets the result (a maximum: the tree's shape cannot change it)
+__device__ __forceinline__ double block_max(PickShared& sh, double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh.dv[w] = v;
+    __syncthreads();
+    double t = sh.dv[0];
+    for (int k = 1; k < PICK_THREADS / 64; ++k) t = fmax(t, sh.dv[k]);
+    return t;
+}
+
+// fsmg_cache_score's mix_logprob (api_cache.hip) on the device: log((1 - lambda) exp(lp) + lambda pc) in fp64, rounded once
+__device__ __forceinline__ float mix_logprob(float lp, float pc, double log1m_lambda, double log_lambda) {
+    const double a = log1m_lambda + (double)lp;
+    const double b = log_lambda + log((double)pc);
+    if (a != a || b != b) return (float)(a + b);
+    const double hi = fmax(a, b), lo = fmin(a, b);
+    if (hi == -INFINITY) return -INFINITY;
+    return (float)(hi + log1p(exp(lo - hi)));
+}
+
+// One row per workgroup; the steps are CacheMixArgs' comment.  The barriers inside the block reductions order a step's global
+// stores (the masses over D, the pc row) before the next step's loads: a workgroup reads back only what it wrote itself.
+__global__ __launch_bounds__(PICK_THREADS) void k_cache_mix(CacheMixArgs a) {
+    __shared__ PickShared sh;
+    const int b = blockIdx.x, tid = threadIdx.x, Mg = a.Mg, ncols = a.ncols;
+    float* row = a.logits + (long long)b * a.ldl;
+    float* pc = a.pc + (long long)b * a.ldl;
+    double* d = a.D + (long long)b * Mg;
+    const int g = a.row_group[b];
+
+    float mx; int mi;
+    const float lse = row_max_lse<false>(sh, row, nullptr, ncols, mx, mi);
+
+    double m = -INFINITY;
+    for (int i = tid; i < Mg; i += PICK_THREADS) m = fmax(m, d[i]);
+    m = block_max(sh, m);
+    const double S = ceil(a.u * m);
+    double z = 0.0;
+    for (int i = tid; i < Mg; i += PICK_THREADS) {
+        const double w = ca_exp2(fma(a.u, d[i], -S));
+        d[i] = w;
+        z += w;
+    }
+    for (int v = tid; v < ncols; v += PICK_THREADS) pc[v] = 0.0f;
+    const double Z = block_sum(sh, z);
+
+    // the distinct values of the group: the long segments of the value index one wave each (lanes stride the segment, then a
+    // butterfly), the short ones one thread each
+    const int* order = a.order + (long long)g * Mg;
+    const int* seg_beg = a.seg_beg + (long long)g * Mg;
+    const int* seg_end = a.seg_end + (long long)g * Mg;
+    const int* seg_val = a.seg_val + (long long)g * Mg;
+    const int n_seg = a.n_seg[g], n_long = a.n_long[g], lane = tid & 63;
+    for (int sg = tid >> 6; sg < n_long; sg += PICK_THREADS / 64) {
+        const int j1 = seg_end[sg];
+        double mass = 0.0;
+        for (int j = seg_beg[sg] + lane; j < j1; j += 64) mass += d[order[j]];
+        for (int o = 32; o > 0; o >>= 1) mass += __shfl_xor(mass, o);
+        if (lane == 0) pc[seg_val[sg]] = mass == 0.0 ? 0.0f : (float)(mass / Z);
+    }
+    for (int sg = n_long + tid; sg < n_seg; sg += PICK_THREADS) {
+        const int j1 = seg_end[sg];
+        double mass = 0.0;
+        for (int j = seg_beg[sg]; j < j1; ++j) mass += d[order[j]];
+        pc[seg_val[sg]] = mass == 0.0 ? 0.0f : (float)(mass / Z);
+    }
+    __syncthreads();
+
+    for (int v = tid; v < ncols; v += PICK_THREADS) {
+        const float lp = row[v] - lse, p = pc[v];
+        float out = lp;
+        if (a.mix) out = p == 0.0f ? (float)(a.log1m_lambda + (double)lp) : mix_logprob(lp, p, a.log1m_lambda, a.log_lambda);
+        row[v] = out;
+    }
+    if (tid == 0 && a.out_lse) a.out_lse[b] = lse;
+}
+
 }  // namespace
+
+hipError_t launch_cache_mix(hipStream_t s, int R, const CacheMixArgs& a) {
+    if (R <= 0) return hipSuccess;
+    if (a.ncols <= 0 || a.ncols > a.ldl || a.Mg < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_cache_mix, dim3(R), dim3(PICK_THREADS), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_gen_cell(hipStream_t s, const float* Kx, int in_dim, const float* Kh, const float* bias, int Hp, const float* emb, int ldemb,
                            const int* tok, int ldtok, int pos, const float* x, const float* h_in, float* h_out, float* c, int B) {

@@ -456,6 +456,16 @@ hipError_t launch_score_rows(hipStream_t s, const float* logits, int ld, int row
 // its vector, its group's entries and theta alone.  No allocation, no synchronisation.
 constexpr int CACHE_ATTEND_QT = 32;
 constexpr int CACHE_MAX_THETA = 8;
+// the exponent arithmetic every cache kernel shares (cache.hip's header comment): u = theta log2(e), and
+// 2^t, t <= 0 in fp64: the fp32 exponential of the rounded exponent, corrected to first order for what the rounding dropped
+constexpr double CA_LOG2E = 1.4426950408889634;
+constexpr float CA_LN2 = 0.693147180559945f;
+__device__ __forceinline__ double ca_exp2(double t) {
+    const float hi = (float)t;
+    const float lo = (float)(t - (double)hi);
+    const float e = exp2f(hi);
+    return (double)fmaf(e, lo * CA_LN2, e);
+}
 struct CacheAttendArgs {
     const float* keys;          // [G][Mg][Hp], pad units exact zeros
     const int* vals;            // [G][Mg]
@@ -475,5 +485,52 @@ hipError_t launch_cache_attend(hipStream_t s, const CacheAttendArgs& a);
 // [rows][T] entries; units >= H are written as zeros
 hipError_t launch_cache_fill(hipStream_t s, const float* Hs1, const int* Y, int B, int T, int H, int Hp, long long r0, float* keys,
                              int* vals);
+
+// ---- cache-conditioned generation (fsmg_cache_generate / fsmg_cache_distribution): the WHOLE mixed next-token
+// distribution of R decode rows at one position, in two launches.  No allocation, no synchronisation, no atomics.
+// Stage one (cache.hip), the raw scores: D[r][i] = Q_r . keys[g_r][i] for every key i < Mg of row r's group, k_cache_attend's
+// arithmetic (fp32 inputs widened exactly, products on the fp64 MFMA, fp64 accumulation in one fixed k order).  The grid is
+// (query tile of one group) x (chunk of CACHE_GEN_CHUNK keys), one wave each: a decode step has few rows, so the keys are what is
+// spread over the chip.  The host sorts the rows by group once per call into tiles of CACHE_ATTEND_QT slots (make_tiles' layout: -1
+// in an empty slot; a tile whose slot 16 is empty runs one MFMA per key fragment instead of two).  A tail key (index >= Mg in the last
+// chunk) is not stored: stage two never sees it.  Every score is an accumulator element of its own: its bits depend on the row's
+// vector and that key alone.
+constexpr int CACHE_GEN_CHUNK = 16;
+struct CacheScoresArgs {
+    const float* keys;          // [G][Mg][Hp], pad units exact zeros
+    int Mg, Hp;
+    const float* Q; int ldq;    // row r's query: Q + r * ldq (Hp floats; the pad units finite)
+    const int* slot_query;      // [n_tiles][CACHE_ATTEND_QT]
+    const int* tile_group;      // [n_tiles]
+    int n_tiles;
+    double* D;                  // [R][Mg]
+};
+hipError_t launch_cache_scores(hipStream_t s, const CacheScoresArgs& a);
+// Stage two (decode.hip: it shares the picks' row sweep), one workgroup per row r of group g = row_group[r]:
+//   lse    the picks' logsumexp of the logits row (row_max_lse: bitwise the number k_gen_pick subtracts), lp_v = fl32(z_v - lse);
+//   d_max  the exact maximum of the row's Mg scores, ONE shift S = ceil(u d_max) for every entry, w_i = ca_exp2(u d_i - S) (written
+//          over D), Z = sum_i w_i over a fixed tree that depends on Mg alone;
+//   mass   of each distinct value of the group through the cache's value index (order: the entries in stable order by value;
+//          seg_beg / seg_end / seg_val: the segments of equal value, those longer than CACHE_MIX_SHORT first, n_long of n_seg): a
+//          long segment is summed by one wave (lanes stride it, then a butterfly), a short one by one thread in entry order -- a
+//          vocabulary of thousands gives thousands of segments of one or two entries --, either way in an order that depends on
+//          the segment's length alone; pc[r][v] = fl32(mass / Z), exactly 0 for a column no entry holds;
+//   z''_v  = fl32(logaddexp(log1p(-lambda) + lp_v, log(lambda) + log(pc_v))) in fp64 (fsmg_cache_score's mix_logprob), over the logits
+//          row in place; fl32(log1p(-lambda) + lp_v) where pc_v = 0; lambda = 0 (mix == 0): lp_v.
+// A row's bits depend on its logits row, its scores, its group's values, theta and lambda alone.
+constexpr int CACHE_MIX_SHORT = 32;
+struct CacheMixArgs {
+    float* logits; int ldl, ncols;      // [R][ldl]: z in, z'' out
+    double* D; int Mg;                  // [R][Mg]: scores in, masses out
+    const int* row_group;               // [R]
+    const int *order, *seg_beg, *seg_end, *seg_val;   // [G][Mg] each
+    const int *n_seg, *n_long;          // [G]
+    float* pc;                          // [R][ldl]
+    float* out_lse;                     // [R] or nullptr
+    double u;                           // theta log2(e)
+    double log1m_lambda, log_lambda;
+    int mix;                            // lambda > 0
+};
+hipError_t launch_cache_mix(hipStream_t s, int R, const CacheMixArgs& a);
 
 }  // namespace fsmg

@@ -10,7 +10,8 @@
 //   api_unigram.hip   unigram baseline                                 api_debug.hip debug reads, timers, clock probe
 //   api_decode.hip    decoding: fsmg_generate(_filtered), fsmg_beam_search, their MAML twins, fsmg_sample (one driver); decode states (fsmg_dstate_*)
 //   api_score.hip     scoring of given songs: fsmg_score, fsmg_maml_score
-//   api_cache.hip     support-set neural cache: fsmg_cache_* (build, attend, score and eval against a cache)
+//   api_cache.hip     support-set neural cache: fsmg_cache_* (build, attend, score and eval against a cache; the cache side of
+//                     cache-conditioned generation, whose entry points sit beside the decode driver in api_decode.hip)
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
@@ -76,6 +77,12 @@ struct fsmg_cache_s {
     char* mem = nullptr;
     float* keys = nullptr;              // [G][Mg][Hp], pad units exact zeros
     int* vals = nullptr;                // [G][Mg]
+    // the value index (cache-conditioned generation): per group the entries in stable order by value and the segments
+    // of equal value (CacheMixArgs in fsmg_kernels.h).  An allocation of its own, built on the first call that needs it (ensure_value_index), counted in `bytes` from
+    // then on, freed with the cache.
+    char* idx_mem = nullptr;
+    int *order = nullptr, *seg_beg = nullptr, *seg_end = nullptr, *seg_val = nullptr;   // [G][Mg] each; the long segments first
+    int *n_seg = nullptr, *n_long = nullptr;                                            // [G]
 };
 
 struct fsmg_model {
@@ -615,6 +622,27 @@ int poll_skipped(fsmg_model* h);
 int report(fsmg_model* h, int what);
 int check_tokens_and_read(fsmg_model* h, const float* d_src, float scale, float* host_out, int n, bool train_tail = false);
 int after_update(fsmg_model* h, float grad_scale, float* loss);
+// api_decode.hip / api_cache.hip: what cache-conditioned generation shares between the decode driver and the cache
+int gen_reserve(fsmg_model* h, size_t bytes);              // h->gen holds at least `bytes`: grown between calls, after a stream sync
+fsmg_cache_s* find_cache(fsmg_model* h, fsmg_cache c);     // the cache if this handle owns it, else nullptr with the error set
+// One call's cache side: the rows sorted by group into tiles once, the kernels' scratch inside the caller's block of h->gen.
+struct CacheGen {
+    const fsmg_cache_s* c = nullptr;
+    float theta = 0.f, lambda = 0.f;
+    int R = 0, ldl = 0;
+    std::vector<int> slot_query, tile_group, row_group;     // host copies: alive until the stream has been synchronised
+    int *d_slot_query = nullptr, *d_tile_group = nullptr, *d_row_group = nullptr;
+    double* D = nullptr;                                    // [R][Mg]
+    float* pc = nullptr;                                    // [R][ldl]
+};
+// the argument checks (no device work): config, cache against the handle, group ids, the R * Mg limit; fills cg's host side
+int cache_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const int32_t* group, int64_t R, CacheGen* cg);
+int ensure_value_index(fsmg_model* h, fsmg_cache_s* c);    // outside the token loop: allocates and synchronises on first use
+size_t cache_gen_bytes(const fsmg_model* h, const CacheGen& cg);
+int cache_gen_place(fsmg_model* h, CacheGen& cg, char* base);       // the pointers into `base` (cache_gen_bytes of it), tiles uploaded
+// the two launches at one position: the rows' queries Q [R][Hp], their logits [R][ldl] overwritten with z''
+int cache_gen_step(fsmg_model* h, const CacheGen& cg, const float* Q, float* logits, float* out_lse);
+void free_cache(fsmg_cache_s* c);
 // api_comm.hip
 int exchange_gradients(fsmg_model* h);
 void comm_destroy(fsmg_model* h);       // fsmg_destroy's share: communicator, its stream and event

@@ -106,6 +106,14 @@ class FsmgCacheScoreConfig(C.Structure):
                 ('thetas', C.c_float * 8), ('lambdas', C.c_float * 16), ('reserved', C.c_int32 * 8)]
 
 
+FSMG_CACHE_GEN_CONFIG_VERSION = 1
+FSMG_CACHE_GEN_CHUNK = 16       # keys per wave of the score kernel of cache-conditioned generation (include/fsmg.h)
+
+
+class FsmgCacheGenConfig(C.Structure):
+    _fields_ = [('version', C.c_int32), ('theta', C.c_float), ('lambda_', C.c_float), ('reserved', C.c_int32 * 13)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -178,6 +186,11 @@ SIGNATURES = {
     'fsmg_cache_attend': (C.c_int, [_P, _P, C.c_int32, _F32P, _I32P, _I32P, _F32P, C.c_int32, _F32P]),
     'fsmg_cache_score': (C.c_int, [_P, _P, C.POINTER(FsmgCacheScoreConfig), _P, _I32P, _F32P, _F32P, _F32P, _F32P]),
     'fsmg_cache_eval_step': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _F32P]),
+    'fsmg_cache_generate': (C.c_int, [_P, _P, C.POINTER(FsmgCacheGenConfig), C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _I32P, _P,
+                                      _I32P, _F32P]),
+    'fsmg_dstate_cache_generate': (C.c_int, [_P, _P, _P, C.POINTER(FsmgCacheGenConfig), C.POINTER(FsmgGenConfig),
+                                             C.POINTER(FsmgGenFilters), _I32P, _I32P, _F32P]),
+    'fsmg_cache_distribution': (C.c_int, [_P, _P, C.POINTER(FsmgCacheGenConfig), C.c_int32, _F32P, _F32P, _I32P, _F32P, _F32P, _F32P]),
     'fsmg_read_losses': (C.c_int, [_P, _F32P, C.c_int32]),
     'fsmg_get_stats': (C.c_int, [_P, C.POINTER(FsmgStats)]),
     'fsmg_debug_read': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
@@ -938,6 +951,65 @@ class FsmgModel(object):
         self._ck(self._lib.fsmg_cache_eval_step(self._h, C.c_void_p(s.ctypes.data), C.c_void_p(q.ctypes.data), s.shape[0], s.shape[1],
                                                 q.shape[1], float(theta), float(lam), C.byref(nll)))
         return nll.value
+
+    # -- cache-conditioned generation (include/fsmg.h fsmg_cache_generate) ----------------------------------------
+    @staticmethod
+    def cache_gen_config(theta, lam):
+        return FsmgCacheGenConfig(version=FSMG_CACHE_GEN_CONFIG_VERSION, theta=float(theta), lambda_=float(lam))
+
+    @staticmethod
+    def _group(group, n):
+        if group is None:
+            return None
+        g = np.ascontiguousarray(group, dtype=np.int32)
+        if g.shape != (int(n),):
+            raise ValueError('group must be [%d], got %r' % (int(n), g.shape))
+        return g
+
+    def cache_generate(self, cache, n_seq, num, theta, lam, group=None, state=None, temperature=1.0, top_k=0, seed=0, primer=None,
+                       logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
+        """generate() drawing every token from the mixture (1 - lam) p_lstm + lam p_cache, row r attending over group group[r] of
+        the cache (int32 [n_seq]; None: group 0) with sharpness theta.  lam = 0 is generate() bitwise.  state: a DecodeState of
+        n_seq rows to continue and leave advanced (fsmg_dstate_cache_generate; no primer then).  The other keywords and the result
+        are generate()'s; the log-probs are those of the mixture."""
+        n_seq, num = int(n_seq), int(num)
+        cc = self.cache_gen_config(theta, lam)
+        g = self._group(group, n_seq)
+        gp = g.ctypes.data_as(_I32P) if g is not None else None
+        f = self.gen_filters(top_p, min_p, repetition_penalty, repeat_window)
+        fp = C.byref(f) if f is not None else None
+        toks = np.empty((n_seq, num), np.int32)
+        lp = np.empty((n_seq, num), np.float32) if logprobs else None
+        outs = (toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None)
+        if state is None:
+            gc, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
+            self._ck(self._lib.fsmg_cache_generate(self._h, cache._ptr(), C.byref(cc), C.byref(gc), fp, gp, pp, *outs))
+        else:
+            if primer is not None:
+                raise ValueError('a state takes no primer: feed it first')
+            if n_seq != state.rows:
+                raise ValueError('n_seq %d is not the row count of the state (%d)' % (n_seq, state.rows))
+            gc = self.gen_config(n_seq, num, temperature, top_k, seed)
+            state._call(self._lib.fsmg_dstate_cache_generate, cache._ptr(), C.byref(cc), C.byref(gc), fp, gp, *outs)
+        return (toks, lp) if logprobs else toks
+
+    def cache_distribution(self, cache, queries, logits, theta, lam, group=None):
+        """the mixture of given vectors: queries float32 [n, H], logits float32 [n, input_size + 1], group int32 [n] (None: all in
+        group 0) -> a dict of 'cache_prob' float32 [n, V1] (p_cache of every column, exactly 0 where no entry holds it), 'logprob'
+        float32 [n, V1] (the mixed log-probabilities a pick would read) and 'lse' float32 [n] (the logsumexp of each logits row)"""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        z = np.ascontiguousarray(logits, dtype=np.float32)
+        H, V1 = int(self.cfg.hidden_size), int(self.cfg.input_size) + 1
+        if q.ndim != 2 or q.shape[1] != H or z.shape != (q.shape[0], V1):
+            raise ValueError('queries must be [n, %d] and logits [n, %d], got %r and %r' % (H, V1, q.shape, z.shape))
+        n = q.shape[0]
+        g = self._group(group, n)
+        cc = self.cache_gen_config(theta, lam)
+        out = dict(cache_prob=np.empty((n, V1), np.float32), logprob=np.empty((n, V1), np.float32), lse=np.empty(n, np.float32))
+        self._ck(self._lib.fsmg_cache_distribution(self._h, cache._ptr(), C.byref(cc), n, _f32p(q), _f32p(z),
+                                                   g.ctypes.data_as(_I32P) if g is not None else None, _f32p(out['cache_prob']),
+                                                   _f32p(out['logprob']), _f32p(out['lse'])))
+        return out
 
     def read_losses(self, n):
         out = np.empty(n, np.float32)

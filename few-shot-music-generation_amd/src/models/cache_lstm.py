@@ -1,7 +1,7 @@
 """LSTM baseline with a support-set neural cache at evaluation time -- MI355X-native plugin.
 
 The baseline's eval ignores each episode's support set.  CacheLSTM trains exactly like LSTMBaseline (train and sample are
-inherited) and uses the support set at evaluation time without a gradient (Grave, Joulin, Usunier: Improving neural language
+inherited; generate too unless cache=True) and uses the support set at evaluation time without a gradient (Grave, Joulin, Usunier: Improving neural language
 models with a continuous cache): the top-layer hidden states the model produced while reading an artist's support songs are
 kept with the token that followed each (include/fsmg.h fsmg_cache_*); at every query position the model's own hidden state
 attends over its artist's entries, and the resulting distribution is mixed with the model's:
@@ -10,6 +10,8 @@ attends over its artist's entries, and the resulting distribution is mixed with 
 
 Config keys beyond LSTMBaseline's: cache_theta (sharpness, >= 0) and cache_lambda (mixing weight in [0, 1]; 0 is the baseline).
 
+  generate(..., cache=True)  LSTMBaseline.generate's rows drawn from the mixture: every generated token attends over ONE cache group
+                       built from the whole support set (fsmg_cache_generate); the default (cache=False) is the baseline's generate
   eval(episode)        mean NLL of the query tokens under the mixture (one fsmg_cache_eval_step)
   eval_many(episodes)  one call per episode
   score(s, songs)      builds a one-group cache from the support set and scores the songs against it
@@ -61,6 +63,23 @@ class CacheLSTM(LSTMBaseline):
                                            self._lambda if lambdas is None else lambdas, **kw)
         finally:
             cache.close()
+
+    def generate(self, support_set, num, n=1, cache=False, **kw):
+        """LSTMBaseline.generate (its keywords; cache=False: exactly it).  cache=True: a one-group cache is built from the whole
+        support set (int32 [.., max_len]), every generated token is drawn from the mixture at the configured cache_theta and
+        cache_lambda, and the cache is closed.  With condition_on_support=True the rows also start from a decode state primed on the
+        support songs.  The log-probs (logprobs=True) are the mixture's."""
+        if not cache:
+            return super(CacheLSTM, self).generate(support_set, num, n=n, **kw)
+        self._require_init()
+        songs = np.ascontiguousarray(support_set, dtype=np.int32).reshape(-1, self._time_steps)
+        built = self._model.cache_build(songs, n_groups=1)
+        try:
+            return super(CacheLSTM, self).generate(
+                support_set, num, n=n, _draw=lambda n_seq, count, **g: self._model.cache_generate(built, n_seq, count, self._theta,
+                                                                                               self._lambda, **g), **kw)
+        finally:
+            built.close()
 
     def tune(self, episodes, thetas, lambdas):
         """float64 [n_theta, n_lambda]: the mean over the episodes of the query NLL at every (theta, lambda) -- what eval would

@@ -170,15 +170,16 @@ class LSTMBaseline(HIPModel):
         return float(-np.mean(lp[:, 1:].astype(np.float64)))
 
     def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0,
-                 condition_on_support=False):
+                 condition_on_support=False, _draw=None):
         """n independent samples of num tokens (int32 [n, num]), drawn on the device (temperature, top_k, seed; include/fsmg.h
         fsmg_generate).  Each row continues the first primer_len tokens of a support song (dealt round-robin); with
         primer_len 0 the support set is not used.  top_p, min_p, repetition_penalty, repeat_window: the sampling filters
         (include/fsmg.h fsmg_generate_filtered; all off by default).
         condition_on_support=True: the support songs are read first (condition: one state row per artist, dealt round-robin over the
         n rows), then [start] and the first primer_len tokens of one of that artist's support songs, and the rows continue from
-        there."""
+        there.  (_draw: what stands in for FsmgModel.generate -- a subclass's own decoder with the same keywords.)"""
         self._require_init()
+        draw = _draw if _draw is not None else self._model.generate
         if condition_on_support:
             n, num = int(n), int(num)
             K, T = np.shape(support_set)[-2:]
@@ -194,14 +195,14 @@ class LSTMBaseline(HIPModel):
                     raise ValueError('primer_len %d exceeds the song length %d' % (primer_len, T))
                 head = np.full((n, 1), self._start_word, np.int32)
                 self._model.feed(rows, np.concatenate([head, songs[i % state.rows, (i // state.rows) % K, :max(int(primer_len), 0)]], axis=1))
-                return self._model.generate(n, num, temperature=temperature, top_k=top_k, seed=seed, logprobs=logprobs, top_p=top_p,
-                                            min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window, state=rows)
+                return draw(n, num, temperature=temperature, top_k=top_k, seed=seed, logprobs=logprobs, top_p=top_p,
+                            min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window, state=rows)
             finally:
                 rows.close()
                 state.close()
-        return self._model.generate(int(n), int(num), temperature=temperature, top_k=top_k, seed=seed,
-                                    primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs,
-                                    top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window)
+        return draw(int(n), int(num), temperature=temperature, top_k=top_k, seed=seed,
+                    primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs,
+                    top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window)
 
     def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False):
         """n independent beam searches of width beam_width, num tokens each, on the device (include/fsmg.h fsmg_beam_search):

@@ -571,6 +571,62 @@ int fsmg_cache_score(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_con
 int fsmg_cache_eval_step(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q, float theta,
                          float lambda, float* nll);
 
+/* ---- cache-conditioned generation (DESIGN.md "Cache-conditioned generation").  fsmg_generate_filtered with a support-set cache beside
+ * the model: at every GENERATED position each row's next token is drawn from the mixture fsmg_cache_score scores,
+ * p = (1 - lambda) p_lstm + lambda p_cache, the row attending over group group[r] of the cache (host [n_seq], NULL = all 0) with its
+ * own top-layer hidden state -- the vector whose projection is the position's logits row -- as the query.  On the device, per row:
+ *   d_i = q . k_i over the group's Mg keys (fsmg_cache_attend's arithmetic: exact products of the fp32 inputs, fp64 accumulation in a
+ *   fixed order), w_i = exp(theta (d_i - d_max)), Z = sum_i w_i, p_cache(v) = fl32((sum_{i : v_i = v} w_i) / Z), exactly 0 for a v no
+ *   entry holds; lp_v = fl32(z_v - lse), lse bitwise the number fsmg_generate subtracts for its log-probs;
+ *   z''_v = fl32(logaddexp(log1p(-lambda) + lp_v, log(lambda) + log(p_cache(v)))) in fp64 from the two fp32 numbers (fsmg_cache_score's
+ *   out_logprob formula); fl32(log1p(-lambda) + lp_v) where p_cache(v) = 0, which is -inf at lambda = 1.
+ * The unchanged pick of fsmg_generate(_filtered) then reads z'' as if it were the logits row: temperature, top_k, the filters, the
+ * Philox counters and the tie rules are fsmg_generate's, and out_logprob is what that pick reports on z'': z''_tok - lse(z''), with
+ * lse(z'') = 0 up to rounding.  Primer positions run the cells only: the cache is read at generated positions only.
+ *   fsmg_cache_generate         fsmg_generate_filtered's arguments and outputs.  lambda = 0: the cache is not read at all, and tokens and
+ *                               log-probs are fsmg_generate_filtered's BITWISE.
+ *   fsmg_dstate_cache_generate  fsmg_dstate_generate likewise (lambda = 0: its bits): from a decode state and back into it.  With the
+ *                               same cache and config its composition laws hold bitwise: generate(a) then generate(b) equals
+ *                               generate(a + b); a fresh state, fsmg_dstate_feed(primer), generate equals the one-shot call.
+ *   fsmg_cache_distribution     the kernels on given vectors: queries host [n][H], logits host [n][V1] (V1 = input_size + 1), group host
+ *                               [n] or NULL.  Outputs, any may be NULL but not all: out_cache_prob [n][V1] (p_cache), out_logprob [n][V1]
+ *                               (z''), out_lse [n] (lse).  lambda = 0 still returns out_cache_prob, and out_logprob = lp bitwise.
+ * Everything fsmg_generate promises holds: two identical calls give identical bits; a row's tokens and log-probs depend on its own
+ * primer, row index, group and that group's entries, the config and the seed -- not on n_seq, the other rows or their groups; no
+ * handle state is changed (the cache gains a value index -- its entries in stable order by value -- on the first call with lambda > 0
+ * or the first fsmg_cache_distribution: fsmg_cache_info's byte count grows once, fsmg_cache_get / _attend / _score keep their bits).
+ * A row's z'' bits in fsmg_cache_distribution depend on its query, its logits row, its group's entries, theta and lambda alone.
+ * A stale cache is legal, as for fsmg_cache_score.  The keys of a call are walked in chunks of FSMG_CACHE_GEN_CHUNK entries, one
+ * wave each; no result depends on it.
+ * Errors: FSMG_ERR_INVALID for a cache (or state) this handle does not own or one already destroyed, a cache whose H is not the
+ * handle's, a wrong version, nonzero reserved words, theta negative or not finite, lambda outside [0, 1] or NaN, a group id outside
+ * [0, G), n < 1 or n > 2^20, rows * Mg > 2^26 (the fp64 score scratch), every output NULL, NULL queries / logits, and everything
+ * fsmg_generate_filtered / fsmg_dstate_generate refuse; FSMG_ERR_TOKEN_RANGE as they return it.  Argument errors are found before any
+ * device work: outputs and states are untouched.
+ * Out of scope: beam search over the mixture; a self-cache over the row's own history; caches or states at MAML's theta'; several
+ * thetas per call. */
+#define FSMG_CACHE_GEN_CONFIG_VERSION 1
+#define FSMG_CACHE_GEN_CHUNK 16
+typedef struct fsmg_cache_gen_config {
+    int32_t version;      /* FSMG_CACHE_GEN_CONFIG_VERSION                               */
+    float   theta;        /* finite, >= 0                                                */
+    float   lambda;       /* in [0, 1]; 0: the cache is not read at all                  */
+    int32_t reserved[13]; /* must be 0                                                   */
+} fsmg_cache_gen_config;
+
+/* fsmg_generate_filtered with the cache beside the model; group host [n_seq] or NULL (all 0) */
+int fsmg_cache_generate(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_gen_config* g,
+                        const fsmg_gen_filters* f, const int32_t* group, const int32_t* primer,
+                        int32_t* out_tokens, float* out_logprob);
+/* fsmg_dstate_generate likewise: from a carried state and back into it */
+int fsmg_dstate_cache_generate(fsmg_handle h, fsmg_dstate st, fsmg_cache cache, const fsmg_cache_gen_config* cc,
+                               const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* group,
+                               int32_t* out_tokens, float* out_logprob);
+/* the kernels on given vectors: queries host [n][H], logits host [n][V1], group host [n] or NULL;
+   outputs, any may be NULL but not all: out_cache_prob [n][V1], out_logprob [n][V1] (z''), out_lse [n] */
+int fsmg_cache_distribution(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, int32_t n, const float* queries,
+                            const float* logits, const int32_t* group, float* out_cache_prob, float* out_logprob, float* out_lse);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
