@@ -21,6 +21,7 @@
 // other LDS buffer afterwards, one barrier per K tile; blocks are numbered so that the 8 XCDs (block b -> XCD
 // b % 8 as observed on MI355X) each walk a contiguous range of tiles and share operand panels in their private L2.
 #include "fsmg_kernels.h"
+#include "gemm_edge.h"
 #include <cstdlib>
 #include <algorithm>
 #include <type_traits>
@@ -1160,6 +1161,12 @@ __global__ __launch_bounds__(256 * (MT + 1), MT == 1 ? 2 : 1) void k_gemm_bx3w(c
 // waves 0-3 read their fragments, multiply, then split and write their share of the next tile; waves 4-7 split and write
 // first (their loads were issued a whole iteration earlier), then read and multiply.  Same LDS image per 128 rows / columns,
 // k order and term order as k_gemm_bx3: the same bits for the same K split.
+// Edge tiles (gemm_edge.h): a wave whose 128 x 64 sub-tile lies outside M x N -- rows 128 .. 255 of a last row tile of at most 128
+// rows, the column slices behind N in the last column tile -- runs a k loop of staging and barriers only and leaves the matrix pipe
+// of its SIMD to the wave beside it; where at most four sub-tiles are live they sit on waves 0-3, one per SIMD (a sliver of at most
+// 128 columns beside full rows is the one extent the plain map would pair on SIMDs 0 / 1: remapped).  Which wave computes a
+// sub-tile changes nothing in it; a dead wave's epilogue writes what it always wrote (nothing, or the empty softmax partials of
+// its slices).  `wave` is what STAGING goes by (stager rows, LDS-DMA regions, the ep slice, late, column sums), (wm, wn) the sub-tile.
 // QUEUE (GemmArgs::xcd_first != 0): the tile comes from the work queue of k_gemm_queue instead of blockIdx -- a restricted launch
 // (xcd_first > 0) lets only blocks on XCDs >= xcd_first draw, only items below work_limit and only while *stop == 0; the clean-up
 // launch (xcd_first < 0) takes what nobody claimed.  Which block computes an item never changes the item.
@@ -1177,7 +1184,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bx3h(const GemmArgs g) {
     __shared__ float s_cs[256];
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = (wave >> 2) & 1, wn = wave & 3;      // wave tile: rows 128 wm ..., columns 64 wn ...
     const bool late = wave >= 4;                          // order of the k tile, see above
     const int l31 = lane & 31, khalf = lane >> 5;
     const int tilesM = (g.M + XT - 1) / XT, tilesN = (g.N + XT - 1) / XT;
@@ -1241,6 +1247,14 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bx3h(const GemmArgs g) {
         z = blockIdx.y;
     }
     const int m0 = tm * XT, n0 = tn * XT;
+    // wave tile: rows 128 wm ..., columns 64 wn ... of the block tile (gemm_edge.h: wave >> 2, wave & 3 unless an edge tile has at most
+    // four live sub-tiles and the plain map would pair them on a SIMD).  `wave` itself stays what everything about STAGING goes by.
+    const GemmEdgeWave ew = gemm_edge_wave(min(XT, g.M - m0), min(XT, g.N - n0), wave);
+    const int wm = __builtin_amdgcn_readfirstlane(ew.wm), wn = __builtin_amdgcn_readfirstlane(ew.wn);
+    // wave-uniform, in an SGPR: a dead wave skips the fragment reads and the MFMAs of the k loop and nothing else -- its share of the
+    // staging, every barrier and the epilogue of its sub-tile (zero accumulators; what it stores or leaves as a softmax partial never
+    // depended on them: rows >= M and columns >= N are masked there) stay where they are
+    const bool live = __builtin_amdgcn_readfirstlane((int)ew.live) != 0;
     unsigned long long pacc[5] = {0, 0, 0, 0, 0}, plast = 0, p_entry = 0, p_loop = 0;
     if (PROF) { p_entry = plast = __builtin_amdgcn_s_memtime(); }
 
@@ -1316,6 +1330,19 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bx3h(const GemmArgs g) {
     bx_barrier();
     const int fa = khalf * (XT * 16) + (wm * 128 + l31) * 16, fb = khalf * (XT * 16) + (wn * 64 + l31) * 16;
     if (PROF) { p_loop = plast = __builtin_amdgcn_s_memtime(); }
+    // A wave whose sub-tile lies outside M x N has a k loop of its own: its share of the staging and the barrier of every k tile, no
+    // fragment reads, no MFMAs -- the LDS path and the matrix pipe of its SIMD belong to the live wave beside it.  (A branch around the
+    // reads and the MFMAs inside ONE loop made them basic blocks of their own: the early waves' split no longer interleaved with
+    // their MFMAs, 16-18 more VGPRs.  The live loop below is the loop as it was.)  Early or late makes no difference without MFMAs.
+    if (!live) {
+        for (int kt = 0; kt < nk; ++kt) {
+            if (kt + 1 < nk) {
+                BXH_COMMIT((kt + 1) & 1)
+                if (kt + 2 < nk) { BXH_FETCH(kt + 2) }
+            }
+            bx_barrier();
+        }
+    } else
     for (int kt = 0; kt < nk; ++kt) {
         const bool more = kt + 1 < nk;
         // every wave starts with the fragments of the FIRST term (a[2], b[0]: 6 of the 18 reads), so that the late waves'

@@ -151,6 +151,10 @@ int main(int argc, char** argv) {
         {"edge    <XC,XC> 48x260x49  ", OP_XC, OP_XC, 48, 260, 49, 0, true},
         {"edge    <XC,XC> 16x64x7    ", OP_XC, OP_XC, 16, 64, 7, 1, true},
         {"edge    <KC,XC> 6x200x12   ", OP_KC, OP_XC, 6, 200, 12, 1, false},
+        // 256 block tiles that are all edge tiles of the 256 x 256-tile kernel (BX3=3): 128 live rows each (waves 4-7 multiply nothing) /
+        // 20 live columns each (cfg-B's last column tile: two live sub-tiles, remapped onto two SIMDs)
+        {"halfrow <KC,XC> 128x65536x512", OP_KC, OP_XC, 128, 65536, 512, 1, false},
+        {"sliver  <KC,XC> 65536x20x512 ", OP_KC, OP_XC, 65536, 20, 512, 1, false},
     };
     hipStream_t s; CK(hipStreamCreate(&s));
     hipEvent_t e0, e1, e2; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1)); CK(hipEventCreate(&e2));
