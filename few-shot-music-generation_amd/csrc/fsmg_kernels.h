@@ -26,6 +26,8 @@ struct GemmArgs {
     // forward-only cross entropy: when ce_part != nullptr C is NOT stored; instead every wave writes, per row of its
     // 64-column slice, (max, sum exp(x - max)) over the columns < ce_nvocab into ce_part[row][2*tile_n + half] and
     // the logit of the row's target column into ce_tgt_logit[row]
+    // On the bf16-split kernels (bx3 != 0) the cross-entropy epilogues -- this one and ce_store below -- are instantiated for the
+    // projection's operand layout only, (OP_KC, OP_XC): launch_gemm returns hipErrorInvalidValue for the other two layouts there.
     float2* ce_part; const int* ce_tgt; float* ce_tgt_logit; int ce_nvocab;
     // ce_store != 0 (train passes, "fused softmax"): besides the partials the epilogue stores E = exp(x) (x = logit incl. bias; 0 in the
     // pad columns) into C -- the un-normalised softmax with NO shift, which launch_ce_finish turns into the loss gradient by patching

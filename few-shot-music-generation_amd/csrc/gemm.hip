@@ -150,15 +150,37 @@ __device__ __forceinline__ float row16_sum(float v) { FSMG_ROW16(row16_add_) ret
 __device__ __forceinline__ float row16_max(float v) { FSMG_ROW16(fmaxf) return v; }
 #undef FSMG_ROW16
 
+// The epilogue's mode is a compile-time property of the kernel (EM): one path per instantiation, chosen by launch_t from GemmArgs
+// (ce_part / ce_store) exactly as the run-time branches used to choose it.
+enum { EPI_PLAIN = 0, EPI_CE_FWD = 1, EPI_CE_STORE = 2 };   // plain store / forward-only cross entropy / fused softmax (ce_store)
+
+// The bias of a lane's four columns.  They are the same in every store pass of a block tile (col = ncol0 + 4 * (lane & 15)), but the
+// compiler may not hoist the load out of the passes itself -- the stores to C in between might alias g.bias -- and on this ISA a load
+// per pass means a `s_waitcnt vmcnt(0)` per pass, which waits for the previous pass's STORES as well (vmcnt counts both).  So: one
+// load per block tile, behind the k loop (no live range across it), and its wait paid here, once, in front of the first pass.
+// `add` keeps the add conditional as it always was (col < N; z == 0 in the plain path): adding a zero would turn -0.0 into +0.0.
+struct EpiBias { float4 v; bool add; };
+template <int EM>
+__device__ __forceinline__ EpiBias epi_bias(const GemmArgs& g, int z, int ncol0, int lane) {
+    const int col = ncol0 + 4 * (lane & 15);
+    EpiBias b;
+    b.v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    b.add = g.bias != nullptr && col < g.N && (EM != EPI_PLAIN || z == 0);
+    if (b.add) b.v = *reinterpret_cast<const float4*>(g.bias + col);
+    __builtin_amdgcn_s_waitcnt(0x0f70);                        // vmcnt(0): the bias is here; no store pass waits on memory again
+    return b;
+}
+
+template <int EM>
 __device__ __forceinline__ void store_tile_at(const GemmArgs& g, f32x16 (&acc)[2][2], float* ep, int z, int mrow0, int ncol0,
-                                              int tn, int tilesN, int wn, int lane) {
+                                              int tn, int tilesN, int wn, int lane, const EpiBias& bias) {
     const int l31 = lane & 31, khalf = lane >> 5;
     float* C = g.C + (long long)z * g.c_slab;
     constexpr int EP_LD = 68;                                  // 64 + 4: rows stay 16-byte aligned
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         int tg[8];                                             // forward-only cross entropy: the targets of this lane's eight rows, loaded
-        if (g.ce_part != nullptr && !g.ce_store) {             // together ahead of the transpose (one load latency, not one per pass)
+        if constexpr (EM == EPI_CE_FWD) {                      // together ahead of the transpose (one load latency, not one per pass)
 #pragma unroll
             for (int p = 0; p < 8; ++p) { const int row = mrow0 + i * 32 + p * 4 + (lane >> 4); tg[p] = row < g.M ? g.ce_tgt[row] : -1; }
         }
@@ -167,20 +189,19 @@ __device__ __forceinline__ void store_tile_at(const GemmArgs& g, f32x16 (&acc)[2
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 ep[((r & 3) + 8 * (r >> 2) + 4 * khalf) * EP_LD + j * 32 + l31] = acc[i][j][r];
-        __builtin_amdgcn_s_waitcnt(0xc07f);                    // lgkmcnt(0): own LDS writes landed (wave-private slice)
+        // lgkmcnt(0): own LDS writes landed (wave-private slice); forward-only cross entropy: vmcnt(0) too -- the eight targets are
+        // waited for here, once per block of passes, not at their first use inside a pass
+        __builtin_amdgcn_s_waitcnt(EM == EPI_CE_FWD ? 0x0070 : 0xc07f);
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
             const int rl = p * 4 + (lane >> 4), c4 = (lane & 15) * 4;
             const int row = mrow0 + i * 32 + rl, col = ncol0 + c4;
             float4 v = *reinterpret_cast<const float4*>(ep + rl * EP_LD + c4);
-            if (g.ce_part != nullptr && g.ce_store) {
+            if (bias.add) { v.x += bias.v.x; v.y += bias.v.y; v.z += bias.v.z; v.w += bias.v.w; }
+            if constexpr (EM == EPI_CE_STORE) {
                 // train pass, fused softmax (GemmArgs::ce_store): E = exp(x) with NO shift into C (zero in the pad columns) and the sum of
                 // the wave's 64 columns as this row's partial -- no row maximum, no target lookup (a dependent global load per pass cost
                 // 14 % of the tile): k_ce_finish range-checks the row SUM and takes the target logit as log(E[target])
-                if (g.bias != nullptr && col < g.N) {
-                    const float4 bv = *reinterpret_cast<const float4*>(g.bias + col);
-                    v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                }
                 float4 e;
                 e.x = (col + 0 < g.ce_nvocab) ? __expf(v.x) : 0.0f; e.y = (col + 1 < g.ce_nvocab) ? __expf(v.y) : 0.0f;
                 e.z = (col + 2 < g.ce_nvocab) ? __expf(v.z) : 0.0f; e.w = (col + 3 < g.ce_nvocab) ? __expf(v.w) : 0.0f;
@@ -194,15 +215,9 @@ __device__ __forceinline__ void store_tile_at(const GemmArgs& g, f32x16 (&acc)[2
                         __builtin_nontemporal_store(e.z, dst + 2); __builtin_nontemporal_store(e.w, dst + 3);
                     }
                 }
-                continue;
-            }
-            if (g.ce_part != nullptr) {
+            } else if constexpr (EM == EPI_CE_FWD) {
                 // forward-only cross entropy: softmax statistics of this row over the wave's 64 columns; the 16
                 // lanes of a row (lane>>4 picks the row of this pass) reduce with width-16 shuffles
-                if (g.bias != nullptr && col < g.N) {
-                    const float4 bv = *reinterpret_cast<const float4*>(g.bias + col);
-                    v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                }
                 const float NEG = -INFINITY;
                 const float x0 = (col + 0 < g.ce_nvocab) ? v.x : NEG, x1 = (col + 1 < g.ce_nvocab) ? v.y : NEG;
                 const float x2 = (col + 2 < g.ce_nvocab) ? v.z : NEG, x3 = (col + 3 < g.ce_nvocab) ? v.w : NEG;
@@ -216,19 +231,15 @@ __device__ __forceinline__ void store_tile_at(const GemmArgs& g, f32x16 (&acc)[2
                     if (t >= col && t < col + 4) g.ce_tgt_logit[row] = (t == col) ? v.x : (t == col + 1) ? v.y : (t == col + 2) ? v.z : v.w;
                     if ((lane & 15) == 0) g.ce_part[(long long)row * (2 * tilesN) + 2 * tn + wn] = make_float2(m, sm);
                 }
-                continue;
-            }
-            if (row < g.M && col < g.N) {                      // N, ldc are multiples of 4: whole float4 in or out
-                if (g.bias != nullptr && z == 0) {
-                    const float4 bv = *reinterpret_cast<const float4*>(g.bias + col);
-                    v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                }
-                float4* dst = reinterpret_cast<float4*>(C + (long long)row * g.ldc + col);
-                if (g.nt_store) {       // write-once streaming output (logits): keep it out of the way of L2-resident data
-                    __builtin_nontemporal_store(v.x, &dst->x); __builtin_nontemporal_store(v.y, &dst->y);
-                    __builtin_nontemporal_store(v.z, &dst->z); __builtin_nontemporal_store(v.w, &dst->w);
-                } else {
-                    *dst = v;
+            } else {
+                if (row < g.M && col < g.N) {                  // N, ldc are multiples of 4: whole float4 in or out
+                    float4* dst = reinterpret_cast<float4*>(C + (long long)row * g.ldc + col);
+                    if (g.nt_store) {   // write-once streaming output (logits): keep it out of the way of L2-resident data
+                        __builtin_nontemporal_store(v.x, &dst->x); __builtin_nontemporal_store(v.y, &dst->y);
+                        __builtin_nontemporal_store(v.z, &dst->z); __builtin_nontemporal_store(v.w, &dst->w);
+                    } else {
+                        *dst = v;
+                    }
                 }
             }
         }
@@ -236,10 +247,21 @@ __device__ __forceinline__ void store_tile_at(const GemmArgs& g, f32x16 (&acc)[2
     }
 }
 
+template <int EM>
 __device__ __forceinline__ void store_tile(const GemmArgs& g, f32x16 (&acc)[2][2], float* smem, int z, int m0, int n0,
                                            int tn, int tilesN, int wave, int lane) {
     const int wm = wave >> 1, wn = wave & 1;
-    store_tile_at(g, acc, smem + wave * (32 * 68), z, m0 + wm * 64, n0 + wn * 64, tn, tilesN, wn, lane);   // one 8.5 KiB slice per wave
+    const EpiBias bias = epi_bias<EM>(g, z, n0 + wn * 64, lane);
+    store_tile_at<EM>(g, acc, smem + wave * (32 * 68), z, m0 + wm * 64, n0 + wn * 64, tn, tilesN, wn, lane, bias);   // one 8.5 KiB slice per wave
+}
+
+// the fp32-MFMA kernels (k_gemm, k_gemm_staged, k_gemm_queue) keep the mode a run-time property, all three modes as before (a work-queue
+// launch with bx3 = 1 or 2 runs k_gemm_queue whatever bx3 says, ce_store included): one branch in front of the passes
+__device__ __forceinline__ void store_tile_rt(const GemmArgs& g, f32x16 (&acc)[2][2], float* smem, int z, int m0, int n0,
+                                              int tn, int tilesN, int wave, int lane) {
+    if (g.ce_part != nullptr && g.ce_store) store_tile<EPI_CE_STORE>(g, acc, smem, z, m0, n0, tn, tilesN, wave, lane);
+    else if (g.ce_part != nullptr) store_tile<EPI_CE_FWD>(g, acc, smem, z, m0, n0, tn, tilesN, wave, lane);
+    else store_tile<EPI_PLAIN>(g, acc, smem, z, m0, n0, tn, tilesN, wave, lane);
 }
 
 // XCD-aware tile numbering (bijective for any tile count): block b runs on XCD b % 8; each XCD walks a contiguous
@@ -349,7 +371,7 @@ __global__ __launch_bounds__(NTHREADS, (BK == 16 ? 1024 : 512) / NTHREADS) void 
         __syncthreads();
     }
 
-    store_tile(g, acc, smem, z, m0, n0, tn, tilesN, wave, lane);
+    store_tile_rt(g, acc, smem, z, m0, n0, tn, tilesN, wave, lane);
     if (do_colsum && n0 + tid < g.N) g.colsum[(long long)z * g.colsum_slab + n0 + tid] = csum;
 }
 
@@ -522,7 +544,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, float* smem, int tm
         __syncthreads();
     }
 
-    store_tile(g, acc, smem, z, m0, n0, tn, tilesN, wave, lane);
+    store_tile_rt(g, acc, smem, z, m0, n0, tn, tilesN, wave, lane);
     if (do_colsum && n0 + tid < g.N) g.colsum[(long long)z * g.colsum_slab + n0 + tid] = csum;
 }
 
@@ -880,7 +902,8 @@ template <int XT, int NT, bool BUF, bool GATHER> struct BxStagerSel<true, OP_XC,
 #define BX_STAMP(i) if (PROF) { __builtin_amdgcn_sched_barrier(0); const unsigned long long n_ = __builtin_amdgcn_s_memtime(); \
                                 __builtin_amdgcn_sched_barrier(0); pacc[i] += n_ - plast; plast = n_; }
 // BUFM: which operands are fetched with buffer loads (0 none, 1 B only, 2 both; BxStager)
-template <int AMODE, int BMODE, bool PROF = false, int BUFM = 0>
+// EM: the epilogue's mode (EPI_*), see store_tile_at
+template <int AMODE, int BMODE, bool PROF = false, int BUFM = 0, int EM = EPI_PLAIN>
 __global__ __launch_bounds__(256, 2) void k_gemm_bx3(const GemmArgs g) {
     constexpr int EPI = 4 * 32 * 68 * 4;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[(2 * BX_STAGE > EPI) ? 2 * BX_STAGE : EPI];
@@ -976,7 +999,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bx3(const GemmArgs g) {
         __syncthreads();
         if (tid < 128 && n0 + tid < g.N) g.colsum[(long long)z * g.colsum_slab + n0 + tid] = csum + s_cs[tid];
     }
-    store_tile(g, acc, smem_f, z, m0, n0, tn, tilesN, wave, lane);
+    store_tile<EM>(g, acc, smem_f, z, m0, n0, tn, tilesN, wave, lane);
     if (PROF && g.prof != nullptr && lane == 0) {
         __builtin_amdgcn_s_waitcnt(0);
         const unsigned long long p_end = __builtin_amdgcn_s_memtime();
@@ -1002,7 +1025,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bx3(const GemmArgs g) {
 // The loaders fetch two tiles ahead (two register sets taking alternate tiles).
 __device__ __forceinline__ void bx_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <int AMODE, int BMODE, int MT, bool PROF = false, int BUFM = 0>
+template <int AMODE, int BMODE, int MT, bool PROF = false, int BUFM = 0, int EM = EPI_PLAIN>
 __global__ __launch_bounds__(256 * (MT + 1), MT == 1 ? 2 : 1) void k_gemm_bx3w(const GemmArgs g) {
     constexpr int XA = 128 * MT;                       // rows of the block tile
     constexpr int A_PLANE = 2 * XA * 16, A_OPER = 3 * A_PLANE, STAGE = A_OPER + BX_OPER;
@@ -1139,7 +1162,7 @@ __global__ __launch_bounds__(256 * (MT + 1), MT == 1 ? 2 : 1) void k_gemm_bx3w(c
         }
         if (PROF) p_exit_loop = __builtin_amdgcn_s_memtime();
         bx_barrier();
-        store_tile(g, acc, reinterpret_cast<float*>(smem), z, m0, n0, tn, tilesN, wave, lane);
+        store_tile<EM>(g, acc, reinterpret_cast<float*>(smem), z, m0, n0, tn, tilesN, wave, lane);
     }
     if (PROF && g.prof != nullptr && lane == 0) {
         __builtin_amdgcn_s_waitcnt(0);
@@ -1171,7 +1194,7 @@ __global__ __launch_bounds__(256 * (MT + 1), MT == 1 ? 2 : 1) void k_gemm_bx3w(c
 // (xcd_first > 0) lets only blocks on XCDs >= xcd_first draw, only items below work_limit and only while *stop == 0; the clean-up
 // launch (xcd_first < 0) takes what nobody claimed.  Which block computes an item never changes the item.
 // AG: two-part op(A) (GemmArgs::m_split; x-contiguous operands through LDS-DMA only)
-template <int AMODE, int BMODE, bool PROF = false, int BUFM = 0, bool QUEUE = false, bool AG = false>
+template <int AMODE, int BMODE, bool PROF = false, int BUFM = 0, bool QUEUE = false, bool AG = false, int EM = EPI_PLAIN>
 __global__ __launch_bounds__(512, 1) void k_gemm_bx3h(const GemmArgs g) {
     constexpr int XT = 256;
     constexpr int PLANE = 2 * XT * 16, OPER = 3 * PLANE;                              // 8 KiB, 24 KiB
@@ -1405,13 +1428,15 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bx3h(const GemmArgs g) {
                 for (int r = 0; r < 16; ++r) sink += acc[i][j][r];
         if (sink == 1.2345e-30f) g.C[0] = sink;
     } else
+    // a 256-column tile may reach past the last 128-column tile of N: nothing to store there, and the forward-only cross
+    // entropy has no partial slot for it (a write would land in the next row's slots)
+    if ((n0 + wn * 64) / 128 < (g.N + 127) / 128) {
+        const EpiBias bias = epi_bias<EM>(g, z, n0 + wn * 64, lane);       // both halves have the same 64 columns: one load per tile
 #pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2) {    // the wave's 128 x 64 tile as two 64 x 64 halves
-        // a 256-column tile may reach past the last 128-column tile of N: nothing to store there, and the forward-only cross
-        // entropy has no partial slot for it (a write would land in the next row's slots)
-        if ((n0 + wn * 64) / 128 >= (g.N + 127) / 128) break;
-        f32x16 (&sub)[2][2] = *reinterpret_cast<f32x16 (*)[2][2]>(&acc[2 * h2][0]);
-        store_tile_at(g, sub, ep, z, m0 + wm * 128 + h2 * 64, n0 + wn * 64, (n0 + wn * 64) / 128, (g.N + 127) / 128, wn & 1, lane);
+        for (int h2 = 0; h2 < 2; ++h2) {    // the wave's 128 x 64 tile as two 64 x 64 halves
+            f32x16 (&sub)[2][2] = *reinterpret_cast<f32x16 (*)[2][2]>(&acc[2 * h2][0]);
+            store_tile_at<EM>(g, sub, ep, z, m0 + wm * 128 + h2 * 64, n0 + wn * 64, (n0 + wn * 64) / 128, (g.N + 127) / 128, wn & 1, lane, bias);
+        }
     }
     if (PROF && g.prof != nullptr && lane == 0) {
         __builtin_amdgcn_s_waitcnt(0);
@@ -1426,12 +1451,30 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bx3h(const GemmArgs g) {
 }
 #undef BX_STAMP
 
+// Launch of a bf16-split kernel with the epilogue's mode as its last template argument.  The two cross-entropy modes exist for the
+// projection's operand layout only (A k-contiguous, B x-contiguous: launch_t refuses them elsewhere), so only that layout carries
+// three instantiations per kernel form.
+#define FSMG_LAUNCH_EPI(GRID, BLOCK, LDS, KERNEL, ...)                                                                          \
+    do {                                                                                                                        \
+        if constexpr (AMODE == OP_KC && BMODE == OP_XC) {                                                                       \
+            if (em == EPI_CE_STORE) { hipLaunchKernelGGL((KERNEL<__VA_ARGS__, EPI_CE_STORE>), GRID, BLOCK, LDS, s, g); break; } \
+            if (em == EPI_CE_FWD) { hipLaunchKernelGGL((KERNEL<__VA_ARGS__, EPI_CE_FWD>), GRID, BLOCK, LDS, s, g); break; }     \
+        }                                                                                                                       \
+        hipLaunchKernelGGL((KERNEL<__VA_ARGS__, EPI_PLAIN>), GRID, BLOCK, LDS, s, g);                                           \
+    } while (0)
+
 template <int AMODE, int BMODE>
 hipError_t launch_t(hipStream_t s, const GemmArgs& g, int lds_pad) {
     const int tilesM = (g.M + BM - 1) / BM, tilesN = (g.N + BN - 1) / BN;
     // weighted column sums: the 256 x 256-tile kernels' x-contiguous-operand instantiations only; exp(logit) stores: the bf16-split kernels
     if (g.colsum_w != nullptr && !(g.bx3 == 3 && AMODE == OP_XC && BMODE == OP_XC && g.colsum != nullptr)) return hipErrorInvalidValue;
     if (g.ce_store && !(g.bx3 != 0 && g.ce_part != nullptr && g.ksplit <= 1)) return hipErrorInvalidValue;      // (every bf16-split kernel: one epilogue)
+    // the epilogue's mode, a template argument of the bf16-split kernels (store_tile_at).  Where one of them will really run -- bx3 != 0,
+    // and for a work-queue launch bx3 == 3: the others take the fp32-MFMA k_gemm_queue, whose mode stays a run-time property -- the two
+    // cross-entropy modes exist for the projection's operand layout only (GemmArgs::ce_part)
+    const int em = g.ce_part == nullptr ? EPI_PLAIN : g.ce_store ? EPI_CE_STORE : EPI_CE_FWD;
+    const bool split_kernel = g.bx3 != 0 && (g.xcd_first == 0 || g.bx3 == 3);
+    if (split_kernel && em != EPI_PLAIN && !(AMODE == OP_KC && BMODE == OP_XC)) return hipErrorInvalidValue;
     if (g.xcd_first != 0 && g.bx3 == 3) {      // work-queue launch of the 256 x 256-tile kernel (one block per CU)
         if (g.work == nullptr || g.claim == nullptr || (g.xcd_first > 0 && g.stop == nullptr) || g.gather != nullptr || g.prof != nullptr) return hipErrorInvalidValue;
         const long long a_b = 4LL * g.lda * (AMODE == OP_KC ? g.M : g.K), b_b = 4LL * g.ldb * (BMODE == OP_KC ? g.N : g.K);
@@ -1446,13 +1489,13 @@ hipError_t launch_t(hipStream_t s, const GemmArgs& g, int lds_pad) {
                 const bool ok = g.m_split % 256 == 0 && g.m_split < g.M && g.A2 != nullptr && b_dma && g.lda % 4 == 0 && g.lda2 % 4 == 0 &&
                                 (g.M - g.m_split) % 4 == 0 && (((uintptr_t)g.A | (uintptr_t)g.A2) & 15) == 0 && 4LL * g.lda2 * g.K < 0xfffff000LL;
                 if (!ok) return hipErrorInvalidValue;
-                hipLaunchKernelGGL((k_gemm_bx3h<AMODE, BMODE, false, 3, true, true>), dim3(blocks), dim3(512), 0, s, g);
+                FSMG_LAUNCH_EPI(dim3(blocks), dim3(512), 0, k_gemm_bx3h, AMODE, BMODE, false, 3, true, true);
                 return hipGetLastError();
             }
-            if (a_dma && b_dma) { hipLaunchKernelGGL((k_gemm_bx3h<AMODE, BMODE, false, 3, true>), dim3(blocks), dim3(512), 0, s, g); return hipGetLastError(); }
+            if (a_dma && b_dma) { FSMG_LAUNCH_EPI(dim3(blocks), dim3(512), 0, k_gemm_bx3h, AMODE, BMODE, false, 3, true, false); return hipGetLastError(); }
         }
         if (g.m_split > 0) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_gemm_bx3h<AMODE, BMODE, false, 2, true>), dim3(blocks), dim3(512), 0, s, g);
+        FSMG_LAUNCH_EPI(dim3(blocks), dim3(512), 0, k_gemm_bx3h, AMODE, BMODE, false, 2, true, false);
         return hipGetLastError();
     }
     if (g.xcd_first != 0) {             // work-queue launch: one resident set of blocks (4 per CU), see k_gemm_queue
@@ -1485,7 +1528,7 @@ hipError_t launch_t(hipStream_t s, const GemmArgs& g, int lds_pad) {
                                 (((uintptr_t)g.A | (uintptr_t)g.A2 | (uintptr_t)g.B) & 15) == 0 && 4LL * g.lda2 * g.K < 0xfffff000LL &&
                                 (g.gather != nullptr || 4LL * g.lda * g.K < 0xfffff000LL);
                 if (!ok) return hipErrorInvalidValue;
-                hipLaunchKernelGGL((k_gemm_bx3h<AMODE, BMODE, false, 3, false, true>), grid3, dim3(512), lds_pad, s, g);
+                FSMG_LAUNCH_EPI(grid3, dim3(512), lds_pad, k_gemm_bx3h, AMODE, BMODE, false, 3, false, true);
                 return hipGetLastError();
             }
             return hipErrorInvalidValue;
@@ -1499,34 +1542,34 @@ hipError_t launch_t(hipStream_t s, const GemmArgs& g, int lds_pad) {
         const bool dma = !dma_off && bufm == 2 && a_dma && b_dma;
         if constexpr (AMODE == OP_XC && BMODE == OP_XC) {
 #ifdef FSMG_EXPERIMENTS
-            if (dma && g.prof != nullptr) { hipLaunchKernelGGL((k_gemm_bx3h<AMODE, BMODE, true, 3>), grid3, dim3(512), lds_pad, s, g); return hipGetLastError(); }
+            if (dma && g.prof != nullptr) { FSMG_LAUNCH_EPI(grid3, dim3(512), lds_pad, k_gemm_bx3h, AMODE, BMODE, true, 3, false, false); return hipGetLastError(); }
 #endif
-            if (dma) { hipLaunchKernelGGL((k_gemm_bx3h<AMODE, BMODE, false, 3>), grid3, dim3(512), lds_pad, s, g); return hipGetLastError(); }
+            if (dma) { FSMG_LAUNCH_EPI(grid3, dim3(512), lds_pad, k_gemm_bx3h, AMODE, BMODE, false, 3, false, false); return hipGetLastError(); }
         }
 #ifdef FSMG_EXPERIMENTS
-        if (g.prof != nullptr) { hipLaunchKernelGGL((k_gemm_bx3h<AMODE, BMODE, true, 2>), grid3, dim3(512), lds_pad, s, g); return hipGetLastError(); }
+        if (g.prof != nullptr) { FSMG_LAUNCH_EPI(grid3, dim3(512), lds_pad, k_gemm_bx3h, AMODE, BMODE, true, 2, false, false); return hipGetLastError(); }
 #endif
-        if (bufm == 2) hipLaunchKernelGGL((k_gemm_bx3h<AMODE, BMODE, false, 2>), grid3, dim3(512), lds_pad, s, g);
-        else if (bufm == 1) hipLaunchKernelGGL((k_gemm_bx3h<AMODE, BMODE, false, 1>), grid3, dim3(512), lds_pad, s, g);
-        else hipLaunchKernelGGL((k_gemm_bx3h<AMODE, BMODE>), grid3, dim3(512), lds_pad, s, g);
+        if (bufm == 2) FSMG_LAUNCH_EPI(grid3, dim3(512), lds_pad, k_gemm_bx3h, AMODE, BMODE, false, 2, false, false);
+        else if (bufm == 1) FSMG_LAUNCH_EPI(grid3, dim3(512), lds_pad, k_gemm_bx3h, AMODE, BMODE, false, 1, false, false);
+        else FSMG_LAUNCH_EPI(grid3, dim3(512), lds_pad, k_gemm_bx3h, AMODE, BMODE, false, 0, false, false);
         return hipGetLastError();
     }
     if (g.bx3 == 2) {        // wave-specialised variant
 #ifdef FSMG_EXPERIMENTS
-        if (g.prof != nullptr) { hipLaunchKernelGGL((k_gemm_bx3w<AMODE, BMODE, 1, true, 2>), grid, dim3(512), lds_pad, s, g); return hipGetLastError(); }
+        if (g.prof != nullptr) { FSMG_LAUNCH_EPI(grid, dim3(512), lds_pad, k_gemm_bx3w, AMODE, BMODE, 1, true, 2); return hipGetLastError(); }
 #endif
-        if (bufm == 2) hipLaunchKernelGGL((k_gemm_bx3w<AMODE, BMODE, 1, false, 2>), grid, dim3(512), lds_pad, s, g);
-        else if (bufm == 1) hipLaunchKernelGGL((k_gemm_bx3w<AMODE, BMODE, 1, false, 1>), grid, dim3(512), lds_pad, s, g);
-        else hipLaunchKernelGGL((k_gemm_bx3w<AMODE, BMODE, 1>), grid, dim3(512), lds_pad, s, g);
+        if (bufm == 2) FSMG_LAUNCH_EPI(grid, dim3(512), lds_pad, k_gemm_bx3w, AMODE, BMODE, 1, false, 2);
+        else if (bufm == 1) FSMG_LAUNCH_EPI(grid, dim3(512), lds_pad, k_gemm_bx3w, AMODE, BMODE, 1, false, 1);
+        else FSMG_LAUNCH_EPI(grid, dim3(512), lds_pad, k_gemm_bx3w, AMODE, BMODE, 1, false, 0);
         return hipGetLastError();
     }
     if (g.bx3) {             // (gathered K rows included: BxStager)
 #ifdef FSMG_EXPERIMENTS
-        if (g.prof != nullptr) { hipLaunchKernelGGL((k_gemm_bx3<AMODE, BMODE, true, 2>), grid, dim3(256), lds_pad, s, g); return hipGetLastError(); }
+        if (g.prof != nullptr) { FSMG_LAUNCH_EPI(grid, dim3(256), lds_pad, k_gemm_bx3, AMODE, BMODE, true, 2); return hipGetLastError(); }
 #endif
-        if (bufm == 2) hipLaunchKernelGGL((k_gemm_bx3<AMODE, BMODE, false, 2>), grid, dim3(256), lds_pad, s, g);
-        else if (bufm == 1) hipLaunchKernelGGL((k_gemm_bx3<AMODE, BMODE, false, 1>), grid, dim3(256), lds_pad, s, g);
-        else hipLaunchKernelGGL((k_gemm_bx3<AMODE, BMODE>), grid, dim3(256), lds_pad, s, g);
+        if (bufm == 2) FSMG_LAUNCH_EPI(grid, dim3(256), lds_pad, k_gemm_bx3, AMODE, BMODE, false, 2);
+        else if (bufm == 1) FSMG_LAUNCH_EPI(grid, dim3(256), lds_pad, k_gemm_bx3, AMODE, BMODE, false, 1);
+        else FSMG_LAUNCH_EPI(grid, dim3(256), lds_pad, k_gemm_bx3, AMODE, BMODE, false, 0);
         return hipGetLastError();
     }
     // lds_pad: unused dynamic LDS that only lowers the number of co-resident blocks per CU
@@ -1535,6 +1578,7 @@ hipError_t launch_t(hipStream_t s, const GemmArgs& g, int lds_pad) {
     else hipLaunchKernelGGL((k_gemm<AMODE, BMODE>), grid, dim3(NTHREADS), lds_pad, s, g);
     return hipGetLastError();
 }
+#undef FSMG_LAUNCH_EPI
 
 __global__ void k_reduce_slabs(const float* __restrict__ slabs, long long stride, int nslab,
                                float* __restrict__ out, long long n) {

@@ -3,6 +3,9 @@
 //       -Ifew-shot-music-generation_amd/csrc -Iinclude few-shot-music-generation_amd/build/exp/gemm.o tools/gemm_bench.cpp -o tools/gemm_bench.bin   (make -C few-shot-music-generation_amd/csrc experiments: the stamped instantiations live in the experiment build)
 // Usage: gemm_bench.bin [reps] [blocks_per_cu] [verify 0/1: compare every result with a naive fp32 kernel]      (blocks_per_cu < 4 applies the aux-stream LDS cap)
 // Prints per shape: ksplit, kernel-only ms (GEMM without the slab reduce), total ms, TF on the total.
+// EPI=0 (default) plain store without bias; EPI=1 plain store with bias (the x-part GEMM's epilogue); EPI=2 forward-only cross entropy;
+// EPI=3 fused-softmax store (the train step's projection) -- bias, ce_part, ce_tgt, ce_nvocab, ce_store filled as api_forward.hip does.
+// 2 and 3 apply where the step uses them (<KC,XC>, unsplit K; 3: BX3 != 0); other shapes keep the plain store.  verify checks EPI <= 1.
 #include "fsmg_kernels.h"
 #include <cstdio>
 #include <cstring>
@@ -16,7 +19,7 @@ using namespace fsmg;
 struct Shape { const char* name; int amode, bmode; int M, N, K; int ksplit; bool colsum; };
 
 // reference: one thread per element, fp64 accumulation
-__global__ void k_ref(const float* A, int lda, int amode, const float* B, int ldb, int bmode, float* C, int M, int N, int K) {
+__global__ void k_ref(const float* A, int lda, int amode, const float* B, int ldb, int bmode, float* C, int M, int N, int K, const float* bias) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)M * N) return;
     const int m = (int)(i / N), n = (int)(i % N);
@@ -26,7 +29,7 @@ __global__ void k_ref(const float* A, int lda, int amode, const float* B, int ld
         const float b = (bmode == OP_KC) ? B[(long long)n * ldb + k] : B[(long long)k * ldb + n];
         s += (double)a * (double)b;
     }
-    C[i] = (float)s;
+    C[i] = (float)(s + (bias ? (double)bias[n] : 0.0));
 }
 __global__ void k_ref_colsum(const float* B, int ldb, float* cs, int N, int K) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -166,16 +169,29 @@ int main(int argc, char** argv) {
     const int bx3 = getenv("BX3") ? atoi(getenv("BX3")) : 0;      // BX3=1: the bf16-split kernel (k_gemm_bx3)
     int* ctl; CK(hipMalloc(&ctl, 4 * 65536));
     const char* only = getenv("ONLY");                         // ONLY=substring of the shape name
+    const int epi = getenv("EPI") ? atoi(getenv("EPI")) : 0;
     for (const Shape& sh : shapes) {
         if (only && !strstr(sh.name, only)) continue;
         const size_t an = (size_t)sh.M * sh.K, bn = (size_t)sh.K * sh.N, cn = (size_t)sh.M * sh.N;
         float* A = dev_random(an, 1); float* B = dev_random(bn, 2);
         float* C; CK(hipMalloc(&C, cn * 4)); float* cs; CK(hipMalloc(&cs, sh.N * 4));
         float* Cref = nullptr; float* csref = nullptr;
-        if (verify) {
+        // the epilogue's inputs (EPI=): a bias per column, and for the cross-entropy modes one (max, sum) slot per row and 64-column
+        // slice, a target id per row and the target logits
+        const bool ce = epi >= 2 && sh.amode == OP_KC && sh.bmode == OP_XC && sh.ksplit == 1 && (epi == 2 || bx3 != 0);
+        const int nparts = 2 * ((sh.N + 127) / 128), nvocab = std::max(1, sh.N - 3);
+        float* bias = epi >= 1 ? dev_random((size_t)sh.N, 3) : nullptr;
+        float2* ce_part = nullptr; int* ce_tgt = nullptr; float* ce_tl = nullptr;
+        if (ce) {
+            CK(hipMalloc(&ce_part, (size_t)sh.M * nparts * sizeof(float2))); CK(hipMalloc(&ce_tgt, (size_t)sh.M * 4)); CK(hipMalloc(&ce_tl, (size_t)sh.M * 4));
+            std::vector<int> t(sh.M);
+            for (int i = 0; i < sh.M; ++i) t[i] = (int)((i * 2654435761u >> 8) % (unsigned)nvocab);
+            CK(hipMemcpy(ce_tgt, t.data(), (size_t)sh.M * 4, hipMemcpyHostToDevice));
+        }
+        if (verify && !ce) {
             CK(hipMalloc(&Cref, cn * 4)); CK(hipMalloc(&csref, sh.N * 4));
             hipLaunchKernelGGL(k_ref, dim3((unsigned)((cn + 255) / 256)), dim3(256), 0, s, A, (sh.amode == OP_KC) ? sh.K : sh.M, sh.amode,
-                               B, (sh.bmode == OP_KC) ? sh.K : sh.N, sh.bmode, Cref, sh.M, sh.N, sh.K);
+                               B, (sh.bmode == OP_KC) ? sh.K : sh.N, sh.bmode, Cref, sh.M, sh.N, sh.K, bias);
             if (sh.colsum) hipLaunchKernelGGL(k_ref_colsum, dim3((sh.N + 255) / 256), dim3(256), 0, s, B, sh.N, csref, sh.N, sh.K);
             CK(hipStreamSynchronize(s));
         }
@@ -187,6 +203,11 @@ int main(int argc, char** argv) {
             g.C = (S > 1) ? slabs : C; g.ldc = sh.N; g.M = sh.M; g.N = sh.N; g.K = sh.K;
             g.ksplit = S; g.c_slab = (long long)cn; g.bx3 = bx3;
             g.group_m = getenv("GROUP_M") ? atoi(getenv("GROUP_M")) : 0;
+            g.bias = bias;
+            if (ce) {
+                g.nt_store = 1; g.ce_part = ce_part; g.ce_nvocab = nvocab;
+                if (epi == 2) { g.ce_tgt = ce_tgt; g.ce_tgt_logit = ce_tl; } else g.ce_store = 1;
+            }
             if (sh.colsum) { g.colsum = (S > 1) ? csl : cs; g.colsum_slab = sh.N; }
             float ms_k = 0, ms_t = 0;
             for (int r = -2; r < reps; ++r) {
@@ -212,18 +233,21 @@ int main(int argc, char** argv) {
             }
             ms_k /= reps; ms_t /= reps;
             const int tiles = bx3 == 3 ? ((sh.M + 255) / 256) * ((sh.N + 255) / 256) : ((sh.M + gemm_tile_m() - 1) / gemm_tile_m()) * ((sh.N + 127) / 128);
-            if (verify) {
+            if (verify && !ce) {
                 CK(hipStreamSynchronize(s));
                 const double e = max_rel(C, Cref, cn), ec = sh.colsum ? max_rel(cs, csref, sh.N) : 0.0;
                 printf("  verify S %d: C max err / max|C| %.2e  rms err / rms %.2e  colsum err %.2e  %s\n", S, e, rms_rel(C, Cref, cn), ec, (e < 2e-5 && ec < 2e-4) ? "ok" : "MISMATCH");
                 CK(hipMemset(C, 0xff, cn * 4));
             }
+            if (epi) printf("EPI %d%s ", epi, (epi >= 2 && !ce) ? " (plain here)" : "");
             printf("%s  M %5d N %5d K %5d  S %d  blocks %5d (%.2f rounds of %d)  gemm %.3f ms  total %.3f ms  %.1f TF\n", sh.name, sh.M, sh.N, sh.K, S,
                    tiles * S, tiles * S / (256.0 * bpc), 256 * bpc, ms_k, ms_t, 2.0 * sh.M * sh.N * sh.K / (ms_t * 1e-3) / 1e12);
             if (getenv("PROF") && atoi(getenv("PROF")) && bx3 && xcd_first == 0) profile_launch(s, sh.amode, sh.bmode, g, pad, tiles * S, ms_k);
         }
         CK(hipFree(A)); CK(hipFree(B)); CK(hipFree(C)); CK(hipFree(cs));
         if (Cref) { CK(hipFree(Cref)); CK(hipFree(csref)); }
+        if (bias) CK(hipFree(bias));
+        if (ce) { CK(hipFree(ce_part)); CK(hipFree(ce_tgt)); CK(hipFree(ce_tl)); }
     }
     return 0;
 }
