@@ -120,6 +120,56 @@ int attend_launch(fsmg_model* h, const fsmg_cache_s* c, const Tiles& t, const At
     return FSMG_OK;
 }
 
+// The layout of a self-cache attention call in h->cat: [out n_theta x n floats | row groups | (raw form) values n ints | vectors n x Hp floats]
+struct SelfScratch {
+    float* out = nullptr; int* row_group = nullptr; int* val = nullptr; float* V = nullptr;
+};
+int self_scratch(fsmg_model* h, int rows, int n, int n_theta, bool raw, SelfScratch* s) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (size_t)round_up((int64_t)(off + bytes), 256); return o; };
+    const size_t o_out = take(sizeof(float) * (size_t)n_theta * n);
+    const size_t o_grp = take(sizeof(int) * (size_t)rows);
+    const size_t o_val = take(raw ? sizeof(int) * (size_t)n : 0);
+    const size_t o_v = take(raw ? sizeof(float) * (size_t)n * h->Hp : 0);
+    const int rc = cat_reserve(h, off);
+    if (rc != FSMG_OK) return rc;
+    s->out = (float*)(h->cat + o_out); s->row_group = (int*)(h->cat + o_grp); s->val = (int*)(h->cat + o_val); s->V = (float*)(h->cat + o_v);
+    return FSMG_OK;
+}
+
+// uploads the rows' groups (a support cache given) and launches the causal attention kernel over `rows` rows of T positions; `group`
+// stays alive until the stream has been synchronised
+int self_launch(fsmg_model* h, const fsmg_cache_s* c, const SelfScratch& s, int rows, int T, int W, const float* V, long long vs_r,
+                long long vs_t, const int* val, long long ys_r, long long ys_t, const int32_t* group, const float* thetas, int n_theta) {
+    CacheSelfArgs a{};
+    if (c) {
+        a.keys = c->keys; a.vals = c->vals; a.Mg = c->Mg;
+        if (group) {
+            HIPCK(h, hipMemcpyAsync(s.row_group, group, sizeof(int) * (size_t)rows, hipMemcpyHostToDevice, h->stream));
+            a.row_group = s.row_group;
+        }
+    }
+    a.H = h->H; a.Hp = h->Hp;
+    a.V = V; a.vs_r = vs_r; a.vs_t = vs_t; a.val = val; a.ys_r = ys_r; a.ys_t = ys_t;
+    a.n_rows = rows; a.T = T; a.W = W;
+    for (int k = 0; k < n_theta; ++k) a.theta[k] = thetas[k];
+    a.n_theta = n_theta; a.out = s.out;
+    ScopedTimer tm(h, "cache_attend_self");
+    HIPCK(h, launch_cache_attend_self(h->stream, a));
+    return FSMG_OK;
+}
+
+int check_self_config(fsmg_model* h, const fsmg_cache_self_config* sc) {
+    if (!sc) return fail(h, FSMG_ERR_INVALID, "null fsmg_cache_self_config");
+    if (sc->version != FSMG_CACHE_SELF_CONFIG_VERSION)
+        return fail(h, FSMG_ERR_INVALID, "fsmg_cache_self_config.version is " + std::to_string(sc->version) + ", this library expects " +
+                                             std::to_string(FSMG_CACHE_SELF_CONFIG_VERSION));
+    for (int32_t r : sc->reserved)
+        if (r != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_cache_self_config.reserved must be zero");
+    if (sc->window < 1) return fail(h, FSMG_ERR_INVALID, "fsmg_cache_self_config.window must be >= 1");
+    return FSMG_OK;
+}
+
 bool thetas_ok(const float* thetas, int n) {
     for (int k = 0; k < n; ++k)
         if (!std::isfinite(thetas[k]) || thetas[k] < 0.0f) return false;
@@ -247,9 +297,11 @@ inline float mix_logprob(float lp, float pc, double log1m_lambda, double log_lam
     return (float)(hi + std::log1p(std::exp(lo - hi)));
 }
 
-// fsmg_cache_score's work behind the argument checks
+// fsmg_cache_score's work behind the argument checks; with `self` fsmg_cache_self_score's: the row's own history joins the set (the
+// causal kernel instead of k_cache_attend), `cache` may then be null, and a position whose set is empty keeps the model's log-prob
 int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_config* c, const int32_t* tokens, const int32_t* group,
-               float* out_logprob, float* out_cache_prob, float* out_lstm_logprob, float* out_row_nll) {
+               float* out_logprob, float* out_cache_prob, float* out_lstm_logprob, float* out_row_nll,
+               const fsmg_cache_self_config* self = nullptr) {
     const int R = c->n_rows, T = h->T, NT = c->n_theta, NL = c->n_lambda;
     const int P = c->pass_rows > 0 ? c->pass_rows : FSMG_SCORE_PASS_ROWS;
     const size_t RT = (size_t)R * T;
@@ -272,7 +324,11 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
         if ((rc = prepare_pass(h, B, tokens + (size_t)r0 * T, c->tokens_on_device)) != FSMG_OK) return rc;
         Tiles tiles;
         AttendScratch as;
-        if (want_pc) {              // query q = b * T + t of the pass, in its row's group
+        SelfScratch ss;
+        if (want_pc && self) {
+            if ((rc = self_scratch(h, B, n, NT, false, &ss)) != FSMG_OK) return rc;
+            as.out = ss.out;
+        } else if (want_pc) {       // query q = b * T + t of the pass, in its row's group
             tiles = make_tiles(n, cache->G, [&](int q) { return group ? group[r0 + q / T] : 0; });
             if ((rc = attend_scratch(h, n, NT, tiles, false, &as)) != FSMG_OK) return rc;
         }
@@ -288,7 +344,12 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
         });
         if (rc != FSMG_OK) return rc;
         h->lastB = B;
-        if (want_pc && (rc = attend_launch(h, cache, tiles, as, n, h->Hs[h->L - 1], B, h->Y, c->thetas, NT)) != FSMG_OK) return rc;
+        if (want_pc && self) {      // row b's vector t: slot t + 1 of the time-major top-layer states; its value t: Y[t][b]
+            const float* hs1 = h->Hs[h->L - 1] + (size_t)B * h->Hp;
+            rc = self_launch(h, cache, ss, B, T, self->window, hs1, h->Hp, (long long)B * h->Hp, h->Y, 1, B, group ? group + r0 : nullptr,
+                             c->thetas, NT);
+            if (rc != FSMG_OK) return rc;
+        } else if (want_pc && (rc = attend_launch(h, cache, tiles, as, n, h->Hs[h->L - 1], B, h->Y, c->thetas, NT)) != FSMG_OK) return rc;
         const size_t o = (size_t)r0 * T;
         int err = 0;
         if (want_lp) HIPCK(h, hipMemcpyAsync(lp_host + o, d_lp, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
@@ -312,6 +373,8 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
             float* plane = out_logprob ? mix + ((size_t)k * NL + j) * RT : mix;
             const float* pc = pc_host + k * RT;
             for (size_t i = 0; i < RT; ++i) plane[i] = mix_logprob(lp_host[i], pc[i], l1m, ll);
+            if (self && !cache)         // position 0 of a row has an empty set: the model alone, at every lambda
+                for (size_t i = 0; i < RT; i += T) plane[i] = lp_host[i];
             if (!out_row_nll) continue;
             for (int r = 0; r < R; ++r) {
                 double s = 0.0;         // fp64, increasing t, rounded once: bitwise recomputable from out_logprob
@@ -325,9 +388,7 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
 }  // namespace
 
 // ---- cache-conditioned generation: the cache side (the decode driver in api_decode.hip calls these)
-int cache_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const int32_t* group, int64_t R, CacheGen* cg) {
-    fsmg_cache_s* c = find_cache(h, cache);
-    if (!c) return FSMG_ERR_INVALID;
+static int check_gen_cc(fsmg_model* h, const fsmg_cache_gen_config* cc, int64_t R) {
     if (!cc) return fail(h, FSMG_ERR_INVALID, "null fsmg_cache_gen_config");
     if (cc->version != FSMG_CACHE_GEN_CONFIG_VERSION)
         return fail(h, FSMG_ERR_INVALID, "fsmg_cache_gen_config.version is " + std::to_string(cc->version) + ", this library expects " +
@@ -337,6 +398,14 @@ int cache_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config
     if (!thetas_ok(&cc->theta, 1)) return fail(h, FSMG_ERR_INVALID, "theta must be finite and >= 0");
     if (!(cc->lambda >= 0.0f && cc->lambda <= 1.0f)) return fail(h, FSMG_ERR_INVALID, "lambda must lie in [0, 1]");
     if (R < 1 || R > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "the row count must be in [1, 2^20]");
+    return FSMG_OK;
+}
+
+int cache_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const int32_t* group, int64_t R, CacheGen* cg) {
+    fsmg_cache_s* c = find_cache(h, cache);
+    if (!c) return FSMG_ERR_INVALID;
+    const int rc0 = check_gen_cc(h, cc, R);
+    if (rc0 != FSMG_OK) return rc0;
     if (c->H != h->H || c->Hp != h->Hp) return fail(h, FSMG_ERR_INVALID, "the cache's hidden size is not the handle's");
     if (R * c->Mg > CACHE_GEN_MAX_SCORES) return fail(h, FSMG_ERR_INVALID, "rows * entries_per_group must be <= 2^26");
     if (group)
@@ -349,6 +418,27 @@ int cache_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config
     cg->tile_group = std::move(t.tile_group);
     cg->row_group.resize((size_t)R);
     for (int64_t r = 0; r < R; ++r) cg->row_group[r] = group ? group[r] : 0;
+    return FSMG_OK;
+}
+
+constexpr int64_t SELF_GEN_MAX_KEY_FLOATS = 1LL << 29;   // R * NP * Hp of one call (2 GiB of own keys)
+
+int cache_self_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_cache_self_config* sc,
+                         const int32_t* group, int64_t R, int64_t NP, bool raw, CacheGen* cg) {
+    int rc;
+    if (cache) {
+        if ((rc = cache_gen_check(h, cache, cc, group, R, cg)) != FSMG_OK) return rc;
+    } else {
+        if ((rc = check_gen_cc(h, cc, R)) != FSMG_OK) return rc;
+        cg->c = nullptr; cg->theta = cc->theta; cg->lambda = cc->lambda;
+        cg->R = (int)R; cg->ldl = (int)round_up(h->V1, 64);
+    }
+    if ((rc = check_self_config(h, sc)) != FSMG_OK) return rc;
+    if (NP < 1) NP = 1;
+    if (R * NP * h->Hp > SELF_GEN_MAX_KEY_FLOATS)
+        return fail(h, FSMG_ERR_INVALID, "rows * (primer_len + num) * Hp (Hp the padded hidden size) must be <= 2^29");
+    cg->W = sc->window; cg->Hp = h->Hp; cg->NP = (int)NP; cg->ldo = (int)std::min<int64_t>(sc->window, NP); cg->raw = raw;
+    if (R * cg->ldo > CACHE_GEN_MAX_SCORES) return fail(h, FSMG_ERR_INVALID, "rows * min(window, positions) must be <= 2^26");
     return FSMG_OK;
 }
 
@@ -407,16 +497,23 @@ int ensure_value_index(fsmg_model* h, fsmg_cache_s* c) {
 
 namespace {
 // [D R * Mg doubles | pc R * ldl floats | slot_query | tile_group | row_group], each 256-byte aligned
-struct CacheGenLayout { size_t o_D, o_pc, o_slot, o_tile, o_row, total; };
+struct CacheGenLayout { size_t o_D, o_pc, o_slot, o_tile, o_row, o_keys, o_D2, o_pm, o_len, o_val, total; };
 CacheGenLayout cache_gen_layout(const CacheGen& cg) {
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off = (size_t)round_up((int64_t)(off + bytes), 256); return o; };
     CacheGenLayout l{};
-    l.o_D = take(sizeof(double) * (size_t)cg.R * cg.c->Mg);
+    l.o_D = take(sizeof(double) * (size_t)cg.R * (cg.c ? cg.c->Mg : 0));
     l.o_pc = take(sizeof(float) * (size_t)cg.R * cg.ldl);
     l.o_slot = take(sizeof(int) * cg.slot_query.size());
     l.o_tile = take(sizeof(int) * cg.tile_group.size());
     l.o_row = take(sizeof(int) * cg.row_group.size());
+    if (cg.W > 0) {         // (behind everything else: without a self-cache the layout is what it was)
+        l.o_keys = take(sizeof(float) * (size_t)cg.R * cg.NP * cg.Hp);
+        l.o_D2 = take(sizeof(double) * (size_t)cg.R * cg.ldo);
+        l.o_pm = take(sizeof(double) * (size_t)cg.R * cg.ldl);
+        l.o_len = take(cg.raw ? sizeof(int) * (size_t)cg.R : 0);
+        l.o_val = take(cg.raw ? sizeof(int) * (size_t)cg.R * cg.NP : 0);
+    }
     l.total = off;
     return l;
 }
@@ -428,9 +525,52 @@ int cache_gen_place(fsmg_model* h, CacheGen& cg, char* base) {
     const CacheGenLayout l = cache_gen_layout(cg);
     cg.D = (double*)(base + l.o_D); cg.pc = (float*)(base + l.o_pc);
     cg.d_slot_query = (int*)(base + l.o_slot); cg.d_tile_group = (int*)(base + l.o_tile); cg.d_row_group = (int*)(base + l.o_row);
+    if (cg.W > 0) {
+        cg.own_keys = (float*)(base + l.o_keys); cg.D2 = (double*)(base + l.o_D2); cg.pm = (double*)(base + l.o_pm);
+        cg.d_len = (int*)(base + l.o_len); cg.d_val = (int*)(base + l.o_val);
+    }
+    if (!cg.c) return FSMG_OK;          // no support entries: no tiles
     HIPCK(h, hipMemcpyAsync(cg.d_slot_query, cg.slot_query.data(), sizeof(int) * cg.slot_query.size(), hipMemcpyHostToDevice, h->stream));
     HIPCK(h, hipMemcpyAsync(cg.d_tile_group, cg.tile_group.data(), sizeof(int) * cg.tile_group.size(), hipMemcpyHostToDevice, h->stream));
     HIPCK(h, hipMemcpyAsync(cg.d_row_group, cg.row_group.data(), sizeof(int) * cg.row_group.size(), hipMemcpyHostToDevice, h->stream));
+    return FSMG_OK;
+}
+
+int cache_self_file(fsmg_model* h, const CacheGen& cg, const float* h_out, int p) {
+    ScopedTimer tm(h, "self_file");
+    HIPCK(h, launch_self_file(h->stream, h_out, cg.R, h->H, h->Hp, cg.own_keys, cg.NP, p));
+    return FSMG_OK;
+}
+
+int cache_self_step(fsmg_model* h, const CacheGen& cg, int len, const float* Q, float* logits, const int* val, int ldv, float* out_lse) {
+    const fsmg_cache_s* c = cg.c;
+    if (c) {
+        CacheScoresArgs sa{};
+        sa.keys = c->keys; sa.Mg = c->Mg; sa.Hp = c->Hp; sa.Q = Q; sa.ldq = c->Hp;
+        sa.slot_query = cg.d_slot_query; sa.tile_group = cg.d_tile_group; sa.n_tiles = (int)cg.tile_group.size(); sa.D = cg.D;
+        ScopedTimer tm(h, "cache_scores");
+        HIPCK(h, launch_cache_scores(h->stream, sa));
+    }
+    const int* row_len = cg.raw ? cg.d_len : nullptr;
+    SelfScoresArgs ss{};
+    ss.own_keys = cg.own_keys; ss.NP = cg.NP; ss.Hp = h->Hp; ss.Q = Q; ss.ldq = h->Hp;
+    ss.row_len = row_len; ss.len = len; ss.W = cg.W; ss.D2 = cg.D2; ss.ldo = cg.ldo; ss.R = cg.R;
+    {
+        ScopedTimer tm(h, "self_scores");
+        HIPCK(h, launch_self_scores(h->stream, ss));
+    }
+    const double lam = (double)cg.lambda;
+    CacheMixSelfArgs ma{};
+    ma.m.logits = logits; ma.m.ldl = cg.ldl; ma.m.ncols = h->V1; ma.m.pc = cg.pc; ma.m.out_lse = out_lse;
+    if (c) {
+        ma.m.D = cg.D; ma.m.Mg = c->Mg; ma.m.row_group = cg.d_row_group;
+        ma.m.order = c->order; ma.m.seg_beg = c->seg_beg; ma.m.seg_end = c->seg_end; ma.m.seg_val = c->seg_val;
+        ma.m.n_seg = c->n_seg; ma.m.n_long = c->n_long;
+    }
+    ma.m.u = (double)cg.theta * CA_LOG2E; ma.m.log1m_lambda = std::log1p(-lam); ma.m.log_lambda = std::log(lam); ma.m.mix = cg.lambda > 0.0f;
+    ma.D2 = cg.D2; ma.ldo = cg.ldo; ma.val = val; ma.ldv = ldv; ma.row_len = row_len; ma.len = len; ma.W = cg.W; ma.pm = cg.pm;
+    ScopedTimer tm(h, "cache_mix_self");
+    HIPCK(h, launch_cache_mix_self(h->stream, cg.R, ma));
     return FSMG_OK;
 }
 
@@ -601,6 +741,65 @@ int fsmg_cache_distribution(fsmg_handle h, fsmg_cache cache, const fsmg_cache_ge
     return rc;
 }
 
+int fsmg_cache_self_distribution(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_cache_self_config* sc,
+                                 int32_t n, const float* queries, const float* logits, const float* self_keys, const int32_t* self_values,
+                                 const int32_t* self_len, int32_t S, const int32_t* group, float* out_cache_prob, float* out_logprob,
+                                 float* out_lse) {
+    if (!h) return FSMG_ERR_INVALID;
+    if (cache && !find_cache(h, cache)) return FSMG_ERR_INVALID;
+    if (n < 1 || n > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n must be in [1, 2^20]");
+    if (!queries || !logits || !self_len) return fail(h, FSMG_ERR_INVALID, "null queries / logits / self_len");
+    if (S < 0 || (S > 0 && (!self_keys || !self_values))) return fail(h, FSMG_ERR_INVALID, "S must be >= 0, with self_keys and self_values when S > 0");
+    if (!out_cache_prob && !out_logprob && !out_lse) return fail(h, FSMG_ERR_INVALID, "every output is null");
+    CacheGen cg;
+    int rc = cache_self_gen_check(h, cache, cc, sc, cache ? group : nullptr, n, S, true, &cg);
+    if (rc != FSMG_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        if (self_len[i] < 0 || self_len[i] > S) return fail(h, FSMG_ERR_INVALID, "self_len outside [0, S]");
+    for (size_t i = 0; i < (size_t)n * S; ++i)
+        if (self_values[i] < 0 || self_values[i] >= h->V1) return fail(h, FSMG_ERR_TOKEN_RANGE, "own value outside [0, input_size]");
+    BEGIN_CALL(h);
+    if (cg.c && (rc = ensure_value_index(h, const_cast<fsmg_cache_s*>(cg.c))) != FSMG_OK) return rc;
+    // [cache_gen's block | queries n x Hp | logits n x ldl | lse n]
+    const int Hp = h->Hp, ldl = cg.ldl, V1 = h->V1, NP = cg.NP;
+    const size_t o_q = (size_t)round_up((int64_t)cache_gen_bytes(h, cg), 256);
+    const size_t o_z = (size_t)round_up((int64_t)(o_q + sizeof(float) * (size_t)n * Hp), 256);
+    const size_t o_lse = (size_t)round_up((int64_t)(o_z + sizeof(float) * (size_t)n * ldl), 256);
+    if ((rc = gen_reserve(h, o_lse + sizeof(float) * (size_t)n)) != FSMG_OK) return rc;
+    float* d_q = (float*)(h->gen + o_q);
+    float* d_z = (float*)(h->gen + o_z);
+    float* d_lse = (float*)(h->gen + o_lse);
+    std::vector<float> qp((size_t)n * Hp, 0.0f), kp((size_t)n * NP * Hp, 0.0f);      // the pad units are exact zeros
+    std::vector<int> vp((size_t)n * NP, 0);
+    for (int q = 0; q < n; ++q) {
+        std::memcpy(qp.data() + (size_t)q * Hp, queries + (size_t)q * h->H, sizeof(float) * h->H);
+        for (int e = 0; e < S; ++e) {
+            std::memcpy(kp.data() + ((size_t)q * NP + e) * Hp, self_keys + ((size_t)q * S + e) * h->H, sizeof(float) * h->H);
+            vp[(size_t)q * NP + e] = self_values[(size_t)q * S + e];
+        }
+    }
+    auto run = [&]() -> int {
+        int r = cache_gen_place(h, cg, h->gen);
+        if (r != FSMG_OK) return r;
+        HIPCK(h, hipMemcpyAsync(d_q, qp.data(), sizeof(float) * qp.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCK(h, hipMemcpyAsync(cg.own_keys, kp.data(), sizeof(float) * kp.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCK(h, hipMemcpyAsync(cg.d_val, vp.data(), sizeof(int) * vp.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCK(h, hipMemcpyAsync(cg.d_len, self_len, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        HIPCK(h, hipMemcpy2DAsync(d_z, sizeof(float) * ldl, logits, sizeof(float) * V1, sizeof(float) * V1, n, hipMemcpyHostToDevice, h->stream));
+        if ((r = cache_self_step(h, cg, 0, d_q, d_z, cg.d_val, NP, d_lse)) != FSMG_OK) return r;
+        if (out_cache_prob)
+            HIPCK(h, hipMemcpy2DAsync(out_cache_prob, sizeof(float) * V1, cg.pc, sizeof(float) * ldl, sizeof(float) * V1, n, hipMemcpyDeviceToHost, h->stream));
+        if (out_logprob)
+            HIPCK(h, hipMemcpy2DAsync(out_logprob, sizeof(float) * V1, d_z, sizeof(float) * ldl, sizeof(float) * V1, n, hipMemcpyDeviceToHost, h->stream));
+        if (out_lse) HIPCK(h, hipMemcpyAsync(out_lse, d_lse, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        return FSMG_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(h->stream);       // the host vectors go out of scope
+    if (rc == FSMG_OK && e != hipSuccess) return fail(h, FSMG_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
+}
+
 int fsmg_cache_score(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const int32_t* tokens, const int32_t* group,
                      float* out_logprob, float* out_cache_prob, float* out_lstm_logprob, float* out_row_nll) {
     if (!h) return FSMG_ERR_INVALID;
@@ -611,6 +810,63 @@ int fsmg_cache_score(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_con
     if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
     return score_core(h, s, c, tokens, group, out_logprob, out_cache_prob, out_lstm_logprob, out_row_nll);
+}
+
+int fsmg_cache_self_score(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const fsmg_cache_self_config* sc,
+                          const int32_t* tokens, const int32_t* group, float* out_logprob, float* out_cache_prob,
+                          float* out_lstm_logprob, float* out_row_nll) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_cache_s* s = nullptr;
+    if (cache && !(s = find_cache(h, cache))) return FSMG_ERR_INVALID;
+    fsmg_cache_s shape;                 // (no support cache: the checks read a shape, and the groups are ignored)
+    shape.G = 1; shape.H = h->H; shape.Hp = h->Hp;
+    if (!s) group = nullptr;
+    const void* outs[4] = {out_logprob, out_cache_prob, out_lstm_logprob, out_row_nll};
+    int rc = check_score_config(h, s ? s : &shape, c, tokens, group, outs);
+    if (rc == FSMG_OK) rc = check_self_config(h, sc);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return score_core(h, s, c, tokens, group, out_logprob, out_cache_prob, out_lstm_logprob, out_row_nll, sc);
+}
+
+int fsmg_cache_self_attend(fsmg_handle h, fsmg_cache cache, const fsmg_cache_self_config* sc, int32_t n_rows, int32_t n_pos,
+                           const float* vectors, const int32_t* values, const int32_t* group, const float* thetas, int32_t n_theta,
+                           float* out_prob) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_cache_s* c = nullptr;
+    if (cache && !(c = find_cache(h, cache))) return FSMG_ERR_INVALID;
+    int rc = check_self_config(h, sc);
+    if (rc != FSMG_OK) return rc;
+    if (n_rows < 1 || n_pos < 1 || (int64_t)n_rows * n_pos > (1 << 22)) return fail(h, FSMG_ERR_INVALID, "n_rows, n_pos must be >= 1 and n_rows * n_pos <= 2^22");
+    if (!vectors || !values || !thetas || !out_prob) return fail(h, FSMG_ERR_INVALID, "null vectors / values / thetas / out_prob");
+    if (n_theta < 1 || n_theta > FSMG_CACHE_MAX_THETA) return fail(h, FSMG_ERR_INVALID, "n_theta must be in [1, 8]");
+    if (!thetas_ok(thetas, n_theta)) return fail(h, FSMG_ERR_INVALID, "every theta must be finite and >= 0");
+    if (c && (c->H != h->H || c->Hp != h->Hp)) return fail(h, FSMG_ERR_INVALID, "the cache's hidden size is not the handle's");
+    if (!c) group = nullptr;
+    if (group)
+        for (int r = 0; r < n_rows; ++r)
+            if (group[r] < 0 || group[r] >= c->G) return fail(h, FSMG_ERR_INVALID, "group id outside [0, groups of the cache)");
+    const int n = n_rows * n_pos;
+    for (int i = 0; i < n; ++i)
+        if (values[i] < 0 || values[i] >= h->V1) return fail(h, FSMG_ERR_TOKEN_RANGE, "value outside [0, input_size]");
+    BEGIN_CALL(h);
+    SelfScratch ss;
+    if ((rc = self_scratch(h, n_rows, n, n_theta, true, &ss)) != FSMG_OK) return rc;
+    const int Hp = h->Hp;
+    std::vector<float> vp((size_t)n * Hp, 0.0f);
+    for (int q = 0; q < n; ++q) std::memcpy(vp.data() + (size_t)q * Hp, vectors + (size_t)q * h->H, sizeof(float) * h->H);
+    auto run = [&]() -> int {
+        HIPCK(h, hipMemcpyAsync(ss.V, vp.data(), sizeof(float) * vp.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCK(h, hipMemcpyAsync(ss.val, values, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        const int r = self_launch(h, c, ss, n_rows, n_pos, sc->window, ss.V, (long long)n_pos * Hp, Hp, ss.val, n_pos, 1, group, thetas, n_theta);
+        if (r != FSMG_OK) return r;
+        HIPCK(h, hipMemcpyAsync(out_prob, ss.out, sizeof(float) * (size_t)n_theta * n, hipMemcpyDeviceToHost, h->stream));
+        return FSMG_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(h->stream);       // the host vector goes out of scope
+    if (rc == FSMG_OK && e != hipSuccess) return fail(h, FSMG_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
 }
 
 int fsmg_cache_eval_step(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q, float theta,

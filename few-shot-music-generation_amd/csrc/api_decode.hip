@@ -243,7 +243,11 @@ int generate_core(fsmg_model* h, const fsmg_gen_config* g, const fsmg_gen_filter
     for (int p = p0; p < d.P + d.num; ++p) {
         if ((rc = advance(h, d, p, p >= d.P)) != FSMG_OK) return rc;
         // the rows' queries: the top layer's h_out of this position, whose projection the logits are
-        if (p >= d.P && cg && (rc = cache_gen_step(h, *cg, d.h_out + (size_t)(h->L - 1) * d.R * h->Hp, d.logits, nullptr)) != FSMG_OK) return rc;
+        const float* top = d.h_out + (size_t)(h->L - 1) * d.R * h->Hp;
+        if (cg && cg->W > 0) {      // the self-cache: every position files its key, primer positions included; entry e's value is tok[e + 1]
+            if ((rc = cache_self_file(h, *cg, top, p)) != FSMG_OK) return rc;
+            if (p >= d.P && (rc = cache_self_step(h, *cg, p, top, d.logits, d.tok + 1, d.ldtok, nullptr)) != FSMG_OK) return rc;
+        } else if (p >= d.P && cg && (rc = cache_gen_step(h, *cg, d.h_out + (size_t)(h->L - 1) * d.R * h->Hp, d.logits, nullptr)) != FSMG_OK) return rc;
         if (p >= d.P)
             HIPCK(h, launch_gen_pick(h->stream, d.logits, d.ldl, h->V1, d.R, g->temperature, g->top_k, pick_f, g->seed, p - d.P,
                                      ctr0 + p - d.P, d.tok, d.ldtok, p + 1, d.out_tok, d.out_lp, d.num));
@@ -355,7 +359,7 @@ int check_state_generate(fsmg_model* h, const fsmg_dstate_s* s, const fsmg_gen_c
 int cache_generate_core(fsmg_model* h, CacheGen& cg, const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* primer,
                         int32_t* out_tokens, float* out_logprob, fsmg_dstate_s* st) {
     if (cg.lambda == 0.0f) return generate_core(h, g, f, primer, out_tokens, out_logprob, st);
-    int rc = ensure_value_index(h, const_cast<fsmg_cache_s*>(cg.c));
+    int rc = cg.c ? ensure_value_index(h, const_cast<fsmg_cache_s*>(cg.c)) : FSMG_OK;
     if (rc != FSMG_OK) return rc;
     rc = generate_core(h, g, f, primer, out_tokens, out_logprob, st, &cg);
     if (rc != FSMG_OK) hipStreamSynchronize(h->stream);
@@ -592,6 +596,21 @@ int fsmg_cache_generate(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_co
     if (rc == FSMG_OK) rc = check_gen_filters(h, f);
     CacheGen cg;
     if (rc == FSMG_OK) rc = cache_gen_check(h, cache, cc, group, g->n_seq, &cg);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return cache_generate_core(h, cg, g, f, primer, out_tokens, out_logprob, nullptr);
+}
+
+// the same with the row's own history in the set; cache may be null
+int fsmg_cache_self_generate(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_cache_self_config* sc,
+                             const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* group, const int32_t* primer,
+                             int32_t* out_tokens, float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    if (cache && !find_cache(h, cache)) return FSMG_ERR_INVALID;
+    int rc = check_gen_config(h, g, primer, out_tokens);
+    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    CacheGen cg;
+    if (rc == FSMG_OK) rc = cache_self_gen_check(h, cache, cc, sc, cache ? group : nullptr, g->n_seq, (int64_t)g->primer_len + g->num, false, &cg);
     if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
     return cache_generate_core(h, cg, g, f, primer, out_tokens, out_logprob, nullptr);

@@ -1,5 +1,5 @@
 // Support-set neural cache (include/fsmg.h fsmg_cache_*): the fused attention kernel and the kernel that files a pass's
-// top-layer hidden states into a cache.
+// top-layer hidden states into a cache; k_cache_attend_self, the causal sibling over a row's own history.
 //
 // k_cache_attend: p_cache(y) = sum_{i : v_i = y} exp(theta (d_i - d_max)) / sum_i exp(theta (d_i - d_max)), d_i = q . k_i over the
 // Mg keys of the query's group, for up to 8 values of theta in one pass over the keys.  One 256-thread workgroup owns a tile of 32
@@ -221,6 +221,171 @@ __global__ __launch_bounds__(256) void k_cache_attend(CacheAttendArgs a) {
         if (k < n_theta) a.out[(long long)k * a.n + q] = st.num[k] == 0.0 ? 0.0f : (float)(st.num[k] / st.den[k]);
 }
 
+// ---------------------------------------------------------------- self-cache (fsmg_kernels.h CacheSelfArgs)
+// ca_update with the tail rule kbase + 4 i < Mg generalised to a mask: bit i of `mask` says that score i of this lane counts for
+// this lane's query.  The arithmetic is ca_update's, statement by statement (k_cache_attend keeps its own copy and its bits).
+__device__ __forceinline__ void ca_update_masked(CaState& st, const f64x4& d, unsigned mask, const int v[4], int y, const double* u,
+                                                 int n_theta) {
+    double mt = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (mask >> i & 1u) mt = fmax(mt, d[i]);
+    if (mt > st.m) {
+#pragma unroll
+        for (int k = 0; k < CACHE_MAX_THETA; ++k)
+            if (k < n_theta) {
+                const double sc = ca_scale(u[k], st.m, mt);
+                st.den[k] *= sc; st.num[k] *= sc;
+            }
+        st.m = mt;
+    }
+#pragma unroll
+    for (int k = 0; k < CACHE_MAX_THETA; ++k) {
+        if (k >= n_theta) continue;
+        const double S = ceil(u[k] * st.m);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (!(mask >> i & 1u)) continue;            // a masked key has no mass
+            const double e = ca_exp2(fma(u[k], d[i], -S));
+            st.den[k] += e;
+            if (v[i] == y) st.num[k] += e;
+        }
+    }
+}
+
+// four floats at p, units c .. c + 3 of a vector of H: a pad unit reads as an exact zero whatever the memory holds
+__device__ __forceinline__ float4 ca_load4_h(const float* p, int c, int H) {
+    float4 v = *reinterpret_cast<const float4*>(p);
+    if (c + 0 >= H) v.x = 0.0f;
+    if (c + 1 >= H) v.y = 0.0f;
+    if (c + 2 >= H) v.z = 0.0f;
+    if (c + 3 >= H) v.w = 0.0f;
+    return v;
+}
+
+// one 16-key tile against the 32 queries in LDS, k_cache_attend's k order; PADS: the key's pad units are masked (a vector of the pass)
+template <bool PADS>
+__device__ __forceinline__ void ca_key_tile(const float* __restrict__ kp, const float* qp0, const float* qp1, int Hp, int H, int c0,
+                                            f64x4& acc0, f64x4& acc1) {
+    int k = 0;
+    for (; k + 32 <= Hp; k += 32) {
+        const float4 kv = PADS ? ca_load4_h(kp + k, c0 + k, H) : *reinterpret_cast<const float4*>(kp + k);
+        const float4 kw = PADS ? ca_load4_h(kp + k + 16, c0 + k + 16, H) : *reinterpret_cast<const float4*>(kp + k + 16);
+        const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k), c0v = *reinterpret_cast<const float4*>(qp0 + k + 16);
+        const float4 b1 = *reinterpret_cast<const float4*>(qp1 + k), c1v = *reinterpret_cast<const float4*>(qp1 + k + 16);
+        ca_mfma4(acc0, acc1, kv, b0, b1);
+        ca_mfma4(acc0, acc1, kw, c0v, c1v);
+    }
+    if (k < Hp) {
+        const float4 kv = PADS ? ca_load4_h(kp + k, c0 + k, H) : *reinterpret_cast<const float4*>(kp + k);
+        const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k);
+        const float4 b1 = *reinterpret_cast<const float4*>(qp1 + k);
+        ca_mfma4(acc0, acc1, kv, b0, b1);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cache_attend_self(CacheSelfArgs a) {
+    // k_cache_attend's LDS plan: the query tile, then the waves' partials over the same bytes
+    extern __shared__ double ca_lds[];
+    float* ca_q = reinterpret_cast<float*>(ca_lds);
+    CaMerge& mg = *reinterpret_cast<CaMerge*>(ca_lds);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int Hp = a.Hp, H = a.H, Mg = a.Mg, T = a.T, W = a.W, ldl = Hp + CA_PAD, n_theta = a.n_theta;
+    const int tiles_per_row = (T + CA_QT - 1) / CA_QT;
+    const int r = blockIdx.x / tiles_per_row, t0 = (blockIdx.x - r * tiles_per_row) * CA_QT;
+    const float* vr = a.V + (long long)r * a.vs_r;
+    const int* yr = a.val + (long long)r * a.ys_r;
+    double theta[CACHE_MAX_THETA];                  // u = theta log2(e)
+#pragma unroll
+    for (int k = 0; k < CACHE_MAX_THETA; ++k) theta[k] = (double)a.theta[k] * CA_LOG2E;
+
+    // positions t0 .. t0 + 31 of the row into LDS with their pad units zeroed; a position past the row's end as zeros
+    const int c4n = Hp >> 2;
+    for (int idx = tid; idx < CA_QT * c4n; idx += 256) {
+        const int s = idx / c4n, c4 = idx - s * c4n;
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (t0 + s < T) v = ca_load4_h(vr + (long long)(t0 + s) * a.vs_t + 4 * c4, 4 * c4, H);
+        *reinterpret_cast<float4*>(ca_q + s * ldl + 4 * c4) = v;
+    }
+    __syncthreads();
+
+    const int kq = lane & 15, ks = lane >> 4;
+    const int ta = t0 + kq, tb = t0 + 16 + kq;      // this lane's two positions
+    const int y0 = ta < T ? yr[(long long)ta * a.ys_t] : -1, y1 = tb < T ? yr[(long long)tb * a.ys_t] : -1;
+    CaState st0, st1;
+    const float* qp0 = ca_q + kq * ldl + 4 * ks;
+    const float* qp1 = qp0 + 16 * ldl;
+    // phase one: the group's support keys, every one visible to every position of the row (k_cache_attend's walk)
+    const int n_kt = (Mg + 15) >> 4;
+    if (Mg > 0) {
+        const int g = a.row_group ? a.row_group[r] : 0;
+        const float* kg = a.keys + (long long)g * Mg * Hp;
+        const int* vg = a.vals + (long long)g * Mg;
+        for (int kt = wave; kt < n_kt; kt += CA_WAVES) {
+            const int krow = min(kt * 16 + kq, Mg - 1);
+            f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+            ca_key_tile<false>(kg + (long long)krow * Hp + 4 * ks, qp0, qp1, Hp, H, 4 * ks, acc0, acc1);
+            const int kbase = kt * 16 + ks;
+            int v[4];
+            unsigned m = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                v[i] = vg[min(kbase + 4 * i, Mg - 1)];
+                if (kbase + 4 * i < Mg) m |= 1u << i;
+            }
+            ca_update_masked(st0, acc0, ta < T ? m : 0u, v, y0, theta, n_theta);
+            ca_update_masked(st1, acc1, tb < T ? m : 0u, v, y1, theta, n_theta);
+        }
+    }
+    // phase two: the row's own keys lo .. hi - 1, the only ones some position of this tile sees (key i is seen by position t when
+    // t - W <= i < t); own tile j goes to wave (n_kt + j) % 4, so the round robin goes on where the support keys left it
+    const int lo = max(0, t0 - W), hi = min(t0 + CA_QT - 1, T - 1);
+    const int n_ot = hi > lo ? (hi - lo + 15) >> 4 : 0;
+    for (int j = (wave + CA_WAVES - (n_kt & 3)) & 3; j < n_ot; j += CA_WAVES) {
+        // lane l loads own key row l % 16 of the tile (a tail row: key hi - 1, in bounds, masked below)
+        const int krow = min(lo + j * 16 + kq, hi - 1);
+        f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+        ca_key_tile<true>(vr + (long long)krow * a.vs_t + 4 * ks, qp0, qp1, Hp, H, 4 * ks, acc0, acc1);
+        const int kbase = lo + j * 16 + ks;
+        int v[4];
+        unsigned m0 = 0, m1 = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int ki = kbase + 4 * i;           // (ki >= hi is >= every position of the tile: never visible)
+            v[i] = yr[(long long)min(ki, hi - 1) * a.ys_t];
+            if (ta < T && ki < ta && ki >= ta - W) m0 |= 1u << i;
+            if (tb < T && ki < tb && ki >= tb - W) m1 |= 1u << i;
+        }
+        ca_update_masked(st0, acc0, m0, v, y0, theta, n_theta);
+        ca_update_masked(st1, acc1, m1, v, y1, theta, n_theta);
+    }
+    // k_cache_attend's merges: lanes 16 / 32 apart, then the four waves in order
+    ca_merge_lanes(st0, 16, theta, n_theta); ca_merge_lanes(st0, 32, theta, n_theta);
+    ca_merge_lanes(st1, 16, theta, n_theta); ca_merge_lanes(st1, 32, theta, n_theta);
+    __syncthreads();                                 // every wave is done with the query tile
+    if (ks == 0) {
+        mg.m[wave][kq] = st0.m; mg.m[wave][16 + kq] = st1.m;
+#pragma unroll
+        for (int k = 0; k < CACHE_MAX_THETA; ++k) {
+            mg.den[wave][k][kq] = st0.den[k]; mg.den[wave][k][16 + kq] = st1.den[k];
+            mg.num[wave][k][kq] = st0.num[k]; mg.num[wave][k][16 + kq] = st1.num[k];
+        }
+    }
+    __syncthreads();
+    if (tid >= CA_QT || t0 + tid >= T) return;
+    CaState st;                                      // waves 0, 1, 2, 3 in this order
+    for (int w = 0; w < CA_WAVES; ++w) {
+        double deno[CACHE_MAX_THETA], numo[CACHE_MAX_THETA];
+#pragma unroll
+        for (int k = 0; k < CACHE_MAX_THETA; ++k) { deno[k] = mg.den[w][k][tid]; numo[k] = mg.num[w][k][tid]; }
+        ca_merge(st, mg.m[w][tid], deno, numo, theta, n_theta);
+    }
+    const long long q = (long long)r * T + t0 + tid, n = (long long)a.n_rows * T;
+#pragma unroll
+    for (int k = 0; k < CACHE_MAX_THETA; ++k)
+        if (k < n_theta) a.out[k * n + q] = st.num[k] == 0.0 ? 0.0f : (float)(st.num[k] / st.den[k]);
+}
+
 // Hs1: slot 1 of the pass's top-layer hidden states, time-major [T][B][Hp]; Y [T][B].  Pass row b is row r0 + b of the cache's
 // [rows][T] entries (group-major: group = row / rows_per_group, entry = (row % rows_per_group) * T + t).  Pad units are written as zeros.
 __global__ __launch_bounds__(256) void k_cache_fill(const float* __restrict__ Hs1, const int* __restrict__ Y, int B, int T, int H, int Hp,
@@ -310,7 +475,63 @@ __global__ __launch_bounds__(64) void k_cache_scores(CacheScoresArgs a, int n_ch
     }
 }
 
+// ---------------------------------------------------------------- decode-time self-cache (fsmg_kernels.h)
+__global__ __launch_bounds__(256) void k_self_file(const float* __restrict__ h_out, int R, int H, int Hp, float* __restrict__ own_keys,
+                                                   int NP, int p) {
+    const int c4n = Hp >> 2;
+    const long long total = (long long)R * c4n;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const int r = (int)(idx / c4n), c4 = (int)(idx - (long long)r * c4n);
+        *reinterpret_cast<float4*>(own_keys + ((long long)r * NP + p) * Hp + 4 * c4) = ca_load4_h(h_out + (long long)r * Hp + 4 * c4, 4 * c4, H);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_self_scores(SelfScoresArgs a, int n_chunks) {
+    const int r = blockIdx.x / n_chunks, chunk = blockIdx.x - r * n_chunks;
+    const int len = a.row_len ? a.row_len[r] : a.len;
+    const int n = min(len, a.W), lo = len - n;
+    if (chunk * 16 >= n) return;                    // (wave-uniform)
+    const int lane = threadIdx.x, kq = lane & 15, ks = lane >> 4;
+    const int j = chunk * 16 + kq;
+    // a tail lane reads the row's last visible key, in bounds, and stores nothing
+    const float* kp = a.own_keys + ((long long)r * a.NP + lo + min(j, n - 1)) * a.Hp + 4 * ks;
+    const float* qp = a.Q + (long long)r * a.ldq + 4 * ks;
+    double acc = 0.0;
+    for (int k = 0; k < a.Hp; k += 16) {
+        const float4 kv = *reinterpret_cast<const float4*>(kp + k);
+        const float4 qv = *reinterpret_cast<const float4*>(qp + k);
+        acc = fma((double)kv.x, (double)qv.x, acc);
+        acc = fma((double)kv.y, (double)qv.y, acc);
+        acc = fma((double)kv.z, (double)qv.z, acc);
+        acc = fma((double)kv.w, (double)qv.w, acc);
+    }
+    acc += ca_shfl(acc, 16);                        // (0 + 1), (2 + 3)
+    acc += ca_shfl(acc, 32);                        // ((0 + 1) + (2 + 3)): the same bits in every lane of a key
+    if (ks == 0 && j < n) a.D2[(long long)r * a.ldo + j] = acc;
+}
+
 }  // namespace
+
+hipError_t launch_self_file(hipStream_t s, const float* h_out, int R, int H, int Hp, float* own_keys, int NP, int p) {
+    if (R <= 0) return hipSuccess;
+    if ((Hp & 3) != 0 || H < 1 || H > Hp || p < 0 || p >= NP) return hipErrorInvalidValue;
+    const long long total = (long long)R * (Hp >> 2);
+    hipLaunchKernelGGL(k_self_file, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, s, h_out, R, H, Hp, own_keys, NP, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_self_scores(hipStream_t s, const SelfScoresArgs& a) {
+    if (a.R <= 0) return hipSuccess;
+    const int cap = std::min(a.W, a.NP);
+    if (a.W < 1 || a.NP < 1 || a.Hp < 16 || (a.Hp & 15) != 0 || (a.ldq & 3) != 0 || a.ldo < cap || (!a.row_len && (a.len < 0 || a.len > a.NP)))
+        return hipErrorInvalidValue;
+    const int most = a.row_len ? cap : std::min(a.len, cap);       // the longest visible set of the call
+    const long long n_chunks = (most + 15) / 16;
+    if (n_chunks == 0) return hipSuccess;
+    if (n_chunks * a.R > 0x7FFFFFFFLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_self_scores, dim3((unsigned)(n_chunks * a.R)), dim3(64), 0, s, a, (int)n_chunks);
+    return hipGetLastError();
+}
 
 size_t cache_attend_lds_bytes(int Hp) { return std::max(sizeof(float) * (size_t)CA_QT * (Hp + CA_PAD), sizeof(CaMerge)); }
 
@@ -324,6 +545,21 @@ hipError_t launch_cache_attend(hipStream_t s, const CacheAttendArgs& a) {
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_cache_attend, dim3(a.n_tiles), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cache_attend_self(hipStream_t s, const CacheSelfArgs& a) {
+    if (a.n_rows <= 0 || a.T <= 0) return hipSuccess;
+    const long long tiles = (long long)a.n_rows * ((a.T + CA_QT - 1) / CA_QT);
+    if (a.Mg < 0 || a.Hp < 16 || (a.Hp & 15) != 0 || a.H < 1 || a.H > a.Hp || a.n_theta < 1 || a.n_theta > CACHE_MAX_THETA || a.W < 1 ||
+        (a.vs_r & 3) != 0 || (a.vs_t & 3) != 0 || tiles > 0x7FFFFFFFLL)
+        return hipErrorInvalidValue;
+    const size_t lds = cache_attend_lds_bytes(a.Hp);
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)k_cache_attend_self, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_cache_attend_self, dim3((unsigned)tiles), dim3(256), lds, s, a);
     return hipGetLastError();
 }
 

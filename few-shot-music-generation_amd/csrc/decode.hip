@@ -781,7 +781,101 @@ __global__ __launch_bounds__(PICK_THREADS) void k_cache_mix(CacheMixArgs a) {
     if (tid == 0 && a.out_lse) a.out_lse[b] = lse;
 }
 
+// k_cache_mix over the union of the support entries and the row's visible own entries (CacheMixSelfArgs' comment)
+__global__ __launch_bounds__(PICK_THREADS) void k_cache_mix_self(CacheMixSelfArgs s) {
+    __shared__ PickShared sh;
+    const CacheMixArgs& a = s.m;
+    const int b = blockIdx.x, tid = threadIdx.x, Mg = a.Mg, ncols = a.ncols;
+    float* row = a.logits + (long long)b * a.ldl;
+    float* pc = a.pc + (long long)b * a.ldl;
+    double* pm = s.pm + (long long)b * a.ldl;
+    double* d = Mg > 0 ? a.D + (long long)b * Mg : nullptr;
+    double* d2 = s.D2 + (long long)b * s.ldo;
+    const int len = s.row_len ? s.row_len[b] : s.len;
+    const int n = min(len, s.W), lo = len - n;
+    const int* val = s.val + (long long)b * s.ldv + lo;
+
+    float mx; int mi;
+    const float lse = row_max_lse<false>(sh, row, nullptr, ncols, mx, mi);
+
+    double m = -INFINITY;
+    for (int i = tid; i < Mg; i += PICK_THREADS) m = fmax(m, d[i]);
+    for (int i = tid; i < n; i += PICK_THREADS) m = fmax(m, d2[i]);
+    m = block_max(sh, m);
+    if (Mg == 0 && n == 0) {                        // the empty union: the model alone (block-uniform)
+        for (int v = tid; v < ncols; v += PICK_THREADS) { pc[v] = 0.0f; row[v] = row[v] - lse; }
+        if (tid == 0 && a.out_lse) a.out_lse[b] = lse;
+        return;
+    }
+    const double S = ceil(a.u * m);
+    double z = 0.0;
+    for (int i = tid; i < Mg; i += PICK_THREADS) {
+        const double w = ca_exp2(fma(a.u, d[i], -S));
+        d[i] = w;
+        z += w;
+    }
+    for (int i = tid; i < n; i += PICK_THREADS) {
+        const double w = ca_exp2(fma(a.u, d2[i], -S));
+        d2[i] = w;
+        z += w;
+    }
+    for (int v = tid; v < ncols; v += PICK_THREADS) pm[v] = 0.0;
+    const double Z = block_sum(sh, z);
+
+    if (Mg > 0) {                                   // k_cache_mix's walk of the value index, the masses kept in fp64
+        const int g = a.row_group[b];
+        const int* order = a.order + (long long)g * Mg;
+        const int* seg_beg = a.seg_beg + (long long)g * Mg;
+        const int* seg_end = a.seg_end + (long long)g * Mg;
+        const int* seg_val = a.seg_val + (long long)g * Mg;
+        const int n_seg = a.n_seg[g], n_long = a.n_long[g], lane = tid & 63;
+        for (int sg = tid >> 6; sg < n_long; sg += PICK_THREADS / 64) {
+            const int j1 = seg_end[sg];
+            double mass = 0.0;
+            for (int j = seg_beg[sg] + lane; j < j1; j += 64) mass += d[order[j]];
+            for (int o = 32; o > 0; o >>= 1) mass += __shfl_xor(mass, o);
+            if (lane == 0) pm[seg_val[sg]] = mass;
+        }
+        for (int sg = n_long + tid; sg < n_seg; sg += PICK_THREADS) {
+            const int j1 = seg_end[sg];
+            double mass = 0.0;
+            for (int j = seg_beg[sg]; j < j1; ++j) mass += d[order[j]];
+            pm[seg_val[sg]] = mass;
+        }
+    }
+    __syncthreads();
+    // the own entries: the first visible occurrence of a value owns its column and sums its later duplicates in entry order
+    for (int j = tid; j < n; j += PICK_THREADS) {
+        const int v = val[j];
+        bool first = v >= 0 && v < ncols;
+        for (int i = 0; i < j && first; ++i) first = val[i] != v;
+        if (!first) continue;
+        double mass = d2[j];
+        for (int i = j + 1; i < n; ++i)
+            if (val[i] == v) mass += d2[i];
+        pm[v] += mass;
+    }
+    __syncthreads();
+
+    for (int v = tid; v < ncols; v += PICK_THREADS) {
+        const double mass = pm[v];
+        const float lp = row[v] - lse, p = mass == 0.0 ? 0.0f : (float)(mass / Z);
+        pc[v] = p;
+        float out = lp;
+        if (a.mix) out = p == 0.0f ? (float)(a.log1m_lambda + (double)lp) : mix_logprob(lp, p, a.log1m_lambda, a.log_lambda);
+        row[v] = out;
+    }
+    if (tid == 0 && a.out_lse) a.out_lse[b] = lse;
+}
+
 }  // namespace
+
+hipError_t launch_cache_mix_self(hipStream_t s, int R, const CacheMixSelfArgs& a) {
+    if (R <= 0) return hipSuccess;
+    if (a.m.ncols <= 0 || a.m.ncols > a.m.ldl || a.m.Mg < 0 || a.W < 1 || a.ldo < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_cache_mix_self, dim3(R), dim3(PICK_THREADS), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_cache_mix(hipStream_t s, int R, const CacheMixArgs& a) {
     if (R <= 0) return hipSuccess;

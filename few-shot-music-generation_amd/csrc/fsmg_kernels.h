@@ -488,6 +488,30 @@ hipError_t launch_cache_attend(hipStream_t s, const CacheAttendArgs& a);
 hipError_t launch_cache_fill(hipStream_t s, const float* Hs1, const int* Y, int B, int T, int H, int Hp, long long r0, float* keys,
                              int* vals);
 
+// ---- self-cache (fsmg_cache_self_attend / fsmg_cache_self_score): position t of a row attends over its group's Mg
+// support entries (Mg == 0: none) and over the row's OWN entries i with t - W <= i < t, entry i = (key = the row's vector i, value =
+// the row's value i); the target of position t is the row's value t.  One softmax over the union, k_cache_attend's arithmetic:
+//   out[k * n_rows * T + r * T + t] = sum_{i visible, v_i = y_t} exp(theta_k (d_i - d_max)) / sum_{i visible} exp(theta_k (d_i - d_max)),
+// exactly 0 when no visible entry holds y_t or none is visible at all.  Row r's vector t is V + r * vs_r + t * vs_t (Hp floats: only
+// the first H are read as data, a pad unit of V may hold anything), its value t is val[r * ys_r + t * ys_t].
+// One workgroup owns CACHE_ATTEND_QT consecutive positions t0 .. t0 + 31 of one row: the support keys unmasked, then the own keys
+// max(0, t0 - W) .. min(t0 + 31, T - 1) - 1 in tiles of 16 under the per-(position, key) mask -- no other own key is walked.  A
+// masked key is skipped, not scored as zero.  No atomics, fixed merge order: a position's bits depend on its row's vectors and values
+// 0 .. t, its group's entries, theta and W alone, not on n_rows or the other rows.  No allocation, no synchronisation.
+struct CacheSelfArgs {
+    const float* keys;          // [G][Mg][Hp], pad units exact zeros; unused at Mg == 0
+    const int* vals;            // [G][Mg]
+    int Mg;                     // 0: no support cache
+    const int* row_group;       // [n_rows], or nullptr: all 0
+    int H, Hp;
+    const float* V; long long vs_r, vs_t;       // multiples of 4 floats
+    const int* val; long long ys_r, ys_t;
+    int n_rows, T, W;           // W >= 1
+    float theta[CACHE_MAX_THETA]; int n_theta;  // theta >= 0
+    float* out;                 // [n_theta][n_rows * T]
+};
+hipError_t launch_cache_attend_self(hipStream_t s, const CacheSelfArgs& a);
+
 // ---- cache-conditioned generation (fsmg_cache_generate / fsmg_cache_distribution): the WHOLE mixed next-token
 // distribution of R decode rows at one position, in two launches.  No allocation, no synchronisation, no atomics.
 // Stage one (cache.hip), the raw scores: D[r][i] = Q_r . keys[g_r][i] for every key i < Mg of row r's group, k_cache_attend's
@@ -534,5 +558,39 @@ struct CacheMixArgs {
     int mix;                            // lambda > 0
 };
 hipError_t launch_cache_mix(hipStream_t s, int R, const CacheMixArgs& a);
+
+// ---- decode-time self-cache (fsmg_cache_self_generate / fsmg_cache_self_distribution).  Row r keeps its own keys in
+// own_keys[r][0 .. NP)[Hp] (pad units exact zeros); with len_r entries filed (row_len[r], or `len` for every row when row_len is
+// null) it sees the last n_r = min(len_r, W) of them, entries lo_r = len_r - n_r .. len_r - 1; the value of own entry e is
+// val[r * ldv + e] (generation: the token buffer shifted by one, the token that followed input e).  No allocation, no atomics.
+// launch_self_file: the top layer's h_out [R][Hp] of position p into own_keys[r][p], units >= H as zeros.
+hipError_t launch_self_file(hipStream_t s, const float* h_out, int R, int H, int Hp, float* own_keys, int NP, int p);
+// launch_self_scores: D2[r * ldo + j] = Q_r . own_keys[r][lo_r + j], j < n_r: fp32 inputs widened exactly, every product exact in
+// fp64, fp64 accumulation in one fixed order (one wave per 16 keys: lane l takes key l % 16 and the units 16 i + 4 (l / 16) .. + 3 in
+// increasing i, the four partial sums of a key are added as (0 + 1) + (2 + 3)).  A score's bits depend on the two vectors alone.
+struct SelfScoresArgs {
+    const float* own_keys; int NP, Hp;
+    const float* Q; int ldq;            // row r's query: Q + r * ldq (Hp floats, the pad units finite)
+    const int* row_len; int len, W;
+    double* D2; int ldo;                // ldo >= min(W, NP)
+    int R;
+};
+hipError_t launch_self_scores(hipStream_t s, const SelfScoresArgs& a);
+// launch_cache_mix_self: k_cache_mix over the UNION of the row's group's Mg support entries (Mg == 0: none; scores in D, values through
+// the value index) and its n_r visible own entries (scores in D2, values in val): one exact maximum d_max and ONE shift
+// S = ceil(u d_max) over both, w_i = ca_exp2(u d_i - S), Z = the sum of all of them over a tree that depends on Mg and n_r alone.
+// Masses: the support segments as k_cache_mix sums them, into pm[r][v] (fp64); then the own entries, whose values change every
+// step, scattered on the device without atomics: the thread of own entry j adds to pm[v_j] only if no earlier visible own entry
+// holds v_j, and then the masses of j and of its later duplicates in entry order.  pc[v] = fl32(pm[v] / Z), exactly 0 for a column
+// no entry holds; z'' as k_cache_mix.  An empty union (Mg == 0 and n_r == 0): pc = 0 and the row becomes lp_v = fl32(z_v - lse)
+// whatever lambda is.  A row's bits depend on its logits row, its scores, its entries' values, theta and lambda alone.
+struct CacheMixSelfArgs {
+    CacheMixArgs m;                     // Mg == 0: D, row_group and the value index are not read
+    double* D2; int ldo;                // own scores in, masses out (written over)
+    const int* val; int ldv;
+    const int* row_len; int len, W;
+    double* pm;                         // [R][m.ldl]
+};
+hipError_t launch_cache_mix_self(hipStream_t s, int R, const CacheMixSelfArgs& a);
 
 }  // namespace fsmg

@@ -634,7 +634,21 @@ struct CacheGen {
     int *d_slot_query = nullptr, *d_tile_group = nullptr, *d_row_group = nullptr;
     double* D = nullptr;                                    // [R][Mg]
     float* pc = nullptr;                                    // [R][ldl]
+    // the self-cache beside it (W > 0; c may then be null: no support entries): NP positions of own keys per row, ldo = min(W, NP)
+    int W = 0, NP = 0, ldo = 0, Hp = 0;
+    bool raw = false;                                       // fsmg_cache_self_distribution: per-row lengths and values from the host
+    float* own_keys = nullptr;                              // [R][NP][Hp]
+    double* D2 = nullptr;                                   // [R][ldo]
+    double* pm = nullptr;                                   // [R][ldl]
+    int *d_len = nullptr, *d_val = nullptr;                 // raw: [R], [R][NP]
 };
+// fsmg_cache_self_generate / _distribution: cache_gen_check (cache may be null) plus the self config and the scratch bounds
+int cache_self_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_cache_self_config* sc,
+                         const int32_t* group, int64_t R, int64_t NP, bool raw, CacheGen* cg);
+// position p of a generate call: the top layer's h_out [R][Hp] becomes own entry p of every row
+int cache_self_file(fsmg_model* h, const CacheGen& cg, const float* h_out, int p);
+// the launches at one position over the union: len own entries filed per row (raw: cg.d_len), own entry e of row r holds val[r * ldv + e]
+int cache_self_step(fsmg_model* h, const CacheGen& cg, int len, const float* Q, float* logits, const int* val, int ldv, float* out_lse);
 // the argument checks (no device work): config, cache against the handle, group ids, the R * Mg limit; fills cg's host side
 int cache_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const int32_t* group, int64_t R, CacheGen* cg);
 int ensure_value_index(fsmg_model* h, fsmg_cache_s* c);    // outside the token loop: allocates and synchronises on first use

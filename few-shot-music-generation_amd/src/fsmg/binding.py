@@ -114,6 +114,13 @@ class FsmgCacheGenConfig(C.Structure):
     _fields_ = [('version', C.c_int32), ('theta', C.c_float), ('lambda_', C.c_float), ('reserved', C.c_int32 * 13)]
 
 
+FSMG_CACHE_SELF_CONFIG_VERSION = 1
+
+
+class FsmgCacheSelfConfig(C.Structure):
+    _fields_ = [('version', C.c_int32), ('window', C.c_int32), ('reserved', C.c_int32 * 14)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -191,6 +198,14 @@ SIGNATURES = {
     'fsmg_dstate_cache_generate': (C.c_int, [_P, _P, _P, C.POINTER(FsmgCacheGenConfig), C.POINTER(FsmgGenConfig),
                                              C.POINTER(FsmgGenFilters), _I32P, _I32P, _F32P]),
     'fsmg_cache_distribution': (C.c_int, [_P, _P, C.POINTER(FsmgCacheGenConfig), C.c_int32, _F32P, _F32P, _I32P, _F32P, _F32P, _F32P]),
+    'fsmg_cache_self_score': (C.c_int, [_P, _P, C.POINTER(FsmgCacheScoreConfig), C.POINTER(FsmgCacheSelfConfig), _P, _I32P, _F32P, _F32P,
+                                        _F32P, _F32P]),
+    'fsmg_cache_self_attend': (C.c_int, [_P, _P, C.POINTER(FsmgCacheSelfConfig), C.c_int32, C.c_int32, _F32P, _I32P, _I32P, _F32P, C.c_int32,
+                                         _F32P]),
+    'fsmg_cache_self_generate': (C.c_int, [_P, _P, C.POINTER(FsmgCacheGenConfig), C.POINTER(FsmgCacheSelfConfig), C.POINTER(FsmgGenConfig),
+                                           C.POINTER(FsmgGenFilters), _I32P, _P, _I32P, _F32P]),
+    'fsmg_cache_self_distribution': (C.c_int, [_P, _P, C.POINTER(FsmgCacheGenConfig), C.POINTER(FsmgCacheSelfConfig), C.c_int32, _F32P, _F32P,
+                                               _F32P, _I32P, _I32P, C.c_int32, _I32P, _F32P, _F32P, _F32P]),
     'fsmg_read_losses': (C.c_int, [_P, _F32P, C.c_int32]),
     'fsmg_get_stats': (C.c_int, [_P, C.POINTER(FsmgStats)]),
     'fsmg_debug_read': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
@@ -1009,6 +1024,97 @@ class FsmgModel(object):
         self._ck(self._lib.fsmg_cache_distribution(self._h, cache._ptr(), C.byref(cc), n, _f32p(q), _f32p(z),
                                                    g.ctypes.data_as(_I32P) if g is not None else None, _f32p(out['cache_prob']),
                                                    _f32p(out['logprob']), _f32p(out['lse'])))
+        return out
+
+    # -- self-cache (include/fsmg.h fsmg_cache_self_*) -------------------------------------------------------------
+    @staticmethod
+    def cache_self_config(window):
+        return FsmgCacheSelfConfig(version=FSMG_CACHE_SELF_CONFIG_VERSION, window=int(window))
+
+    def cache_self_attend(self, vectors, values, thetas, window, cache=None, group=None):
+        """p_cache of given rows under the self-cache: vectors float32 [n_rows, n_pos, H], values int32 [n_rows, n_pos] -- values[r,
+        t] is the target of position t and the value of the row's own entry t.  Position t attends over its row's own entries
+        max(0, t - window) .. t - 1 and, with a cache, over group group[r] of it (None: group 0), in one softmax -> float32
+        [n_theta, n_rows, n_pos]; exactly 0 where no visible entry holds the target, position 0 without a cache included."""
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        y = np.ascontiguousarray(values, dtype=np.int32)
+        th = np.atleast_1d(np.ascontiguousarray(thetas, dtype=np.float32))
+        if v.ndim != 3 or v.shape[2] != int(self.cfg.hidden_size) or y.shape != v.shape[:2]:
+            raise ValueError('vectors must be [n_rows, n_pos, %d] and values [n_rows, n_pos], got %r and %r'
+                             % (int(self.cfg.hidden_size), v.shape, y.shape))
+        g = self._group(group, v.shape[0])
+        sc = self.cache_self_config(window)
+        out = np.empty((th.size,) + y.shape, np.float32)
+        self._ck(self._lib.fsmg_cache_self_attend(self._h, cache._ptr() if cache is not None else None, C.byref(sc), v.shape[0], v.shape[1],
+                                                  _f32p(v), y.ctypes.data_as(_I32P), g.ctypes.data_as(_I32P) if g is not None else None,
+                                                  _f32p(th), th.size, _f32p(out)))
+        return out
+
+    def cache_self_score(self, tokens, thetas, lambdas, window, cache=None, group=None, logprob=True, cache_prob=False,
+                         lstm_logprob=False, row_nll=True, nll_first=0, nll_count=0, pass_rows=0, n_rows=None):
+        """cache_score() with every song's own history in the set: position t also attends over the hidden states of its own
+        positions max(0, t - window) .. t - 1, each with the token that followed.  cache=None: the own history alone (group is then
+        ignored; position 0 is scored by the model alone).  The keywords and the result are cache_score's."""
+        tp, dev, _keep, R = self._rows(tokens, n_rows)
+        c = self.cache_score_config(R, thetas, lambdas, nll_first, nll_count, pass_rows, dev)
+        sc = self.cache_self_config(window)
+        g = self._group(group, R)
+        T, NT, NL = self.max_len, c.n_theta, c.n_lambda
+        out = {}
+        if logprob:
+            out['logprob'] = np.empty((NT, NL, R, T), np.float32)
+        if cache_prob:
+            out['cache_prob'] = np.empty((NT, R, T), np.float32)
+        if lstm_logprob:
+            out['lstm_logprob'] = np.empty((R, T), np.float32)
+        if row_nll:
+            out['row_nll'] = np.empty((NT, NL, R), np.float32)
+        f = lambda k: _f32p(out[k]) if k in out else None
+        self._ck(self._lib.fsmg_cache_self_score(self._h, cache._ptr() if cache is not None else None, C.byref(c), C.byref(sc), tp,
+                                                 g.ctypes.data_as(_I32P) if g is not None else None, f('logprob'), f('cache_prob'),
+                                                 f('lstm_logprob'), f('row_nll')))
+        return out
+
+    def cache_self_generate(self, n_seq, num, theta, lam, window, cache=None, group=None, temperature=1.0, top_k=0, seed=0, primer=None,
+                            logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
+        """cache_generate() with every row's own history in the set: at a generated position p the row also attends over the hidden
+        states of its own positions max(0, p - window) .. p - 1 (primer positions included), each with the token that followed.
+        cache=None: the own history alone (group is then ignored).  lam = 0 is generate() bitwise.  No decode-state variant."""
+        n_seq, num = int(n_seq), int(num)
+        cc, sc = self.cache_gen_config(theta, lam), self.cache_self_config(window)
+        g = self._group(group, n_seq)
+        gp = g.ctypes.data_as(_I32P) if g is not None else None
+        f = self.gen_filters(top_p, min_p, repetition_penalty, repeat_window)
+        fp = C.byref(f) if f is not None else None
+        toks = np.empty((n_seq, num), np.int32)
+        lp = np.empty((n_seq, num), np.float32) if logprobs else None
+        gc, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
+        self._ck(self._lib.fsmg_cache_self_generate(self._h, cache._ptr() if cache is not None else None, C.byref(cc), C.byref(sc),
+                                                    C.byref(gc), fp, gp, pp, toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None))
+        return (toks, lp) if logprobs else toks
+
+    def cache_self_distribution(self, queries, logits, self_keys, self_values, self_len, theta, lam, window, cache=None, group=None):
+        """cache_distribution() over the union: row i also sees the last min(self_len[i], window) of its self_len[i] own entries
+        (self_keys float32 [n, S, H], self_values int32 [n, S], self_len int32 [n], each in [0, S]).  An empty union (no cache,
+        self_len 0) gives cache_prob 0 and logprob = the model's log-probabilities whatever lam is."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        z = np.ascontiguousarray(logits, dtype=np.float32)
+        k = np.ascontiguousarray(self_keys, dtype=np.float32)
+        v = np.ascontiguousarray(self_values, dtype=np.int32)
+        ln = np.ascontiguousarray(self_len, dtype=np.int32)
+        H, V1 = int(self.cfg.hidden_size), int(self.cfg.input_size) + 1
+        if q.ndim != 2 or q.shape[1] != H or z.shape != (q.shape[0], V1):
+            raise ValueError('queries must be [n, %d] and logits [n, %d], got %r and %r' % (H, V1, q.shape, z.shape))
+        n = q.shape[0]
+        if k.ndim != 3 or k.shape[0] != n or k.shape[2] != H or v.shape != k.shape[:2] or ln.shape != (n,):
+            raise ValueError('self_keys must be [n, S, %d], self_values [n, S] and self_len [n], got %r, %r and %r' % (H, k.shape, v.shape, ln.shape))
+        g = self._group(group, n)
+        cc, sc = self.cache_gen_config(theta, lam), self.cache_self_config(window)
+        out = dict(cache_prob=np.empty((n, V1), np.float32), logprob=np.empty((n, V1), np.float32), lse=np.empty(n, np.float32))
+        self._ck(self._lib.fsmg_cache_self_distribution(self._h, cache._ptr() if cache is not None else None, C.byref(cc), C.byref(sc), n,
+                                                        _f32p(q), _f32p(z), _f32p(k), v.ctypes.data_as(_I32P), ln.ctypes.data_as(_I32P),
+                                                        k.shape[1], g.ctypes.data_as(_I32P) if g is not None else None,
+                                                        _f32p(out['cache_prob']), _f32p(out['logprob']), _f32p(out['lse'])))
         return out
 
     def read_losses(self, n):

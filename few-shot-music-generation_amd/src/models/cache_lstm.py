@@ -9,6 +9,10 @@ attends over its artist's entries, and the resulting distribution is mixed with 
     p(y) = (1 - cache_lambda) p_lstm(y) + cache_lambda p_cache(y),   p_cache = softmax(cache_theta q . k) mass on the entries holding y
 
 Config keys beyond LSTMBaseline's: cache_theta (sharpness, >= 0) and cache_lambda (mixing weight in [0, 1]; 0 is the baseline).
+Optional: cache_self (default false) adds every song's OWN history to the set it attends over -- the hidden states of its earlier
+positions, each with the token that followed (include/fsmg.h fsmg_cache_self_*): one softmax over the union, the same theta and
+lambda -- and cache_window (default max_len) is how many of its own last positions a position sees.  With cache_self unset every
+path below is what it was, bit for bit.
 
   generate(..., cache=True)  LSTMBaseline.generate's rows drawn from the mixture: every generated token attends over ONE cache group
                        built from the whole support set (fsmg_cache_generate); the default (cache=False) is the baseline's generate
@@ -16,6 +20,10 @@ Config keys beyond LSTMBaseline's: cache_theta (sharpness, >= 0) and cache_lambd
   eval_many(episodes)  one call per episode
   score(s, songs)      builds a one-group cache from the support set and scores the songs against it
   tune(episodes, thetas, lambdas)  the [n_theta][n_lambda] grid of mean NLLs, one device pass per episode for the whole grid
+  score_self(songs)    the songs under the pure self-cache: no support set at all
+
+With cache_self set, eval, score, tune and generate(cache=True) use the union; generate(self_cache=True) draws from the rows' own
+history alone and needs no support set.
 """
 import numpy as np
 
@@ -23,6 +31,9 @@ from models.lstm_baseline import LSTMBaseline
 
 
 class CacheLSTM(LSTMBaseline):
+    _self = False               # the defaults of the optional keys: the own history stays out of the set
+    _window = None              # None: max_len
+
     def __init__(self, config):
         for key in ('cache_theta', 'cache_lambda'):
             if key not in config:
@@ -32,7 +43,11 @@ class CacheLSTM(LSTMBaseline):
             raise RuntimeError('cache_theta must be finite and >= 0, got %r' % config['cache_theta'])
         if not 0.0 <= self._lambda <= 1.0:
             raise RuntimeError('cache_lambda must lie in [0, 1], got %r' % config['cache_lambda'])
+        self._self = bool(config.get('cache_self', False))
+        if 'cache_window' in config and int(config['cache_window']) < 1:
+            raise RuntimeError('cache_window must be >= 1, got %r' % config['cache_window'])
         super(CacheLSTM, self).__init__(config)
+        self._window = int(config.get('cache_window', self._time_steps))
 
     def _episode(self, episode):
         support, query = self._tokens(episode.support, 3), self._tokens(episode.query, 3)
@@ -43,7 +58,10 @@ class CacheLSTM(LSTMBaseline):
     def eval(self, episode):
         self._require_init()
         support, query = self._episode(episode)
-        nll = self._model.cache_eval_step(support, query, self._theta, self._lambda)
+        if self._self:
+            nll = float(self._grid(support, query, [self._theta], [self._lambda])[0, 0])
+        else:
+            nll = self._model.cache_eval_step(support, query, self._theta, self._lambda)
         self._log_scalar('Eval/Avg_NLL', nll, self._eval_calls)
         self._eval_calls += 1
         return nll
@@ -58,28 +76,65 @@ class CacheLSTM(LSTMBaseline):
         cache_prob=True, lstm_logprob=True).  Keywords: FsmgModel.cache_score's."""
         self._require_init()
         cache = self._model.cache_build(support_set, n_groups=1)
+        thetas, lambdas = self._theta if thetas is None else thetas, self._lambda if lambdas is None else lambdas
         try:
-            return self._model.cache_score(cache, songs, self._theta if thetas is None else thetas,
-                                           self._lambda if lambdas is None else lambdas, **kw)
+            if self._self:
+                return self._model.cache_self_score(songs, thetas, lambdas, self._window, cache=cache, **kw)
+            return self._model.cache_score(cache, songs, thetas, lambdas, **kw)
         finally:
             cache.close()
 
-    def generate(self, support_set, num, n=1, cache=False, **kw):
-        """LSTMBaseline.generate (its keywords; cache=False: exactly it).  cache=True: a one-group cache is built from the whole
-        support set (int32 [.., max_len]), every generated token is drawn from the mixture at the configured cache_theta and
-        cache_lambda, and the cache is closed.  With condition_on_support=True the rows also start from a decode state primed on the
-        support songs.  The log-probs (logprobs=True) are the mixture's."""
-        if not cache:
+    def score_self(self, songs, thetas=None, lambdas=None, window=None, **kw):
+        """score() without a support set: every song attends over its own history alone (its last `window` positions; default the
+        configured cache_window).  Works whether or not cache_self is set.  Position 0, which has no history, is scored by the model."""
+        self._require_init()
+        return self._model.cache_self_score(songs, self._theta if thetas is None else thetas, self._lambda if lambdas is None else lambdas,
+                                            self._window if window is None else window, **kw)
+
+    def _own_window(self):
+        return self._time_steps if self._window is None else self._window
+
+    def _grid(self, support, query, thetas, lambdas):
+        """float64 [n_theta, n_lambda]: one episode's mean query NLL at every pair, artist a's songs over artist a's entries"""
+        N, Q, T = query.shape
+        cache = self._model.cache_build(support, n_groups=N)
+        try:
+            group = np.repeat(np.arange(N), Q)
+            if self._self:
+                lp = self._model.cache_self_score(query, thetas, lambdas, self._window, cache=cache, group=group, row_nll=False)['logprob']
+            else:
+                lp = self._model.cache_score(cache, query, thetas, lambdas, group=group, row_nll=False)['logprob']
+        finally:
+            cache.close()
+        return -lp.astype(np.float64).mean(axis=(2, 3))
+
+    def generate(self, support_set, num, n=1, cache=False, self_cache=False, **kw):
+        """LSTMBaseline.generate (its keywords; cache=False and self_cache=False: exactly it).  cache=True: a one-group cache is
+        built from the whole support set (int32 [.., max_len]), every generated token is drawn from the mixture at the configured
+        cache_theta and cache_lambda, and the cache is closed; with the config's cache_self set the rows' own history (the last
+        cache_window positions, primer included) joins the set, as in eval, score and tune.  self_cache=True: the own history is in
+        the set whatever the config says, and with cache=False it is the whole set -- the support set may then be empty (primer_len
+        0).  The union has no decode-state variant: condition_on_support=True is refused with it.  With cache=True and no self-cache,
+        condition_on_support=True also starts the rows from a decode state primed on the support songs.  The log-probs
+        (logprobs=True) are the mixture's."""
+        if not cache and not self_cache:
             return super(CacheLSTM, self).generate(support_set, num, n=n, **kw)
         self._require_init()
+        own = self_cache or self._self
+        if own and kw.get('condition_on_support'):
+            raise ValueError('the self-cache has no decode-state variant: condition_on_support=True cannot be combined with it')
         songs = np.ascontiguousarray(support_set, dtype=np.int32).reshape(-1, self._time_steps)
-        built = self._model.cache_build(songs, n_groups=1)
+        built = self._model.cache_build(songs, n_groups=1) if cache else None
+        if own:
+            draw = lambda n_seq, count, **g: self._model.cache_self_generate(n_seq, count, self._theta, self._lambda, self._own_window(),
+                                                                             cache=built, **g)
+        else:
+            draw = lambda n_seq, count, **g: self._model.cache_generate(built, n_seq, count, self._theta, self._lambda, **g)
         try:
-            return super(CacheLSTM, self).generate(
-                support_set, num, n=n, _draw=lambda n_seq, count, **g: self._model.cache_generate(built, n_seq, count, self._theta,
-                                                                                               self._lambda, **g), **kw)
+            return super(CacheLSTM, self).generate(support_set, num, n=n, _draw=draw, **kw)
         finally:
-            built.close()
+            if built is not None:
+                built.close()
 
     def tune(self, episodes, thetas, lambdas):
         """float64 [n_theta, n_lambda]: the mean over the episodes of the query NLL at every (theta, lambda) -- what eval would
@@ -88,13 +143,7 @@ class CacheLSTM(LSTMBaseline):
         total, count = None, 0
         for e in episodes:
             support, query = self._episode(e)
-            N, Q, T = query.shape
-            cache = self._model.cache_build(support, n_groups=N)
-            try:
-                lp = self._model.cache_score(cache, query, thetas, lambdas, group=np.repeat(np.arange(N), Q), row_nll=False)['logprob']
-            finally:
-                cache.close()
-            nll = -lp.astype(np.float64).mean(axis=(2, 3))
+            nll = self._grid(support, query, thetas, lambdas)
             total = nll if total is None else total + nll
             count += 1
         if count == 0:

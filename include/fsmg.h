@@ -603,8 +603,8 @@ int fsmg_cache_eval_step(fsmg_handle h, const int32_t* support, const int32_t* q
  * [0, G), n < 1 or n > 2^20, rows * Mg > 2^26 (the fp64 score scratch), every output NULL, NULL queries / logits, and everything
  * fsmg_generate_filtered / fsmg_dstate_generate refuse; FSMG_ERR_TOKEN_RANGE as they return it.  Argument errors are found before any
  * device work: outputs and states are untouched.
- * Out of scope: beam search over the mixture; a self-cache over the row's own history; caches or states at MAML's theta'; several
- * thetas per call. */
+ * Out of scope: beam search over the mixture; the row's own history in the set (fsmg_cache_self_generate has it); caches or states
+ * at MAML's theta'; several thetas per call. */
 #define FSMG_CACHE_GEN_CONFIG_VERSION 1
 #define FSMG_CACHE_GEN_CHUNK 16
 typedef struct fsmg_cache_gen_config {
@@ -626,6 +626,80 @@ int fsmg_dstate_cache_generate(fsmg_handle h, fsmg_dstate st, fsmg_cache cache, 
    outputs, any may be NULL but not all: out_cache_prob [n][V1], out_logprob [n][V1] (z''), out_lse [n] */
 int fsmg_cache_distribution(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, int32_t n, const float* queries,
                             const float* logits, const int32_t* group, float* out_cache_prob, float* out_logprob, float* out_lse);
+
+/* ---- self-cache (DESIGN.md "Self-cache"): the continuous cache of Grave, Joulin and Usunier over the sequence's OWN history.  It
+ * needs no support set; with one, the own entries join the group's entries in ONE softmax.
+ * A row is read exactly as fsmg_score reads it: the inputs are [start, x_0 .. x_{T-2}], q_t is the top-layer h after input t (the
+ * vector whose projection is the logits row at t), the target is y_t = x_t.
+ *   own entries  own entry i of a row is (key = q_i, value = x_i): the entry fsmg_cache_build would file for that row at position i.
+ *   window       with window W >= 1, position t sees its own entries max(0, t - W) .. t - 1.  Strictly causal: entry t itself, whose
+ *                value is the target, is never visible.
+ *   union        with a support cache the row's group's Mg entries are added; one softmax over the union, one theta, one lambda:
+ *                  d_i = q_t . k_i,  p_cache(y) = sum_{i in set, v_i = y} exp(theta (d_i - d_max)) / sum_{i in set} exp(theta (d_i - d_max)),
+ *                exactly 0 when no visible entry holds y.
+ *   empty set    no support cache and t = 0: the position is scored by the model alone: p_cache = 0 and the mixed log-prob is lp
+ *                BITWISE at every lambda, lambda = 1 included (no mixture that normalises exists there).
+ *   arithmetic   fsmg_cache_attend's: fp32 inputs widened exactly, exact products, fp64 accumulation in a fixed k order; the exponent
+ *                in fp64 up to the last step with integer shifts ceil(u m); fp64 sums in an order that depends on Mg, t and W alone;
+ *                no atomics.  The pad units of an own key contribute exact zeros whatever the pass left in them.
+ *   fsmg_cache_self_score   fsmg_cache_score's arguments, outputs, passes, state rules and time-out retry, with the own entries in
+ *                           the set; cache == NULL is the pure self-cache (group is then ignored).  out_lstm_logprob is bitwise
+ *                           fsmg_score's; out_logprob is fsmg_cache_score's host formula over the two device outputs, except at an
+ *                           empty-set position (above); the whole (theta, lambda) grid costs one device pass.
+ *   fsmg_cache_self_attend  the scoring kernel on given vectors: vectors host [n_rows][n_pos][H], values host [n_rows][n_pos] (ids in
+ *                           [0, input_size]): values[r][t] is both the target of position t and the value of own entry t; group host
+ *                           [n_rows] or NULL (all 0; ignored without a cache); out_prob host [n_theta][n_rows][n_pos].
+ * Two identical calls give identical bits.  A position's bits depend on its row's vectors and values 0 .. t, its group's entries,
+ * theta and W alone: not on the number of rows of the call or pass, nor on the other rows.  fsmg_cache_score / _attend / _get and
+ * fsmg_cache_generate keep their bits; the cache is not changed.
+ * Errors: FSMG_ERR_INVALID for everything fsmg_cache_score / fsmg_cache_attend refuse, a NULL or wrongly versioned
+ * fsmg_cache_self_config, nonzero reserved words, window < 1, n_rows < 1, n_pos < 1, n_rows * n_pos > 2^22; FSMG_ERR_TOKEN_RANGE for
+ * a value outside [0, input_size] (a token outside [0, input_size) in fsmg_cache_self_score).  Argument errors are found before any
+ * device work: outputs are untouched.
+ * Decode time.  fsmg_cache_self_generate is fsmg_cache_generate (its arguments, outputs, picks, filters, Philox counters and promises)
+ * with the row's own history in the set; cache == NULL: the own history alone, group ignored.  Own entry j of a row is (the top
+ * layer's h_out when input j of the row's token buffer [start, primer, generated tokens] was read, the token at position j + 1 of
+ * that buffer): primer positions are entries too.  At generated position p the visible own entries are max(0, p - W) .. p - 1, in
+ * one softmax with the group's support entries: one d_max, one shift, one Z over the union,
+ *   p_cache(v) = fl32((support mass of v + own mass of v) / Z),  z'' as fsmg_cache_generate;
+ * the own scores have exact fp64 products of the fp32 inputs and fp64 accumulation in one fixed order, the own masses of a value are
+ * summed in entry order, no atomics.  An empty union (no cache, p = 0, no primer) leaves the row lp: the model alone.  lambda = 0
+ * reads no cache at all and is fsmg_generate_filtered BITWISE.  Two identical calls give identical bits; a row's tokens and
+ * log-probs do not depend on n_seq or the other rows; no handle state is changed (a support cache gains its value index once, as
+ * for fsmg_cache_generate).
+ *   fsmg_cache_self_distribution  the decode-time kernels on given vectors, fsmg_cache_distribution's outputs: queries host [n][H],
+ *     logits host [n][V1], self_keys host [n][S][H], self_values host [n][S] (ids in [0, input_size]), self_len host [n], each in
+ *     [0, S]: row i sees the LAST min(self_len[i], W) of its first self_len[i] entries.  An empty union gives out_cache_prob 0 and
+ *     out_logprob = lp whatever lambda is; lambda = 0 gives lp bitwise.  A row's bits depend on its own inputs alone.
+ * Further errors, FSMG_ERR_INVALID: everything fsmg_cache_generate / fsmg_cache_distribution refuse, self_len outside [0, S], S < 0,
+ * rows * (primer_len + num) * Hp > 2^29 (the own keys of a call: 2 GiB; Hp the padded hidden size; rows * S * Hp likewise),
+ * rows * min(W, primer_len + num) > 2^26 (the fp64 own scores); FSMG_ERR_TOKEN_RANGE for an own value outside [0, input_size].
+ * Out of scope: decode-state variants (a state would have to carry keys); beam search over the mixture; separate theta or lambda for
+ * own and support entries; anything at MAML's theta'. */
+#define FSMG_CACHE_SELF_CONFIG_VERSION 1
+typedef struct fsmg_cache_self_config {
+    int32_t version;       /* FSMG_CACHE_SELF_CONFIG_VERSION                              */
+    int32_t window;        /* W >= 1: a position sees its last min(t, W) own entries      */
+    int32_t reserved[14];  /* must be 0                                                   */
+} fsmg_cache_self_config;
+
+/* fsmg_cache_score with the row's own history in the set; cache may be NULL */
+int fsmg_cache_self_score(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const fsmg_cache_self_config* sc,
+                          const int32_t* tokens, const int32_t* group, float* out_logprob, float* out_cache_prob,
+                          float* out_lstm_logprob, float* out_row_nll);
+/* vectors host [n_rows][n_pos][H], values host [n_rows][n_pos], group host [n_rows] or NULL, out_prob host [n_theta][n_rows][n_pos] */
+int fsmg_cache_self_attend(fsmg_handle h, fsmg_cache cache, const fsmg_cache_self_config* sc, int32_t n_rows, int32_t n_pos,
+                           const float* vectors, const int32_t* values, const int32_t* group, const float* thetas, int32_t n_theta,
+                           float* out_prob);
+/* fsmg_cache_generate with the row's own history in the set; cache may be NULL (group is then ignored) */
+int fsmg_cache_self_generate(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_cache_self_config* sc,
+                             const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* group, const int32_t* primer,
+                             int32_t* out_tokens, float* out_logprob);
+/* fsmg_cache_distribution over the union: self_keys host [n][S][H], self_values host [n][S], self_len host [n] (each in [0, S]) */
+int fsmg_cache_self_distribution(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_cache_self_config* sc,
+                                 int32_t n, const float* queries, const float* logits, const float* self_keys, const int32_t* self_values,
+                                 const int32_t* self_len, int32_t S, const int32_t* group, float* out_cache_prob, float* out_logprob,
+                                 float* out_lse);
 
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
