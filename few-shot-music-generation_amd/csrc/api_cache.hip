@@ -90,14 +90,13 @@ struct AttendScratch {
     float* out = nullptr; int* slot_query = nullptr; int* tile_group = nullptr; int* tgt = nullptr; float* Q = nullptr;
 };
 int attend_scratch(fsmg_model* h, int n, int n_theta, const Tiles& t, bool raw, AttendScratch* s) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (size_t)round_up((int64_t)(off + bytes), 256); return o; };
-    const size_t o_out = take(sizeof(float) * (size_t)n_theta * n);
-    const size_t o_slot = take(sizeof(int) * t.slot_query.size());
-    const size_t o_grp = take(sizeof(int) * t.tile_group.size());
-    const size_t o_tgt = take(raw ? sizeof(int) * (size_t)n : 0);
-    const size_t o_q = take(raw ? sizeof(float) * (size_t)n * h->Hp : 0);
-    const int rc = cat_reserve(h, off);
+    Carver cv;
+    const size_t o_out = cv.take(sizeof(float) * (size_t)n_theta * n);
+    const size_t o_slot = cv.take(sizeof(int) * t.slot_query.size());
+    const size_t o_grp = cv.take(sizeof(int) * t.tile_group.size());
+    const size_t o_tgt = cv.take(raw ? sizeof(int) * (size_t)n : 0);
+    const size_t o_q = cv.take(raw ? sizeof(float) * (size_t)n * h->Hp : 0);
+    const int rc = cat_reserve(h, cv.off);
     if (rc != FSMG_OK) return rc;
     s->out = (float*)(h->cat + o_out); s->slot_query = (int*)(h->cat + o_slot); s->tile_group = (int*)(h->cat + o_grp);
     s->tgt = (int*)(h->cat + o_tgt); s->Q = (float*)(h->cat + o_q);
@@ -125,13 +124,12 @@ struct SelfScratch {
     float* out = nullptr; int* row_group = nullptr; int* val = nullptr; float* V = nullptr;
 };
 int self_scratch(fsmg_model* h, int rows, int n, int n_theta, bool raw, SelfScratch* s) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (size_t)round_up((int64_t)(off + bytes), 256); return o; };
-    const size_t o_out = take(sizeof(float) * (size_t)n_theta * n);
-    const size_t o_grp = take(sizeof(int) * (size_t)rows);
-    const size_t o_val = take(raw ? sizeof(int) * (size_t)n : 0);
-    const size_t o_v = take(raw ? sizeof(float) * (size_t)n * h->Hp : 0);
-    const int rc = cat_reserve(h, off);
+    Carver cv;
+    const size_t o_out = cv.take(sizeof(float) * (size_t)n_theta * n);
+    const size_t o_grp = cv.take(sizeof(int) * (size_t)rows);
+    const size_t o_val = cv.take(raw ? sizeof(int) * (size_t)n : 0);
+    const size_t o_v = cv.take(raw ? sizeof(float) * (size_t)n * h->Hp : 0);
+    const int rc = cat_reserve(h, cv.off);
     if (rc != FSMG_OK) return rc;
     s->out = (float*)(h->cat + o_out); s->row_group = (int*)(h->cat + o_grp); s->val = (int*)(h->cat + o_val); s->V = (float*)(h->cat + o_v);
     return FSMG_OK;
@@ -160,12 +158,8 @@ int self_launch(fsmg_model* h, const fsmg_cache_s* c, const SelfScratch& s, int 
 }
 
 int check_self_config(fsmg_model* h, const fsmg_cache_self_config* sc) {
-    if (!sc) return fail(h, FSMG_ERR_INVALID, "null fsmg_cache_self_config");
-    if (sc->version != FSMG_CACHE_SELF_CONFIG_VERSION)
-        return fail(h, FSMG_ERR_INVALID, "fsmg_cache_self_config.version is " + std::to_string(sc->version) + ", this library expects " +
-                                             std::to_string(FSMG_CACHE_SELF_CONFIG_VERSION));
-    for (int32_t r : sc->reserved)
-        if (r != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_cache_self_config.reserved must be zero");
+    const int rc = check_config_header(h, sc, "fsmg_cache_self_config", FSMG_CACHE_SELF_CONFIG_VERSION);
+    if (rc != FSMG_OK) return rc;
     if (sc->window < 1) return fail(h, FSMG_ERR_INVALID, "fsmg_cache_self_config.window must be >= 1");
     return FSMG_OK;
 }
@@ -176,50 +170,24 @@ bool thetas_ok(const float* thetas, int n) {
     return true;
 }
 
-int check_host_tokens(fsmg_model* h, const int32_t* tokens, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (tokens[i] < 0 || tokens[i] >= h->V) return fail(h, FSMG_ERR_TOKEN_RANGE, "token id outside [0, input_size)");
+// the n group ids of a call against a cache of G groups (null: every row in group 0)
+int check_group_ids(fsmg_model* h, const int32_t* group, int64_t n, int G) {
+    if (group)
+        for (int64_t i = 0; i < n; ++i)
+            if (group[i] < 0 || group[i] >= G) return fail(h, FSMG_ERR_INVALID, "group id outside [0, groups of the cache)");
     return FSMG_OK;
 }
 
 int check_build_config(fsmg_model* h, const fsmg_cache_config* c, const int32_t* tokens, fsmg_cache* out) {
     if (!c || !out) return fail(h, FSMG_ERR_INVALID, "null fsmg_cache_config / out");
-    if (c->version != FSMG_CACHE_CONFIG_VERSION)
-        return fail(h, FSMG_ERR_INVALID, "fsmg_cache_config.version is " + std::to_string(c->version) + ", this library expects " +
-                                             std::to_string(FSMG_CACHE_CONFIG_VERSION));
-    for (int32_t r : c->reserved)
-        if (r != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_cache_config.reserved must be zero");
+    const int rc = check_config_header(h, c, "fsmg_cache_config", FSMG_CACHE_CONFIG_VERSION);
+    if (rc != FSMG_OK) return rc;
     if (c->n_rows < 1 || c->n_rows > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n_rows must be in [1, 2^20]");
     if (c->n_groups < 1 || c->n_rows % c->n_groups != 0) return fail(h, FSMG_ERR_INVALID, "n_groups must be >= 1 and divide n_rows");
     if (c->tokens_on_device != 0 && c->tokens_on_device != 1) return fail(h, FSMG_ERR_INVALID, "tokens_on_device must be 0 or 1");
     if (c->pass_rows < 0 || c->pass_rows > 1024) return fail(h, FSMG_ERR_INVALID, "pass_rows must be 0 or in [1, 1024]");
     if (!tokens) return fail(h, FSMG_ERR_INVALID, "null tokens");
     return check_cache_size(h, c->n_groups, (int64_t)(c->n_rows / c->n_groups) * h->T);
-}
-
-// one pass's read-back of the error word, fsmg_score's way: *again = repeat this pass on per-step launches
-int pass_status(fsmg_model* h, int err, bool* retried, bool* again) {
-    *again = false;
-    if (!err) { *retried = false; return FSMG_OK; }
-    HIPCK(h, hipMemsetAsync(h->d_err, 0, sizeof(int), h->stream));
-    if (err == 2) on_timeout(h);
-    const int rc = report(h, err);
-    if (is_retry(rc) && h->retry_armed && !*retried) {
-        h->retry_armed = false;
-        *retried = true;
-        *again = true;
-        return FSMG_OK;
-    }
-    return rc;
-}
-
-// what a scoring-style pass over B rows needs before its launches (score_core's prologue)
-int prepare_pass(fsmg_model* h, int B, const int32_t* rows, int on_device) {
-    choose_schedule(h, B);
-    h->ov_call = false;
-    int rc;
-    if (pass_reads_cs(h, B, false) && (rc = ensure_cs(h)) != FSMG_OK) return rc;
-    return stage_tokens(h, rows, 0, rows, B, on_device);
 }
 
 // fsmg_cache_build's work behind the argument checks
@@ -232,42 +200,28 @@ int build_core(fsmg_model* h, const fsmg_cache_config* c, const int32_t* tokens,
     if ((rc = ensure_khf(h)) != FSMG_OK) return rc;
     fsmg_cache_s* cache = nullptr;
     if ((rc = alloc_cache(h, c->n_groups, R / c->n_groups * T, &cache)) != FSMG_OK) return rc;
-    auto passes = [&]() -> int {
-        bool retried = false;
-        for (int r0 = 0; r0 < R; r0 += P) {
-            const int B = std::min(P, R - r0);
-            int r = prepare_pass(h, B, tokens + (size_t)r0 * T, c->tokens_on_device);
-            if (r != FSMG_OK) return r;
-            r = run_graphed(h, "cb:" + std::to_string(B), [&]() -> int {
+    rc = run_passes(
+        h, tokens, R, P, c->tokens_on_device,
+        [&](int r0, int B) -> int {
+            const int r = run_graphed(h, "cb:" + std::to_string(B), [&]() -> int {
                 const int rr = token_prep(h, 0, B);
                 return rr == FSMG_OK ? forward(h, B, B, 1, nullptr, false, HEAD_NONE) : rr;
             });
             if (r != FSMG_OK) return r;
-            h->lastB = B;
             // rows r0 .. r0 + B - 1 of the cache's [rows][T] entries: a pass repeated after a time-out overwrites what it wrote
             HIPCK(h, launch_cache_fill(h->stream, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Y, B, T, h->H, h->Hp, r0, cache->keys, cache->vals));
-            int err = 0;
-            HIPCK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIPCK(h, hipStreamSynchronize(h->stream));
-            bool again = false;
-            if ((r = pass_status(h, err, &retried, &again)) != FSMG_OK) return r;
-            if (again) r0 -= P;
-        }
-        return FSMG_OK;
-    };
-    if ((rc = passes()) != FSMG_OK) { hipStreamSynchronize(h->stream); free_cache(cache); return rc; }
+            return FSMG_OK;
+        },
+        [](int, int) { return FSMG_OK; });          // (nothing comes back but the error word)
+    if (rc != FSMG_OK) { hipStreamSynchronize(h->stream); free_cache(cache); return rc; }
     *out = cache;
     return FSMG_OK;
 }
 
 int check_score_config(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_config* c, const int32_t* tokens,
                        const int32_t* group, const void* const outs[4]) {
-    if (!c) return fail(h, FSMG_ERR_INVALID, "null fsmg_cache_score_config");
-    if (c->version != FSMG_CACHE_SCORE_CONFIG_VERSION)
-        return fail(h, FSMG_ERR_INVALID, "fsmg_cache_score_config.version is " + std::to_string(c->version) + ", this library expects " +
-                                             std::to_string(FSMG_CACHE_SCORE_CONFIG_VERSION));
-    for (int32_t r : c->reserved)
-        if (r != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_cache_score_config.reserved must be zero");
+    const int rc = check_config_header(h, c, "fsmg_cache_score_config", FSMG_CACHE_SCORE_CONFIG_VERSION);
+    if (rc != FSMG_OK) return rc;
     if (c->n_rows < 1 || c->n_rows > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n_rows must be in [1, 2^20]");
     if (c->tokens_on_device != 0 && c->tokens_on_device != 1) return fail(h, FSMG_ERR_INVALID, "tokens_on_device must be 0 or 1");
     if (c->nll_first < 0 || c->nll_first >= h->T || c->nll_count < 0 || (int64_t)c->nll_first + c->nll_count > h->T)
@@ -281,20 +235,7 @@ int check_score_config(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cach
     if (!tokens) return fail(h, FSMG_ERR_INVALID, "null tokens");
     if (!outs[0] && !outs[1] && !outs[2] && !outs[3]) return fail(h, FSMG_ERR_INVALID, "every output is null");
     if (cache->H != h->H || cache->Hp != h->Hp) return fail(h, FSMG_ERR_INVALID, "the cache's hidden size is not the handle's");
-    if (group)
-        for (int r = 0; r < c->n_rows; ++r)
-            if (group[r] < 0 || group[r] >= cache->G) return fail(h, FSMG_ERR_INVALID, "group id outside [0, groups of the cache)");
-    return FSMG_OK;
-}
-
-// log((1 - lambda) exp(lp) + lambda pc) in fp64, rounded once
-inline float mix_logprob(float lp, float pc, double log1m_lambda, double log_lambda) {
-    const double a = log1m_lambda + (double)lp;                         // lambda = 0: 0 + lp
-    const double b = log_lambda + std::log((double)pc);                 // -inf at pc = 0 (and at lambda = 0)
-    if (std::isnan(a) || std::isnan(b)) return (float)(a + b);
-    const double hi = std::max(a, b), lo = std::min(a, b);
-    if (hi == -INFINITY) return -INFINITY;
-    return (float)(hi + std::log1p(std::exp(lo - hi)));
+    return check_group_ids(h, group, c->n_rows, cache->G);
 }
 
 // fsmg_cache_score's work behind the argument checks; with `self` fsmg_cache_self_score's: the row's own history joins the set (the
@@ -317,55 +258,48 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
     float* pc_host = out_cache_prob;
     if (want_lp && !lp_host) { lp_own.resize(RT); lp_host = lp_own.data(); }
     if (want_pc && !pc_host) { pc_own.resize(RT * NT); pc_host = pc_own.data(); }
-    bool retried = false;
-    for (int r0 = 0; r0 < R; r0 += P) {
-        const int B = std::min(P, R - r0);
-        const int n = B * T;
-        if ((rc = prepare_pass(h, B, tokens + (size_t)r0 * T, c->tokens_on_device)) != FSMG_OK) return rc;
-        Tiles tiles;
-        AttendScratch as;
-        SelfScratch ss;
-        if (want_pc && self) {
-            if ((rc = self_scratch(h, B, n, NT, false, &ss)) != FSMG_OK) return rc;
-            as.out = ss.out;
-        } else if (want_pc) {       // query q = b * T + t of the pass, in its row's group
-            tiles = make_tiles(n, cache->G, [&](int q) { return group ? group[r0 + q / T] : 0; });
-            if ((rc = attend_scratch(h, n, NT, tiles, false, &as)) != FSMG_OK) return rc;
-        }
-        float* d_lp = h->score_out;
-        // fsmg_score's pass with the log-prob as its one output (the same graph key: the same launches)
-        rc = run_graphed(h, "sc:" + std::to_string(B) + ":1", [&]() -> int {
-            int r = token_prep(h, 0, B);
-            if (r == FSMG_OK) r = forward(h, B, B, 1, nullptr, false, HEAD_LOGITS);
-            if (r != FSMG_OK) return r;
-            ScopedTimer tm(h, "ce");
-            HIPCK(h, launch_score_rows(h->stream, h->logits, h->V1p, n, h->V1, h->Y, B, T, d_lp, nullptr, nullptr, nullptr));
+    Tiles tiles;                        // a pass's attention scratch, from its launches to its read-back
+    AttendScratch as;
+    SelfScratch ss;
+    rc = run_passes(
+        h, tokens, R, P, c->tokens_on_device,
+        [&](int r0, int B) -> int {
+            const int n = B * T;
+            int r;
+            if (want_pc && self) {
+                if ((r = self_scratch(h, B, n, NT, false, &ss)) != FSMG_OK) return r;
+                as.out = ss.out;
+            } else if (want_pc) {       // query q = b * T + t of the pass, in its row's group
+                tiles = make_tiles(n, cache->G, [&](int q) { return group ? group[r0 + q / T] : 0; });
+                if ((r = attend_scratch(h, n, NT, tiles, false, &as)) != FSMG_OK) return r;
+            }
+            // fsmg_score's pass with the log-prob as its one output (the same graph key: the same launches)
+            r = run_graphed(h, "sc:" + std::to_string(B) + ":1", [&]() -> int {
+                int rr = token_prep(h, 0, B);
+                if (rr == FSMG_OK) rr = forward(h, B, B, 1, nullptr, false, HEAD_LOGITS);
+                if (rr != FSMG_OK) return rr;
+                ScopedTimer tm(h, "ce");
+                HIPCK(h, launch_score_rows(h->stream, h->logits, h->V1p, n, h->V1, h->Y, B, T, h->score_out, nullptr, nullptr, nullptr));
+                return FSMG_OK;
+            });
+            if (r != FSMG_OK || !want_pc) return r;
+            if (!self) return attend_launch(h, cache, tiles, as, n, h->Hs[h->L - 1], B, h->Y, c->thetas, NT);
+            // row b's vector t: slot t + 1 of the time-major top-layer states; its value t: Y[t][b]
+            return self_launch(h, cache, ss, B, T, self->window, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Hp, (long long)B * h->Hp, h->Y, 1, B,
+                               group ? group + r0 : nullptr, c->thetas, NT);
+        },
+        [&](int r0, int B) -> int {
+            const size_t o = (size_t)r0 * T, n = (size_t)B * T;
+            if (want_lp) HIPCK(h, hipMemcpyAsync(lp_host + o, h->score_out, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
+            if (want_pc)
+                for (int k = 0; k < NT; ++k)
+                    HIPCK(h, hipMemcpyAsync(pc_host + k * RT + o, as.out + (size_t)k * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
             return FSMG_OK;
         });
-        if (rc != FSMG_OK) return rc;
-        h->lastB = B;
-        if (want_pc && self) {      // row b's vector t: slot t + 1 of the time-major top-layer states; its value t: Y[t][b]
-            const float* hs1 = h->Hs[h->L - 1] + (size_t)B * h->Hp;
-            rc = self_launch(h, cache, ss, B, T, self->window, hs1, h->Hp, (long long)B * h->Hp, h->Y, 1, B, group ? group + r0 : nullptr,
-                             c->thetas, NT);
-            if (rc != FSMG_OK) return rc;
-        } else if (want_pc && (rc = attend_launch(h, cache, tiles, as, n, h->Hs[h->L - 1], B, h->Y, c->thetas, NT)) != FSMG_OK) return rc;
-        const size_t o = (size_t)r0 * T;
-        int err = 0;
-        if (want_lp) HIPCK(h, hipMemcpyAsync(lp_host + o, d_lp, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-        if (want_pc)
-            for (int k = 0; k < NT; ++k)
-                HIPCK(h, hipMemcpyAsync(pc_host + k * RT + o, as.out + (size_t)k * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        bool again = false;
-        if ((rc = pass_status(h, err, &retried, &again)) != FSMG_OK) return rc;
-        if (again) r0 -= P;
-    }
+    if (rc != FSMG_OK) return rc;
     if (!want_mix) return FSMG_OK;
     float* mix = out_logprob;
     if (!mix) { mix_own.resize(RT); mix = mix_own.data(); }            // (row NLL alone: one (theta, lambda) plane at a time)
-    const int t0 = c->nll_first, t1 = c->nll_count > 0 ? t0 + c->nll_count : T;
     for (int k = 0; k < NT; ++k)
         for (int j = 0; j < NL; ++j) {
             const double lam = (double)c->lambdas[j];
@@ -375,12 +309,7 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
             for (size_t i = 0; i < RT; ++i) plane[i] = mix_logprob(lp_host[i], pc[i], l1m, ll);
             if (self && !cache)         // position 0 of a row has an empty set: the model alone, at every lambda
                 for (size_t i = 0; i < RT; i += T) plane[i] = lp_host[i];
-            if (!out_row_nll) continue;
-            for (int r = 0; r < R; ++r) {
-                double s = 0.0;         // fp64, increasing t, rounded once: bitwise recomputable from out_logprob
-                for (int t = t0; t < t1; ++t) s += (double)plane[(size_t)r * T + t];
-                out_row_nll[((size_t)k * NL + j) * R + r] = (float)(-s / (double)(t1 - t0));
-            }
+            if (out_row_nll) row_nll(plane, R, T, c->nll_first, c->nll_count, out_row_nll + ((size_t)k * NL + j) * R);
         }
     return FSMG_OK;
 }
@@ -388,31 +317,25 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
 }  // namespace
 
 // ---- cache-conditioned generation: the cache side (the decode driver in api_decode.hip calls these)
-static int check_gen_cc(fsmg_model* h, const fsmg_cache_gen_config* cc, int64_t R) {
-    if (!cc) return fail(h, FSMG_ERR_INVALID, "null fsmg_cache_gen_config");
-    if (cc->version != FSMG_CACHE_GEN_CONFIG_VERSION)
-        return fail(h, FSMG_ERR_INVALID, "fsmg_cache_gen_config.version is " + std::to_string(cc->version) + ", this library expects " +
-                                             std::to_string(FSMG_CACHE_GEN_CONFIG_VERSION));
-    for (int32_t r : cc->reserved)
-        if (r != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_cache_gen_config.reserved must be zero");
+constexpr int64_t SELF_GEN_MAX_KEY_FLOATS = 1LL << 29;   // R * NP * Hp of one call (2 GiB of own keys)
+
+// what cache_gen_check and cache_self_gen_check share: the config, then -- with a support cache (it may be absent only where
+// `need_cache` is false) -- the cache against the handle, the R * Mg limit, the group ids and the rows' tiles
+static int gen_check(fsmg_model* h, fsmg_cache cache, bool need_cache, const fsmg_cache_gen_config* cc, const int32_t* group, int64_t R,
+                     CacheGen* cg) {
+    fsmg_cache_s* c = nullptr;
+    if ((cache || need_cache) && !(c = find_cache(h, cache))) return FSMG_ERR_INVALID;
+    int rc = check_config_header(h, cc, "fsmg_cache_gen_config", FSMG_CACHE_GEN_CONFIG_VERSION);
+    if (rc != FSMG_OK) return rc;
     if (!thetas_ok(&cc->theta, 1)) return fail(h, FSMG_ERR_INVALID, "theta must be finite and >= 0");
     if (!(cc->lambda >= 0.0f && cc->lambda <= 1.0f)) return fail(h, FSMG_ERR_INVALID, "lambda must lie in [0, 1]");
     if (R < 1 || R > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "the row count must be in [1, 2^20]");
-    return FSMG_OK;
-}
-
-int cache_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const int32_t* group, int64_t R, CacheGen* cg) {
-    fsmg_cache_s* c = find_cache(h, cache);
-    if (!c) return FSMG_ERR_INVALID;
-    const int rc0 = check_gen_cc(h, cc, R);
-    if (rc0 != FSMG_OK) return rc0;
-    if (c->H != h->H || c->Hp != h->Hp) return fail(h, FSMG_ERR_INVALID, "the cache's hidden size is not the handle's");
-    if (R * c->Mg > CACHE_GEN_MAX_SCORES) return fail(h, FSMG_ERR_INVALID, "rows * entries_per_group must be <= 2^26");
-    if (group)
-        for (int64_t r = 0; r < R; ++r)
-            if (group[r] < 0 || group[r] >= c->G) return fail(h, FSMG_ERR_INVALID, "group id outside [0, groups of the cache)");
     cg->c = c; cg->theta = cc->theta; cg->lambda = cc->lambda;
     cg->R = (int)R; cg->ldl = (int)round_up(h->V1, 64);
+    if (!c) return FSMG_OK;
+    if (c->H != h->H || c->Hp != h->Hp) return fail(h, FSMG_ERR_INVALID, "the cache's hidden size is not the handle's");
+    if (R * c->Mg > CACHE_GEN_MAX_SCORES) return fail(h, FSMG_ERR_INVALID, "rows * entries_per_group must be <= 2^26");
+    if ((rc = check_group_ids(h, group, R, c->G)) != FSMG_OK) return rc;
     Tiles t = make_tiles((int)R, c->G, [&](int q) { return group ? group[q] : 0; });
     cg->slot_query = std::move(t.slot_query);
     cg->tile_group = std::move(t.tile_group);
@@ -421,19 +344,15 @@ int cache_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config
     return FSMG_OK;
 }
 
-constexpr int64_t SELF_GEN_MAX_KEY_FLOATS = 1LL << 29;   // R * NP * Hp of one call (2 GiB of own keys)
+int cache_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const int32_t* group, int64_t R, CacheGen* cg) {
+    return gen_check(h, cache, true, cc, group, R, cg);
+}
 
 int cache_self_gen_check(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_cache_self_config* sc,
                          const int32_t* group, int64_t R, int64_t NP, bool raw, CacheGen* cg) {
-    int rc;
-    if (cache) {
-        if ((rc = cache_gen_check(h, cache, cc, group, R, cg)) != FSMG_OK) return rc;
-    } else {
-        if ((rc = check_gen_cc(h, cc, R)) != FSMG_OK) return rc;
-        cg->c = nullptr; cg->theta = cc->theta; cg->lambda = cc->lambda;
-        cg->R = (int)R; cg->ldl = (int)round_up(h->V1, 64);
-    }
-    if ((rc = check_self_config(h, sc)) != FSMG_OK) return rc;
+    int rc = gen_check(h, cache, false, cc, group, R, cg);
+    if (rc == FSMG_OK) rc = check_self_config(h, sc);
+    if (rc != FSMG_OK) return rc;
     if (NP < 1) NP = 1;
     if (R * NP * h->Hp > SELF_GEN_MAX_KEY_FLOATS)
         return fail(h, FSMG_ERR_INVALID, "rows * (primer_len + num) * Hp (Hp the padded hidden size) must be <= 2^29");
@@ -499,22 +418,21 @@ namespace {
 // [D R * Mg doubles | pc R * ldl floats | slot_query | tile_group | row_group], each 256-byte aligned
 struct CacheGenLayout { size_t o_D, o_pc, o_slot, o_tile, o_row, o_keys, o_D2, o_pm, o_len, o_val, total; };
 CacheGenLayout cache_gen_layout(const CacheGen& cg) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (size_t)round_up((int64_t)(off + bytes), 256); return o; };
+    Carver cv;
     CacheGenLayout l{};
-    l.o_D = take(sizeof(double) * (size_t)cg.R * (cg.c ? cg.c->Mg : 0));
-    l.o_pc = take(sizeof(float) * (size_t)cg.R * cg.ldl);
-    l.o_slot = take(sizeof(int) * cg.slot_query.size());
-    l.o_tile = take(sizeof(int) * cg.tile_group.size());
-    l.o_row = take(sizeof(int) * cg.row_group.size());
+    l.o_D = cv.take(sizeof(double) * (size_t)cg.R * (cg.c ? cg.c->Mg : 0));
+    l.o_pc = cv.take(sizeof(float) * (size_t)cg.R * cg.ldl);
+    l.o_slot = cv.take(sizeof(int) * cg.slot_query.size());
+    l.o_tile = cv.take(sizeof(int) * cg.tile_group.size());
+    l.o_row = cv.take(sizeof(int) * cg.row_group.size());
     if (cg.W > 0) {         // (behind everything else: without a self-cache the layout is what it was)
-        l.o_keys = take(sizeof(float) * (size_t)cg.R * cg.NP * cg.Hp);
-        l.o_D2 = take(sizeof(double) * (size_t)cg.R * cg.ldo);
-        l.o_pm = take(sizeof(double) * (size_t)cg.R * cg.ldl);
-        l.o_len = take(cg.raw ? sizeof(int) * (size_t)cg.R : 0);
-        l.o_val = take(cg.raw ? sizeof(int) * (size_t)cg.R * cg.NP : 0);
+        l.o_keys = cv.take(sizeof(float) * (size_t)cg.R * cg.NP * cg.Hp);
+        l.o_D2 = cv.take(sizeof(double) * (size_t)cg.R * cg.ldo);
+        l.o_pm = cv.take(sizeof(double) * (size_t)cg.R * cg.ldl);
+        l.o_len = cv.take(cg.raw ? sizeof(int) * (size_t)cg.R : 0);
+        l.o_val = cv.take(cg.raw ? sizeof(int) * (size_t)cg.R * cg.NP : 0);
     }
-    l.total = off;
+    l.total = cv.off;
     return l;
 }
 }  // namespace
@@ -542,15 +460,34 @@ int cache_self_file(fsmg_model* h, const CacheGen& cg, const float* h_out, int p
     return FSMG_OK;
 }
 
-int cache_self_step(fsmg_model* h, const CacheGen& cg, int len, const float* Q, float* logits, const int* val, int ldv, float* out_lse) {
+// stage one over the support entries: the rows' queries Q against their groups' keys into cg.D
+static int scores_launch(fsmg_model* h, const CacheGen& cg, const float* Q) {
     const fsmg_cache_s* c = cg.c;
-    if (c) {
-        CacheScoresArgs sa{};
-        sa.keys = c->keys; sa.Mg = c->Mg; sa.Hp = c->Hp; sa.Q = Q; sa.ldq = c->Hp;
-        sa.slot_query = cg.d_slot_query; sa.tile_group = cg.d_tile_group; sa.n_tiles = (int)cg.tile_group.size(); sa.D = cg.D;
-        ScopedTimer tm(h, "cache_scores");
-        HIPCK(h, launch_cache_scores(h->stream, sa));
+    CacheScoresArgs sa{};
+    sa.keys = c->keys; sa.Mg = c->Mg; sa.Hp = c->Hp; sa.Q = Q; sa.ldq = c->Hp;
+    sa.slot_query = cg.d_slot_query; sa.tile_group = cg.d_tile_group; sa.n_tiles = (int)cg.tile_group.size(); sa.D = cg.D;
+    ScopedTimer tm(h, "cache_scores");
+    HIPCK(h, launch_cache_scores(h->stream, sa));
+    return FSMG_OK;
+}
+
+// stage two's arguments; without a support cache Mg stays 0 and D, row_group and the value index stay null
+static CacheMixArgs mix_args(const fsmg_model* h, const CacheGen& cg, float* logits, float* out_lse) {
+    const double lam = (double)cg.lambda;
+    CacheMixArgs ma{};
+    ma.logits = logits; ma.ldl = cg.ldl; ma.ncols = h->V1; ma.pc = cg.pc; ma.out_lse = out_lse;
+    if (const fsmg_cache_s* c = cg.c) {
+        ma.D = cg.D; ma.Mg = c->Mg; ma.row_group = cg.d_row_group;
+        ma.order = c->order; ma.seg_beg = c->seg_beg; ma.seg_end = c->seg_end; ma.seg_val = c->seg_val;
+        ma.n_seg = c->n_seg; ma.n_long = c->n_long;
     }
+    ma.u = (double)cg.theta * CA_LOG2E; ma.log1m_lambda = std::log1p(-lam); ma.log_lambda = std::log(lam); ma.mix = cg.lambda > 0.0f;
+    return ma;
+}
+
+int cache_self_step(fsmg_model* h, const CacheGen& cg, int len, const float* Q, float* logits, const int* val, int ldv, float* out_lse) {
+    int rc;
+    if (cg.c && (rc = scores_launch(h, cg, Q)) != FSMG_OK) return rc;
     const int* row_len = cg.raw ? cg.d_len : nullptr;
     SelfScoresArgs ss{};
     ss.own_keys = cg.own_keys; ss.NP = cg.NP; ss.Hp = h->Hp; ss.Q = Q; ss.ldq = h->Hp;
@@ -559,15 +496,8 @@ int cache_self_step(fsmg_model* h, const CacheGen& cg, int len, const float* Q, 
         ScopedTimer tm(h, "self_scores");
         HIPCK(h, launch_self_scores(h->stream, ss));
     }
-    const double lam = (double)cg.lambda;
     CacheMixSelfArgs ma{};
-    ma.m.logits = logits; ma.m.ldl = cg.ldl; ma.m.ncols = h->V1; ma.m.pc = cg.pc; ma.m.out_lse = out_lse;
-    if (c) {
-        ma.m.D = cg.D; ma.m.Mg = c->Mg; ma.m.row_group = cg.d_row_group;
-        ma.m.order = c->order; ma.m.seg_beg = c->seg_beg; ma.m.seg_end = c->seg_end; ma.m.seg_val = c->seg_val;
-        ma.m.n_seg = c->n_seg; ma.m.n_long = c->n_long;
-    }
-    ma.m.u = (double)cg.theta * CA_LOG2E; ma.m.log1m_lambda = std::log1p(-lam); ma.m.log_lambda = std::log(lam); ma.m.mix = cg.lambda > 0.0f;
+    ma.m = mix_args(h, cg, logits, out_lse);
     ma.D2 = cg.D2; ma.ldo = cg.ldo; ma.val = val; ma.ldv = ldv; ma.row_len = row_len; ma.len = len; ma.W = cg.W; ma.pm = cg.pm;
     ScopedTimer tm(h, "cache_mix_self");
     HIPCK(h, launch_cache_mix_self(h->stream, cg.R, ma));
@@ -575,25 +505,86 @@ int cache_self_step(fsmg_model* h, const CacheGen& cg, int len, const float* Q, 
 }
 
 int cache_gen_step(fsmg_model* h, const CacheGen& cg, const float* Q, float* logits, float* out_lse) {
-    const fsmg_cache_s* c = cg.c;
-    CacheScoresArgs sa{};
-    sa.keys = c->keys; sa.Mg = c->Mg; sa.Hp = c->Hp; sa.Q = Q; sa.ldq = c->Hp;
-    sa.slot_query = cg.d_slot_query; sa.tile_group = cg.d_tile_group; sa.n_tiles = (int)cg.tile_group.size(); sa.D = cg.D;
-    {
-        ScopedTimer tm(h, "cache_scores");
-        HIPCK(h, launch_cache_scores(h->stream, sa));
-    }
-    const double lam = (double)cg.lambda;
-    CacheMixArgs ma{};
-    ma.logits = logits; ma.ldl = cg.ldl; ma.ncols = h->V1; ma.D = cg.D; ma.Mg = c->Mg; ma.row_group = cg.d_row_group;
-    ma.order = c->order; ma.seg_beg = c->seg_beg; ma.seg_end = c->seg_end; ma.seg_val = c->seg_val;
-    ma.n_seg = c->n_seg; ma.n_long = c->n_long;
-    ma.pc = cg.pc; ma.out_lse = out_lse;
-    ma.u = (double)cg.theta * CA_LOG2E; ma.log1m_lambda = std::log1p(-lam); ma.log_lambda = std::log(lam); ma.mix = cg.lambda > 0.0f;
+    const int rc = scores_launch(h, cg, Q);
+    if (rc != FSMG_OK) return rc;
     ScopedTimer tm(h, "cache_mix");
-    HIPCK(h, launch_cache_mix(h->stream, cg.R, ma));
+    HIPCK(h, launch_cache_mix(h->stream, cg.R, mix_args(h, cg, logits, out_lse)));
     return FSMG_OK;
 }
+
+namespace {
+// what fsmg_cache_self_distribution adds to fsmg_cache_distribution: per query up to S own entries, self_len[q] of them filed
+struct SelfEntries {
+    const fsmg_cache_self_config* sc;
+    const float* keys; const int32_t* values; const int32_t* len; int32_t S;
+};
+
+// fsmg_cache_distribution, and with `self` fsmg_cache_self_distribution (the cache may then be null)
+int distribution(fsmg_model* h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const SelfEntries* self, int32_t n, const float* queries,
+                 const float* logits, const int32_t* group, float* out_cache_prob, float* out_logprob, float* out_lse) {
+    if ((cache || !self) && !find_cache(h, cache)) return FSMG_ERR_INVALID;
+    if (n < 1 || n > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n must be in [1, 2^20]");
+    if (!self && (!queries || !logits)) return fail(h, FSMG_ERR_INVALID, "null queries / logits");
+    if (self && (!queries || !logits || !self->len)) return fail(h, FSMG_ERR_INVALID, "null queries / logits / self_len");
+    const int S = self ? self->S : 0;
+    if (S < 0 || (S > 0 && (!self->keys || !self->values))) return fail(h, FSMG_ERR_INVALID, "S must be >= 0, with self_keys and self_values when S > 0");
+    if (!out_cache_prob && !out_logprob && !out_lse) return fail(h, FSMG_ERR_INVALID, "every output is null");
+    CacheGen cg;
+    int rc = self ? cache_self_gen_check(h, cache, cc, self->sc, cache ? group : nullptr, n, S, true, &cg) : cache_gen_check(h, cache, cc, group, n, &cg);
+    if (rc != FSMG_OK) return rc;
+    if (self) {
+        for (int i = 0; i < n; ++i)
+            if (self->len[i] < 0 || self->len[i] > S) return fail(h, FSMG_ERR_INVALID, "self_len outside [0, S]");
+        for (size_t i = 0; i < (size_t)n * S; ++i)
+            if (self->values[i] < 0 || self->values[i] >= h->V1) return fail(h, FSMG_ERR_TOKEN_RANGE, "own value outside [0, input_size]");
+    }
+    BEGIN_CALL(h);
+    if (cg.c && (rc = ensure_value_index(h, const_cast<fsmg_cache_s*>(cg.c))) != FSMG_OK) return rc;
+    // [cache_gen's block | queries n x Hp | logits n x ldl | lse n]
+    const int Hp = h->Hp, ldl = cg.ldl, V1 = h->V1, NP = cg.NP;
+    Carver cv;
+    cv.take(cache_gen_bytes(h, cg));
+    const size_t o_q = cv.take(sizeof(float) * (size_t)n * Hp);
+    const size_t o_z = cv.take(sizeof(float) * (size_t)n * ldl);
+    const size_t o_lse = cv.off;
+    if ((rc = gen_reserve(h, o_lse + sizeof(float) * (size_t)n)) != FSMG_OK) return rc;
+    float* d_q = (float*)(h->gen + o_q);
+    float* d_z = (float*)(h->gen + o_z);
+    float* d_lse = (float*)(h->gen + o_lse);
+    std::vector<float> qp((size_t)n * Hp, 0.0f), kp(self ? (size_t)n * NP * Hp : 0, 0.0f);       // the pad units are exact zeros
+    std::vector<int> vp(self ? (size_t)n * NP : 0, 0);
+    for (int q = 0; q < n; ++q) {
+        std::memcpy(qp.data() + (size_t)q * Hp, queries + (size_t)q * h->H, sizeof(float) * h->H);
+        for (int e = 0; e < S; ++e) {
+            std::memcpy(kp.data() + ((size_t)q * NP + e) * Hp, self->keys + ((size_t)q * S + e) * h->H, sizeof(float) * h->H);
+            vp[(size_t)q * NP + e] = self->values[(size_t)q * S + e];
+        }
+    }
+    auto run = [&]() -> int {
+        int r = cache_gen_place(h, cg, h->gen);
+        if (r != FSMG_OK) return r;
+        HIPCK(h, hipMemcpyAsync(d_q, qp.data(), sizeof(float) * qp.size(), hipMemcpyHostToDevice, h->stream));
+        if (self) {
+            HIPCK(h, hipMemcpyAsync(cg.own_keys, kp.data(), sizeof(float) * kp.size(), hipMemcpyHostToDevice, h->stream));
+            HIPCK(h, hipMemcpyAsync(cg.d_val, vp.data(), sizeof(int) * vp.size(), hipMemcpyHostToDevice, h->stream));
+            HIPCK(h, hipMemcpyAsync(cg.d_len, self->len, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        }
+        HIPCK(h, hipMemcpy2DAsync(d_z, sizeof(float) * ldl, logits, sizeof(float) * V1, sizeof(float) * V1, n, hipMemcpyHostToDevice, h->stream));
+        r = self ? cache_self_step(h, cg, 0, d_q, d_z, cg.d_val, NP, d_lse) : cache_gen_step(h, cg, d_q, d_z, d_lse);
+        if (r != FSMG_OK) return r;
+        if (out_cache_prob)
+            HIPCK(h, hipMemcpy2DAsync(out_cache_prob, sizeof(float) * V1, cg.pc, sizeof(float) * ldl, sizeof(float) * V1, n, hipMemcpyDeviceToHost, h->stream));
+        if (out_logprob)
+            HIPCK(h, hipMemcpy2DAsync(out_logprob, sizeof(float) * V1, d_z, sizeof(float) * ldl, sizeof(float) * V1, n, hipMemcpyDeviceToHost, h->stream));
+        if (out_lse) HIPCK(h, hipMemcpyAsync(out_lse, d_lse, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        return FSMG_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(h->stream);       // the host vectors go out of scope
+    if (rc == FSMG_OK && e != hipSuccess) return fail(h, FSMG_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
+}
+}  // namespace
 
 }  // namespace fsmg_host
 
@@ -681,14 +672,12 @@ int fsmg_cache_attend(fsmg_handle h, fsmg_cache cache, int32_t n, const float* q
     if (n_theta < 1 || n_theta > FSMG_CACHE_MAX_THETA) return fail(h, FSMG_ERR_INVALID, "n_theta must be in [1, 8]");
     if (!thetas_ok(thetas, n_theta)) return fail(h, FSMG_ERR_INVALID, "every theta must be finite and >= 0");
     if (c->H != h->H || c->Hp != h->Hp) return fail(h, FSMG_ERR_INVALID, "the cache's hidden size is not the handle's");
-    if (group)
-        for (int q = 0; q < n; ++q)
-            if (group[q] < 0 || group[q] >= c->G) return fail(h, FSMG_ERR_INVALID, "group id outside [0, groups of the cache)");
+    int rc = check_group_ids(h, group, n, c->G);
+    if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
     const Tiles tiles = make_tiles(n, c->G, [&](int q) { return group ? group[q] : 0; });
     AttendScratch as;
-    int rc = attend_scratch(h, n, n_theta, tiles, true, &as);
-    if (rc != FSMG_OK) return rc;
+    if ((rc = attend_scratch(h, n, n_theta, tiles, true, &as)) != FSMG_OK) return rc;
     std::vector<float> qp((size_t)n * h->Hp, 0.0f);
     for (int q = 0; q < n; ++q) std::memcpy(qp.data() + (size_t)q * h->Hp, queries + (size_t)q * h->H, sizeof(float) * h->H);
     HIPCK(h, hipMemcpyAsync(as.Q, qp.data(), sizeof(float) * qp.size(), hipMemcpyHostToDevice, h->stream));
@@ -702,43 +691,7 @@ int fsmg_cache_attend(fsmg_handle h, fsmg_cache cache, int32_t n, const float* q
 int fsmg_cache_distribution(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, int32_t n, const float* queries,
                             const float* logits, const int32_t* group, float* out_cache_prob, float* out_logprob, float* out_lse) {
     if (!h) return FSMG_ERR_INVALID;
-    if (!find_cache(h, cache)) return FSMG_ERR_INVALID;
-    if (n < 1 || n > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n must be in [1, 2^20]");
-    if (!queries || !logits) return fail(h, FSMG_ERR_INVALID, "null queries / logits");
-    if (!out_cache_prob && !out_logprob && !out_lse) return fail(h, FSMG_ERR_INVALID, "every output is null");
-    CacheGen cg;
-    int rc = cache_gen_check(h, cache, cc, group, n, &cg);
-    if (rc != FSMG_OK) return rc;
-    BEGIN_CALL(h);
-    if ((rc = ensure_value_index(h, const_cast<fsmg_cache_s*>(cg.c))) != FSMG_OK) return rc;
-    // [cache_gen's block | queries n x Hp | logits n x ldl | lse n]
-    const int Hp = h->Hp, ldl = cg.ldl, V1 = h->V1;
-    const size_t o_q = (size_t)round_up((int64_t)cache_gen_bytes(h, cg), 256);
-    const size_t o_z = (size_t)round_up((int64_t)(o_q + sizeof(float) * (size_t)n * Hp), 256);
-    const size_t o_lse = (size_t)round_up((int64_t)(o_z + sizeof(float) * (size_t)n * ldl), 256);
-    if ((rc = gen_reserve(h, o_lse + sizeof(float) * (size_t)n)) != FSMG_OK) return rc;
-    float* d_q = (float*)(h->gen + o_q);
-    float* d_z = (float*)(h->gen + o_z);
-    float* d_lse = (float*)(h->gen + o_lse);
-    std::vector<float> qp((size_t)n * Hp, 0.0f);
-    for (int q = 0; q < n; ++q) std::memcpy(qp.data() + (size_t)q * Hp, queries + (size_t)q * h->H, sizeof(float) * h->H);
-    auto run = [&]() -> int {
-        int r = cache_gen_place(h, cg, h->gen);
-        if (r != FSMG_OK) return r;
-        HIPCK(h, hipMemcpyAsync(d_q, qp.data(), sizeof(float) * qp.size(), hipMemcpyHostToDevice, h->stream));
-        HIPCK(h, hipMemcpy2DAsync(d_z, sizeof(float) * ldl, logits, sizeof(float) * V1, sizeof(float) * V1, n, hipMemcpyHostToDevice, h->stream));
-        if ((r = cache_gen_step(h, cg, d_q, d_z, d_lse)) != FSMG_OK) return r;
-        if (out_cache_prob)
-            HIPCK(h, hipMemcpy2DAsync(out_cache_prob, sizeof(float) * V1, cg.pc, sizeof(float) * ldl, sizeof(float) * V1, n, hipMemcpyDeviceToHost, h->stream));
-        if (out_logprob)
-            HIPCK(h, hipMemcpy2DAsync(out_logprob, sizeof(float) * V1, d_z, sizeof(float) * ldl, sizeof(float) * V1, n, hipMemcpyDeviceToHost, h->stream));
-        if (out_lse) HIPCK(h, hipMemcpyAsync(out_lse, d_lse, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-        return FSMG_OK;
-    };
-    rc = run();
-    const hipError_t e = hipStreamSynchronize(h->stream);       // the host vectors go out of scope
-    if (rc == FSMG_OK && e != hipSuccess) return fail(h, FSMG_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    return rc;
+    return distribution(h, cache, cc, nullptr, n, queries, logits, group, out_cache_prob, out_logprob, out_lse);
 }
 
 int fsmg_cache_self_distribution(fsmg_handle h, fsmg_cache cache, const fsmg_cache_gen_config* cc, const fsmg_cache_self_config* sc,
@@ -746,58 +699,8 @@ int fsmg_cache_self_distribution(fsmg_handle h, fsmg_cache cache, const fsmg_cac
                                  const int32_t* self_len, int32_t S, const int32_t* group, float* out_cache_prob, float* out_logprob,
                                  float* out_lse) {
     if (!h) return FSMG_ERR_INVALID;
-    if (cache && !find_cache(h, cache)) return FSMG_ERR_INVALID;
-    if (n < 1 || n > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n must be in [1, 2^20]");
-    if (!queries || !logits || !self_len) return fail(h, FSMG_ERR_INVALID, "null queries / logits / self_len");
-    if (S < 0 || (S > 0 && (!self_keys || !self_values))) return fail(h, FSMG_ERR_INVALID, "S must be >= 0, with self_keys and self_values when S > 0");
-    if (!out_cache_prob && !out_logprob && !out_lse) return fail(h, FSMG_ERR_INVALID, "every output is null");
-    CacheGen cg;
-    int rc = cache_self_gen_check(h, cache, cc, sc, cache ? group : nullptr, n, S, true, &cg);
-    if (rc != FSMG_OK) return rc;
-    for (int i = 0; i < n; ++i)
-        if (self_len[i] < 0 || self_len[i] > S) return fail(h, FSMG_ERR_INVALID, "self_len outside [0, S]");
-    for (size_t i = 0; i < (size_t)n * S; ++i)
-        if (self_values[i] < 0 || self_values[i] >= h->V1) return fail(h, FSMG_ERR_TOKEN_RANGE, "own value outside [0, input_size]");
-    BEGIN_CALL(h);
-    if (cg.c && (rc = ensure_value_index(h, const_cast<fsmg_cache_s*>(cg.c))) != FSMG_OK) return rc;
-    // [cache_gen's block | queries n x Hp | logits n x ldl | lse n]
-    const int Hp = h->Hp, ldl = cg.ldl, V1 = h->V1, NP = cg.NP;
-    const size_t o_q = (size_t)round_up((int64_t)cache_gen_bytes(h, cg), 256);
-    const size_t o_z = (size_t)round_up((int64_t)(o_q + sizeof(float) * (size_t)n * Hp), 256);
-    const size_t o_lse = (size_t)round_up((int64_t)(o_z + sizeof(float) * (size_t)n * ldl), 256);
-    if ((rc = gen_reserve(h, o_lse + sizeof(float) * (size_t)n)) != FSMG_OK) return rc;
-    float* d_q = (float*)(h->gen + o_q);
-    float* d_z = (float*)(h->gen + o_z);
-    float* d_lse = (float*)(h->gen + o_lse);
-    std::vector<float> qp((size_t)n * Hp, 0.0f), kp((size_t)n * NP * Hp, 0.0f);      // the pad units are exact zeros
-    std::vector<int> vp((size_t)n * NP, 0);
-    for (int q = 0; q < n; ++q) {
-        std::memcpy(qp.data() + (size_t)q * Hp, queries + (size_t)q * h->H, sizeof(float) * h->H);
-        for (int e = 0; e < S; ++e) {
-            std::memcpy(kp.data() + ((size_t)q * NP + e) * Hp, self_keys + ((size_t)q * S + e) * h->H, sizeof(float) * h->H);
-            vp[(size_t)q * NP + e] = self_values[(size_t)q * S + e];
-        }
-    }
-    auto run = [&]() -> int {
-        int r = cache_gen_place(h, cg, h->gen);
-        if (r != FSMG_OK) return r;
-        HIPCK(h, hipMemcpyAsync(d_q, qp.data(), sizeof(float) * qp.size(), hipMemcpyHostToDevice, h->stream));
-        HIPCK(h, hipMemcpyAsync(cg.own_keys, kp.data(), sizeof(float) * kp.size(), hipMemcpyHostToDevice, h->stream));
-        HIPCK(h, hipMemcpyAsync(cg.d_val, vp.data(), sizeof(int) * vp.size(), hipMemcpyHostToDevice, h->stream));
-        HIPCK(h, hipMemcpyAsync(cg.d_len, self_len, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-        HIPCK(h, hipMemcpy2DAsync(d_z, sizeof(float) * ldl, logits, sizeof(float) * V1, sizeof(float) * V1, n, hipMemcpyHostToDevice, h->stream));
-        if ((r = cache_self_step(h, cg, 0, d_q, d_z, cg.d_val, NP, d_lse)) != FSMG_OK) return r;
-        if (out_cache_prob)
-            HIPCK(h, hipMemcpy2DAsync(out_cache_prob, sizeof(float) * V1, cg.pc, sizeof(float) * ldl, sizeof(float) * V1, n, hipMemcpyDeviceToHost, h->stream));
-        if (out_logprob)
-            HIPCK(h, hipMemcpy2DAsync(out_logprob, sizeof(float) * V1, d_z, sizeof(float) * ldl, sizeof(float) * V1, n, hipMemcpyDeviceToHost, h->stream));
-        if (out_lse) HIPCK(h, hipMemcpyAsync(out_lse, d_lse, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-        return FSMG_OK;
-    };
-    rc = run();
-    const hipError_t e = hipStreamSynchronize(h->stream);       // the host vectors go out of scope
-    if (rc == FSMG_OK && e != hipSuccess) return fail(h, FSMG_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    return rc;
+    const SelfEntries self{sc, self_keys, self_values, self_len, S};
+    return distribution(h, cache, cc, &self, n, queries, logits, group, out_cache_prob, out_logprob, out_lse);
 }
 
 int fsmg_cache_score(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const int32_t* tokens, const int32_t* group,
@@ -843,9 +746,7 @@ int fsmg_cache_self_attend(fsmg_handle h, fsmg_cache cache, const fsmg_cache_sel
     if (!thetas_ok(thetas, n_theta)) return fail(h, FSMG_ERR_INVALID, "every theta must be finite and >= 0");
     if (c && (c->H != h->H || c->Hp != h->Hp)) return fail(h, FSMG_ERR_INVALID, "the cache's hidden size is not the handle's");
     if (!c) group = nullptr;
-    if (group)
-        for (int r = 0; r < n_rows; ++r)
-            if (group[r] < 0 || group[r] >= c->G) return fail(h, FSMG_ERR_INVALID, "group id outside [0, groups of the cache)");
+    if (c && (rc = check_group_ids(h, group, n_rows, c->G)) != FSMG_OK) return rc;
     const int n = n_rows * n_pos;
     for (int i = 0; i < n; ++i)
         if (values[i] < 0 || values[i] >= h->V1) return fail(h, FSMG_ERR_TOKEN_RANGE, "value outside [0, input_size]");

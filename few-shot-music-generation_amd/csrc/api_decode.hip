@@ -61,17 +61,16 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
     d.ldl = (int)round_up(h->V1, 64);
     d.ldtok = P + num + 1;
     const size_t layer = (size_t)h->L * R * h->Hp, n = (size_t)R * num, cands = (size_t)R * W;
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off = (size_t)round_up((int64_t)(off + bytes), 256); return o; };
-    const size_t o_state = place(sizeof(float) * layer * (beam ? 4 : 3));
-    const size_t o_logits = place(sizeof(float) * R * d.ldl);
-    const size_t o_tok = place(sizeof(int) * R * d.ldtok);
-    const size_t o_beam = place(beam ? sizeof(float) * (R + 3 * cands + 3 * n) : 0);
-    const size_t o_out = place(sizeof(float) * (2 * n + (beam ? R : 0) + 1));
-    const size_t o_primer = place(sizeof(int) * n_primer);
-    const size_t o_err = place(sizeof(int));
-    const size_t o_extra = place(d.extra_bytes);
-    int rc = gen_reserve(h, off);
+    Carver cv;
+    const size_t o_state = cv.take(sizeof(float) * layer * (beam ? 4 : 3));
+    const size_t o_logits = cv.take(sizeof(float) * R * d.ldl);
+    const size_t o_tok = cv.take(sizeof(int) * R * d.ldtok);
+    const size_t o_beam = cv.take(beam ? sizeof(float) * (R + 3 * cands + 3 * n) : 0);
+    const size_t o_out = cv.take(sizeof(float) * (2 * n + (beam ? R : 0) + 1));
+    const size_t o_primer = cv.take(sizeof(int) * n_primer);
+    const size_t o_err = cv.take(sizeof(int));
+    const size_t o_extra = cv.take(d.extra_bytes);
+    int rc = gen_reserve(h, cv.off);
     if (rc != FSMG_OK) return rc;
     char* base = h->gen;
     d.h_in = (float*)(base + o_state);
@@ -168,11 +167,8 @@ int read_outputs(fsmg_model* h, const Decode& d, int32_t* out_tokens, float* out
 template <class Config>
 int check_config_common(fsmg_model* h, const Config* c, const char* name, int32_t version, const int32_t* primer, int64_t rows,
                         const char* rows_name) {
-    if (c->version != version)
-        return fail(h, FSMG_ERR_INVALID, std::string(name) + ".version is " + std::to_string(c->version) + ", this library expects " +
-                                             std::to_string(version));
-    for (int32_t r : c->reserved)
-        if (r != 0) return fail(h, FSMG_ERR_INVALID, std::string(name) + ".reserved must be zero");
+    const int rc = check_config_header(h, c, name, version);
+    if (rc != FSMG_OK) return rc;
     if (c->primer_on_device != 0 && c->primer_on_device != 1) return fail(h, FSMG_ERR_INVALID, "primer_on_device must be 0 or 1");
     if (c->primer_len > 0 && !primer) return fail(h, FSMG_ERR_INVALID, "primer_len > 0 needs a primer");
     if (rows > (1 << 20) || rows * ((int64_t)c->primer_len + c->num + 1) > (1LL << 30))
@@ -193,11 +189,8 @@ int check_gen_config(fsmg_model* h, const fsmg_gen_config* g, const int32_t* pri
 
 int check_gen_filters(fsmg_model* h, const fsmg_gen_filters* f) {
     if (!f) return FSMG_OK;
-    if (f->version != FSMG_GEN_FILTERS_VERSION)
-        return fail(h, FSMG_ERR_INVALID, "fsmg_gen_filters.version is " + std::to_string(f->version) + ", this library expects " +
-                                             std::to_string(FSMG_GEN_FILTERS_VERSION));
-    for (int i = 0; i < 8; ++i)
-        if (f->reserved[i] != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_gen_filters.reserved must be zero");
+    const int rc = check_config_header(h, f, "fsmg_gen_filters", FSMG_GEN_FILTERS_VERSION);
+    if (rc != FSMG_OK) return rc;
     if (!(f->top_p >= 0.f && f->top_p <= 1.f)) return fail(h, FSMG_ERR_INVALID, "top_p must be in [0, 1]");
     if (!(f->min_p >= 0.f && f->min_p <= 1.f)) return fail(h, FSMG_ERR_INVALID, "min_p must be in [0, 1]");
     if (!(f->repetition_penalty >= 0.f) || !std::isfinite(f->repetition_penalty))
@@ -436,11 +429,8 @@ int fsmg_maml_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_
 int fsmg_dstate_create(fsmg_handle h, const fsmg_dstate_config* c, fsmg_dstate* out) {
     if (!h) return FSMG_ERR_INVALID;
     if (!c || !out) return fail(h, FSMG_ERR_INVALID, "null fsmg_dstate_config / out");
-    if (c->version != FSMG_DSTATE_CONFIG_VERSION)
-        return fail(h, FSMG_ERR_INVALID, "fsmg_dstate_config.version is " + std::to_string(c->version) + ", this library expects " +
-                                             std::to_string(FSMG_DSTATE_CONFIG_VERSION));
-    for (int32_t r : c->reserved)
-        if (r != 0) return fail(h, FSMG_ERR_INVALID, "fsmg_dstate_config.reserved must be zero");
+    int rc = check_config_header(h, c, "fsmg_dstate_config", FSMG_DSTATE_CONFIG_VERSION);
+    if (rc != FSMG_OK) return rc;
     if (c->n_rows < 1 || c->n_rows > (1 << 20)) return fail(h, FSMG_ERR_INVALID, "n_rows must be in [1, 2^20]");
     if (c->history < 1 || (int64_t)c->n_rows * ((int64_t)c->history + 1) > (1LL << 30))
         return fail(h, FSMG_ERR_INVALID, "history must be >= 1 and n_rows * (history + 1) <= 2^30");
@@ -454,7 +444,7 @@ int fsmg_dstate_create(fsmg_handle h, const fsmg_dstate_config* c, fsmg_dstate* 
     st->h = (float*)st->mem;
     st->c = (float*)(st->mem + layer);
     st->ctx = (int*)(st->mem + 2 * layer);
-    const int rc = reset_state(h, st);
+    rc = reset_state(h, st);
     if (rc != FSMG_OK) { hipFree(st->mem); delete st; return rc; }
     h->dstates.push_back(st);
     *out = st;

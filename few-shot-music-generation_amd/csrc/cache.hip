@@ -1,5 +1,7 @@
 // Support-set neural cache (include/fsmg.h fsmg_cache_*): the fused attention kernel and the kernel that files a pass's
-// top-layer hidden states into a cache; k_cache_attend_self, the causal sibling over a row's own history.
+// top-layer hidden states into a cache; k_cache_attend_self, the causal sibling over a row's own history.  The two
+// attention kernels are one product loop (ca_key_tile), one online-softmax update (ca_update_masked) and one epilogue (ca_finish);
+// they differ in the keys they walk and in the masks they build.
 //
 // k_cache_attend: p_cache(y) = sum_{i : v_i = y} exp(theta (d_i - d_max)) / sum_i exp(theta (d_i - d_max)), d_i = q . k_i over the
 // Mg keys of the query's group, for up to 8 values of theta in one pass over the keys.  One 256-thread workgroup owns a tile of 32
@@ -44,13 +46,14 @@ __device__ __forceinline__ double ca_scale(double u, double m_from, double m_to)
     return ldexp(1.0, (int)fmax(ceil(u * m_from) - ceil(u * m_to), -4000.0));
 }
 
-// the four scores of a lane (keys kbase, kbase + 4, kbase + 8, kbase + 12 of the group, values v) into its running state
-__device__ __forceinline__ void ca_update(CaState& st, const f64x4& d, int kbase, int Mg, const int v[4], int y, const double* u,
-                                          int n_theta) {
+// the four scores of a lane (values v) into its running state; bit i of `mask` says that score i counts for this lane's query (a
+// tail key, a key the position does not see: skipped, not scored as zero)
+__device__ __forceinline__ void ca_update_masked(CaState& st, const f64x4& d, unsigned mask, const int v[4], int y, const double* u,
+                                                 int n_theta) {
     double mt = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-        if (kbase + 4 * i < Mg) mt = fmax(mt, d[i]);
+        if (mask >> i & 1u) mt = fmax(mt, d[i]);
     if (mt > st.m) {
 #pragma unroll
         for (int k = 0; k < CACHE_MAX_THETA; ++k)
@@ -66,7 +69,7 @@ __device__ __forceinline__ void ca_update(CaState& st, const f64x4& d, int kbase
         const double S = ceil(u[k] * st.m);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            if (kbase + 4 * i >= Mg) continue;          // a tail key has no mass
+            if (!(mask >> i & 1u)) continue;            // a masked key has no mass
             const double e = ca_exp2(fma(u[k], d[i], -S));
             st.den[k] += e;
             if (v[i] == y) st.num[k] += e;
@@ -104,16 +107,50 @@ __device__ __forceinline__ void ca_merge_lanes(CaState& st, int off, const doubl
     ca_merge(st, mo, deno, numo, u, n_theta);
 }
 
-// 16 keys x 32 queries x 16 k: the key fragment feeds both query halves; k order x, y, z, w
+// 16 keys x 32 (TWO) or 16 queries x 16 k: the key fragment feeds both query halves; k order x, y, z, w
+template <bool TWO>
 __device__ __forceinline__ void ca_mfma4(f64x4& acc0, f64x4& acc1, const float4& kv, const float4& b0, const float4& b1) {
     acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.x, (double)b0.x, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.x, (double)b1.x, acc1, 0, 0, 0);
+    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.x, (double)b1.x, acc1, 0, 0, 0);
     acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.y, (double)b0.y, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.y, (double)b1.y, acc1, 0, 0, 0);
+    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.y, (double)b1.y, acc1, 0, 0, 0);
     acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.z, (double)b0.z, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.z, (double)b1.z, acc1, 0, 0, 0);
+    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.z, (double)b1.z, acc1, 0, 0, 0);
     acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.w, (double)b0.w, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.w, (double)b1.w, acc1, 0, 0, 0);
+    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.w, (double)b1.w, acc1, 0, 0, 0);
+}
+
+// four floats at p, units c .. c + 3 of a vector of H: a pad unit reads as an exact zero whatever the memory holds
+__device__ __forceinline__ float4 ca_load4_h(const float* p, int c, int H) {
+    float4 v = *reinterpret_cast<const float4*>(p);
+    if (c + 0 >= H) v.x = 0.0f;
+    if (c + 1 >= H) v.y = 0.0f;
+    if (c + 2 >= H) v.z = 0.0f;
+    if (c + 3 >= H) v.w = 0.0f;
+    return v;
+}
+
+// one 16-key tile against the 32 queries in LDS, groups of 16 in increasing k; PADS: the key's pad units are masked (a vector of the
+// pass).  Two k groups per trip by hand: the loads of the second go out before the first one's products; a requested unroll of this
+// loop is refused by the compiler.
+template <bool PADS>
+__device__ __forceinline__ void ca_key_tile(const float* __restrict__ kp, const float* qp0, const float* qp1, int Hp, int H, int c0,
+                                            f64x4& acc0, f64x4& acc1) {
+    int k = 0;
+    for (; k + 32 <= Hp; k += 32) {
+        const float4 kv = PADS ? ca_load4_h(kp + k, c0 + k, H) : *reinterpret_cast<const float4*>(kp + k);
+        const float4 kw = PADS ? ca_load4_h(kp + k + 16, c0 + k + 16, H) : *reinterpret_cast<const float4*>(kp + k + 16);
+        const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k), c0v = *reinterpret_cast<const float4*>(qp0 + k + 16);
+        const float4 b1 = *reinterpret_cast<const float4*>(qp1 + k), c1v = *reinterpret_cast<const float4*>(qp1 + k + 16);
+        ca_mfma4<true>(acc0, acc1, kv, b0, b1);
+        ca_mfma4<true>(acc0, acc1, kw, c0v, c1v);
+    }
+    if (k < Hp) {
+        const float4 kv = PADS ? ca_load4_h(kp + k, c0 + k, H) : *reinterpret_cast<const float4*>(kp + k);
+        const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k);
+        const float4 b1 = *reinterpret_cast<const float4*>(qp1 + k);
+        ca_mfma4<true>(acc0, acc1, kv, b0, b1);
+    }
 }
 
 // what the four waves of a workgroup hand to the threads that merge them
@@ -121,6 +158,41 @@ struct CaMerge {
     double m[CA_WAVES][CA_QT];
     double den[CA_WAVES][CACHE_MAX_THETA][CA_QT], num[CA_WAVES][CACHE_MAX_THETA][CA_QT];
 };
+
+// The end of an attention workgroup (all 256 threads call it): the four key subsets of a wave as (0 + 1) + (2 + 3), read from the
+// lanes with l / 16 == 0; then the four waves through `mg` -- the bytes of the query tile, behind a barrier -- merged in the order
+// 0, 1, 2, 3 by thread s < CA_QT for slot s.  owner(s) is that slot's index into a row of `out` ([n_theta][n]), negative for an
+// empty slot: out[k * n + owner(s)] = num_k / den_k, exactly 0 where no mass met the target.
+template <class Owner>
+__device__ __forceinline__ void ca_finish(CaState& st0, CaState& st1, CaMerge& mg, const double* u, int n_theta, float* out, long long n,
+                                          Owner&& owner) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane & 15, ks = lane >> 4;
+    ca_merge_lanes(st0, 16, u, n_theta); ca_merge_lanes(st0, 32, u, n_theta);
+    ca_merge_lanes(st1, 16, u, n_theta); ca_merge_lanes(st1, 32, u, n_theta);
+    __syncthreads();                                 // every wave is done with the query tile
+    if (ks == 0) {
+        mg.m[wave][kq] = st0.m; mg.m[wave][16 + kq] = st1.m;
+#pragma unroll
+        for (int k = 0; k < CACHE_MAX_THETA; ++k) {
+            mg.den[wave][k][kq] = st0.den[k]; mg.den[wave][k][16 + kq] = st1.den[k];
+            mg.num[wave][k][kq] = st0.num[k]; mg.num[wave][k][16 + kq] = st1.num[k];
+        }
+    }
+    __syncthreads();
+    if (tid >= CA_QT) return;
+    const long long q = owner(tid);
+    if (q < 0) return;
+    CaState st;
+    for (int w = 0; w < CA_WAVES; ++w) {
+        double deno[CACHE_MAX_THETA], numo[CACHE_MAX_THETA];
+#pragma unroll
+        for (int k = 0; k < CACHE_MAX_THETA; ++k) { deno[k] = mg.den[w][k][tid]; numo[k] = mg.num[w][k][tid]; }
+        ca_merge(st, mg.m[w][tid], deno, numo, u, n_theta);
+    }
+#pragma unroll
+    for (int k = 0; k < CACHE_MAX_THETA; ++k)
+        if (k < n_theta) out[k * n + q] = st.num[k] == 0.0 ? 0.0f : (float)(st.num[k] / st.den[k]);
+}
 
 // where query id q lives and what its target is (CacheAttendArgs)
 __device__ __forceinline__ long long ca_query_row(const CacheAttendArgs& a, int q) {
@@ -169,121 +241,23 @@ __global__ __launch_bounds__(256) void k_cache_attend(CacheAttendArgs a) {
         const int krow = min(kt * 16 + kq, Mg - 1);
         const float* kp = kg + (long long)krow * Hp + 4 * ks;
         f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-        // (two k groups per trip by hand: the loads of the second go out before the first one's products; a requested unroll of this
-        // loop is refused by the compiler)
-        int k = 0;
-        for (; k + 32 <= Hp; k += 32) {
-            const float4 kv = *reinterpret_cast<const float4*>(kp + k), kw = *reinterpret_cast<const float4*>(kp + k + 16);
-            const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k), c0 = *reinterpret_cast<const float4*>(qp0 + k + 16);
-            const float4 b1 = *reinterpret_cast<const float4*>(qp1 + k), c1 = *reinterpret_cast<const float4*>(qp1 + k + 16);
-            ca_mfma4(acc0, acc1, kv, b0, b1);
-            ca_mfma4(acc0, acc1, kw, c0, c1);
-        }
-        if (k < Hp) {
-            const float4 kv = *reinterpret_cast<const float4*>(kp + k);
-            const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k);
-            const float4 b1 = *reinterpret_cast<const float4*>(qp1 + k);
-            ca_mfma4(acc0, acc1, kv, b0, b1);
-        }
+        ca_key_tile<false>(kp, qp0, qp1, Hp, Hp, 4 * ks, acc0, acc1);
         // accumulator register i of lane l (the fp64 instruction's layout): key 4 i + l / 16 of the tile against query l % 16
         const int kbase = kt * 16 + ks;
         int v[4];
+        unsigned m = 0;                             // a tail key has no mass
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = vg[min(kbase + 4 * i, Mg - 1)];
-        ca_update(st0, acc0, kbase, Mg, v, y0, theta, n_theta);
-        ca_update(st1, acc1, kbase, Mg, v, y1, theta, n_theta);
-    }
-    // the four key subsets of a wave: (0 + 1) + (2 + 3), read from the lanes with l / 16 == 0
-    ca_merge_lanes(st0, 16, theta, n_theta); ca_merge_lanes(st0, 32, theta, n_theta);
-    ca_merge_lanes(st1, 16, theta, n_theta); ca_merge_lanes(st1, 32, theta, n_theta);
-    __syncthreads();                                 // every wave is done with the query tile
-    if (ks == 0) {
-        mg.m[wave][kq] = st0.m; mg.m[wave][16 + kq] = st1.m;
-#pragma unroll
-        for (int k = 0; k < CACHE_MAX_THETA; ++k) {
-            mg.den[wave][k][kq] = st0.den[k]; mg.den[wave][k][16 + kq] = st1.den[k];
-            mg.num[wave][k][kq] = st0.num[k]; mg.num[wave][k][16 + kq] = st1.num[k];
+        for (int i = 0; i < 4; ++i) {
+            v[i] = vg[min(kbase + 4 * i, Mg - 1)];
+            if (kbase + 4 * i < Mg) m |= 1u << i;
         }
+        ca_update_masked(st0, acc0, m, v, y0, theta, n_theta);
+        ca_update_masked(st1, acc1, m, v, y1, theta, n_theta);
     }
-    __syncthreads();
-    if (tid >= CA_QT) return;
-    const int q = slots[tid];
-    if (q < 0) return;
-    CaState st;                                      // waves 0, 1, 2, 3 in this order
-    for (int w = 0; w < CA_WAVES; ++w) {
-        double deno[CACHE_MAX_THETA], numo[CACHE_MAX_THETA];
-#pragma unroll
-        for (int k = 0; k < CACHE_MAX_THETA; ++k) { deno[k] = mg.den[w][k][tid]; numo[k] = mg.num[w][k][tid]; }
-        ca_merge(st, mg.m[w][tid], deno, numo, theta, n_theta);
-    }
-#pragma unroll
-    for (int k = 0; k < CACHE_MAX_THETA; ++k)
-        if (k < n_theta) a.out[(long long)k * a.n + q] = st.num[k] == 0.0 ? 0.0f : (float)(st.num[k] / st.den[k]);
+    ca_finish(st0, st1, mg, theta, n_theta, a.out, a.n, [&](int s) { return (long long)slots[s]; });
 }
 
 // ---------------------------------------------------------------- self-cache (fsmg_kernels.h CacheSelfArgs)
-// ca_update with the tail rule kbase + 4 i < Mg generalised to a mask: bit i of `mask` says that score i of this lane counts for
-// this lane's query.  The arithmetic is ca_update's, statement by statement (k_cache_attend keeps its own copy and its bits).
-__device__ __forceinline__ void ca_update_masked(CaState& st, const f64x4& d, unsigned mask, const int v[4], int y, const double* u,
-                                                 int n_theta) {
-    double mt = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (mask >> i & 1u) mt = fmax(mt, d[i]);
-    if (mt > st.m) {
-#pragma unroll
-        for (int k = 0; k < CACHE_MAX_THETA; ++k)
-            if (k < n_theta) {
-                const double sc = ca_scale(u[k], st.m, mt);
-                st.den[k] *= sc; st.num[k] *= sc;
-            }
-        st.m = mt;
-    }
-#pragma unroll
-    for (int k = 0; k < CACHE_MAX_THETA; ++k) {
-        if (k >= n_theta) continue;
-        const double S = ceil(u[k] * st.m);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (!(mask >> i & 1u)) continue;            // a masked key has no mass
-            const double e = ca_exp2(fma(u[k], d[i], -S));
-            st.den[k] += e;
-            if (v[i] == y) st.num[k] += e;
-        }
-    }
-}
-
-// four floats at p, units c .. c + 3 of a vector of H: a pad unit reads as an exact zero whatever the memory holds
-__device__ __forceinline__ float4 ca_load4_h(const float* p, int c, int H) {
-    float4 v = *reinterpret_cast<const float4*>(p);
-    if (c + 0 >= H) v.x = 0.0f;
-    if (c + 1 >= H) v.y = 0.0f;
-    if (c + 2 >= H) v.z = 0.0f;
-    if (c + 3 >= H) v.w = 0.0f;
-    return v;
-}
-
-// one 16-key tile against the 32 queries in LDS, k_cache_attend's k order; PADS: the key's pad units are masked (a vector of the pass)
-template <bool PADS>
-__device__ __forceinline__ void ca_key_tile(const float* __restrict__ kp, const float* qp0, const float* qp1, int Hp, int H, int c0,
-                                            f64x4& acc0, f64x4& acc1) {
-    int k = 0;
-    for (; k + 32 <= Hp; k += 32) {
-        const float4 kv = PADS ? ca_load4_h(kp + k, c0 + k, H) : *reinterpret_cast<const float4*>(kp + k);
-        const float4 kw = PADS ? ca_load4_h(kp + k + 16, c0 + k + 16, H) : *reinterpret_cast<const float4*>(kp + k + 16);
-        const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k), c0v = *reinterpret_cast<const float4*>(qp0 + k + 16);
-        const float4 b1 = *reinterpret_cast<const float4*>(qp1 + k), c1v = *reinterpret_cast<const float4*>(qp1 + k + 16);
-        ca_mfma4(acc0, acc1, kv, b0, b1);
-        ca_mfma4(acc0, acc1, kw, c0v, c1v);
-    }
-    if (k < Hp) {
-        const float4 kv = PADS ? ca_load4_h(kp + k, c0 + k, H) : *reinterpret_cast<const float4*>(kp + k);
-        const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k);
-        const float4 b1 = *reinterpret_cast<const float4*>(qp1 + k);
-        ca_mfma4(acc0, acc1, kv, b0, b1);
-    }
-}
-
 __global__ __launch_bounds__(256) void k_cache_attend_self(CacheSelfArgs a) {
     // k_cache_attend's LDS plan: the query tile, then the waves' partials over the same bytes
     extern __shared__ double ca_lds[];
@@ -359,31 +333,8 @@ __global__ __launch_bounds__(256) void k_cache_attend_self(CacheSelfArgs a) {
         ca_update_masked(st0, acc0, m0, v, y0, theta, n_theta);
         ca_update_masked(st1, acc1, m1, v, y1, theta, n_theta);
     }
-    // k_cache_attend's merges: lanes 16 / 32 apart, then the four waves in order
-    ca_merge_lanes(st0, 16, theta, n_theta); ca_merge_lanes(st0, 32, theta, n_theta);
-    ca_merge_lanes(st1, 16, theta, n_theta); ca_merge_lanes(st1, 32, theta, n_theta);
-    __syncthreads();                                 // every wave is done with the query tile
-    if (ks == 0) {
-        mg.m[wave][kq] = st0.m; mg.m[wave][16 + kq] = st1.m;
-#pragma unroll
-        for (int k = 0; k < CACHE_MAX_THETA; ++k) {
-            mg.den[wave][k][kq] = st0.den[k]; mg.den[wave][k][16 + kq] = st1.den[k];
-            mg.num[wave][k][kq] = st0.num[k]; mg.num[wave][k][16 + kq] = st1.num[k];
-        }
-    }
-    __syncthreads();
-    if (tid >= CA_QT || t0 + tid >= T) return;
-    CaState st;                                      // waves 0, 1, 2, 3 in this order
-    for (int w = 0; w < CA_WAVES; ++w) {
-        double deno[CACHE_MAX_THETA], numo[CACHE_MAX_THETA];
-#pragma unroll
-        for (int k = 0; k < CACHE_MAX_THETA; ++k) { deno[k] = mg.den[w][k][tid]; numo[k] = mg.num[w][k][tid]; }
-        ca_merge(st, mg.m[w][tid], deno, numo, theta, n_theta);
-    }
-    const long long q = (long long)r * T + t0 + tid, n = (long long)a.n_rows * T;
-#pragma unroll
-    for (int k = 0; k < CACHE_MAX_THETA; ++k)
-        if (k < n_theta) a.out[k * n + q] = st.num[k] == 0.0 ? 0.0f : (float)(st.num[k] / st.den[k]);
+    ca_finish(st0, st1, mg, theta, n_theta, a.out, (long long)a.n_rows * T,
+              [&](int s) { return t0 + s < T ? (long long)r * T + t0 + s : -1LL; });
 }
 
 // Hs1: slot 1 of the pass's top-layer hidden states, time-major [T][B][Hp]; Y [T][B].  Pass row b is row r0 + b of the cache's
@@ -396,12 +347,8 @@ __global__ __launch_bounds__(256) void k_cache_fill(const float* __restrict__ Hs
         const long long row = idx / c4n;                // t * B + b
         const int c4 = (int)(idx - row * c4n);
         const int t = (int)(row / B), b = (int)(row - (long long)t * B);
-        float4 v = *reinterpret_cast<const float4*>(Hs1 + row * Hp + 4 * c4);
         const int c = 4 * c4;
-        if (c + 0 >= H) v.x = 0.0f;
-        if (c + 1 >= H) v.y = 0.0f;
-        if (c + 2 >= H) v.z = 0.0f;
-        if (c + 3 >= H) v.w = 0.0f;
+        const float4 v = ca_load4_h(Hs1 + row * Hp + c, c, H);
         const long long e = (r0 + b) * T + t;
         *reinterpret_cast<float4*>(keys + e * Hp + c) = v;
         if (c4 == 0) vals[e] = Y[row];
@@ -413,18 +360,6 @@ __global__ __launch_bounds__(256) void k_cache_fill(const float* __restrict__ Hs
 // fragment is read once, and the tile's queries are a few KiB that every wave of the group reads and the caches keep.  Four k groups
 // per trip so that eight (twelve) 16-byte loads are in flight: at a decode step one wave per SIMD is all the occupancy there is.
 // The k order is k_cache_attend's: groups of 16 in increasing k, x, y, z, w inside a group.
-template <bool TWO>
-__device__ __forceinline__ void cs_mfma4(f64x4& acc0, f64x4& acc1, const float4& kv, const float4& b0, const float4& b1) {
-    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.x, (double)b0.x, acc0, 0, 0, 0);
-    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.x, (double)b1.x, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.y, (double)b0.y, acc0, 0, 0, 0);
-    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.y, (double)b1.y, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.z, (double)b0.z, acc0, 0, 0, 0);
-    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.z, (double)b1.z, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.w, (double)b0.w, acc0, 0, 0, 0);
-    if (TWO) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)kv.w, (double)b1.w, acc1, 0, 0, 0);
-}
-
 template <bool TWO>
 __device__ __forceinline__ void cs_tile(const float* __restrict__ kp, const float* __restrict__ qp0, const float* __restrict__ qp1, int Hp,
                                         f64x4& acc0, f64x4& acc1) {
@@ -439,13 +374,13 @@ __device__ __forceinline__ void cs_tile(const float* __restrict__ kp, const floa
             b1[j] = TWO ? *reinterpret_cast<const float4*>(qp1 + k + 16 * j) : zero;
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) cs_mfma4<TWO>(acc0, acc1, kv[j], b0[j], b1[j]);
+        for (int j = 0; j < 4; ++j) ca_mfma4<TWO>(acc0, acc1, kv[j], b0[j], b1[j]);
     }
     for (; k < Hp; k += 16) {
         const float4 kv = *reinterpret_cast<const float4*>(kp + k);
         const float4 b0 = *reinterpret_cast<const float4*>(qp0 + k);
         const float4 b1 = TWO ? *reinterpret_cast<const float4*>(qp1 + k) : zero;
-        cs_mfma4<TWO>(acc0, acc1, kv, b0, b1);
+        ca_mfma4<TWO>(acc0, acc1, kv, b0, b1);
     }
 }
 

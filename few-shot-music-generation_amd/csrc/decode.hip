@@ -714,18 +714,50 @@ __device__ __forceinline__ double block_max(PickShared& sh, double v) {
     return t;
 }
 
-// fsmg_cache_score's mix_logprob (api_cache.hip) on the device: log((1 - lambda) exp(lp) + lambda pc) in fp64, rounded once
-__device__ __forceinline__ float mix_logprob(float lp, float pc, double log1m_lambda, double log_lambda) {
-    const double a = log1m_lambda + (double)lp;
-    const double b = log_lambda + log((double)pc);
-    if (a != a || b != b) return (float)(a + b);
-    const double hi = fmax(a, b), lo = fmin(a, b);
-    if (hi == -INFINITY) return -INFINITY;
-    return (float)(hi + log1p(exp(lo - hi)));
+// The three pieces k_cache_mix and k_cache_mix_self share (CacheMixArgs' comment has the steps).
+// w_i = ca_exp2(u d_i - S) written over the n scores at d; this thread's share of their sum goes on top of z
+__device__ __forceinline__ void mix_weights(double* d, int n, double u, double S, double& z) {
+    for (int i = threadIdx.x; i < n; i += PICK_THREADS) {
+        const double w = ca_exp2(fma(u, d[i], -S));
+        d[i] = w;
+        z += w;
+    }
 }
 
-// One row per workgroup; the steps are CacheMixArgs' comment.  The barriers inside the block reductions order a step's global
-// stores (the masses over D, the pc row) before the next step's loads: a workgroup reads back only what it wrote itself.
+// The distinct values of group g through the value index: the long segments one wave each (lanes stride the segment, then a
+// butterfly), the short ones one thread each; put(&value, mass) once per segment, by one thread (the value is loaded where it is
+// used, behind the mass's arithmetic).
+template <class Put>
+__device__ __forceinline__ void mix_walk(const CacheMixArgs& a, int g, const double* d, Put&& put) {
+    const int tid = threadIdx.x, Mg = a.Mg;
+    const int* order = a.order + (long long)g * Mg;
+    const int* seg_beg = a.seg_beg + (long long)g * Mg;
+    const int* seg_end = a.seg_end + (long long)g * Mg;
+    const int* seg_val = a.seg_val + (long long)g * Mg;
+    const int n_seg = a.n_seg[g], n_long = a.n_long[g], lane = tid & 63;
+    for (int sg = tid >> 6; sg < n_long; sg += PICK_THREADS / 64) {
+        const int j1 = seg_end[sg];
+        double mass = 0.0;
+        for (int j = seg_beg[sg] + lane; j < j1; j += 64) mass += d[order[j]];
+        for (int o = 32; o > 0; o >>= 1) mass += __shfl_xor(mass, o);
+        if (lane == 0) put(seg_val + sg, mass);
+    }
+    for (int sg = n_long + tid; sg < n_seg; sg += PICK_THREADS) {
+        const int j1 = seg_end[sg];
+        double mass = 0.0;
+        for (int j = seg_beg[sg]; j < j1; ++j) mass += d[order[j]];
+        put(seg_val + sg, mass);
+    }
+}
+
+// column v of the output row from the model's log-prob and the cache's probability
+__device__ __forceinline__ float mix_column(const CacheMixArgs& a, float lp, float p) {
+    if (!a.mix) return lp;
+    return p == 0.0f ? (float)(a.log1m_lambda + (double)lp) : mix_logprob(lp, p, a.log1m_lambda, a.log_lambda);
+}
+
+// One row per workgroup.  The barriers inside the block reductions order a step's global stores (the masses over D, the pc row)
+// before the next step's loads: a workgroup reads back only what it wrote itself.
 __global__ __launch_bounds__(PICK_THREADS) void k_cache_mix(CacheMixArgs a) {
     __shared__ PickShared sh;
     const int b = blockIdx.x, tid = threadIdx.x, Mg = a.Mg, ncols = a.ncols;
@@ -740,44 +772,15 @@ __global__ __launch_bounds__(PICK_THREADS) void k_cache_mix(CacheMixArgs a) {
     double m = -INFINITY;
     for (int i = tid; i < Mg; i += PICK_THREADS) m = fmax(m, d[i]);
     m = block_max(sh, m);
-    const double S = ceil(a.u * m);
     double z = 0.0;
-    for (int i = tid; i < Mg; i += PICK_THREADS) {
-        const double w = ca_exp2(fma(a.u, d[i], -S));
-        d[i] = w;
-        z += w;
-    }
+    mix_weights(d, Mg, a.u, ceil(a.u * m), z);
     for (int v = tid; v < ncols; v += PICK_THREADS) pc[v] = 0.0f;
     const double Z = block_sum(sh, z);
 
-    // the distinct values of the group: the long segments of the value index one wave each (lanes stride the segment, then a
-    // butterfly), the short ones one thread each
-    const int* order = a.order + (long long)g * Mg;
-    const int* seg_beg = a.seg_beg + (long long)g * Mg;
-    const int* seg_end = a.seg_end + (long long)g * Mg;
-    const int* seg_val = a.seg_val + (long long)g * Mg;
-    const int n_seg = a.n_seg[g], n_long = a.n_long[g], lane = tid & 63;
-    for (int sg = tid >> 6; sg < n_long; sg += PICK_THREADS / 64) {
-        const int j1 = seg_end[sg];
-        double mass = 0.0;
-        for (int j = seg_beg[sg] + lane; j < j1; j += 64) mass += d[order[j]];
-        for (int o = 32; o > 0; o >>= 1) mass += __shfl_xor(mass, o);
-        if (lane == 0) pc[seg_val[sg]] = mass == 0.0 ? 0.0f : (float)(mass / Z);
-    }
-    for (int sg = n_long + tid; sg < n_seg; sg += PICK_THREADS) {
-        const int j1 = seg_end[sg];
-        double mass = 0.0;
-        for (int j = seg_beg[sg]; j < j1; ++j) mass += d[order[j]];
-        pc[seg_val[sg]] = mass == 0.0 ? 0.0f : (float)(mass / Z);
-    }
+    mix_walk(a, g, d, [&](const int* v, double mass) { pc[*v] = mass == 0.0 ? 0.0f : (float)(mass / Z); });
     __syncthreads();
 
-    for (int v = tid; v < ncols; v += PICK_THREADS) {
-        const float lp = row[v] - lse, p = pc[v];
-        float out = lp;
-        if (a.mix) out = p == 0.0f ? (float)(a.log1m_lambda + (double)lp) : mix_logprob(lp, p, a.log1m_lambda, a.log_lambda);
-        row[v] = out;
-    }
+    for (int v = tid; v < ncols; v += PICK_THREADS) row[v] = mix_column(a, row[v] - lse, pc[v]);
     if (tid == 0 && a.out_lse) a.out_lse[b] = lse;
 }
 
@@ -809,40 +812,12 @@ __global__ __launch_bounds__(PICK_THREADS) void k_cache_mix_self(CacheMixSelfArg
     }
     const double S = ceil(a.u * m);
     double z = 0.0;
-    for (int i = tid; i < Mg; i += PICK_THREADS) {
-        const double w = ca_exp2(fma(a.u, d[i], -S));
-        d[i] = w;
-        z += w;
-    }
-    for (int i = tid; i < n; i += PICK_THREADS) {
-        const double w = ca_exp2(fma(a.u, d2[i], -S));
-        d2[i] = w;
-        z += w;
-    }
+    mix_weights(d, Mg, a.u, S, z);
+    mix_weights(d2, n, a.u, S, z);
     for (int v = tid; v < ncols; v += PICK_THREADS) pm[v] = 0.0;
     const double Z = block_sum(sh, z);
 
-    if (Mg > 0) {                                   // k_cache_mix's walk of the value index, the masses kept in fp64
-        const int g = a.row_group[b];
-        const int* order = a.order + (long long)g * Mg;
-        const int* seg_beg = a.seg_beg + (long long)g * Mg;
-        const int* seg_end = a.seg_end + (long long)g * Mg;
-        const int* seg_val = a.seg_val + (long long)g * Mg;
-        const int n_seg = a.n_seg[g], n_long = a.n_long[g], lane = tid & 63;
-        for (int sg = tid >> 6; sg < n_long; sg += PICK_THREADS / 64) {
-            const int j1 = seg_end[sg];
-            double mass = 0.0;
-            for (int j = seg_beg[sg] + lane; j < j1; j += 64) mass += d[order[j]];
-            for (int o = 32; o > 0; o >>= 1) mass += __shfl_xor(mass, o);
-            if (lane == 0) pm[seg_val[sg]] = mass;
-        }
-        for (int sg = n_long + tid; sg < n_seg; sg += PICK_THREADS) {
-            const int j1 = seg_end[sg];
-            double mass = 0.0;
-            for (int j = seg_beg[sg]; j < j1; ++j) mass += d[order[j]];
-            pm[seg_val[sg]] = mass;
-        }
-    }
+    if (Mg > 0) mix_walk(a, a.row_group[b], d, [&](const int* v, double mass) { pm[*v] = mass; });     // the masses kept in fp64
     __syncthreads();
     // the own entries: the first visible occurrence of a value owns its column and sums its later duplicates in entry order
     for (int j = tid; j < n; j += PICK_THREADS) {
@@ -859,11 +834,9 @@ __global__ __launch_bounds__(PICK_THREADS) void k_cache_mix_self(CacheMixSelfArg
 
     for (int v = tid; v < ncols; v += PICK_THREADS) {
         const double mass = pm[v];
-        const float lp = row[v] - lse, p = mass == 0.0 ? 0.0f : (float)(mass / Z);
+        const float p = mass == 0.0 ? 0.0f : (float)(mass / Z);
         pc[v] = p;
-        float out = lp;
-        if (a.mix) out = p == 0.0f ? (float)(a.log1m_lambda + (double)lp) : mix_logprob(lp, p, a.log1m_lambda, a.log_lambda);
-        row[v] = out;
+        row[v] = mix_column(a, row[v] - lse, p);
     }
     if (tid == 0 && a.out_lse) a.out_lse[b] = lse;
 }

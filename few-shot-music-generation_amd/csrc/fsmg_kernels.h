@@ -468,6 +468,16 @@ __device__ __forceinline__ double ca_exp2(double t) {
     const float e = exp2f(hi);
     return (double)fmaf(e, lo * CA_LN2, e);
 }
+// log((1 - lambda) exp(lp) + lambda pc) in fp64, rounded once: fsmg_cache_score's mixture on the host, k_cache_mix's on the device,
+// each with its own side's log / log1p / exp
+__host__ __device__ inline float mix_logprob(float lp, float pc, double log1m_lambda, double log_lambda) {
+    const double a = log1m_lambda + (double)lp;                         // lambda = 0: 0 + lp
+    const double b = log_lambda + log((double)pc);                      // -inf at pc = 0 (and at lambda = 0)
+    if (a != a || b != b) return (float)(a + b);
+    const double hi = fmax(a, b), lo = fmin(a, b);
+    if (hi == -INFINITY) return -INFINITY;
+    return (float)(hi + log1p(exp(lo - hi)));
+}
 struct CacheAttendArgs {
     const float* keys;          // [G][Mg][Hp], pad units exact zeros
     const int* vals;            // [G][Mg]
@@ -541,7 +551,7 @@ hipError_t launch_cache_scores(hipStream_t s, const CacheScoresArgs& a);
 //          long segment is summed by one wave (lanes stride it, then a butterfly), a short one by one thread in entry order -- a
 //          vocabulary of thousands gives thousands of segments of one or two entries --, either way in an order that depends on
 //          the segment's length alone; pc[r][v] = fl32(mass / Z), exactly 0 for a column no entry holds;
-//   z''_v  = fl32(logaddexp(log1p(-lambda) + lp_v, log(lambda) + log(pc_v))) in fp64 (fsmg_cache_score's mix_logprob), over the logits
+//   z''_v  = fl32(logaddexp(log1p(-lambda) + lp_v, log(lambda) + log(pc_v))) in fp64 (mix_logprob above), over the logits
 //          row in place; fl32(log1p(-lambda) + lp_v) where pc_v = 0; lambda = 0 (mix == 0): lp_v.
 // A row's bits depend on its logits row, its scores, its group's values, theta and lambda alone.
 constexpr int CACHE_MIX_SHORT = 32;

@@ -9,7 +9,7 @@
 //   api_step.hip      train / eval / MAML-style entry points          api_comm.hip  RCCL glue (fsmg_comm_*)
 //   api_unigram.hip   unigram baseline                                 api_debug.hip debug reads, timers, clock probe
 //   api_decode.hip    decoding: fsmg_generate(_filtered), fsmg_beam_search, their MAML twins, fsmg_sample (one driver); decode states (fsmg_dstate_*)
-//   api_score.hip     scoring of given songs: fsmg_score, fsmg_maml_score
+//   api_score.hip     scoring of given songs: fsmg_score, fsmg_maml_score; the pass driver of every score-style call (run_passes)
 //   api_cache.hip     support-set neural cache: fsmg_cache_* (build, attend, score and eval against a cache; the cache side of
 //                     cache-conditioned generation, whose entry points sit beside the decode driver in api_decode.hip)
 #pragma once
@@ -321,6 +321,24 @@ inline int fail(fsmg_model* h, int code, const std::string& msg) {
     return code;
 }
 
+// the head of every versioned config struct of include/fsmg.h: not null, the version this library was built for, zero reserved words
+template <class Config>
+int check_config_header(fsmg_model* h, const Config* c, const char* name, int32_t version) {
+    if (!c) return fail(h, FSMG_ERR_INVALID, std::string("null ") + name);
+    if (c->version != version)
+        return fail(h, FSMG_ERR_INVALID, std::string(name) + ".version is " + std::to_string(c->version) + ", this library expects " +
+                                             std::to_string(version));
+    for (int32_t r : c->reserved)
+        if (r != 0) return fail(h, FSMG_ERR_INVALID, std::string(name) + ".reserved must be zero");
+    return FSMG_OK;
+}
+
+// carves one allocation into pieces that start 256 bytes aligned: take() returns a piece's offset, `off` is what has been used
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off = (size_t)round_up((int64_t)(off + bytes), 256); return o; }
+};
+
 #define HIPCK(h, call)                                                                         \
     do {                                                                                       \
         hipError_t e_ = (call);                                                                \
@@ -622,6 +640,17 @@ int poll_skipped(fsmg_model* h);
 int report(fsmg_model* h, int what);
 int check_tokens_and_read(fsmg_model* h, const float* d_src, float scale, float* host_out, int n, bool train_tail = false);
 int after_update(fsmg_model* h, float grad_scale, float* loss);
+// api_score.hip: what the score-style calls share (fsmg_score, fsmg_cache_build, fsmg_cache_score and their variants)
+// The R rows of `tokens` ([R][T], on the host or the device) in passes of P rows.  Per pass of B rows from row r0: choose_schedule,
+// one stream for the call (ov_call = false), ensure_cs where the pass reads the column-split copies, stage_tokens; launch(r0, B)
+// enqueues the pass's launches and read_back(r0, B) its device-to-host copies; the error word comes back behind them with the
+// pass's one stream synchronisation and is cleared.  After a time-out the handle has switched to per-step launches and the pass is
+// repeated that way, at most once.
+int run_passes(fsmg_model* h, const int32_t* tokens, int R, int P, int on_device, const std::function<int(int, int)>& launch,
+               const std::function<int(int, int)>& read_back);
+int check_host_tokens(fsmg_model* h, const int32_t* tokens, size_t n);      // every id in [0, input_size), before any device work
+// out[r] = -mean of logprob[r][t0 .. t1) over R rows of T: fp64, increasing t, rounded once -- bitwise recomputable from the log-probs
+void row_nll(const float* logprob, int R, int T, int nll_first, int nll_count, float* out);
 // api_decode.hip / api_cache.hip: what cache-conditioned generation shares between the decode driver and the cache
 int gen_reserve(fsmg_model* h, size_t bytes);              // h->gen holds at least `bytes`: grown between calls, after a stream sync
 fsmg_cache_s* find_cache(fsmg_model* h, fsmg_cache c);     // the cache if this handle owns it, else nullptr with the error set
