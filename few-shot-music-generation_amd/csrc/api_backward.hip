@@ -145,18 +145,21 @@ int backward(fsmg_model* h, int B, int part) {
         }
         // tail[1] = the mean loss of the pass: nobody reads it before the step's last kernels, so it rides with the slab sums (one
         // block of a launch that keeps the rest of the chip busy) instead of costing a launch behind the cross entropy
-        const bool loss_in_batch = late.r.count > 0;
+        // (a padding-masked pass: the masked sum over n_valid, a launch of its own below)
+        const bool masked = h->masked_call;
+        const bool loss_in_batch = late.r.count > 0 && !masked;
         if (loss_in_batch) GEMMCK(late.mean(h->ce, rows, h->G + h->n_flat + 1));
         GEMMCK(late.flush());
         // tail[0] = squared norm of the embedding-slice gradients, tail[1] = mean loss of the pass, tail[2] / tail[3] = time-out /
         // token-range indicators: one block's work, which rides in the embedding gradient's first launch where the partials are there already
         const int nb = sqnorm_blocks(rows * h->Ep);
-        const SumPartialsArgs sp{h->partials, nb, h->G + h->n_flat + 0, h->d_err, loss_in_batch ? nullptr : h->ce, (int)rows, h->G + h->n_flat + 1};
+        const SumPartialsArgs sp{h->partials, nb, h->G + h->n_flat + 0, h->d_err, (loss_in_batch || masked) ? nullptr : h->ce, (int)rows, h->G + h->n_flat + 1};
         const bool sum_rides = dx_sq_done && h->dXpart != nullptr && h->tok_first != nullptr;
         HIPCK(h, launch_embed_grad(ts, h->X, (int)rows, h->dXemb, h->Ep, h->G + h->off_emb, h->tok_first, h->tok_count, h->dXpart, sum_rides ? &sp : nullptr));
         h->tok_table_open = false;
         if (!dx_sq_done) HIPCK(h, launch_sqnorm_partials(ts, h->dXemb, rows * h->Ep, h->partials));
         if (!sum_rides) HIPCK(h, launch_sum_partials(ts, sp.partials, sp.n, sp.dst, sp.flag_src, sp.ce, sp.ce_n, sp.loss_out));
+        if (masked) HIPCK(h, launch_loss_reduce_w(ts, h->ce, T, B, B, 1, h->roww, h->d_nvalid, h->G + h->n_flat + 1));
         if (ts != s) {
             HIPCK(h, hipEventRecord(h->ev_side, ts));
             late.s = s;

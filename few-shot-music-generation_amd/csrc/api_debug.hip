@@ -69,6 +69,15 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
     else if (!std::strcmp(what, "dlogits")) { src = dlogits_buf(h); cap = rows * h->V1p; }
     else if (!std::strcmp(what, "lse")) { src = h->lse; cap = rows; }
     else if (!std::strcmp(what, "ce")) { src = h->ce; cap = rows; }
+    else if (!std::strcmp(what, "row_weight")) { src = h->roww; cap = h->last_mask_groups > 0 ? rows : 0; }      // the last masked pass's w[t * B + b]
+    else if (!std::strcmp(what, "n_valid")) {                                                                   // ... and its groups' n_valid
+        if (count > h->last_mask_groups) return fail(h, FSMG_ERR_SIZE, "debug read larger than the buffer");
+        std::vector<int> nv((size_t)count);
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        HIPCK(h, hipMemcpy(nv.data(), h->d_nvalid, sizeof(int) * count, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < count; ++i) host[i] = (float)nv[(size_t)i];
+        return FSMG_OK;
+    }
     else if (!std::strcmp(what, "dx")) { src = h->dXemb; cap = rows * h->Ep; }
     else if (!std::strcmp(what, "dh")) { src = h->dH; cap = rows * Hp; }
     else if (!std::strcmp(what, "gnorm")) { src = h->d_gnorm; cap = 1; }

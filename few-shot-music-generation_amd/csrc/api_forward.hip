@@ -22,6 +22,15 @@ int stage_tokens(fsmg_model* h, const int32_t* support, int n_sup, const int32_t
     return FSMG_OK;
 }
 
+// the lengths of a masked pass -> the handle's fixed buffer, support rows first (host lengths have been validated by the caller)
+int stage_lengths(fsmg_model* h, const int32_t* support_len, int n_sup, const int32_t* query_len, int n_qry, int on_device) {
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (n_sup > 0) HIPCK(h, hipMemcpyAsync(h->d_len, support_len, sizeof(int) * n_sup, kind, h->stream));
+    if (n_qry > 0) HIPCK(h, hipMemcpyAsync(h->d_len + n_sup, query_len, sizeof(int) * n_qry, kind, h->stream));
+    h->cur_len = h->d_len;
+    return FSMG_OK;
+}
+
 // (INT_MAX, 0) in every entry of the occurrence table
 int reset_tok_table(fsmg_model* h) {
     if (!h->tok_first) return FSMG_OK;
@@ -34,6 +43,13 @@ int reset_tok_table(fsmg_model* h) {
 // train: the pass ends in k_embed_grad, which wants the occurrence table of the input ids
 int token_prep(fsmg_model* h, int n_sup, int n_qry, bool train) {
     const bool table = train && h->tok_first != nullptr;
+    if (h->masked_call) {      // padding-masked pass: the row weights + n_valid, and fixed ids behind every song's end
+        HIPCK(h, launch_row_weights(h->stream, h->cur_len, n_sup + n_qry, h->T, h->mask_rpg, h->mask_groups, h->roww, h->d_nvalid, h->d_err));
+        HIPCK(h, launch_token_prep_len(h->stream, h->cur_sup, n_sup, h->cur_qry, n_qry, h->T, h->V, h->V,
+                                       h->X, h->Y, h->d_err, table ? h->tok_first : nullptr, table ? h->tok_count : nullptr, h->cur_len));
+        h->last_mask_groups = h->mask_groups;
+        return FSMG_OK;
+    }
     HIPCK(h, launch_token_prep(h->stream, h->cur_sup, n_sup, h->cur_qry, n_qry, h->T, h->V, h->V,
                                h->X, h->Y, h->d_err, table ? h->tok_first : nullptr, table ? h->tok_count : nullptr));
     return FSMG_OK;
@@ -57,6 +73,11 @@ inline void fused_softmax_args(fsmg_model* h, GemmArgs& g) {
 // ... and one kernel turns them into lse, ce, the row scales and c_r * h_r, and patches E[r][y_r] (all rows of the pass)
 int ce_finish(fsmg_model* h, hipStream_t s, int B, int64_t rows) {
     ScopedTimer tm(h, "ce");
+    if (h->masked_call) {
+        HIPCK(h, launch_ce_finish_w(s, h->ce_part, h->ce_nparts, h->Y, (int)rows, h->roww, h->logits, h->V1p,
+                                    h->lse, h->ce, h->crow, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Hsc, h->Hp, h->d_err, h->d_counters + 4));
+        return FSMG_OK;
+    }
     HIPCK(h, launch_ce_finish(s, h->ce_part, h->ce_nparts, h->Y, (int)rows, (float)(1.0 / ((double)rows + 1e-12)), h->logits, h->V1p,
                               h->lse, h->ce, h->crow, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Hsc, h->Hp, h->d_err, h->d_counters + 4));
     return FSMG_OK;
@@ -65,6 +86,11 @@ int ce_rows(fsmg_model* h, hipStream_t s, int B, int t0, int t1, int64_t rows_to
     ScopedTimer tm(h, "ce");
     const int64_t r0 = (int64_t)t0 * B, m = (int64_t)(t1 - t0) * B;
     // (a row is read into registers as a whole before any of it is written back: dlogits may be the logits buffer itself)
+    if (h->masked_call) {
+        HIPCK(h, launch_ce_rows_w(s, h->logits + (size_t)r0 * h->V1p, h->V1p, (int)m, h->V1, h->Y + r0, h->lse + r0,
+                                  h->ce + r0, dlogits_buf(h) + (size_t)r0 * h->V1p, h->roww + r0));
+        return FSMG_OK;
+    }
     HIPCK(h, launch_ce_rows(s, h->logits + (size_t)r0 * h->V1p, h->V1p, (int)m, h->V1, h->Y + r0, h->lse + r0,
                             h->ce + r0, dlogits_buf(h) + (size_t)r0 * h->V1p, (float)(1.0 / ((double)rows_total + 1e-12))));
     return FSMG_OK;
@@ -276,7 +302,8 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
     }
     if (!want_dlogits && head == HEAD_LOSS) {        // (a train pass reduces its loss in backward(): k_sum_partials, no launch of its own)
         ScopedTimer tm(h, "ce");
-        HIPCK(h, launch_loss_reduce(s, h->ce, T, B, rows_per_group, ngroups, loss_out));
+        if (h->masked_call) HIPCK(h, launch_loss_reduce_w(s, h->ce, T, B, rows_per_group, ngroups, h->roww, h->d_nvalid, loss_out));
+        else HIPCK(h, launch_loss_reduce(s, h->ce, T, B, rows_per_group, ngroups, loss_out));
     }
     h->lastB = B;
     return FSMG_OK;

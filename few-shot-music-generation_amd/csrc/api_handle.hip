@@ -110,6 +110,7 @@ static void forget_turn(fsmg_model* h) {          // fsmg_destroy: nobody may wa
 
 int begin_call(fsmg_model* h, bool keep_pending) {
     HIPCK(h, hipSetDevice(h->device));
+    h->masked_call = false;
     const int rc = take_turn(h);
     if (rc != FSMG_OK) return rc;
     return keep_pending ? FSMG_OK : settle_pending(h);
@@ -327,6 +328,7 @@ int fsmg_destroy(fsmg_handle h) {
     if (h->khx) hipFree(h->khx);
     if (h->P_saved) hipFree(h->P_saved);
     for (int* t : h->table) if (t) hipFree(t);
+    for (int* t : h->table_len) if (t) hipFree(t);
     if (h->d_idx) hipFree(h->d_idx);
     if (h->d_gather) hipFree(h->d_gather);
     if (h->d_eval) hipFree(h->d_eval);

@@ -127,6 +127,7 @@ int ensure_scratch(fsmg_model* h, int B) {
     const int64_t o_cslab2 = place(4 * (int64_t)MAX_SPLIT * std::max<int64_t>(h->V1p, G4));
     const int64_t o_arena = place(4 * std::max<int64_t>(arena_need, 64));
     const int64_t o_score = place(4 * 4 * rows);        // fsmg_score's four per-position outputs (last: nothing else moves)
+    const int64_t o_len = place(4 * (int64_t)B), o_roww = place(4 * rows), o_nvalid = place(4 * std::max<int64_t>(B, 64));     // padding-masked passes
     hipError_t e = hipMalloc((void**)&h->scratch, off);
     if (e != hipSuccess) {
         h->Bcap = 0;
@@ -159,6 +160,7 @@ int ensure_scratch(fsmg_model* h, int B) {
     h->slabs = (float*)(s + o_slab); h->colsum_slabs = (float*)(s + o_cslab); h->slab_cap = slab_need;
     h->slabs2 = (float*)(s + o_slab2); h->colsum_slabs2 = (float*)(s + o_cslab2);
     h->score_out = (float*)(s + o_score);
+    h->d_len = (int*)(s + o_len); h->roww = (float*)(s + o_roww); h->d_nvalid = (int*)(s + o_nvalid);
     h->arena = (float*)(s + o_arena); h->arena_cap = arena_need; h->arena_off = 0;
     h->Bcap = B;
     return FSMG_OK;

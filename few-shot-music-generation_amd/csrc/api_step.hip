@@ -39,7 +39,8 @@ int forward_backward_core(fsmg_model* h, int32_t N, int32_t K, int32_t Q, Stage&
     if ((rc = stage()) != FSMG_OK) return rc;
     const int n_sup = N * K, n_qry = N * Q;
     h->bucket0_recorded = false;
-    const std::string shape_key = std::to_string(n_sup) + ":" + std::to_string(n_qry);
+    // (a padding-masked pass has launches of its own -- the row weights, the weighted cross entropy, the masked loss: its own graphs)
+    const std::string shape_key = std::to_string(n_sup) + ":" + std::to_string(n_qry) + (h->masked_call ? ":m" : "");
     if (h->dp_split && !with_update) {
         // episode-parallel order: bucket 0 (softmax gradients, 56 % of the bytes at cfg-B) is final when the first graph ends and
         // travels while the second one (BPTT, weight / input gradients, embedding gradient) runs
@@ -107,6 +108,26 @@ int dp_train_step(fsmg_model* h, float* loss, FB&& forward_backward) {
     return FSMG_OK;
 }
 
+// host lengths of a masked call, checked before any device work: every one in [1, T]
+int validate_lengths(fsmg_model* h, const int32_t* len, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (len[i] < 1 || len[i] > h->T)
+            return fail(h, FSMG_ERR_INVALID, "length " + std::to_string(len[i]) + " of sequence " + std::to_string(i) + " is outside [1, max_len]");
+    return FSMG_OK;
+}
+// what every masked train entry point checks before it touches the device
+int validate_masked_args(fsmg_model* h, const int32_t* support_len, const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int32_t on_device) {
+    if (!support_len || !query_len) return fail(h, FSMG_ERR_INVALID, "null length pointer");
+    int rc = validate_shape(h, N, K, Q);
+    if (rc != FSMG_OK || on_device) return rc;
+    if ((rc = validate_lengths(h, support_len, (int64_t)N * K)) != FSMG_OK) return rc;
+    return validate_lengths(h, query_len, (int64_t)N * Q);
+}
+// the call in progress is a padding-masked pass over `groups` groups of `rows_per_group` sequences (behind BEGIN_CALL, which clears the flag)
+inline void begin_masked(fsmg_model* h, int rows_per_group, int groups) {
+    h->masked_call = true; h->mask_rpg = rows_per_group; h->mask_groups = groups;
+}
+
 // forward + backward + update as ONE captured graph (17 us between two graph launches at cfg-B otherwise)
 template <class Stage>
 int fused_train_step(fsmg_model* h, int32_t N, int32_t K, int32_t Q, float* loss, Stage&& stage) {
@@ -145,6 +166,7 @@ int fsmg_upload_table(fsmg_handle h, int32_t table_id, const int32_t* host_table
     BEGIN_CALL(h);
     HIPCK(h, hipStreamSynchronize(h->stream));
     if (h->table[table_id]) { hipFree(h->table[table_id]); h->table[table_id] = nullptr; h->table_rows[table_id] = 0; }
+    if (h->table_len[table_id]) { hipFree(h->table_len[table_id]); h->table_len[table_id] = nullptr; }      // (the lengths of the table that was here)
     const size_t bytes = sizeof(int) * (size_t)n_songs * h->T;
     if (hipMalloc((void**)&h->table[table_id], bytes) != hipSuccess) return fail(h, FSMG_ERR_NOMEM, "hipMalloc(token table) failed");
     HIPCK(h, hipMemcpy(h->table[table_id], host_table, bytes, hipMemcpyHostToDevice));
@@ -152,8 +174,24 @@ int fsmg_upload_table(fsmg_handle h, int32_t table_id, const int32_t* host_table
     return FSMG_OK;
 }
 
+int fsmg_upload_table_lengths(fsmg_handle h, int32_t table_id, const int32_t* lengths, int64_t n_songs) {
+    if (!h || !lengths || table_id < 0 || table_id >= fsmg_model::MAX_TABLES || n_songs <= 0)
+        return h ? fail(h, FSMG_ERR_INVALID, "bad table id / size / null lengths") : FSMG_ERR_INVALID;
+    if (!h->table[table_id] || h->table_rows[table_id] != n_songs)
+        return fail(h, FSMG_ERR_STATE, "fsmg_upload_table_lengths needs a token table of the same n_songs uploaded under this id first");
+    int rc = validate_lengths(h, lengths, n_songs);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (h->table_len[table_id]) { hipFree(h->table_len[table_id]); h->table_len[table_id] = nullptr; }
+    if (hipMalloc((void**)&h->table_len[table_id], sizeof(int) * (size_t)n_songs) != hipSuccess) return fail(h, FSMG_ERR_NOMEM, "hipMalloc(table lengths) failed");
+    HIPCK(h, hipMemcpy(h->table_len[table_id], lengths, sizeof(int) * (size_t)n_songs, hipMemcpyHostToDevice));
+    return FSMG_OK;
+}
+
 static int stage_indexed(fsmg_handle h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry) {
     if (table_id < 0 || table_id >= fsmg_model::MAX_TABLES || !h->table[table_id]) return fail(h, FSMG_ERR_STATE, "no token table uploaded under this id");
+    if (h->masked_call && !h->table_len[table_id]) return fail(h, FSMG_ERR_STATE, "the table under this id has no lengths (fsmg_upload_table_lengths)");
     const int n = n_sup + n_qry;
     if (h->idx_cap < n) {
         HIPCK(h, hipStreamSynchronize(h->stream));
@@ -163,7 +201,13 @@ static int stage_indexed(fsmg_handle h, int32_t table_id, const int32_t* sup_idx
     }
     if (n_sup > 0) HIPCK(h, hipMemcpyAsync(h->d_idx, sup_idx, sizeof(int) * n_sup, hipMemcpyHostToDevice, h->stream));
     if (n_qry > 0) HIPCK(h, hipMemcpyAsync(h->d_idx + n_sup, qry_idx, sizeof(int) * n_qry, hipMemcpyHostToDevice, h->stream));
-    HIPCK(h, launch_gather_rows(h->stream, h->table[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id], h->d_tok, h->d_err));
+    if (h->masked_call) {      // the rows' lengths travel with them
+        HIPCK(h, launch_gather_rows_len(h->stream, h->table[table_id], h->table_len[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id],
+                                        h->d_tok, h->d_len, h->d_err));
+        h->cur_len = h->d_len;
+    } else {
+        HIPCK(h, launch_gather_rows(h->stream, h->table[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id], h->d_tok, h->d_err));
+    }
     h->cur_sup = h->d_tok; h->cur_qry = h->d_tok + (size_t)n_sup * h->T;
     return FSMG_OK;
 }
@@ -221,6 +265,49 @@ int fsmg_train_step(fsmg_handle h, const int32_t* support, const int32_t* query,
     if (!h || !support || !query) return FSMG_ERR_INVALID;
     BEGIN_CALL(h, true);        // the pass orders itself behind a pending update where it first reads the softmax parameters (forward())
     return fused_train_step(h, N, K, Q, loss, [&]() { return stage_tokens(h, support, N * K, query, N * Q, tokens_on_device); });
+}
+
+// ---- padding-masked forms: the same passes with a length per sequence; position t of row b is scored iff t < len[b]
+int fsmg_train_step_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                           int32_t N, int32_t K, int32_t Q, int32_t tokens_on_device, float* loss) {
+    if (!h || !support || !query) return FSMG_ERR_INVALID;
+    const int rcv = validate_masked_args(h, support_len, query_len, N, K, Q, tokens_on_device);
+    if (rcv != FSMG_OK) return rcv;
+    BEGIN_CALL(h, true);
+    begin_masked(h, N * (K + Q), 1);
+    return fused_train_step(h, N, K, Q, loss, [&]() {
+        const int r = stage_tokens(h, support, N * K, query, N * Q, tokens_on_device);
+        return r != FSMG_OK ? r : stage_lengths(h, support_len, N * K, query_len, N * Q, tokens_on_device);
+    });
+}
+
+int fsmg_forward_backward_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                                 int32_t N, int32_t K, int32_t Q, int32_t tokens_on_device) {
+    if (!h || !support || !query) return FSMG_ERR_INVALID;
+    const int rcv = validate_masked_args(h, support_len, query_len, N, K, Q, tokens_on_device);
+    if (rcv != FSMG_OK) return rcv;
+    BEGIN_CALL(h, true);
+    begin_masked(h, N * (K + Q), 1);
+    return forward_backward_core(h, N, K, Q, [&]() {
+        const int r = stage_tokens(h, support, N * K, query, N * Q, tokens_on_device);
+        return r != FSMG_OK ? r : stage_lengths(h, support_len, N * K, query_len, N * Q, tokens_on_device);
+    });
+}
+
+int fsmg_train_step_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                                   int32_t N, int32_t K, int32_t Q, float* loss) {
+    if (!h || !support_idx || !query_idx) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h, true);
+    begin_masked(h, N * (K + Q), 1);
+    return fused_train_step(h, N, K, Q, loss, [&]() { return stage_indexed(h, table_id, support_idx, N * K, query_idx, N * Q); });
+}
+
+int fsmg_forward_backward_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                                         int32_t N, int32_t K, int32_t Q) {
+    if (!h || !support_idx || !query_idx) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h, true);
+    begin_masked(h, N * (K + Q), 1);
+    return forward_backward_core(h, N, K, Q, [&]() { return stage_indexed(h, table_id, support_idx, N * K, query_idx, N * Q); });
 }
 
 // ---- cfg-E (BASELINE.json configs[4]): MAML-style inner / outer loop, first order.  DESIGN.md "cfg-E".
@@ -359,14 +446,20 @@ int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_
 
 extern "C" {
 
-int fsmg_eval_batch(fsmg_handle h, const int32_t* queries, int32_t n_episodes, int32_t N, int32_t Q,
-                    int32_t tokens_on_device, float* nll) {
+// query_len != nullptr: the padding-masked form -- each episode's NLL over its own n_valid
+static int eval_batch_core(fsmg_handle h, const int32_t* queries, const int32_t* query_len, int32_t n_episodes, int32_t N, int32_t Q,
+                           int32_t tokens_on_device, float* nll, bool masked) {
     if (!h || !queries || !nll || n_episodes <= 0) return FSMG_ERR_INVALID;
-    BEGIN_CALL(h);
     int rc = validate_shape(h, N, 0, Q);
     if (rc != FSMG_OK) return rc;
     const int per = N * Q;
     if (per <= 0) return fail(h, FSMG_ERR_INVALID, "empty query set");
+    if (masked) {
+        if (!query_len) return fail(h, FSMG_ERR_INVALID, "null length pointer");
+        if ((int64_t)n_episodes * per > (1LL << 30)) return fail(h, FSMG_ERR_INVALID, "too many query rows");
+        if (!tokens_on_device && (rc = validate_lengths(h, query_len, (int64_t)n_episodes * per)) != FSMG_OK) return rc;
+    }
+    BEGIN_CALL(h);
     // validation episodes are independent: batch up to EVAL_EPISODES of them per pass so that the recurrent
     // chain (one launch per time step regardless of the row count) is amortised over many rows
     constexpr int EVAL_EPISODES = 16;
@@ -387,7 +480,11 @@ int fsmg_eval_batch(fsmg_handle h, const int32_t* queries, int32_t n_episodes, i
         if (pass_reads_cs(h, B, false) && (rc = ensure_cs(h)) != FSMG_OK) return rc;
         const int32_t* q = queries + (size_t)e0 * per * h->T;
         if ((rc = stage_tokens(h, q, 0, q, B, tokens_on_device)) != FSMG_OK) return rc;
-        rc = run_graphed(h, "ev:" + std::to_string(per) + ":" + std::to_string(ne), [&]() -> int {
+        if (masked) {
+            begin_masked(h, per, ne);
+            if ((rc = stage_lengths(h, query_len, 0, query_len + (size_t)e0 * per, B, tokens_on_device)) != FSMG_OK) return rc;
+        }
+        rc = run_graphed(h, (masked ? "evm:" : "ev:") + std::to_string(per) + ":" + std::to_string(ne), [&]() -> int {
             int r = token_prep(h, 0, B);
             if (r == FSMG_OK) r = forward(h, B, per, ne, h->d_eval, false);
             return r;
@@ -409,8 +506,22 @@ int fsmg_eval_batch(fsmg_handle h, const int32_t* queries, int32_t n_episodes, i
     return FSMG_OK;
 }
 
+int fsmg_eval_batch(fsmg_handle h, const int32_t* queries, int32_t n_episodes, int32_t N, int32_t Q,
+                    int32_t tokens_on_device, float* nll) {
+    return eval_batch_core(h, queries, nullptr, n_episodes, N, Q, tokens_on_device, nll, false);
+}
+
 int fsmg_eval_step(fsmg_handle h, const int32_t* query, int32_t N, int32_t Q, int32_t tokens_on_device, float* nll) {
     return fsmg_eval_batch(h, query, 1, N, Q, tokens_on_device, nll);
+}
+
+int fsmg_eval_batch_masked(fsmg_handle h, const int32_t* queries, const int32_t* query_len, int32_t n_episodes, int32_t N, int32_t Q,
+                           int32_t tokens_on_device, float* nll) {
+    return eval_batch_core(h, queries, query_len, n_episodes, N, Q, tokens_on_device, nll, true);
+}
+
+int fsmg_eval_step_masked(fsmg_handle h, const int32_t* query, const int32_t* query_len, int32_t N, int32_t Q, int32_t tokens_on_device, float* nll) {
+    return fsmg_eval_batch_masked(h, query, query_len, 1, N, Q, tokens_on_device, nll);
 }
 
 }  // extern "C"

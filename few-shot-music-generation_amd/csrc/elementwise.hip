@@ -186,9 +186,16 @@ __global__ __launch_bounds__(256) void k_multi_op(const MultiOps r) {
 // Reference: convert_tokens_to_input_and_target + concat (src/models/base_model.py:63-86,
 // src/models/lstm_baseline.py:91-96).  One thread per (sequence b, step t): coalesced reads
 // of the [nseq][T] token rows, time-major writes.
-__global__ void k_token_prep(const int* __restrict__ support, int n_support, const int* __restrict__ query,
+// MASKED (a padding-masked pass, len[b] in [1, T] per sequence): a position t >= len[b] is not scored, and nothing that is scored reads
+// its input, so it gets fixed ids -- the start word as input, 0 as target -- and the pass does not depend on what the caller put behind a
+// song's end, neither its values nor (the embedding gradient's two-level sum goes by a token's count) its summation orders.  The range
+// check still covers every token of the row.
+__device__ __forceinline__ int clamp_len(int l, int T) { return min(max(l, 1), T); }
+template <bool MASKED>
+__device__ __forceinline__ void token_prep_body(const int* __restrict__ support, int n_support, const int* __restrict__ query,
                              int n_query, int T, int vocab, int start_word, int* __restrict__ X,
-                             int* __restrict__ Y, int* __restrict__ err_flag, int* __restrict__ tok_first, int* __restrict__ tok_count) {
+                             int* __restrict__ Y, int* __restrict__ err_flag, int* __restrict__ tok_first, int* __restrict__ tok_count,
+                             const int* __restrict__ len) {
     __shared__ int s_key[512], s_cnt[512], s_min[512];
     const int B = n_support + n_query;
     const long long total = (long long)B * T;
@@ -205,7 +212,13 @@ __global__ void k_token_prep(const int* __restrict__ support, int n_support, con
                 atomicOr(err_flag, 1);
                 tok = min(max(tok, 0), vocab - 1);
             }
-            Y[(long long)t * B + b] = tok;
+            int tok_y = tok;
+            if (MASKED) {
+                const int l = clamp_len(len[b], T);
+                if (t >= l) tok_y = 0;
+                if (t + 1 >= l) tok = start_word;          // (from here on `tok` is the input id of position t + 1)
+            }
+            Y[(long long)t * B + b] = tok_y;
             if (t + 1 < T) X[(long long)(t + 1) * B + b] = tok;
             if (t == 0) X[b] = start_word;
         }
@@ -238,6 +251,17 @@ __global__ void k_token_prep(const int* __restrict__ support, int n_support, con
         }
     }
 }
+__global__ void k_token_prep(const int* __restrict__ support, int n_support, const int* __restrict__ query,
+                             int n_query, int T, int vocab, int start_word, int* __restrict__ X,
+                             int* __restrict__ Y, int* __restrict__ err_flag, int* __restrict__ tok_first, int* __restrict__ tok_count) {
+    token_prep_body<false>(support, n_support, query, n_query, T, vocab, start_word, X, Y, err_flag, tok_first, tok_count, nullptr);
+}
+__global__ void k_token_prep_len(const int* __restrict__ support, int n_support, const int* __restrict__ query,
+                                 int n_query, int T, int vocab, int start_word, int* __restrict__ X,
+                                 int* __restrict__ Y, int* __restrict__ err_flag, int* __restrict__ tok_first, int* __restrict__ tok_count,
+                                 const int* __restrict__ len) {
+    token_prep_body<true>(support, n_support, query, n_query, T, vocab, start_word, X, Y, err_flag, tok_first, tok_count, len);
+}
 
 // Episode gather from the device-resident split table (reference src/data/episode.py:62-74 fills the same rows from its
 // per-song cache): out[r][t] = table[idx[r]][t]; an index outside [0, n_songs) raises the token-range flag.
@@ -252,15 +276,60 @@ __global__ void k_gather_rows(const int* __restrict__ table, const int* __restri
     }
 }
 
+// The same gather for a table that has lengths (fsmg_upload_table_lengths): the gathered rows' lengths travel with them.
+__global__ void k_gather_rows_len(const int* __restrict__ table, const int* __restrict__ table_len, const int* __restrict__ idx, int n_rows, int T,
+                                  int n_songs, int* __restrict__ out, int* __restrict__ out_len, int* __restrict__ err_flag) {
+    const long long total = (long long)n_rows * T;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int r = (int)(i / T), t = (int)(i % T);
+        int song = idx[r];
+        if (song < 0 || song >= n_songs) { atomicOr(err_flag, 1); song = 0; }
+        out[i] = table[(long long)song * T + t];
+        if (t == 0) out_len[r] = table_len[song];
+    }
+}
+
+// ---------------------------------------------------------------- per-row loss weights of a padding-masked pass
+// Rows b of group g = b / rpg (a train pass: one group; an eval batch: one group per episode) have lengths len[b] in [1, T]:
+//   n_valid[g] = sum of the group's lengths (integers: exact, whatever the order),
+//   w[t * B + b] = t < len[b] ? (float)(1 / ((double)n_valid[g] + 1e-12)) : 0      (device row order).
+// With every length T that is the constant the unmasked kernels are given.  A length outside [1, T] raises the token-range flag and
+// is clamped.  Block (g, y): every block of a group sums the group's lengths itself, block y == 0 publishes the sum.
+__global__ __launch_bounds__(256) void k_row_weights(const int* __restrict__ len, int B, int T, int rpg, float* __restrict__ w,
+                                                     int* __restrict__ n_valid, int* __restrict__ err_flag) {
+    __shared__ int s_sum;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) s_sum = 0;
+    __syncthreads();
+    int mine = 0;
+    bool bad = false;
+    for (int i = tid; i < rpg; i += 256) {
+        const int l = len[g * rpg + i];
+        if (l < 1 || l > T) bad = true;
+        mine += clamp_len(l, T);
+    }
+    if (mine) atomicAdd(&s_sum, mine);
+    if (bad && blockIdx.y == 0) atomicOr(err_flag, 1);
+    __syncthreads();
+    const int nv = s_sum;
+    if (blockIdx.y == 0 && tid == 0) n_valid[g] = nv;
+    const float wv = (float)(1.0 / ((double)nv + 1e-12));
+    const long long n = (long long)T * rpg;
+    for (long long j = (long long)blockIdx.y * 256 + tid; j < n; j += (long long)gridDim.y * 256) {
+        const int t = (int)(j / rpg), b = g * rpg + (int)(j % rpg);
+        w[(long long)t * B + b] = (t < clamp_len(len[b], T)) ? wv : 0.0f;
+    }
+}
+
 // ---------------------------------------------------------------- softmax cross entropy per row (K6)
 // One 256-thread block per logits row; pass 1 row max, pass 2 sum exp (second read is an L2 hit).
 // With dlogits != nullptr a third pass (the row is cache-hot) also writes the loss gradient
 // dlogits = (softmax - onehot) * inv_n for the two backward projection GEMMs, zero in the pad columns.
 // dlogits may BE logits (the train pass writes the gradient over the logits it has just read, fsmg_model::inplace_dlogits): neither
 // pointer is `restrict`, and a thread writes only elements it has itself read before.
-__global__ __launch_bounds__(256) void k_ce_rows(const float* logits, int ld, int n_vocab,
-                                                 const int* __restrict__ tgt, float* __restrict__ lse,
-                                                 float* __restrict__ ce, float* dlogits, float inv_n) {
+__device__ __forceinline__ void ce_rows_body(const float* logits, int ld, int n_vocab,
+                                             const int* __restrict__ tgt, float* __restrict__ lse,
+                                             float* __restrict__ ce, float* dlogits, float inv_n) {
     __shared__ float sh[4];
     __shared__ float s_lse;
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -307,6 +376,17 @@ __global__ __launch_bounds__(256) void k_ce_rows(const float* logits, int ld, in
         __builtin_nontemporal_store(d.x, drow + v); __builtin_nontemporal_store(d.y, drow + v + 1);
         __builtin_nontemporal_store(d.z, drow + v + 2); __builtin_nontemporal_store(d.w, drow + v + 3);
     }
+}
+__global__ __launch_bounds__(256) void k_ce_rows(const float* logits, int ld, int n_vocab,
+                                                 const int* __restrict__ tgt, float* __restrict__ lse,
+                                                 float* __restrict__ ce, float* dlogits, float inv_n) {
+    ce_rows_body(logits, ld, n_vocab, tgt, lse, ce, dlogits, inv_n);
+}
+// padding-masked pass: the row's own weight w[r] (k_row_weights) in place of the constant 1 / n -- a masked row's gradient is +-0
+__global__ __launch_bounds__(256) void k_ce_rows_w(const float* logits, int ld, int n_vocab,
+                                                   const int* __restrict__ tgt, float* __restrict__ lse,
+                                                   float* __restrict__ ce, float* dlogits, const float* __restrict__ w) {
+    ce_rows_body(logits, ld, n_vocab, tgt, lse, ce, dlogits, w[blockIdx.x]);
 }
 
 // Register-resident variant for rows of up to NV * 1024 floats (cfg-B: 10 float4 per thread): the row is read ONCE,
@@ -385,6 +465,13 @@ __global__ __launch_bounds__(256) void k_ce_rows_reg(const float* logits, int ld
     __shared__ float sh[8];
     ce_row_reg<NV, NT>(sh, blockIdx.x, logits, ld, n_vocab, tgt, lse, ce, dlogits, inv_n);
 }
+template <int NV, bool NT>
+__global__ __launch_bounds__(256) void k_ce_rows_reg_w(const float* logits, int ld, int n_vocab,
+                                                       const int* __restrict__ tgt, float* __restrict__ lse,
+                                                       float* __restrict__ ce, float* dlogits, const float* __restrict__ w) {     // the row's own weight (padding-masked pass)
+    __shared__ float sh[8];
+    ce_row_reg<NV, NT>(sh, blockIdx.x, logits, ld, n_vocab, tgt, lse, ce, dlogits, w[blockIdx.x]);
+}
 
 // One wave per row: combine the per-slice (max, sum exp) partials written by the projection GEMM's epilogue.
 __global__ __launch_bounds__(256) void k_ce_combine(const float2* __restrict__ part, int nparts,
@@ -405,15 +492,19 @@ __global__ __launch_bounds__(256) void k_ce_combine(const float2* __restrict__ p
 }
 
 // Second half of the fused softmax of a train pass (launch_ce_finish, fsmg_kernels.h).  One wave per row.
-__global__ __launch_bounds__(256) void k_ce_finish(const float2* __restrict__ part, int nparts,
-                                                   const int* __restrict__ tgt, int rows, float inv_n, float* E, int ld,
-                                                   float* __restrict__ lse, float* __restrict__ ce, float* __restrict__ crow,
-                                                   const float* __restrict__ hs, float* __restrict__ hs_scaled, int hp,
-                                                   int* err_flag, unsigned long long* range_counter) {
+// W: the row's weight is w[row] (padding-masked pass, k_row_weights) instead of the constant inv_n.  A masked row (weight 0) keeps the
+// range check and the patch of E[r][y_r]; its c_r and its row of hs_scaled are 0, so it enters dH, dW and dd as exact zeros.
+template <bool W>
+__device__ __forceinline__ void ce_finish_body(const float2* __restrict__ part, int nparts,
+                                               const int* __restrict__ tgt, int rows, float inv_n, const float* __restrict__ w, float* E, int ld,
+                                               float* __restrict__ lse, float* __restrict__ ce, float* __restrict__ crow,
+                                               const float* __restrict__ hs, float* __restrict__ hs_scaled, int hp,
+                                               int* err_flag, unsigned long long* range_counter) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
     // the weighted column sums of dW read crow[K .. K + 15] past this pass's rows (times zero-filled B rows): never a stale Inf / NaN there
     if (blockIdx.x == 0 && threadIdx.x < 32) crow[rows + threadIdx.x] = 0.0f;
     if (row >= rows) return;
+    if (W) inv_n = w[row];
     const float2* p = part + (long long)row * nparts;
     float S = 0.0f;                               // = sum_v exp(x_v): the partials are un-shifted sums of the stored E values
     for (int i = lane; i < nparts; i += 64) S += p[i].y;
@@ -446,6 +537,20 @@ __global__ __launch_bounds__(256) void k_ce_finish(const float2* __restrict__ pa
         *reinterpret_cast<float4*>(orow + i) = v;
     }
 }
+__global__ __launch_bounds__(256) void k_ce_finish(const float2* __restrict__ part, int nparts,
+                                                   const int* __restrict__ tgt, int rows, float inv_n, float* E, int ld,
+                                                   float* __restrict__ lse, float* __restrict__ ce, float* __restrict__ crow,
+                                                   const float* __restrict__ hs, float* __restrict__ hs_scaled, int hp,
+                                                   int* err_flag, unsigned long long* range_counter) {
+    ce_finish_body<false>(part, nparts, tgt, rows, inv_n, nullptr, E, ld, lse, ce, crow, hs, hs_scaled, hp, err_flag, range_counter);
+}
+__global__ __launch_bounds__(256) void k_ce_finish_w(const float2* __restrict__ part, int nparts,
+                                                     const int* __restrict__ tgt, int rows, const float* __restrict__ w, float* E, int ld,
+                                                     float* __restrict__ lse, float* __restrict__ ce, float* __restrict__ crow,
+                                                     const float* __restrict__ hs, float* __restrict__ hs_scaled, int hp,
+                                                     int* err_flag, unsigned long long* range_counter) {
+    ce_finish_body<true>(part, nparts, tgt, rows, 0.0f, w, E, ld, lse, ce, crow, hs, hs_scaled, hp, err_flag, range_counter);
+}
 
 __global__ __launch_bounds__(256) void k_scale_rows(float* C, const float* __restrict__ row_scale, long long n4, int n_per_row4) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
@@ -471,6 +576,26 @@ __global__ __launch_bounds__(256) void k_loss_reduce(const float* __restrict__ c
     if (lane == 0) sh[wave] = s;
     __syncthreads();
     if (tid == 0) out[g] = (float)(((sh[0] + sh[1]) + (sh[2] + sh[3])) / ((double)n + 1e-12));
+}
+
+// Padding-masked form: out[g] = sum over the group's positions with w != 0 of ce / (n_valid[g] + 1e-12).  The positions are walked and
+// added in k_loss_reduce's order (a masked position adds nothing), so with every length T the result has k_loss_reduce's bits -- and,
+// with one group, those of the mean loss that rides in k_multi_op / sum_partials_body on an unmasked train pass.
+__global__ __launch_bounds__(256) void k_loss_reduce_w(const float* __restrict__ ce, int T, int B, int rpg, const float* __restrict__ w,
+                                                       const int* __restrict__ n_valid, float* __restrict__ out) {
+    __shared__ double sh[4];
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = T * rpg;
+    double s = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        const int t = i / rpg, b = g * rpg + i % rpg;
+        const long long r = (long long)t * B + b;
+        if (w[r] != 0.0f) s += (double)ce[r];
+    }
+    s = wave_sum_d(s);
+    if (lane == 0) sh[wave] = s;
+    __syncthreads();
+    if (tid == 0) out[g] = (float)(((sh[0] + sh[1]) + (sh[2] + sh[3])) / ((double)n_valid[g] + 1e-12));
 }
 
 // ---------------------------------------------------------------- embedding gradient (K7 tail)
@@ -918,6 +1043,18 @@ hipError_t launch_token_prep(hipStream_t s, const int* support, int n_support, c
     return hipGetLastError();
 }
 
+hipError_t launch_token_prep_len(hipStream_t s, const int* support, int n_support, const int* query, int n_query,
+                                 int T, int vocab, int start_word, int* X, int* Y, int* err_flag, int* tok_first, int* tok_count, const int* len) {
+    const long long total = (long long)(n_support + n_query) * T;
+    if (total <= 0) return hipSuccess;
+    if (len == nullptr) return hipErrorInvalidValue;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_token_prep_len, dim3(blocks), dim3(256), 0, s, support, n_support, query, n_query, T, vocab,
+                       start_word, X, Y, err_flag, tok_first, tok_count, len);
+    return hipGetLastError();
+}
+
 hipError_t launch_ce_rows(hipStream_t s, const float* logits, int ld, int rows, int n_vocab, const int* tgt,
                           float* lse, float* ce, float* dlogits, float inv_n) {
     if (rows <= 0) return hipSuccess;
@@ -932,6 +1069,59 @@ hipError_t launch_ce_rows(hipStream_t s, const float* logits, int ld, int rows, 
         else hipLaunchKernelGGL((k_ce_rows_reg<12, false>), dim3(rows), dim3(256), 0, s, logits, ld, n_vocab, tgt, lse, ce, dlogits, inv_n);
     }
     else hipLaunchKernelGGL(k_ce_rows, dim3(rows), dim3(256), 0, s, logits, ld, n_vocab, tgt, lse, ce, dlogits, inv_n);
+    return hipGetLastError();
+}
+
+hipError_t launch_ce_rows_w(hipStream_t s, const float* logits, int ld, int rows, int n_vocab, const int* tgt,
+                            float* lse, float* ce, float* dlogits, const float* w) {
+    if (rows <= 0) return hipSuccess;
+    if (w == nullptr) return hipErrorInvalidValue;
+    static const int nt = std::getenv("FSMG_CE_NT") ? (std::atoi(std::getenv("FSMG_CE_NT")) != 0) : 1;      // (launch_ce_rows' knob)
+    if (ld <= 6 * 1024) {
+        if (nt) hipLaunchKernelGGL((k_ce_rows_reg_w<6, true>), dim3(rows), dim3(256), 0, s, logits, ld, n_vocab, tgt, lse, ce, dlogits, w);
+        else hipLaunchKernelGGL((k_ce_rows_reg_w<6, false>), dim3(rows), dim3(256), 0, s, logits, ld, n_vocab, tgt, lse, ce, dlogits, w);
+    } else if (ld <= 12 * 1024) {
+        if (nt) hipLaunchKernelGGL((k_ce_rows_reg_w<12, true>), dim3(rows), dim3(256), 0, s, logits, ld, n_vocab, tgt, lse, ce, dlogits, w);
+        else hipLaunchKernelGGL((k_ce_rows_reg_w<12, false>), dim3(rows), dim3(256), 0, s, logits, ld, n_vocab, tgt, lse, ce, dlogits, w);
+    }
+    else hipLaunchKernelGGL(k_ce_rows_w, dim3(rows), dim3(256), 0, s, logits, ld, n_vocab, tgt, lse, ce, dlogits, w);
+    return hipGetLastError();
+}
+
+hipError_t launch_row_weights(hipStream_t s, const int* len, int B, int T, int rows_per_group, int ngroups, float* w, int* n_valid, int* err_flag) {
+    if (B <= 0) return hipSuccess;
+    if (rows_per_group <= 0 || ngroups <= 0 || (long long)rows_per_group * ngroups != B || len == nullptr || w == nullptr || n_valid == nullptr ||
+        err_flag == nullptr || ngroups > 65535) return hipErrorInvalidValue;
+    const long long n = (long long)T * rows_per_group;
+    const int by = (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 64));
+    hipLaunchKernelGGL(k_row_weights, dim3(ngroups, by), dim3(256), 0, s, len, B, T, rows_per_group, w, n_valid, err_flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_loss_reduce_w(hipStream_t s, const float* ce, int T, int B, int rows_per_group, int ngroups, const float* w,
+                                const int* n_valid, float* out) {
+    if (w == nullptr || n_valid == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_loss_reduce_w, dim3(ngroups), dim3(256), 0, s, ce, T, B, rows_per_group, w, n_valid, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_ce_finish_w(hipStream_t s, const float2* part, int nparts, const int* tgt, int rows, const float* w,
+                              float* E, int ld, float* lse, float* ce, float* crow, const float* hs, float* hs_scaled, int hp,
+                              int* err_flag, long long* range_counter) {
+    if (rows <= 0) return hipSuccess;
+    if ((hp & 3) != 0 || err_flag == nullptr || range_counter == nullptr || w == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ce_finish_w, dim3((rows + 3) / 4), dim3(256), 0, s, part, nparts, tgt, rows, w, E, ld, lse, ce, crow,
+                       hs, hs_scaled, hp, err_flag, (unsigned long long*)range_counter);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_rows_len(hipStream_t s, const int* table, const int* table_len, const int* idx, int n_rows, int T, int n_songs,
+                                  int* out, int* out_len, int* err_flag) {
+    if (n_rows <= 0) return hipSuccess;
+    if (table_len == nullptr || out_len == nullptr) return hipErrorInvalidValue;
+    const long long total = (long long)n_rows * T;
+    hipLaunchKernelGGL(k_gather_rows_len, dim3((int)std::min<long long>((total + 255) / 256, 1024)), dim3(256), 0, s, table, table_len, idx, n_rows, T,
+                       n_songs, out, out_len, err_flag);
     return hipGetLastError();
 }
 

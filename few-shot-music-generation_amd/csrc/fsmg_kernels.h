@@ -287,6 +287,27 @@ hipError_t launch_token_prep(hipStream_t s, const int* support, int n_support, c
 // (softmax - onehot) * inv_n (pad columns zero) for the backward projection GEMMs
 hipError_t launch_ce_rows(hipStream_t s, const float* logits, int ld, int rows, int n_vocab, const int* tgt,
                           float* lse, float* ce, float* dlogits, float inv_n);
+// ---- padding-masked passes (fsmg_*_masked): a weight per row in place of the constant inv_n
+// w[t * B + b] = t < len[b] ? (float)(1 / ((double)n_valid[g] + 1e-12)) : 0 and n_valid[g] = the sum of the lengths of group g = b / rows_per_group
+// (B = rows_per_group * ngroups rows, lengths in [1, T]; one outside raises *err_flag |= 1 and is clamped).  Integer sums: deterministic.
+hipError_t launch_row_weights(hipStream_t s, const int* len, int B, int T, int rows_per_group, int ngroups, float* w, int* n_valid, int* err_flag);
+// launch_token_prep for sequences of lengths len[b] in [1, T]: positions t >= len[b] get fixed ids (input: the start word, target: 0), so
+// the pass does not depend on the tokens behind a song's end; the range check covers every token all the same
+hipError_t launch_token_prep_len(hipStream_t s, const int* support, int n_support, const int* query, int n_query,
+                                 int T, int vocab, int start_word, int* X, int* Y, int* err_flag, int* tok_first, int* tok_count, const int* len);
+// launch_ce_rows with (softmax - onehot) * w[row] (the same three kernels by ld); a row of weight 0 gets a gradient of +-0
+hipError_t launch_ce_rows_w(hipStream_t s, const float* logits, int ld, int rows, int n_vocab, const int* tgt,
+                            float* lse, float* ce, float* dlogits, const float* w);
+// launch_ce_finish with c = w[row] / S: a row of weight 0 keeps the range check and the patch of E, crow and its row of hs_scaled are 0
+hipError_t launch_ce_finish_w(hipStream_t s, const float2* part, int nparts, const int* tgt, int rows, const float* w,
+                              float* E, int ld, float* lse, float* ce, float* crow, const float* hs, float* hs_scaled, int hp,
+                              int* err_flag, long long* range_counter);
+// out[g] = sum over the positions of group g with w != 0 of ce / (n_valid[g] + 1e-12), in launch_loss_reduce's order
+hipError_t launch_loss_reduce_w(hipStream_t s, const float* ce, int T, int B, int rows_per_group, int ngroups, const float* w,
+                                const int* n_valid, float* out);
+// launch_gather_rows + out_len[r] = table_len[idx[r]]
+hipError_t launch_gather_rows_len(hipStream_t s, const int* table, const int* table_len, const int* idx, int n_rows, int T, int n_songs,
+                                  int* out, int* out_len, int* err_flag);
 // what the shift-free softmax of GemmArgs::ce_store is used for: e^-60 <= S = sum_v exp(x_v) <= 1e30 (the largest logit of a row within
 // about [-60, 69 - log(vocabulary)]) and exp(target logit) >= 1e-30 (its log is taken) -- E, S and c = 1 / (n S) stay normal fp32 numbers
 constexpr float CE_SUM_MIN = 8.0e-27f, CE_SUM_MAX = 1.0e30f, CE_TGT_MIN = 1.0e-30f;

@@ -142,7 +142,17 @@ struct fsmg_model {
     static constexpr int MAX_TABLES = 4;
     int* table[MAX_TABLES] = {};        // device-resident packed splits [n_songs][T] (fsmg_upload_table)
     int64_t table_rows[MAX_TABLES] = {};
+    int* table_len[MAX_TABLES] = {};    // the songs' lengths [n_songs] of a table that has them (fsmg_upload_table_lengths)
     int* d_idx = nullptr; int idx_cap = 0;
+    // padding-masked passes (fsmg_*_masked): the lengths of the pass's sequences, the per-row loss weights and the groups' n_valid, at fixed
+    // addresses in the scratch (a captured pass replays with them)
+    int* d_len = nullptr;               // [Bcap] staged lengths, support rows first
+    float* roww = nullptr;              // [T * Bcap] w[t * B + b] (launch_row_weights)
+    int* d_nvalid = nullptr;            // [max(Bcap, 64)] per group (train pass: one group; eval batch: one per episode)
+    const int* cur_len = nullptr;       // what the pass reads: d_len, or the caller's device buffer (eager pass, one contiguous array)
+    bool masked_call = false;           // the call in progress is a masked one (begin_call clears it, the masked entry points set it)
+    int mask_rpg = 0, mask_groups = 0;  // rows per group / groups of the masked pass in progress
+    int last_mask_groups = 0;           // ... and of the last one that ran (fsmg_debug_read("n_valid"))
     int* d_gather = nullptr; int64_t gather_cap = 0;     // episode rows gathered from a table for the MAML-style step (its two passes take device token buffers)
     // XCD-local recurrence (lstm_xcd.hip; hidden size 512): per layer the forward and backward register images of K_h,
     // the h hand-off buffer, the dh-partial inboxes and the per-launch ticket counters
@@ -609,6 +619,7 @@ int gemm_cleanup(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs g,
 int stage_tokens(fsmg_model* h, const int32_t* support, int n_sup, const int32_t* query, int n_qry, int on_device);
 int reset_tok_table(fsmg_model* h);
 int token_prep(fsmg_model* h, int n_sup, int n_qry, bool train = false);
+int stage_lengths(fsmg_model* h, const int32_t* support_len, int n_sup, const int32_t* query_len, int n_qry, int on_device);
 // what a forward pass ends in: projection + cross entropy + loss, the bare logits (fsmg_score), or the hidden states alone (fsmg_cache_build)
 enum { HEAD_LOSS = 0, HEAD_LOGITS = 1, HEAD_NONE = 2 };
 int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_out, bool want_dlogits, int head = HEAD_LOSS);

@@ -5,6 +5,10 @@ a song file `<path>` has a pre-tokenised sidecar `<path>.<max_len>.npy` (int32
 [max_len]); when the sidecar is missing the song is read, tokenised, truncated /
 ZERO-padded to max_len (padding is not masked downstream and id 0 is also a real
 token -- SURVEY.md Q6) and the sidecar is written.
+
+Beyond the reference: when a song is tokenised, its length goes into a second sidecar `<path>.<max_len>.len.npy` (one int32,
+min(max_len, n_tokens), at least 1) for the padding-masked loss (`mask_padding`).  A token sidecar without a length
+sidecar -- a tree the reference wrote -- means max_len: nothing is guessed from zeros, because id 0 is a real token.
 """
 import os
 
@@ -41,6 +45,30 @@ class Loader(object):
     def sidecar_path(self, filepath):
         return '%s.%s.npy' % (filepath, self.max_len)
 
+    def length_sidecar_path(self, filepath):
+        return '%s.%s.len.npy' % (filepath, self.max_len)
+
+    def _save_atomically(self, path, array):       # another rank must never np.load a half-written sidecar
+        tmp = '%s.%d.tmp.npy' % (path, os.getpid())
+        np.save(tmp, array)
+        os.replace(tmp, path)
+
+    def _length_of(self, ids):
+        return max(1, min(self.max_len, len(ids)))
+
+    def load_length(self, filepath):
+        """-> the song's length in [1, max_len]: the length sidecar; max_len for a token sidecar that has none; else the song is
+        tokenised (and, with persist, both sidecars are written)."""
+        side = self.length_sidecar_path(filepath)
+        if self.persist and os.path.isfile(side):
+            return int(np.load(side).reshape(-1)[0])
+        if self.persist and os.path.isfile(self.sidecar_path(filepath)):
+            return self.max_len
+        if self.persist:
+            self.load(filepath)
+            return int(np.load(side).reshape(-1)[0])
+        return self._length_of(self.tokenize(self.read(filepath)))
+
     def validate(self, filepath):
         """A song is valid iff it loads (base_loader.py:35-50)."""
         try:
@@ -58,8 +86,8 @@ class Loader(object):
         row = np.zeros(self.max_len, dtype=self.dtype)
         n = min(self.max_len, len(ids))
         row[:n] = ids[:n]
-        if self.persist:                        # atomically: another rank must never np.load a half-written sidecar
-            tmp = '%s.%d.tmp.npy' % (sidecar, os.getpid())
-            np.save(tmp, row)
-            os.replace(tmp, sidecar)
+        if self.persist:
+            # the length first: a token sidecar without a length sidecar reads as "max_len"
+            self._save_atomically(self.length_sidecar_path(filepath), np.array([self._length_of(ids)], np.int32))
+            self._save_atomically(sidecar, row)
         return row

@@ -111,6 +111,7 @@ class Dataset(object):
         self.valid_songs_file = valid_songs_file
         self.artists = []
         self._table = None
+        self._lengths = None
 
         valid = {}                    # artist -> ordered list of valid songs
         if validate and persist:
@@ -200,6 +201,15 @@ class Dataset(object):
                 else np.zeros((0, self.loader.max_len), np.int32)
             self._table = (table, np.asarray(offsets, np.int64))
         return self._table
+
+    def length_table(self):
+        """int32 [n_songs]: the songs' lengths (Loader.load_length) in the order of token_table()'s rows."""
+        if self._lengths is None:
+            self.token_table()                  # (tokenises what has no sidecar yet, which also writes the length sidecars)
+            lengths = [self.loader.load_length(os.path.join(self.root, artist.name, song))
+                       for artist in self.artists for song in artist.songs]
+            self._lengths = np.asarray(lengths, np.int32).reshape(-1)
+        return self._lengths
 
     def __len__(self):
         return len(self.artists)

@@ -29,9 +29,14 @@ from data.midi_loader import MIDILoader
 
 
 class Episode(object):
-    def __init__(self, support, query):
+    """support int32 [N,K,T], query int32 [N,Q,T]; support_len int32 [N,K] / query_len int32 [N,Q]: the songs' lengths in [1, T]
+    (EpisodeSampler.gather fills them; None for an episode built by hand)."""
+
+    def __init__(self, support, query, support_len=None, query_len=None):
         self.support = support
         self.query = query
+        self.support_len = support_len
+        self.query_len = query_len
 
 
 class SQSampler(object):
@@ -89,8 +94,11 @@ class EpisodeSampler(object):
 
     def gather(self, support_idx, query_idx):
         table, _ = self.dataset.token_table()
+        lengths = self.length_table()
         return Episode(np.ascontiguousarray(table[support_idx], dtype=self.dtype),
-                       np.ascontiguousarray(table[query_idx], dtype=self.dtype))
+                       np.ascontiguousarray(table[query_idx], dtype=self.dtype),
+                       None if lengths is None else np.ascontiguousarray(lengths[support_idx], dtype=np.int32),
+                       None if lengths is None else np.ascontiguousarray(lengths[query_idx], dtype=np.int32))
 
     def get_episode(self):
         return self.gather(*self.episode_indices())
@@ -102,6 +110,11 @@ class EpisodeSampler(object):
 
     def token_table(self):
         return self.dataset.token_table()[0]
+
+    def length_table(self):
+        """int32 [n_songs] in the order of token_table() (None for a dataset that keeps no lengths)"""
+        get = getattr(self.dataset, 'length_table', None)
+        return get() if get is not None else None
 
     def get_episodes(self, n):
         """The next n episodes of the stream (same as n get_episode() calls)."""

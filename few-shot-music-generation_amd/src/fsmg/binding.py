@@ -163,6 +163,13 @@ SIGNATURES = {
     'fsmg_maml_step_indexed': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _F32P]),
     'fsmg_eval_step': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _F32P]),
     'fsmg_eval_batch': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F32P]),
+    'fsmg_train_step_masked': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F32P]),
+    'fsmg_forward_backward_masked': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'fsmg_eval_step_masked': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _F32P]),
+    'fsmg_eval_batch_masked': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F32P]),
+    'fsmg_upload_table_lengths': (C.c_int, [_P, C.c_int32, _P, C.c_int64]),
+    'fsmg_train_step_indexed_masked': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _F32P]),
+    'fsmg_forward_backward_indexed_masked': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     'fsmg_sample': (C.c_int, [_P, C.c_int32, _I32P]),
     'fsmg_generate': (C.c_int, [_P, C.POINTER(FsmgGenConfig), _P, _I32P, _F32P]),
     'fsmg_maml_generate': (C.c_int, [_P, C.POINTER(FsmgGenConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P, _F32P]),
@@ -527,6 +534,81 @@ class FsmgModel(object):
         qp, _, _k2 = _tok_ptr(query)
         self._ck(self._lib.fsmg_forward_backward(self._h, sp, qp, n, k, q, dev))
 
+    # -- padding-masked forms (include/fsmg.h "per-song lengths"): position t of row b is scored iff t < len[b] ---------------
+    @staticmethod
+    def _len_ptr(lengths, count, on_device):
+        """lengths of `count` sequences: a host int32 array, or a raw device address when the tokens are device pointers"""
+        if isinstance(lengths, (int, np.integer)):
+            if not on_device:
+                raise ValueError('device lengths go with device tokens (one flag covers both)')
+            return C.c_void_p(int(lengths)), None
+        if on_device:
+            raise ValueError('device tokens need device lengths (one flag covers both)')
+        if lengths is None:
+            raise ValueError('a masked call needs lengths')
+        a = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        if a.size != count:
+            raise ValueError('%d lengths for %d sequences' % (a.size, count))
+        return C.c_void_p(a.ctypes.data), a
+
+    def train_step_masked(self, support, query, support_len, query_len, shape=None, want_loss=True):
+        """train_step with support_len [N,K] / query_len [N,Q] int32 (host arrays, or device addresses with device tokens)"""
+        n, k, q = self._episode_shape(support, query, shape)
+        sp, dev, _k1 = _tok_ptr(support)
+        qp, _, _k2 = _tok_ptr(query)
+        sl, _k3 = self._len_ptr(support_len, n * k, dev)
+        ql, _k4 = self._len_ptr(query_len, n * q, dev)
+        loss = C.c_float()
+        self._ck(self._lib.fsmg_train_step_masked(self._h, sp, qp, sl, ql, n, k, q, dev, C.byref(loss) if want_loss else None))
+        return loss.value if want_loss else None
+
+    def forward_backward_masked(self, support, query, support_len, query_len, shape=None):
+        n, k, q = self._episode_shape(support, query, shape)
+        sp, dev, _k1 = _tok_ptr(support)
+        qp, _, _k2 = _tok_ptr(query)
+        sl, _k3 = self._len_ptr(support_len, n * k, dev)
+        ql, _k4 = self._len_ptr(query_len, n * q, dev)
+        self._ck(self._lib.fsmg_forward_backward_masked(self._h, sp, qp, sl, ql, n, k, q, dev))
+
+    def eval_step_masked(self, query, query_len, shape=None):
+        if shape is None:
+            n, q, t = query.shape
+            if t != self.max_len:
+                raise ValueError('query %r does not match max_len=%d' % (query.shape, self.max_len))
+        else:
+            n, q = shape
+        qp, dev, _k = _tok_ptr(query)
+        ql, _k2 = self._len_ptr(query_len, n * q, dev)
+        nll = C.c_float()
+        self._ck(self._lib.fsmg_eval_step_masked(self._h, qp, ql, n, q, dev, C.byref(nll)))
+        return nll.value
+
+    def eval_batch_masked(self, queries, query_len, shape=None):
+        """queries [n_episodes,N,Q,T], query_len [n_episodes,N,Q] -> float32 [n_episodes], each over its own n_valid"""
+        if shape is None:
+            ne, n, q, t = queries.shape
+            if t != self.max_len:
+                raise ValueError('queries %r do not match max_len=%d' % (queries.shape, self.max_len))
+        else:
+            ne, n, q = shape
+        qp, dev, _k = _tok_ptr(queries)
+        ql, _k2 = self._len_ptr(query_len, ne * n * q, dev)
+        out = np.empty(ne, np.float32)
+        self._ck(self._lib.fsmg_eval_batch_masked(self._h, qp, ql, ne, n, q, dev, _f32p(out)))
+        return out
+
+    def forward_backward_indexed_masked(self, table_id, support_idx, query_idx):
+        s, q = self._idx(support_idx, query_idx)
+        self._ck(self._lib.fsmg_forward_backward_indexed_masked(self._h, int(table_id), C.c_void_p(s.ctypes.data), C.c_void_p(q.ctypes.data),
+                                                                s.shape[0], s.shape[1], q.shape[1]))
+
+    def train_step_indexed_masked(self, table_id, support_idx, query_idx, want_loss=True):
+        s, q = self._idx(support_idx, query_idx)
+        loss = C.c_float()
+        self._ck(self._lib.fsmg_train_step_indexed_masked(self._h, int(table_id), C.c_void_p(s.ctypes.data), C.c_void_p(q.ctypes.data),
+                                                          s.shape[0], s.shape[1], q.shape[1], C.byref(loss) if want_loss else None))
+        return loss.value if want_loss else None
+
     def grad_buffer(self):
         ptr, count = _P(), C.c_int64()
         self._ck(self._lib.fsmg_grad_buffer(self._h, C.byref(ptr), C.byref(count)))
@@ -568,11 +650,18 @@ class FsmgModel(object):
         self._ck(self._lib.fsmg_comm_release(self._h))
 
     # -- device-resident episode table ----------------------------------------------------------------
-    def upload_table(self, table_id, table):
+    def upload_table(self, table_id, table, lengths=None):
+        """lengths: int32 [n_songs], the songs' lengths for the masked indexed calls (None: the table has none)"""
         a = np.ascontiguousarray(table, dtype=np.int32)
         if a.ndim != 2 or a.shape[1] != self.max_len:
             raise ValueError('token table %r does not match max_len=%d' % (a.shape, self.max_len))
+        if lengths is not None:
+            ln = np.ascontiguousarray(lengths, dtype=np.int32)
+            if ln.shape != (a.shape[0],):
+                raise ValueError('lengths %r do not match the %d songs of the table' % (ln.shape, a.shape[0]))
         self._ck(self._lib.fsmg_upload_table(self._h, int(table_id), C.c_void_p(a.ctypes.data), a.shape[0]))
+        if lengths is not None:
+            self._ck(self._lib.fsmg_upload_table_lengths(self._h, int(table_id), C.c_void_p(ln.ctypes.data), ln.shape[0]))
 
     @staticmethod
     def _idx(support_idx, query_idx):

@@ -56,7 +56,9 @@ class EpisodeParallel(object):
     def train_step(self, support, query, want_loss=True, **kw):
         """kw: shape=(N, K, Q) for raw device token addresses; table=id: support / query are row indices into the uploaded split
         table; maml=(inner_steps, inner_lr) selects the cfg-E step (per-rank
-        inner SGD on the support rows, no communication; the query-set gradients are exchanged exactly like a plain step's)"""
+        inner SGD on the support rows, no communication; the query-set gradients are exchanged exactly like a plain step's);
+        lengths=(support_len, query_len): the padding-masked step (with table=id: lengths=True, the table's own lengths) -- each
+        rank normalises by its own n_valid and grad_scale = 1 / world takes the mean of those, as for the unmasked step"""
         try:
             return self._train_step_once(support, query, want_loss, **kw)
         except Exception as e:
@@ -68,7 +70,11 @@ class EpisodeParallel(object):
                 raise
             return self._train_step_once(support, query, want_loss, **kw)
 
-    def _train_step_once(self, support, query, want_loss=True, maml=None, table=None, **kw):
+    def _train_step_once(self, support, query, want_loss=True, maml=None, table=None, lengths=None, **kw):
+        if lengths is not None:
+            if maml is not None:
+                raise ValueError('the MAML-style step takes no lengths')
+            kw['lengths'] = lengths          # (only a masked step hands the keyword to the engine)
         if self.world == 1 and maml is None and hasattr(self.engine, 'fused_train_step'):
             return self.engine.fused_train_step(support, query, want_loss=want_loss, table=table, **kw)
         if self.world == 1 and maml is not None and table is not None and hasattr(self.engine, 'fused_maml_step'):
@@ -81,7 +87,7 @@ class EpisodeParallel(object):
         if table is not None and maml is not None:      # cfg-E on the device-resident table: per-rank inner loop, then the exchange below
             self.engine.maml_forward_backward_indexed(table, support, query, maml[0], maml[1])
         elif table is not None:               # support / query are [N,K] / [N,Q] row indices into a device-resident split table
-            self.engine.forward_backward_indexed(table, support, query)
+            self.engine.forward_backward_indexed(table, support, query, **kw)
         elif maml is not None:
             self.engine.maml_forward_backward(support, query, maml[0], maml[1], **kw)
         else:

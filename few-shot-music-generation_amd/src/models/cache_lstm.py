@@ -31,6 +31,7 @@ from models.lstm_baseline import LSTMBaseline
 
 
 class CacheLSTM(LSTMBaseline):
+    MASKS_PADDING = False        # fsmg_cache_* / fsmg_score take no lengths: `mask_padding: true` is refused at construction
     _self = False               # the defaults of the optional keys: the own history stays out of the set
     _window = None              # None: max_len
 

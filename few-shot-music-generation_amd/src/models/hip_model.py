@@ -79,10 +79,15 @@ class HIPModel(BaseModel):
             self._scalars = open(os.path.join(config['checkpt_dir'], 'scalars.jsonl'), 'a')
 
     # -- engine interface used by fsmg.dist.EpisodeParallel ------------------------------------
-    def forward_backward(self, support, query, **kw):
+    # (lengths: the padding-masked forms -- (support_len, query_len), or True for the lengths uploaded with a table)
+    def forward_backward(self, support, query, lengths=None, **kw):
+        if lengths is not None:
+            return self._model.forward_backward_masked(support, query, lengths[0], lengths[1], **kw)
         self._model.forward_backward(support, query, **kw)
 
-    def forward_backward_indexed(self, table_id, support_idx, query_idx):
+    def forward_backward_indexed(self, table_id, support_idx, query_idx, lengths=None):
+        if lengths is not None:
+            return self._model.forward_backward_indexed_masked(table_id, support_idx, query_idx)
         self._model.forward_backward_indexed(table_id, support_idx, query_idx)
 
     def maml_forward_backward(self, support, query, inner_steps, inner_lr, **kw):
@@ -90,8 +95,13 @@ class HIPModel(BaseModel):
 
     def fused_train_step(self, support, query, want_loss=True, table=None, **kw):
         """forward + backward + clip + Adam as ONE captured graph (the single-process step: nothing to exchange in between)"""
+        lengths = kw.pop('lengths', None)
+        if table is not None and lengths is not None:
+            return self._model.train_step_indexed_masked(table, support, query, want_loss=want_loss)
         if table is not None:
             return self._model.train_step_indexed(table, support, query, want_loss=want_loss)
+        if lengths is not None:
+            return self._model.train_step_masked(support, query, lengths[0], lengths[1], want_loss=want_loss, **kw)
         return self._model.train_step(support, query, want_loss=want_loss, **kw)
 
     def apply_update(self, grad_scale=1.0, want_loss=True):

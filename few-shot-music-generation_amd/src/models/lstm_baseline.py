@@ -21,7 +21,9 @@ that reads the support set before it scores the query songs.
 
 Optional config keys beyond the reference's: device, clip_norm_mode ('tf1_slices' | 'dense'),
 max_sequences, use_graph, gemm / schedule / recurrence / dp_split_backward (fsmg_config), dp_exchange ('torch': the
-all-reduce is issued through torch.distributed; 'library': libfsmg issues the RCCL calls itself).  When torch.distributed is initialised, train() runs episode-parallel
+all-reduce is issued through torch.distributed; 'library': libfsmg issues the RCCL calls itself), mask_padding (default false; true:
+train / train_indexed / eval / eval_many score position t of a song iff t < its length -- Episode.support_len / query_len, the
+lengths handed to attach_table -- and average over the scored positions, include/fsmg.h "per-song lengths").  When torch.distributed is initialised, train() runs episode-parallel
 (one episode per rank, one gradient all-reduce per step, see fsmg/dist.py).
 """
 import numpy as np
@@ -31,7 +33,13 @@ from models.hip_model import HIPModel
 
 
 class LSTMBaseline(HIPModel):
+    MASKS_PADDING = True         # a subclass that has no masked form says so: it refuses `mask_padding: true` instead of ignoring it
+
     def __init__(self, config):
+        self.mask_padding = bool(config.get('mask_padding', False))
+        if self.mask_padding and not self.MASKS_PADDING:
+            raise RuntimeError('%s has no padding-masked loss: mask_padding: true is supported by LSTMBaseline only '
+                               '(remove the key or set it to false)' % type(self).__name__)
         for key in ('name', 'input_size', 'max_len', 'embedding_size', 'hidden_size', 'n_layers',
                     'lr', 'max_grad_norm', 'n_decay'):
             if key not in config:
@@ -55,9 +63,24 @@ class LSTMBaseline(HIPModel):
             raise ValueError('expected a %d-d token array, got shape %r' % (ndim, a.shape))
         return a
 
+    def _lengths(self, episode, which):
+        """the episode's lengths as int32 [N, K] / [N, Q], checked against its tokens (mask_padding)"""
+        out = []
+        for name in which:
+            ln, tokens = getattr(episode, name + '_len', None), getattr(episode, name)
+            if ln is None:
+                raise ValueError('mask_padding is on and the episode has no %s_len: lengths come from EpisodeSampler.gather '
+                                 '(or Episode(support, query, support_len, query_len))' % name)
+            ln = np.ascontiguousarray(ln, dtype=np.int32)
+            if ln.shape != tuple(np.shape(tokens)[:2]):
+                raise ValueError('%s_len %r does not match the length of %s %r' % (name, ln.shape, name, np.shape(tokens)))
+            out.append(ln)
+        return out
+
     def train(self, episode):
         self._require_init()
-        loss = self._parallel.train_step(self._tokens(episode.support, 3), self._tokens(episode.query, 3))
+        kw = dict(lengths=tuple(self._lengths(episode, ('support', 'query')))) if self.mask_padding else {}
+        loss = self._parallel.train_step(self._tokens(episode.support, 3), self._tokens(episode.query, 3), **kw)
         self._log_scalar('Train/loss', loss, self._train_calls)
         self._train_calls += 1
         return loss
@@ -65,10 +88,13 @@ class LSTMBaseline(HIPModel):
     # -- fast path of train.train: episodes as row indices into a device-resident split table, losses left on the device --
     TABLE_IDS = {'train': 0, 'val': 1, 'test': 2}
 
-    def attach_table(self, split, table):
+    def attach_table(self, split, table, lengths=None):
         """Upload the packed [n_songs, max_len] int32 token table of a split (data.dataset.Dataset.token_table) once; episodes
-        of that split can then be given as row indices (train_indexed)."""
-        self._model.upload_table(self.TABLE_IDS[split], table)
+        of that split can then be given as row indices (train_indexed).  lengths: int32 [n_songs]
+        (data.dataset.Dataset.length_table), needed when mask_padding is on."""
+        if self.mask_padding and lengths is None:
+            raise ValueError('mask_padding is on: attach_table needs the lengths of the table (Dataset.length_table)')
+        self._model.upload_table(self.TABLE_IDS[split], table, lengths if self.mask_padding else None)
 
     def train_indexed(self, split, support_idx, query_idx, want_loss=False):
         """Same step as train(episode) for the episode table[support_idx], table[query_idx]; with want_loss=False nothing is
@@ -76,7 +102,7 @@ class LSTMBaseline(HIPModel):
         self._require_init()
         loss = self._parallel.train_step(np.ascontiguousarray(support_idx, dtype=np.int32),
                                          np.ascontiguousarray(query_idx, dtype=np.int32), want_loss=want_loss,
-                                         table=self.TABLE_IDS[split])
+                                         table=self.TABLE_IDS[split], **(dict(lengths=True) if self.mask_padding else {}))
         if want_loss:
             self._log_scalar('Train/loss', loss, self._train_calls)
         self._train_calls += 1
@@ -100,7 +126,10 @@ class LSTMBaseline(HIPModel):
 
     def eval(self, episode):
         self._require_init()
-        nll = self._model.eval_step(self._tokens(episode.query, 3))
+        if self.mask_padding:
+            nll = self._model.eval_step_masked(self._tokens(episode.query, 3), self._lengths(episode, ('query',))[0])
+        else:
+            nll = self._model.eval_step(self._tokens(episode.query, 3))
         self._log_scalar('Eval/Avg_NLL', nll, self._eval_calls)
         self._eval_calls += 1
         return nll
@@ -109,7 +138,10 @@ class LSTMBaseline(HIPModel):
         """[model.eval(e) for e in episodes] in one device pass (episodes must share N, Q)."""
         self._require_init()
         queries = np.stack([self._tokens(e.query, 3) for e in episodes])
-        nlls = self._model.eval_batch(queries)
+        if self.mask_padding:
+            nlls = self._model.eval_batch_masked(queries, np.stack([self._lengths(e, ('query',))[0] for e in episodes]))
+        else:
+            nlls = self._model.eval_batch(queries)
         for nll in nlls:
             self._log_scalar('Eval/Avg_NLL', float(nll), self._eval_calls)
             self._eval_calls += 1

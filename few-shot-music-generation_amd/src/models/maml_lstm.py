@@ -23,6 +23,7 @@ from models.lstm_baseline import LSTMBaseline
 
 
 class MAMLLSTM(LSTMBaseline):
+    MASKS_PADDING = False        # fsmg_maml_* take no lengths: `mask_padding: true` is refused at construction
     def __init__(self, config):
         super(MAMLLSTM, self).__init__(config)
         self._inner_steps = int(config.get('inner_steps', 1))

@@ -217,6 +217,42 @@ int fsmg_eval_step(fsmg_handle h, const int32_t* query, int32_t N, int32_t Q,
 int fsmg_eval_batch(fsmg_handle h, const int32_t* queries, int32_t n_episodes, int32_t N, int32_t Q,
                     int32_t tokens_on_device, float* nll);
 
+/* ---- per-song lengths: the padding-masked loss ------------------------------------------------
+ * The same passes for songs shorter than max_len = T.  Every row b of a pass has a length len[b] in [1, T]; position t of row b
+ * is scored iff t < len[b] (its inputs are [start, x_0 .. x_{t-1}], its target x_t), and with n_valid = the sum of the lengths
+ *   loss = sum_{b, t < len[b]} ce[b][t] / (n_valid + 1e-12),   dlogits[b][t] = (softmax - onehot) * w[b][t],
+ *   w[b][t] = t < len[b] ? (float)(1 / ((double)n_valid + 1e-12)) : 0
+ * -- TF's sequence_loss with 0 / 1 weights, averaged across time steps and batch.  All T steps of every row are still computed.
+ * Two laws: with every length T a masked call has the unmasked call's bits (loss, gradients, tail, updated state); and the
+ * tokens at t >= len[b] never matter (a position behind a song's end gets fixed ids on the device, and its row enters every
+ * gradient with an exact 0) -- they must still be in range.  The range check of the fused softmax covers all rows.
+ * support_len [N*K] and query_len [N*Q] follow the token pointers and live where they do: tokens_on_device covers both.  Host
+ * lengths are checked before any device work (one outside [1, T], or a NULL pointer: FSMG_ERR_INVALID, nothing touched); device
+ * lengths are checked by the kernel that builds the weights, which raises the flag of an out-of-range token: the step is
+ * skipped on the device, the read-back returns FSMG_ERR_TOKEN_RANGE, and in an episode-parallel job every rank skips.
+ * Everything else is the unmasked call's: the loss ring, fsmg_apply_update behind fsmg_forward_backward_masked (loss in
+ * tail[1]), buckets, time-out and range retries, the library-owned exchange.  In an episode-parallel job each rank normalises
+ * by its OWN n_valid and grad_scale = 1 / world takes the mean of those: the unmasked convention, a mean of per-episode means
+ * (not a mean over all ranks' tokens).  A handle may alternate masked and unmasked calls freely.
+ * fsmg_eval_batch_masked: query_len [n_episodes*N*Q], each episode's NLL over its own n_valid.
+ * fsmg_upload_table_lengths: the lengths [n_songs] of the token table uploaded under table_id (FSMG_ERR_STATE without a table
+ * of the same n_songs; every length checked here; uploading the table again drops them); the indexed masked calls gather a
+ * row's length with the row (the host sends indices only) and return FSMG_ERR_STATE for a table without lengths.
+ * fsmg_debug_read: "row_weight" = the T*B weights of the last masked pass in device row order t*B + b, "n_valid" = its groups'. */
+int fsmg_train_step_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len,
+                           const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int32_t tokens_on_device, float* loss);
+int fsmg_forward_backward_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len,
+                                 const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int32_t tokens_on_device);
+int fsmg_eval_step_masked(fsmg_handle h, const int32_t* query, const int32_t* query_len, int32_t N, int32_t Q,
+                          int32_t tokens_on_device, float* nll);
+int fsmg_eval_batch_masked(fsmg_handle h, const int32_t* queries, const int32_t* query_len, int32_t n_episodes, int32_t N,
+                           int32_t Q, int32_t tokens_on_device, float* nll);
+int fsmg_upload_table_lengths(fsmg_handle h, int32_t table_id, const int32_t* lengths, int64_t n_songs);
+int fsmg_train_step_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                                   int32_t N, int32_t K, int32_t Q, float* loss);
+int fsmg_forward_backward_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                                         int32_t N, int32_t K, int32_t Q);
+
 /* ---- cfg-E (BASELINE.json configs[4]): MAML-style inner / outer loop, first order.
  * The reference has no code for it (READING_LIST.md:5-7 names the direction); semantics: DESIGN.md "cfg-E", oracle:
  * oracle/lstm_oracle.py maml_step / maml_eval.  theta' starts at theta and takes `inner_steps` steps
