@@ -11,6 +11,10 @@ backward_full() does the oracle's arithmetic in the oracle's order -- in fp64 it
 
 The measures themselves (componentwise_ratio, slice_ratio), the fp32-restatement yardstick e32 and the bound
 M * e32 (class Reference) live here too, so that the CPU and the GPU tests use one definition.
+
+The padding-masked pass is the same arithmetic with per-row weights: backward_full and Reference take the 0 / 1
+weights of the rows, in the oracle's row order b*T + t.  A masked row then has S == 0 in dlogits, dh, dx, and an all-zero reference
+in every gate block of its rows of dz -- so the measures hold everything the device writes there to exact zeros.
 """
 import numpy as np
 
@@ -20,8 +24,15 @@ UNDERFLOW = 1e-30          # absolute slack for fp32 underflow, added to every b
 
 
 # ----------------------------------------------------------------------------- the backward pass, with its intermediates
-def backward_full(params, cache, config):
-    """-> dict(grads, aux, dlogits [n,V1], dz [L x [n,4H]], dx [n,E], dh [n,H], scales {name: S})."""
+def backward_full(params, cache, config, weights=None):
+    """-> dict(grads, aux, dlogits [n,V1], dz [L x [n,4H]], dx [n,E], dh [n,H], scales {name: S}).
+
+    weights: None (the oracle's loss, every row counts), or the rows' 0 / 1 weights of the padding-masked loss, [n] in the oracle's
+    row order b*T + t (masked_ref.mask_of).  Row r then enters with mask_r / (n_valid + 1e-12), n_valid = sum(mask), in the division
+    form of masked_ref.masked_backward, whose gradients these are bit for bit:
+        dlogits = (p - onehot) * mask / (n_valid + 1e-12),   scales['dlogits'] = (p + onehot) * mask / (n_valid + 1e-12),
+    and every other scale follows from |dlogits| as without weights.  A masked row has S == 0 in dlogits, dh and dx, and zeros in
+    its rows of every dz.  Without weights every returned array is bit-identical to what this function returned before it took them."""
     d = O.model_dims(config)
     H, L, T = d['H'], d['L'], d['T']
     B = cache['B']
@@ -33,9 +44,16 @@ def backward_full(params, cache, config):
     p = np.exp(cache['logits'] - cache['lse'][:, None])
     s_dlogits = p.copy()
     s_dlogits[np.arange(n), yflat] += 1.0
-    scales['dlogits'] = s_dlogits / dtype.type(n + 1e-12)                 # (p + onehot) / n
     p[np.arange(n), yflat] -= 1.0
-    dlogits = p / dtype.type(n + 1e-12)
+    if weights is None:
+        scales['dlogits'] = s_dlogits / dtype.type(n + 1e-12)             # (p + onehot) / n
+        dlogits = p / dtype.type(n + 1e-12)
+    else:
+        mask = np.asarray(weights).reshape(n).astype(dtype)
+        assert np.all((mask == 0) | (mask == 1)) and mask.any(), 'the weights of the padding-masked loss are 0 / 1, not all 0'
+        n_valid = int(mask.sum())
+        scales['dlogits'] = s_dlogits * mask[:, None] / dtype.type(n_valid + 1e-12)
+        dlogits = p * mask[:, None] / dtype.type(n_valid + 1e-12)
     a_dl = np.abs(dlogits)
     grads['softmax_w'] = cache['out'].T.dot(dlogits)
     grads['softmax_b'] = dlogits.sum(axis=0)
@@ -121,8 +139,9 @@ def componentwise_failures(got, ref, S, tol):
 
 
 def slice_ratio(got, ref, axes):
-    """Norm-wise error per slice, max|err| / max|ref| over `axes`; a slice whose reference is all zero (h_0, c_0) counts
-    max|err| / 1e-30, so anything but exact zeros there is far outside every bound."""
+    """Norm-wise error per slice, max|err| / max|ref| over `axes`; a slice whose reference is all zero (h_0, c_0; with weights
+    every gate block of a masked (t, b) row of dz) counts max|err| / 1e-30, so anything but exact zeros there is far outside every
+    bound."""
     got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
     err = np.abs(got - ref).max(axis=axes)
     den = np.abs(ref).max(axis=axes)
@@ -135,10 +154,14 @@ SLICEWISE = ('hs', 'cs', 'dz')
 FAMILIES = COMPONENTWISE + SLICEWISE
 
 
-def _tensors(params, X, Y, config):
-    """every checked tensor of one forward + backward pass, by (family, layer or None), oracle row order"""
+def _tensors(params, X, Y, config, weights=None):
+    """every checked tensor of one forward + backward pass, by (family, layer or None), oracle row order; with weights the loss
+    is the padding-masked one, sum of the scored rows' ce / (n_valid + 1e-12) (masked_ref.masked_loss)"""
     loss, cache = O.forward(params, X, Y, config)
-    full = backward_full(params, cache, config)
+    full = backward_full(params, cache, config, weights)
+    if weights is not None:
+        mask = np.asarray(weights).reshape(-1)
+        loss = (cache['ce'] * mask.astype(cache['ce'].dtype)).sum() / (int(mask.sum()) + 1e-12)
     H, T, B = config['hidden_size'], config['max_len'], cache['B']
     t = {('logits', None): cache['logits'], ('lse', None): cache['lse'], ('ce', None): cache['ce'],
          ('dlogits', None): full['dlogits'], ('dh', None): full['dh'], ('dx', None): full['dx'],
@@ -171,14 +194,15 @@ def measure(fam, layer, got, ref_t, ref_full):
 class Reference(object):
     """fp64 oracle pass + its fp32 restatement (same parameters, same episode) of one shape; e32[family] = the fp32 pass's
     error in the family's own measure, maximised over the family (all layers): what plain fp32 arithmetic gives.  The
-    device is held to M * e32 -- a yardstick that comes from the reference alone, never from the code under test."""
+    device is held to M * e32 -- a yardstick that comes from the reference alone, never from the code under test.
+    weights: as backward_full's; both passes take the same ones."""
 
-    def __init__(self, params64, X, Y, config):
-        self.config, self.X, self.Y = config, X, Y
+    def __init__(self, params64, X, Y, config, weights=None):
+        self.config, self.X, self.Y, self.weights = config, X, Y, weights
         self.params = params64
-        self.loss, self.cache, self.full, self.t = _tensors(params64, X, Y, config)
+        self.loss, self.cache, self.full, self.t = _tensors(params64, X, Y, config, weights)
         p32 = {k: v.astype(np.float32) for k, v in params64.items()}
-        _, _, _, t32 = _tensors(p32, X, Y, config)
+        _, _, _, t32 = _tensors(p32, X, Y, config, weights)
         self.e32 = {}
         for (fam, layer), a32 in t32.items():
             assert a32.dtype == np.float32, (fam, a32.dtype)

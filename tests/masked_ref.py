@@ -84,6 +84,23 @@ def masked_backward(params, cache, config, lengths):
     return grads, aux
 
 
+def device_xy(sup, qry, support_len, query_len, cfg):
+    """-> X, Y [B, T] as the device's masked pass sees them: O.train_xy, then what token_prep_body<true> does (elementwise.hip
+    k_token_prep_len: `if (t >= l) tok_y = 0; if (t + 1 >= l) tok = start_word;`) -- at t >= len[b] the input id is
+    the start word and the target is 0, whatever the caller put behind the song's end.  A reference built from these has the
+    device's hs, cs, logits, lse and ce on ALL rows, the masked ones included: ce and lse stay per-row values on a masked pass
+    (elementwise.hip: ce_rows_body `ce[r] = l - row[t]`, ce_row_reg `ce[r] = l - xt`, ce_finish_body `ce[row] = l - logf(et)`, each
+    before the row's weight is used at all; k_loss_reduce_w `if (w[r] != 0.0f) s += (double)ce[r];` adds the unweighted values and
+    divides once by n_valid), only dlogits carries the weight."""
+    X, Y = O.train_xy(sup, qry, cfg['input_size'])
+    ln = train_lengths(support_len, query_len)
+    pad = np.arange(X.shape[1])[None, :] >= ln[:, None]
+    X, Y = X.copy(), Y.copy()
+    X[pad] = cfg['input_size']                 # the start word (O.train_xy's third argument)
+    Y[pad] = 0
+    return X, Y
+
+
 def train_lengths(support_len, query_len):
     """[N,K] + [N,Q] -> [N*K + N*Q], support rows first (the order of O.train_xy)"""
     return np.concatenate([np.asarray(support_len).reshape(-1), np.asarray(query_len).reshape(-1)])
@@ -132,3 +149,25 @@ def scramble_padding(tokens, lengths, vocab, rng):
     out = tokens.copy()
     out[pad] = rng.randint(0, vocab, size=int(pad.sum()))
     return out.astype(tokens.dtype)
+
+
+def componentwise_lengths(cfg, N, K, Q, seed):
+    """-> (support_len [N,K], query_len [N,Q]) of the element-by-element masked tests, for a shape of backward_ref.CW_SHAPES: the
+    seeded lengths_for, then forced so that the edges exist whatever the seed gives:
+      * with B >= 32 rows, rows b = 16 .. 31 of the pass's row order (support rows first) get a length <= T // 2: in the late steps
+        one whole 16-row tile of the recurrence is masked while its neighbours are mixed;
+      * a 1, a T and (B >= 3, T >= 3) a value strictly between, at rows outside that tile."""
+    T, B = cfg['max_len'], N * (K + Q)
+    rng = np.random.RandomState(1000 + seed)
+    ln = lengths_for(rng, (B,), T)
+    free = np.arange(B)
+    if B >= 32:
+        ln[16:32] = np.minimum(ln[16:32], T // 2)
+        free = np.concatenate([free[:16], free[32:]])
+    idx = free[rng.permutation(free.size)]
+    ln[idx[0]] = T
+    if B >= 2:
+        ln[idx[1]] = 1
+    if B >= 3 and T >= 3:
+        ln[idx[2]] = T // 2 + 1
+    return ln[:N * K].reshape(N, K).astype(np.int32), ln[N * K:].reshape(N, Q).astype(np.int32)
