@@ -1,5 +1,6 @@
 // Support-set neural cache: fsmg_cache_build / _create_from / _get / _info / _destroy, fsmg_cache_attend, fsmg_cache_score,
-// fsmg_cache_eval_step.  Host-side C++ only (part of the C-ABI of libfsmg, include/fsmg.h); the kernels live in cache.hip (attention,
+// fsmg_cache_eval_step, and their forms with per-song lengths and ragged groups (fsmg_cache_build_masked, _create_from_counts, _counts,
+// _score_masked, _self_score_masked, _eval_step_masked).  Host-side C++ only (part of the C-ABI of libfsmg, include/fsmg.h); the kernels live in cache.hip (attention,
 // cache fill) and score.hip (the model log-prob).  DESIGN.md 17.
 #include "fsmg_model.h"
 
@@ -37,16 +38,19 @@ int check_cache_size(fsmg_model* h, int64_t G, int64_t Mg) {
     return FSMG_OK;
 }
 
-// an empty cache of G x Mg entries on the device, not yet registered
-int alloc_cache(fsmg_model* h, int G, int Mg, fsmg_cache_s** out) {
+// an empty cache of G x Mg entries on the device, not yet registered; `ragged`: with the per-group counts behind the values (the
+// caller fills n_g and uploads it), a uniform cache's block being what it always was
+int alloc_cache(fsmg_model* h, int G, int Mg, fsmg_cache_s** out, bool ragged = false) {
     fsmg_cache_s* c = new (std::nothrow) fsmg_cache_s;
     if (!c) return fail(h, FSMG_ERR_NOMEM, "out of host memory");
     c->G = G; c->Mg = Mg; c->H = h->H; c->Hp = h->Hp;
     const size_t kbytes = (size_t)round_up((int64_t)sizeof(float) * G * Mg * h->Hp, 256);
-    c->bytes = kbytes + sizeof(int) * (size_t)G * Mg;
+    const size_t vbytes = sizeof(int) * (size_t)G * Mg;
+    c->bytes = ragged ? kbytes + (size_t)round_up((int64_t)vbytes, 256) + sizeof(int) * (size_t)G : kbytes + vbytes;
     if (hipMalloc((void**)&c->mem, c->bytes) != hipSuccess) { delete c; return fail(h, FSMG_ERR_NOMEM, "hipMalloc(cache) failed"); }
     c->keys = (float*)c->mem;
     c->vals = (int*)(c->mem + kbytes);
+    if (ragged) c->counts = (int*)(c->mem + c->bytes - sizeof(int) * (size_t)G);
     *out = c;
     return FSMG_OK;
 }
@@ -68,10 +72,12 @@ struct Tiles {
     std::vector<int> slot_query, tile_group;
     int n_tiles() const { return (int)tile_group.size(); }
 };
-template <class GroupOf>
-Tiles make_tiles(int n, int G, GroupOf&& group_of) {
+// keep(q): whether query q gets a slot at all (the scored positions of a *_masked call; the others get no slot and no tile)
+template <class GroupOf, class Keep>
+Tiles make_tiles(int n, int G, GroupOf&& group_of, Keep&& keep) {
     std::vector<int> count(G, 0), first(G + 1, 0);
-    for (int q = 0; q < n; ++q) ++count[group_of(q)];
+    for (int q = 0; q < n; ++q)
+        if (keep(q)) ++count[group_of(q)];
     for (int g = 0; g < G; ++g) first[g + 1] = first[g] + (count[g] + CACHE_ATTEND_QT - 1) / CACHE_ATTEND_QT;
     Tiles t;
     t.tile_group.resize(first[G]);
@@ -81,8 +87,13 @@ Tiles make_tiles(int n, int G, GroupOf&& group_of) {
         next[g] = first[g] * CACHE_ATTEND_QT;
         for (int j = first[g]; j < first[g + 1]; ++j) t.tile_group[j] = g;
     }
-    for (int q = 0; q < n; ++q) t.slot_query[next[group_of(q)]++] = q;
+    for (int q = 0; q < n; ++q)
+        if (keep(q)) t.slot_query[next[group_of(q)]++] = q;
     return t;
+}
+template <class GroupOf>
+Tiles make_tiles(int n, int G, GroupOf&& group_of) {
+    return make_tiles(n, G, group_of, [](int) { return true; });
 }
 
 // The layout of an attention call in h->cat: [out n_theta x n floats | tiles | (raw form) targets n ints | queries n x Hp floats]
@@ -109,7 +120,7 @@ int attend_launch(fsmg_model* h, const fsmg_cache_s* c, const Tiles& t, const At
     HIPCK(h, hipMemcpyAsync(s.slot_query, t.slot_query.data(), sizeof(int) * t.slot_query.size(), hipMemcpyHostToDevice, h->stream));
     HIPCK(h, hipMemcpyAsync(s.tile_group, t.tile_group.data(), sizeof(int) * t.tile_group.size(), hipMemcpyHostToDevice, h->stream));
     CacheAttendArgs a{};
-    a.keys = c->keys; a.vals = c->vals; a.Mg = c->Mg; a.Hp = c->Hp;
+    a.keys = c->keys; a.vals = c->vals; a.count = c->counts; a.Mg = c->Mg; a.Hp = c->Hp;
     a.Q = Q; a.ldq = c->Hp; a.B = B; a.T = h->T; a.tgt = tgt;
     a.slot_query = s.slot_query; a.tile_group = s.tile_group; a.n_tiles = t.n_tiles(); a.n = n;
     for (int k = 0; k < n_theta; ++k) a.theta[k] = thetas[k];
@@ -141,7 +152,7 @@ int self_launch(fsmg_model* h, const fsmg_cache_s* c, const SelfScratch& s, int 
                 long long vs_t, const int* val, long long ys_r, long long ys_t, const int32_t* group, const float* thetas, int n_theta) {
     CacheSelfArgs a{};
     if (c) {
-        a.keys = c->keys; a.vals = c->vals; a.Mg = c->Mg;
+        a.keys = c->keys; a.vals = c->vals; a.count = c->counts; a.Mg = c->Mg;
         if (group) {
             HIPCK(h, hipMemcpyAsync(s.row_group, group, sizeof(int) * (size_t)rows, hipMemcpyHostToDevice, h->stream));
             a.row_group = s.row_group;
@@ -190,8 +201,9 @@ int check_build_config(fsmg_model* h, const fsmg_cache_config* c, const int32_t*
     return check_cache_size(h, c->n_groups, (int64_t)(c->n_rows / c->n_groups) * h->T);
 }
 
-// fsmg_cache_build's work behind the argument checks
-int build_core(fsmg_model* h, const fsmg_cache_config* c, const int32_t* tokens, fsmg_cache_s** out) {
+// fsmg_cache_build's work behind the argument checks; with `len` (host [R], checked) fsmg_cache_build_masked's: the same passes, the
+// compacting fill behind each, a ragged cache of n_g = the group's lengths summed
+int build_core(fsmg_model* h, const fsmg_cache_config* c, const int32_t* tokens, fsmg_cache_s** out, const int32_t* len = nullptr) {
     const int R = c->n_rows, T = h->T;
     const int P = c->pass_rows > 0 ? c->pass_rows : FSMG_SCORE_PASS_ROWS;
     int rc;
@@ -199,7 +211,30 @@ int build_core(fsmg_model* h, const fsmg_cache_config* c, const int32_t* tokens,
     if ((rc = ensure_scratch(h, std::min(R, P))) != FSMG_OK) return rc;
     if ((rc = ensure_khf(h)) != FSMG_OK) return rc;
     fsmg_cache_s* cache = nullptr;
-    if ((rc = alloc_cache(h, c->n_groups, R / c->n_groups * T, &cache)) != FSMG_OK) return rc;
+    const int rpg = R / c->n_groups, Mg = rpg * T;
+    if ((rc = alloc_cache(h, c->n_groups, Mg, &cache, len != nullptr)) != FSMG_OK) return rc;
+    std::vector<int> dst;               // row r's first entry in the flat [G * Mg] entries; alive until the last pass is synchronised
+    int *d_len = nullptr, *d_dst = nullptr;
+    if (len) {
+        cache->n_g.assign((size_t)c->n_groups, 0);
+        dst.resize((size_t)R);
+        for (int r = 0; r < R; ++r) {
+            int& n = cache->n_g[(size_t)(r / rpg)];
+            dst[r] = (r / rpg) * Mg + n;
+            n += len[r];
+        }
+        // a pass's lengths and offsets in h->cat; every slot zero once, so that what lies behind a group's count reads back as zeros
+        Carver cv;
+        const size_t o_len = cv.take(sizeof(int) * (size_t)std::min(R, P)), o_dst = cv.take(sizeof(int) * (size_t)std::min(R, P));
+        rc = cat_reserve(h, cv.off);
+        hipError_t e = hipSuccess;
+        if (rc == FSMG_OK) e = hipMemsetAsync(cache->mem, 0, cache->bytes, h->stream);
+        if (rc == FSMG_OK && e == hipSuccess)
+            e = hipMemcpyAsync(cache->counts, cache->n_g.data(), sizeof(int) * cache->n_g.size(), hipMemcpyHostToDevice, h->stream);
+        if (rc == FSMG_OK && e != hipSuccess) rc = fail(h, FSMG_ERR_HIP, std::string("ragged cache setup: ") + hipGetErrorString(e));
+        if (rc != FSMG_OK) { hipStreamSynchronize(h->stream); free_cache(cache); return rc; }
+        d_len = (int*)(h->cat + o_len); d_dst = (int*)(h->cat + o_dst);
+    }
     rc = run_passes(
         h, tokens, R, P, c->tokens_on_device,
         [&](int r0, int B) -> int {
@@ -209,7 +244,15 @@ int build_core(fsmg_model* h, const fsmg_cache_config* c, const int32_t* tokens,
             });
             if (r != FSMG_OK) return r;
             // rows r0 .. r0 + B - 1 of the cache's [rows][T] entries: a pass repeated after a time-out overwrites what it wrote
-            HIPCK(h, launch_cache_fill(h->stream, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Y, B, T, h->H, h->Hp, r0, cache->keys, cache->vals));
+            if (!len) {
+                HIPCK(h, launch_cache_fill(h->stream, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Y, B, T, h->H, h->Hp, r0, cache->keys, cache->vals));
+                return FSMG_OK;
+            }
+            // the compacting fill, outside the graph as the plain one: the same entries on a repeated pass
+            HIPCK(h, hipMemcpyAsync(d_len, len + r0, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, h->stream));
+            HIPCK(h, hipMemcpyAsync(d_dst, dst.data() + r0, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, h->stream));
+            HIPCK(h, launch_cache_fill_len(h->stream, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Y, B, T, h->H, h->Hp, d_len, d_dst, cache->keys,
+                                           cache->vals));
             return FSMG_OK;
         },
         [](int, int) { return FSMG_OK; });          // (nothing comes back but the error word)
@@ -242,7 +285,9 @@ int check_score_config(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cach
 // causal kernel instead of k_cache_attend), `cache` may then be null, and a position whose set is empty keeps the model's log-prob
 int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_config* c, const int32_t* tokens, const int32_t* group,
                float* out_logprob, float* out_cache_prob, float* out_lstm_logprob, float* out_row_nll,
-               const fsmg_cache_self_config* self = nullptr) {
+               const fsmg_cache_self_config* self = nullptr, const int32_t* len = nullptr) {
+    // `len` (host [R], checked): the *_masked calls.  Position t of row r is scored iff t < len[r]; the passes are the same launches,
+    // the support attention gets tiles over the scored queries only, and every output is +0 behind a song's end.
     const int R = c->n_rows, T = h->T, NT = c->n_theta, NL = c->n_lambda;
     const int P = c->pass_rows > 0 ? c->pass_rows : FSMG_SCORE_PASS_ROWS;
     const size_t RT = (size_t)R * T;
@@ -270,7 +315,8 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
                 if ((r = self_scratch(h, B, n, NT, false, &ss)) != FSMG_OK) return r;
                 as.out = ss.out;
             } else if (want_pc) {       // query q = b * T + t of the pass, in its row's group
-                tiles = make_tiles(n, cache->G, [&](int q) { return group ? group[r0 + q / T] : 0; });
+                tiles = make_tiles(n, cache->G, [&](int q) { return group ? group[r0 + q / T] : 0; },
+                                   [&](int q) { return !len || q % T < len[r0 + q / T]; });
                 if ((r = attend_scratch(h, n, NT, tiles, false, &as)) != FSMG_OK) return r;
             }
             // fsmg_score's pass with the log-prob as its one output (the same graph key: the same launches)
@@ -283,6 +329,7 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
                 return FSMG_OK;
             });
             if (r != FSMG_OK || !want_pc) return r;
+            if (len && !self) HIPCK(h, hipMemsetAsync(as.out, 0, sizeof(float) * (size_t)NT * n, h->stream));   // the queries without a tile
             if (!self) return attend_launch(h, cache, tiles, as, n, h->Hs[h->L - 1], B, h->Y, c->thetas, NT);
             // row b's vector t: slot t + 1 of the time-major top-layer states; its value t: Y[t][b]
             return self_launch(h, cache, ss, B, T, self->window, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Hp, (long long)B * h->Hp, h->Y, 1, B,
@@ -297,6 +344,13 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
             return FSMG_OK;
         });
     if (rc != FSMG_OK) return rc;
+    auto clear_tail = [&](float* plane) {           // +0 at the positions behind each song's end
+        for (int r = 0; r < R; ++r)
+            for (size_t i = (size_t)r * T + len[r]; i < (size_t)(r + 1) * T; ++i) plane[i] = 0.0f;
+    };
+    if (len && want_lp) clear_tail(lp_host);
+    if (len && want_pc)
+        for (int k = 0; k < NT; ++k) clear_tail(pc_host + k * RT);
     if (!want_mix) return FSMG_OK;
     float* mix = out_logprob;
     if (!mix) { mix_own.resize(RT); mix = mix_own.data(); }            // (row NLL alone: one (theta, lambda) plane at a time)
@@ -309,7 +363,9 @@ int score_core(fsmg_model* h, const fsmg_cache_s* cache, const fsmg_cache_score_
             for (size_t i = 0; i < RT; ++i) plane[i] = mix_logprob(lp_host[i], pc[i], l1m, ll);
             if (self && !cache)         // position 0 of a row has an empty set: the model alone, at every lambda
                 for (size_t i = 0; i < RT; i += T) plane[i] = lp_host[i];
-            if (out_row_nll) row_nll(plane, R, T, c->nll_first, c->nll_count, out_row_nll + ((size_t)k * NL + j) * R);
+            if (len) clear_tail(plane);
+            if (out_row_nll && len) row_nll_masked(plane, R, T, c->nll_first, c->nll_count, len, out_row_nll + ((size_t)k * NL + j) * R);
+            else if (out_row_nll) row_nll(plane, R, T, c->nll_first, c->nll_count, out_row_nll + ((size_t)k * NL + j) * R);
         }
     return FSMG_OK;
 }
@@ -379,12 +435,13 @@ int ensure_value_index(fsmg_model* h, fsmg_cache_s* c) {
     for (size_t g = 0; g < G; ++g) {
         const int* v = vals.data() + g * Mg;
         int* o = order + g * Mg;
-        for (size_t i = 0; i < Mg; ++i) o[i] = (int)i;
-        std::stable_sort(o, o + Mg, [&](int x, int y) { return v[x] < v[y]; });
+        const size_t ng = (size_t)c->entries((int)g);       // the entries that exist: the slots behind them are in no segment
+        for (size_t i = 0; i < ng; ++i) o[i] = (int)i;
+        std::stable_sort(o, o + ng, [&](int x, int y) { return v[x] < v[y]; });
         beg.clear();
-        for (size_t j = 0; j < Mg; ++j)
+        for (size_t j = 0; j < ng; ++j)
             if (j == 0 || v[o[j]] != v[o[j - 1]]) beg.push_back((int)j);
-        beg.push_back((int)Mg);
+        beg.push_back((int)ng);
         // the segments longer than CACHE_MIX_SHORT first (a wave each), then the others (a thread each), value order inside both
         int ns = 0;
         for (int pass = 0; pass < 2; ++pass) {
@@ -464,7 +521,7 @@ int cache_self_file(fsmg_model* h, const CacheGen& cg, const float* h_out, int p
 static int scores_launch(fsmg_model* h, const CacheGen& cg, const float* Q) {
     const fsmg_cache_s* c = cg.c;
     CacheScoresArgs sa{};
-    sa.keys = c->keys; sa.Mg = c->Mg; sa.Hp = c->Hp; sa.Q = Q; sa.ldq = c->Hp;
+    sa.keys = c->keys; sa.count = c->counts; sa.Mg = c->Mg; sa.Hp = c->Hp; sa.Q = Q; sa.ldq = c->Hp;
     sa.slot_query = cg.d_slot_query; sa.tile_group = cg.d_tile_group; sa.n_tiles = (int)cg.tile_group.size(); sa.D = cg.D;
     ScopedTimer tm(h, "cache_scores");
     HIPCK(h, launch_cache_scores(h->stream, sa));
@@ -477,7 +534,7 @@ static CacheMixArgs mix_args(const fsmg_model* h, const CacheGen& cg, float* log
     CacheMixArgs ma{};
     ma.logits = logits; ma.ldl = cg.ldl; ma.ncols = h->V1; ma.pc = cg.pc; ma.out_lse = out_lse;
     if (const fsmg_cache_s* c = cg.c) {
-        ma.D = cg.D; ma.Mg = c->Mg; ma.row_group = cg.d_row_group;
+        ma.D = cg.D; ma.Mg = c->Mg; ma.count = c->counts; ma.row_group = cg.d_row_group;
         ma.order = c->order; ma.seg_beg = c->seg_beg; ma.seg_end = c->seg_end; ma.seg_val = c->seg_val;
         ma.n_seg = c->n_seg; ma.n_long = c->n_long;
     }
@@ -770,9 +827,9 @@ int fsmg_cache_self_attend(fsmg_handle h, fsmg_cache cache, const fsmg_cache_sel
     return rc;
 }
 
-int fsmg_cache_eval_step(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q, float theta,
-                         float lambda, float* nll) {
-    if (!h) return FSMG_ERR_INVALID;
+// fsmg_cache_eval_step, and with `masked` fsmg_cache_eval_step_masked (support_len [N * K], query_len [N * Q] on the host)
+static int cache_eval(fsmg_handle h, const int32_t* support, const int32_t* query, bool masked, const int32_t* support_len,
+                      const int32_t* query_len, int32_t N, int32_t K, int32_t Q, float theta, float lambda, float* nll) {
     if (!support || !query || !nll) return fail(h, FSMG_ERR_INVALID, "null support / query / nll");
     if (N < 1 || K < 1 || Q < 1 || (int64_t)N * K > (1 << 20) || (int64_t)N * Q > (1 << 20))
         return fail(h, FSMG_ERR_INVALID, "N, K, Q must be >= 1 and N * K, N * Q <= 2^20");
@@ -792,18 +849,129 @@ int fsmg_cache_eval_step(fsmg_handle h, const int32_t* support, const int32_t* q
     if (rc == FSMG_OK) rc = check_score_config(h, &shape, &sc, query, group.data(), outs);
     if (rc == FSMG_OK) rc = check_host_tokens(h, support, (size_t)N * K * h->T);
     if (rc == FSMG_OK) rc = check_host_tokens(h, query, (size_t)N * Q * h->T);
+    if (rc == FSMG_OK && masked) rc = check_host_lengths(h, support_len, (size_t)N * K);
+    if (rc == FSMG_OK && masked) rc = check_host_lengths(h, query_len, (size_t)N * Q);
     if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
     fsmg_cache_s* cache = nullptr;
-    if ((rc = build_core(h, &bc, support, &cache)) != FSMG_OK) return rc;
-    rc = score_core(h, cache, &sc, query, group.data(), lp.data(), nullptr, nullptr, nullptr);
+    if ((rc = build_core(h, &bc, support, &cache, masked ? support_len : nullptr)) != FSMG_OK) return rc;
+    rc = score_core(h, cache, &sc, query, group.data(), lp.data(), nullptr, nullptr, nullptr, nullptr, masked ? query_len : nullptr);
     hipStreamSynchronize(h->stream);
     free_cache(cache);                  // never registered: nobody else has seen it
     if (rc != FSMG_OK) return rc;
     double s = 0.0;
-    for (float v : lp) s += (double)v;
-    *nll = (float)(-s / (double)lp.size());
+    if (!masked) {
+        for (float v : lp) s += (double)v;
+        *nll = (float)(-s / (double)lp.size());
+        return FSMG_OK;
+    }
+    int64_t n_valid = 0;                // the scored positions in storage order
+    for (int r = 0; r < N * Q; ++r) {
+        for (int t = 0; t < query_len[r]; ++t) s += (double)lp[(size_t)r * h->T + t];
+        n_valid += query_len[r];
+    }
+    *nll = (float)(-s / (double)n_valid);
     return FSMG_OK;
+}
+
+int fsmg_cache_eval_step(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q, float theta,
+                         float lambda, float* nll) {
+    if (!h) return FSMG_ERR_INVALID;
+    return cache_eval(h, support, query, false, nullptr, nullptr, N, K, Q, theta, lambda, nll);
+}
+
+int fsmg_cache_eval_step_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len,
+                                const int32_t* query_len, int32_t N, int32_t K, int32_t Q, float theta, float lambda, float* nll) {
+    if (!h) return FSMG_ERR_INVALID;
+    return cache_eval(h, support, query, true, support_len, query_len, N, K, Q, theta, lambda, nll);
+}
+
+int fsmg_cache_build_masked(fsmg_handle h, const fsmg_cache_config* c, const int32_t* tokens, const int32_t* lengths, fsmg_cache* out) {
+    if (!h) return FSMG_ERR_INVALID;
+    int rc = check_build_config(h, c, tokens, out);
+    if (rc == FSMG_OK) rc = check_host_lengths(h, lengths, (size_t)c->n_rows);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    fsmg_cache_s* cache = nullptr;
+    rc = build_core(h, c, tokens, &cache, lengths);
+    if (rc != FSMG_OK) return rc;
+    h->caches.push_back(cache);
+    *out = cache;
+    return FSMG_OK;
+}
+
+int fsmg_cache_create_from_counts(fsmg_handle h, int32_t n_groups, int32_t entries_per_group, const int32_t* counts, const float* keys,
+                                  const int32_t* values, fsmg_cache* out) {
+    if (!h) return FSMG_ERR_INVALID;
+    if (!counts || !keys || !values || !out) return fail(h, FSMG_ERR_INVALID, "null counts / keys / values / out");
+    int rc = check_cache_size(h, n_groups, entries_per_group);
+    if (rc != FSMG_OK) return rc;
+    const size_t G = (size_t)n_groups, Mg = (size_t)entries_per_group, n = G * Mg;
+    for (size_t g = 0; g < G; ++g)
+        if (counts[g] < 1 || counts[g] > entries_per_group) return fail(h, FSMG_ERR_INVALID, "every count must be in [1, entries_per_group]");
+    for (size_t g = 0; g < G; ++g)      // the slots behind a count are not read
+        for (size_t i = 0; i < (size_t)counts[g]; ++i)
+            if (values[g * Mg + i] < 0 || values[g * Mg + i] >= h->V1) return fail(h, FSMG_ERR_TOKEN_RANGE, "cache value outside [0, input_size]");
+    BEGIN_CALL(h);
+    fsmg_cache_s* c = nullptr;
+    if ((rc = alloc_cache(h, n_groups, entries_per_group, &c, true)) != FSMG_OK) return rc;
+    c->n_g.assign(counts, counts + G);
+    std::vector<float> kp(n * h->Hp, 0.0f);             // the pad units and the slots behind the counts are exact zeros
+    std::vector<int> vp(n, 0);
+    for (size_t g = 0; g < G; ++g)
+        for (size_t i = 0; i < (size_t)counts[g]; ++i) {
+            const size_t e = g * Mg + i;
+            std::memcpy(kp.data() + e * h->Hp, keys + e * h->H, sizeof(float) * h->H);
+            vp[e] = values[e];
+        }
+    hipError_t e = hipMemcpyAsync(c->keys, kp.data(), sizeof(float) * kp.size(), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->vals, vp.data(), sizeof(int) * n, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->counts, c->n_g.data(), sizeof(int) * G, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);           // the host vectors go out of scope
+    if (e != hipSuccess) { free_cache(c); return fail(h, FSMG_ERR_HIP, std::string("cache upload: ") + hipGetErrorString(e)); }
+    h->caches.push_back(c);
+    *out = c;
+    return FSMG_OK;
+}
+
+int fsmg_cache_counts(fsmg_handle h, fsmg_cache cache, int32_t* out) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_cache_s* c = find_cache(h, cache);
+    if (!c) return FSMG_ERR_INVALID;
+    if (!out) return fail(h, FSMG_ERR_INVALID, "null out");
+    for (int g = 0; g < c->G; ++g) out[g] = c->entries(g);
+    return FSMG_OK;
+}
+
+int fsmg_cache_score_masked(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const int32_t* tokens, const int32_t* lengths,
+                            const int32_t* group, float* out_logprob, float* out_cache_prob, float* out_lstm_logprob, float* out_row_nll) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_cache_s* s = find_cache(h, cache);
+    if (!s) return FSMG_ERR_INVALID;
+    const void* outs[4] = {out_logprob, out_cache_prob, out_lstm_logprob, out_row_nll};
+    int rc = check_score_config(h, s, c, tokens, group, outs);
+    if (rc == FSMG_OK) rc = check_host_lengths(h, lengths, (size_t)c->n_rows);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return score_core(h, s, c, tokens, group, out_logprob, out_cache_prob, out_lstm_logprob, out_row_nll, nullptr, lengths);
+}
+
+int fsmg_cache_self_score_masked(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const fsmg_cache_self_config* sc,
+                                 const int32_t* tokens, const int32_t* lengths, const int32_t* group, float* out_logprob,
+                                 float* out_cache_prob, float* out_lstm_logprob, float* out_row_nll) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_cache_s* s = nullptr;
+    if (cache && !(s = find_cache(h, cache))) return FSMG_ERR_INVALID;
+    fsmg_cache_s shape;                 // (no support cache: the checks read a shape, and the groups are ignored)
+    shape.G = 1; shape.H = h->H; shape.Hp = h->Hp;
+    if (!s) group = nullptr;
+    const void* outs[4] = {out_logprob, out_cache_prob, out_lstm_logprob, out_row_nll};
+    int rc = check_score_config(h, s ? s : &shape, c, tokens, group, outs);
+    if (rc == FSMG_OK) rc = check_self_config(h, sc);
+    if (rc == FSMG_OK) rc = check_host_lengths(h, lengths, (size_t)c->n_rows);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return score_core(h, s, c, tokens, group, out_logprob, out_cache_prob, out_lstm_logprob, out_row_nll, sc, lengths);
 }
 
 }  // extern "C"

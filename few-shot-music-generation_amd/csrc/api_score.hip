@@ -23,8 +23,9 @@ int check_score_config(fsmg_model* h, const fsmg_score_config* c, const int32_t*
 }
 
 // fsmg_score's work at the parameters the handle holds now (no BEGIN_CALL: the MAML variant calls it at theta')
+// (`len`: fsmg_score_masked -- the passes are the same launches; the host clears what lies behind a song's end)
 int score_core(fsmg_model* h, const fsmg_score_config* c, const int32_t* tokens, float* out_logprob, int32_t* out_rank,
-               float* out_entropy, int32_t* out_argmax, float* out_row_nll) {
+               float* out_entropy, int32_t* out_argmax, float* out_row_nll, const int32_t* len = nullptr) {
     const int R = c->n_rows, T = h->T;
     const int P = c->pass_rows > 0 ? c->pass_rows : FSMG_SCORE_PASS_ROWS;      // a function of the config alone, never of Bcap
     int rc;
@@ -61,11 +62,37 @@ int score_core(fsmg_model* h, const fsmg_score_config* c, const int32_t* tokens,
             return FSMG_OK;
         });
     if (rc != FSMG_OK) return rc;
-    if (out_row_nll) row_nll(lp_host, R, T, c->nll_first, c->nll_count, out_row_nll);
+    if (len)
+        for (int r = 0; r < R; ++r)
+            for (size_t i = (size_t)r * T + len[r]; i < (size_t)(r + 1) * T; ++i) {
+                if (mask & 1) lp_host[i] = 0.0f;
+                if (mask & 2) out_rank[i] = 0;
+                if (mask & 4) out_entropy[i] = 0.0f;
+                if (mask & 8) out_argmax[i] = 0;
+            }
+    if (out_row_nll && len) row_nll_masked(lp_host, R, T, c->nll_first, c->nll_count, len, out_row_nll);
+    else if (out_row_nll) row_nll(lp_host, R, T, c->nll_first, c->nll_count, out_row_nll);
     return FSMG_OK;
 }
 
 }  // namespace
+
+int check_host_lengths(fsmg_model* h, const int32_t* len, size_t n) {
+    if (!len) return fail(h, FSMG_ERR_INVALID, "null lengths");
+    for (size_t i = 0; i < n; ++i)
+        if (len[i] < 1 || len[i] > h->T) return fail(h, FSMG_ERR_INVALID, "every length must be in [1, max_len]");
+    return FSMG_OK;
+}
+
+void row_nll_masked(const float* logprob, int R, int T, int nll_first, int nll_count, const int32_t* len, float* out) {
+    const int t0 = nll_first, t1 = nll_count > 0 ? t0 + nll_count : T;
+    for (int r = 0; r < R; ++r) {
+        const int te = std::min(t1, (int)len[r]);
+        double s = 0.0;
+        for (int t = t0; t < te; ++t) s += (double)logprob[(size_t)r * T + t];
+        out[r] = te > t0 ? (float)(-s / (double)(te - t0)) : NAN;
+    }
+}
 
 int check_host_tokens(fsmg_model* h, const int32_t* tokens, size_t n) {
     for (size_t i = 0; i < n; ++i)
@@ -126,6 +153,17 @@ int fsmg_score(fsmg_handle h, const fsmg_score_config* c, const int32_t* tokens,
     if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
     return score_core(h, c, tokens, out_logprob, out_rank, out_entropy, out_argmax, out_row_nll);
+}
+
+int fsmg_score_masked(fsmg_handle h, const fsmg_score_config* c, const int32_t* tokens, const int32_t* lengths, float* out_logprob,
+                      int32_t* out_rank, float* out_entropy, int32_t* out_argmax, float* out_row_nll) {
+    if (!h) return FSMG_ERR_INVALID;
+    const void* outs[5] = {out_logprob, out_rank, out_entropy, out_argmax, out_row_nll};
+    int rc = check_score_config(h, c, tokens, outs);
+    if (rc == FSMG_OK) rc = check_host_lengths(h, lengths, (size_t)c->n_rows);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return score_core(h, c, tokens, out_logprob, out_rank, out_entropy, out_argmax, out_row_nll, lengths);
 }
 
 int fsmg_maml_score(fsmg_handle h, const fsmg_score_config* c, const int32_t* support, int32_t n_support_rows, int32_t inner_steps,

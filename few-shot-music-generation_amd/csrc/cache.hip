@@ -6,12 +6,12 @@
 // k_cache_attend: p_cache(y) = sum_{i : v_i = y} exp(theta (d_i - d_max)) / sum_i exp(theta (d_i - d_max)), d_i = q . k_i over the
 // Mg keys of the query's group, for up to 8 values of theta in one pass over the keys.  One 256-thread workgroup owns a tile of 32
 // queries of ONE group (the host sorts the queries by group: CacheAttendArgs::slot_query / tile_group) and keeps them in LDS; its four
-// waves walk the group's 16-key tiles round robin (wave w takes tiles w, w + 4, ...: a function of Mg alone).  Keys are the A operand
+// waves walk the group's 16-key tiles round robin (wave w takes tiles w, w + 4, ...: a function of the group's entry count alone -- Mg, or n_g of a ragged cache).  Keys are the A operand
 // and queries the B operand, so that lane l ends up with the scores of query l % 16 against keys l / 16 + {0, 4, 8, 12} of the tile: every
 // lane runs an online softmax of ITS OWN (query, key subset) pair in registers -- one running maximum for all theta (theta >= 0), a
 // denominator and a numerator per theta -- and nothing crosses lanes inside the key loop.  The score matrix never leaves the
 // registers.  The partial (max, sums) are merged in a fixed order: lanes 16 / 32 apart by shuffles, then the four waves through LDS by
-// one thread per query.  A key index >= Mg is skipped (masked, not scored as zero).  No atomics.  A query's bits depend on its vector,
+// one thread per query.  A key index >= the entry count is skipped (masked, not scored as zero).  No atomics.  A query's bits depend on its vector,
 // its group's entries and theta alone: each score is an accumulator element of its own, and the merge tree does not depend on the slot
 // a query got.
 //
@@ -235,10 +235,12 @@ __global__ __launch_bounds__(256) void k_cache_attend(CacheAttendArgs a) {
     CaState st0, st1;
     const float* qp0 = ca_q + kq * ldl + 4 * ks;
     const float* qp1 = qp0 + 16 * ldl;
-    const int n_kt = (Mg + 15) >> 4;
+    // the group's entries: Mg stays the stride, ng is the extent (g is the tile's one group: a uniform load, uniform trip counts)
+    const int ng = a.count ? a.count[g] : Mg;
+    const int n_kt = (ng + 15) >> 4;
     for (int kt = wave; kt < n_kt; kt += CA_WAVES) {
         // lane l loads key row l % 16 of the tile (a tail row: the group's last key, in bounds, masked below), k = 16 j + 4 (l / 16) .. + 3
-        const int krow = min(kt * 16 + kq, Mg - 1);
+        const int krow = min(kt * 16 + kq, ng - 1);
         const float* kp = kg + (long long)krow * Hp + 4 * ks;
         f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
         ca_key_tile<false>(kp, qp0, qp1, Hp, Hp, 4 * ks, acc0, acc1);
@@ -248,8 +250,8 @@ __global__ __launch_bounds__(256) void k_cache_attend(CacheAttendArgs a) {
         unsigned m = 0;                             // a tail key has no mass
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            v[i] = vg[min(kbase + 4 * i, Mg - 1)];
-            if (kbase + 4 * i < Mg) m |= 1u << i;
+            v[i] = vg[min(kbase + 4 * i, ng - 1)];
+            if (kbase + 4 * i < ng) m |= 1u << i;
         }
         ca_update_masked(st0, acc0, m, v, y0, theta, n_theta);
         ca_update_masked(st1, acc1, m, v, y1, theta, n_theta);
@@ -290,13 +292,15 @@ __global__ __launch_bounds__(256) void k_cache_attend_self(CacheSelfArgs a) {
     const float* qp0 = ca_q + kq * ldl + 4 * ks;
     const float* qp1 = qp0 + 16 * ldl;
     // phase one: the group's support keys, every one visible to every position of the row (k_cache_attend's walk)
-    const int n_kt = (Mg + 15) >> 4;
+    // (r is the workgroup's one row, so its group and the group's entry count ng are uniform; Mg stays the stride)
+    const int g = Mg > 0 && a.row_group ? a.row_group[r] : 0;
+    const int ng = Mg > 0 && a.count ? a.count[g] : Mg;
+    const int n_kt = (ng + 15) >> 4;
     if (Mg > 0) {
-        const int g = a.row_group ? a.row_group[r] : 0;
         const float* kg = a.keys + (long long)g * Mg * Hp;
         const int* vg = a.vals + (long long)g * Mg;
         for (int kt = wave; kt < n_kt; kt += CA_WAVES) {
-            const int krow = min(kt * 16 + kq, Mg - 1);
+            const int krow = min(kt * 16 + kq, ng - 1);
             f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
             ca_key_tile<false>(kg + (long long)krow * Hp + 4 * ks, qp0, qp1, Hp, H, 4 * ks, acc0, acc1);
             const int kbase = kt * 16 + ks;
@@ -304,8 +308,8 @@ __global__ __launch_bounds__(256) void k_cache_attend_self(CacheSelfArgs a) {
             unsigned m = 0;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                v[i] = vg[min(kbase + 4 * i, Mg - 1)];
-                if (kbase + 4 * i < Mg) m |= 1u << i;
+                v[i] = vg[min(kbase + 4 * i, ng - 1)];
+                if (kbase + 4 * i < ng) m |= 1u << i;
             }
             ca_update_masked(st0, acc0, ta < T ? m : 0u, v, y0, theta, n_theta);
             ca_update_masked(st1, acc1, tb < T ? m : 0u, v, y1, theta, n_theta);
@@ -355,6 +359,27 @@ __global__ __launch_bounds__(256) void k_cache_fill(const float* __restrict__ Hs
     }
 }
 
+// k_cache_fill for a ragged cache (fsmg_kernels.h launch_cache_fill_len): position t of pass row b becomes entry dst[b] + t of the flat
+// [G * Mg] entries when t < len[b], and is dropped otherwise.  The host makes dst, so that a group's rows follow each other without
+// gaps: len[b] <= T and the group's capacity Mg = rows_per_group * T keep every index inside the group.
+__global__ __launch_bounds__(256) void k_cache_fill_len(const float* __restrict__ Hs1, const int* __restrict__ Y, int B, int T, int H, int Hp,
+                                                        const int* __restrict__ len, const int* __restrict__ dst, float* __restrict__ keys,
+                                                        int* __restrict__ vals) {
+    const int c4n = Hp >> 2;
+    const long long total = (long long)T * B * c4n;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const long long row = idx / c4n;                // t * B + b
+        const int c4 = (int)(idx - row * c4n);
+        const int t = (int)(row / B), b = (int)(row - (long long)t * B);
+        if (t >= len[b]) continue;                      // behind the song's end: no entry
+        const int c = 4 * c4;
+        const float4 v = ca_load4_h(Hs1 + row * Hp + c, c, H);
+        const long long e = (long long)dst[b] + t;
+        *reinterpret_cast<float4*>(keys + e * Hp + c) = v;
+        if (c4 == 0) vals[e] = Y[row];
+    }
+}
+
 // ---------------------------------------------------------------- cache-conditioned generation, stage one (fsmg_kernels.h)
 // One wave: 16 keys of a chunk against the 16 (or 32) queries of a tile, operands straight from global memory -- a wave's key
 // fragment is read once, and the tile's queries are a few KiB that every wave of the group reads and the caches keep.  Four k groups
@@ -388,13 +413,16 @@ __global__ __launch_bounds__(64) void k_cache_scores(CacheScoresArgs a, int n_ch
     const int tile = blockIdx.x / n_chunks, chunk = blockIdx.x - tile * n_chunks;
     const int lane = threadIdx.x, kq = lane & 15, ks = lane >> 4;
     const int Hp = a.Hp, Mg = a.Mg;
+    const int g = a.tile_group[tile];
+    const int ng = a.count ? a.count[g] : Mg;       // the tile's one group: Mg stays the stride of keys and of D
+    if (chunk * CACHE_GEN_CHUNK >= ng) return;      // a chunk wholly behind the count (wave-uniform: one wave per block)
     const int* slots = a.slot_query + (long long)tile * CACHE_ATTEND_QT;
     const int q0 = slots[kq], q1 = slots[16 + kq];
     const bool two = slots[16] >= 0;                // the slots fill in order: a wave-uniform choice
     const int qa = slots[0];                        // (never empty) an empty slot reads this row, in bounds, and stores nothing
     // lane l loads key row l % 16 of the chunk (a tail row: the group's last key, in bounds, not stored), k = 16 j + 4 (l / 16) .. + 3
-    const int krow = min(chunk * CACHE_GEN_CHUNK + kq, Mg - 1);
-    const float* kp = a.keys + ((long long)a.tile_group[tile] * Mg + krow) * Hp + 4 * ks;
+    const int krow = min(chunk * CACHE_GEN_CHUNK + kq, ng - 1);
+    const float* kp = a.keys + ((long long)g * Mg + krow) * Hp + 4 * ks;
     const float* qp0 = a.Q + (long long)(q0 >= 0 ? q0 : qa) * a.ldq + 4 * ks;
     const float* qp1 = a.Q + (long long)(q1 >= 0 ? q1 : qa) * a.ldq + 4 * ks;
     f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
@@ -404,7 +432,7 @@ __global__ __launch_bounds__(64) void k_cache_scores(CacheScoresArgs a, int n_ch
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int key = chunk * CACHE_GEN_CHUNK + 4 * i + ks;
-        if (key >= Mg) continue;                    // a tail key has no score
+        if (key >= ng) continue;                    // a tail key has no score
         if (q0 >= 0) a.D[(long long)q0 * Mg + key] = acc0[i];
         if (two && q1 >= 0) a.D[(long long)q1 * Mg + key] = acc1[i];
     }
@@ -513,6 +541,16 @@ hipError_t launch_cache_fill(hipStream_t s, const float* Hs1, const int* Y, int 
     const long long total = (long long)T * B * (Hp >> 2);
     const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
     hipLaunchKernelGGL(k_cache_fill, dim3(blocks), dim3(256), 0, s, Hs1, Y, B, T, H, Hp, r0, keys, vals);
+    return hipGetLastError();
+}
+
+hipError_t launch_cache_fill_len(hipStream_t s, const float* Hs1, const int* Y, int B, int T, int H, int Hp, const int* len, const int* dst,
+                                 float* keys, int* vals) {
+    if (B <= 0 || T <= 0) return hipSuccess;
+    if ((Hp & 3) != 0 || !len || !dst) return hipErrorInvalidValue;
+    const long long total = (long long)T * B * (Hp >> 2);
+    const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_cache_fill_len, dim3(blocks), dim3(256), 0, s, Hs1, Y, B, T, H, Hp, len, dst, keys, vals);
     return hipGetLastError();
 }
 

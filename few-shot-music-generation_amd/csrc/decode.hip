@@ -765,15 +765,16 @@ __global__ __launch_bounds__(PICK_THREADS) void k_cache_mix(CacheMixArgs a) {
     float* pc = a.pc + (long long)b * a.ldl;
     double* d = a.D + (long long)b * Mg;
     const int g = a.row_group[b];
+    const int ng = a.count ? a.count[g] : Mg;       // the row's group's entries (block-uniform); Mg stays the stride of D
 
     float mx; int mi;
     const float lse = row_max_lse<false>(sh, row, nullptr, ncols, mx, mi);
 
     double m = -INFINITY;
-    for (int i = tid; i < Mg; i += PICK_THREADS) m = fmax(m, d[i]);
+    for (int i = tid; i < ng; i += PICK_THREADS) m = fmax(m, d[i]);
     m = block_max(sh, m);
     double z = 0.0;
-    mix_weights(d, Mg, a.u, ceil(a.u * m), z);
+    mix_weights(d, ng, a.u, ceil(a.u * m), z);
     for (int v = tid; v < ncols; v += PICK_THREADS) pc[v] = 0.0f;
     const double Z = block_sum(sh, z);
 
@@ -797,12 +798,13 @@ __global__ __launch_bounds__(PICK_THREADS) void k_cache_mix_self(CacheMixSelfArg
     const int len = s.row_len ? s.row_len[b] : s.len;
     const int n = min(len, s.W), lo = len - n;
     const int* val = s.val + (long long)b * s.ldv + lo;
+    const int ng = Mg > 0 && a.count ? a.count[a.row_group[b]] : Mg;       // the row's group's entries (block-uniform)
 
     float mx; int mi;
     const float lse = row_max_lse<false>(sh, row, nullptr, ncols, mx, mi);
 
     double m = -INFINITY;
-    for (int i = tid; i < Mg; i += PICK_THREADS) m = fmax(m, d[i]);
+    for (int i = tid; i < ng; i += PICK_THREADS) m = fmax(m, d[i]);
     for (int i = tid; i < n; i += PICK_THREADS) m = fmax(m, d2[i]);
     m = block_max(sh, m);
     if (Mg == 0 && n == 0) {                        // the empty union: the model alone (block-uniform)
@@ -812,7 +814,7 @@ __global__ __launch_bounds__(PICK_THREADS) void k_cache_mix_self(CacheMixSelfArg
     }
     const double S = ceil(a.u * m);
     double z = 0.0;
-    mix_weights(d, Mg, a.u, S, z);
+    mix_weights(d, ng, a.u, S, z);
     mix_weights(d2, n, a.u, S, z);
     for (int v = tid; v < ncols; v += PICK_THREADS) pm[v] = 0.0;
     const double Z = block_sum(sh, z);

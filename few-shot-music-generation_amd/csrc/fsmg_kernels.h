@@ -499,9 +499,14 @@ __host__ __device__ inline float mix_logprob(float lp, float pc, double log1m_la
     if (hi == -INFINITY) return -INFINITY;
     return (float)(hi + log1p(exp(lo - hi)));
 }
+// Ragged groups: Mg is a capacity and a stride; `count` ([G], or nullptr: every group holds Mg entries) says how many
+// of a group's slots exist, n_g in [1, Mg].  Every kernel that walks a group's entries walks 0 .. n_g - 1 and never scores a slot
+// behind them; the group is uniform over the workgroup (or the wave), so the count is one uniform load and every branch on it is
+// uniform.  With count == nullptr each kernel does what it did before the counts existed, bit for bit.
 struct CacheAttendArgs {
     const float* keys;          // [G][Mg][Hp], pad units exact zeros
     const int* vals;            // [G][Mg]
+    const int* count;           // [G] entries per group, or nullptr: Mg each
     int Mg, Hp;
     const float* Q; long long ldq;
     int B, T;
@@ -518,6 +523,10 @@ hipError_t launch_cache_attend(hipStream_t s, const CacheAttendArgs& a);
 // [rows][T] entries; units >= H are written as zeros
 hipError_t launch_cache_fill(hipStream_t s, const float* Hs1, const int* Y, int B, int T, int H, int Hp, long long r0, float* keys,
                              int* vals);
+// the compacting fill of a ragged cache: pass row b files its positions t < len[b] as entries dst[b] + t of the flat [G * Mg] entry
+// array (dst[b] = g_b * Mg + the lengths of the group's earlier rows: the host's sum) and writes nothing for t >= len[b]
+hipError_t launch_cache_fill_len(hipStream_t s, const float* Hs1, const int* Y, int B, int T, int H, int Hp, const int* len, const int* dst,
+                                 float* keys, int* vals);
 
 // ---- self-cache (fsmg_cache_self_attend / fsmg_cache_self_score): position t of a row attends over its group's Mg
 // support entries (Mg == 0: none) and over the row's OWN entries i with t - W <= i < t, entry i = (key = the row's vector i, value =
@@ -532,6 +541,7 @@ hipError_t launch_cache_fill(hipStream_t s, const float* Hs1, const int* Y, int 
 struct CacheSelfArgs {
     const float* keys;          // [G][Mg][Hp], pad units exact zeros; unused at Mg == 0
     const int* vals;            // [G][Mg]
+    const int* count;           // [G] entries per group, or nullptr: Mg each
     int Mg;                     // 0: no support cache
     const int* row_group;       // [n_rows], or nullptr: all 0
     int H, Hp;
@@ -555,6 +565,7 @@ hipError_t launch_cache_attend_self(hipStream_t s, const CacheSelfArgs& a);
 constexpr int CACHE_GEN_CHUNK = 16;
 struct CacheScoresArgs {
     const float* keys;          // [G][Mg][Hp], pad units exact zeros
+    const int* count;           // [G] entries per group, or nullptr: Mg each; a chunk wholly behind the count stores nothing
     int Mg, Hp;
     const float* Q; int ldq;    // row r's query: Q + r * ldq (Hp floats; the pad units finite)
     const int* slot_query;      // [n_tiles][CACHE_ATTEND_QT]
@@ -566,7 +577,7 @@ hipError_t launch_cache_scores(hipStream_t s, const CacheScoresArgs& a);
 // Stage two (decode.hip: it shares the picks' row sweep), one workgroup per row r of group g = row_group[r]:
 //   lse    the picks' logsumexp of the logits row (row_max_lse: bitwise the number k_gen_pick subtracts), lp_v = fl32(z_v - lse);
 //   d_max  the exact maximum of the row's Mg scores, ONE shift S = ceil(u d_max) for every entry, w_i = ca_exp2(u d_i - S) (written
-//          over D), Z = sum_i w_i over a fixed tree that depends on Mg alone;
+//          over D), Z = sum_i w_i over a fixed tree that depends on the group's entry count alone (Mg without counts);
 //   mass   of each distinct value of the group through the cache's value index (order: the entries in stable order by value;
 //          seg_beg / seg_end / seg_val: the segments of equal value, those longer than CACHE_MIX_SHORT first, n_long of n_seg): a
 //          long segment is summed by one wave (lanes stride it, then a butterfly), a short one by one thread in entry order -- a
@@ -578,7 +589,8 @@ hipError_t launch_cache_scores(hipStream_t s, const CacheScoresArgs& a);
 constexpr int CACHE_MIX_SHORT = 32;
 struct CacheMixArgs {
     float* logits; int ldl, ncols;      // [R][ldl]: z in, z'' out
-    double* D; int Mg;                  // [R][Mg]: scores in, masses out
+    double* D; int Mg;                  // [R][Mg]: scores in, masses out (row stride Mg; the first n_g of a row exist)
+    const int* count;                   // [G] entries per group, or nullptr: Mg each
     const int* row_group;               // [R]
     const int *order, *seg_beg, *seg_end, *seg_val;   // [G][Mg] each
     const int *n_seg, *n_long;          // [G]

@@ -77,6 +77,11 @@ struct fsmg_cache_s {
     char* mem = nullptr;
     float* keys = nullptr;              // [G][Mg][Hp], pad units exact zeros
     int* vals = nullptr;                // [G][Mg]
+    // ragged groups: entries 0 .. n_g - 1 of group g exist, the slots behind them hold zero keys and value 0 and are
+    // never scored.  A uniform cache has neither array: n_g = Mg for every group, and its kernels get a null count pointer.
+    int* counts = nullptr;              // device [G], inside `mem`, or nullptr
+    std::vector<int> n_g;               // the host copy, empty for a uniform cache
+    int entries(int g) const { return n_g.empty() ? Mg : n_g[(size_t)g]; }
     // the value index (cache-conditioned generation): per group the entries in stable order by value and the segments
     // of equal value (CacheMixArgs in fsmg_kernels.h).  An allocation of its own, built on the first call that needs it (ensure_value_index), counted in `bytes` from
     // then on, freed with the cache.
@@ -662,6 +667,10 @@ int run_passes(fsmg_model* h, const int32_t* tokens, int R, int P, int on_device
 int check_host_tokens(fsmg_model* h, const int32_t* tokens, size_t n);      // every id in [0, input_size), before any device work
 // out[r] = -mean of logprob[r][t0 .. t1) over R rows of T: fp64, increasing t, rounded once -- bitwise recomputable from the log-probs
 void row_nll(const float* logprob, int R, int T, int nll_first, int nll_count, float* out);
+// the same over the scored positions t < len[r] of the window; NaN where the window holds none
+void row_nll_masked(const float* logprob, int R, int T, int nll_first, int nll_count, const int32_t* len, float* out);
+// host lengths [n] of a *_masked scoring / cache call: non-null and every value in [1, max_len], before any device work
+int check_host_lengths(fsmg_model* h, const int32_t* len, size_t n);
 // api_decode.hip / api_cache.hip: what cache-conditioned generation shares between the decode driver and the cache
 int gen_reserve(fsmg_model* h, size_t bytes);              // h->gen holds at least `bytes`: grown between calls, after a stream sync
 fsmg_cache_s* find_cache(fsmg_model* h, fsmg_cache c);     // the cache if this handle owns it, else nullptr with the error set

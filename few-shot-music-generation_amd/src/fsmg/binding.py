@@ -200,6 +200,14 @@ SIGNATURES = {
     'fsmg_cache_attend': (C.c_int, [_P, _P, C.c_int32, _F32P, _I32P, _I32P, _F32P, C.c_int32, _F32P]),
     'fsmg_cache_score': (C.c_int, [_P, _P, C.POINTER(FsmgCacheScoreConfig), _P, _I32P, _F32P, _F32P, _F32P, _F32P]),
     'fsmg_cache_eval_step': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _F32P]),
+    'fsmg_score_masked': (C.c_int, [_P, C.POINTER(FsmgScoreConfig), _P, _I32P, _F32P, _I32P, _F32P, _I32P, _F32P]),
+    'fsmg_cache_build_masked': (C.c_int, [_P, C.POINTER(FsmgCacheConfig), _P, _I32P, C.POINTER(_P)]),
+    'fsmg_cache_create_from_counts': (C.c_int, [_P, C.c_int32, C.c_int32, _I32P, _F32P, _I32P, C.POINTER(_P)]),
+    'fsmg_cache_counts': (C.c_int, [_P, _P, _I32P]),
+    'fsmg_cache_score_masked': (C.c_int, [_P, _P, C.POINTER(FsmgCacheScoreConfig), _P, _I32P, _I32P, _F32P, _F32P, _F32P, _F32P]),
+    'fsmg_cache_self_score_masked': (C.c_int, [_P, _P, C.POINTER(FsmgCacheScoreConfig), C.POINTER(FsmgCacheSelfConfig), _P, _I32P, _I32P,
+                                               _F32P, _F32P, _F32P, _F32P]),
+    'fsmg_cache_eval_step_masked': (C.c_int, [_P, _P, _P, _I32P, _I32P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _F32P]),
     'fsmg_cache_generate': (C.c_int, [_P, _P, C.POINTER(FsmgCacheGenConfig), C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _I32P, _P,
                                       _I32P, _F32P]),
     'fsmg_dstate_cache_generate': (C.c_int, [_P, _P, _P, C.POINTER(FsmgCacheGenConfig), C.POINTER(FsmgGenConfig),
@@ -395,6 +403,13 @@ class FsmgCache(object):
         vals = np.empty((self.groups, self.entries), np.int32)
         self._call(self._model._lib.fsmg_cache_get, _f32p(keys), vals.ctypes.data_as(_I32P))
         return keys, vals
+
+    def counts(self):
+        """-> int32 [groups]: the entries each group holds -- `entries` for every group of a uniform cache; a ragged one (cache_build
+        with lengths, cache_from with counts) holds fewer, and the slots behind them read back as zeros"""
+        out = np.empty(self.groups, np.int32)
+        self._call(self._model._lib.fsmg_cache_counts, out.ctypes.data_as(_I32P))
+        return out
 
 
 class FsmgModel(object):
@@ -902,8 +917,17 @@ class FsmgModel(object):
         return FsmgScoreConfig(version=FSMG_SCORE_CONFIG_VERSION, n_rows=int(n_rows), tokens_on_device=int(tokens_on_device),
                                nll_first=int(nll_first), nll_count=int(nll_count), pass_rows=int(pass_rows))
 
-    def _score(self, adapt, tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows):
-        """fsmg_score (adapt = ()) or fsmg_maml_score (adapt = its support arguments)"""
+    def _lengths(self, lengths, n, what='lengths'):
+        """the true lengths of n rows as int32 [n], each in [1, max_len]; ValueError otherwise (before the library is called)"""
+        a = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        if a.size != n:
+            raise ValueError('%s must hold %d values, got %r' % (what, n, np.shape(lengths)))
+        if a.size and (a.min() < 1 or a.max() > self.max_len):
+            raise ValueError('every value of %s must be in [1, %d]' % (what, self.max_len))
+        return a
+
+    def _score(self, adapt, tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows, lengths=None):
+        """fsmg_score (adapt = ()), fsmg_maml_score (adapt = its support arguments) or fsmg_score_masked (lengths)"""
         if isinstance(tokens, (int, np.integer)):
             tp, dev, _keep, R = C.c_void_p(int(tokens)), 1, None, int(n_rows)
         else:
@@ -927,18 +951,24 @@ class FsmgModel(object):
             out['row_nll'] = np.empty(R, np.float32)
         f = lambda k: _f32p(out[k]) if k in out else None
         i = lambda k: out[k].ctypes.data_as(_I32P) if k in out else None
+        if lengths is not None:
+            ln = self._lengths(lengths, R)
+            self._ck(self._lib.fsmg_score_masked(self._h, C.byref(c), tp, ln.ctypes.data_as(_I32P), f('logprob'), i('rank'), f('entropy'),
+                                                 i('argmax'), f('row_nll')))
+            return out
         fn = self._lib.fsmg_maml_score if adapt else self._lib.fsmg_score
         self._ck(fn(self._h, C.byref(c), *adapt, tp, f('logprob'), i('rank'), f('entropy'), i('argmax'), f('row_nll')))
         return out
 
     def score(self, tokens, logprob=True, rank=False, entropy=False, argmax=False, row_nll=True, nll_first=0, nll_count=0,
-              pass_rows=0, n_rows=None):
+              pass_rows=0, n_rows=None, lengths=None):
         """Per-token statistics of given songs: tokens int32 [R, max_len] (or a device address with n_rows) -> a dict with the
         requested arrays: 'logprob' float32 [R, T] (model log-probability of each token), 'rank' int32 [R, T] (0-based rank of the
         true token, lower index first on ties), 'entropy' float32 [R, T] (predictive entropy), 'argmax' int32 [R, T], 'row_nll'
         float32 [R] (mean NLL of positions nll_first .. nll_first + nll_count - 1; nll_count 0 = to the end).  pass_rows: rows
-        per device pass (0 = 128)."""
-        return self._score((), tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows)
+        per device pass (0 = 128).  lengths int32 [R], each in [1, max_len]: position t of row r is scored iff t < lengths[r]; every
+        per-token array is 0 behind a song's end and row_nll averages over the scored positions of its window (NaN if none)."""
+        return self._score((), tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows, lengths)
 
     def maml_score(self, support, tokens, inner_steps, inner_lr, logprob=True, rank=False, entropy=False, argmax=False, row_nll=True,
                    nll_first=0, nll_count=0, pass_rows=0, n_rows=None, n_support_rows=None):
@@ -974,25 +1004,38 @@ class FsmgModel(object):
         a = a.reshape(-1, self.max_len)
         return C.c_void_p(a.ctypes.data), 0, a, a.shape[0]
 
-    def cache_build(self, tokens, n_groups=1, pass_rows=0, n_rows=None):
+    def cache_build(self, tokens, n_groups=1, pass_rows=0, n_rows=None, lengths=None):
         """Read support songs int32 [rows, max_len] ([groups, K, max_len] works too; or a device address with n_rows) into a new
         FsmgCache of n_groups groups: row r belongs to group r // (rows // n_groups), and entry (r % rows_per_group) * T + t holds
-        the top-layer hidden state that predicts token t of the row, with that token as its value."""
+        the top-layer hidden state that predicts token t of the row, with that token as its value.  lengths int32 [rows], each in
+        [1, max_len]: only positions t < lengths[r] are filed, a group's entries packed without gaps (a ragged cache: counts())."""
         tp, dev, _keep, R = self._rows(tokens, n_rows)
         c = FsmgCacheConfig(version=FSMG_CACHE_CONFIG_VERSION, n_rows=R, n_groups=int(n_groups), tokens_on_device=dev,
                             pass_rows=int(pass_rows))
         out = _P()
+        if lengths is not None:
+            ln = self._lengths(lengths, R)
+            self._ck(self._lib.fsmg_cache_build_masked(self._h, C.byref(c), tp, ln.ctypes.data_as(_I32P), C.byref(out)))
+            return FsmgCache(self, out)
         self._ck(self._lib.fsmg_cache_build(self._h, C.byref(c), tp, C.byref(out)))
         return FsmgCache(self, out)
 
-    def cache_from(self, keys, values):
-        """a new FsmgCache from host arrays: keys float32 [groups, entries, H], values int32 [groups, entries]"""
+    def cache_from(self, keys, values, counts=None):
+        """a new FsmgCache from host arrays: keys float32 [groups, entries, H], values int32 [groups, entries]; counts int32
+        [groups], each in [1, entries]: group g holds its first counts[g] entries and what lies behind them is not read"""
         k = np.ascontiguousarray(keys, dtype=np.float32)
         v = np.ascontiguousarray(values, dtype=np.int32)
         if k.ndim != 3 or k.shape[2] != int(self.cfg.hidden_size) or v.shape != k.shape[:2]:
             raise ValueError('keys must be [groups, entries, %d] and values [groups, entries], got %r and %r'
                              % (int(self.cfg.hidden_size), k.shape, v.shape))
         out = _P()
+        if counts is not None:
+            n = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+            if n.size != k.shape[0] or n.min() < 1 or n.max() > k.shape[1]:
+                raise ValueError('counts must hold %d values in [1, %d], got %r' % (k.shape[0], k.shape[1], counts))
+            self._ck(self._lib.fsmg_cache_create_from_counts(self._h, k.shape[0], k.shape[1], n.ctypes.data_as(_I32P), _f32p(k),
+                                                             v.ctypes.data_as(_I32P), C.byref(out)))
+            return FsmgCache(self, out)
         self._ck(self._lib.fsmg_cache_create_from(self._h, k.shape[0], k.shape[1], _f32p(k), v.ctypes.data_as(_I32P), C.byref(out)))
         return FsmgCache(self, out)
 
@@ -1016,12 +1059,12 @@ class FsmgModel(object):
         return out
 
     def cache_score(self, cache, tokens, thetas, lambdas, group=None, logprob=True, cache_prob=False, lstm_logprob=False, row_nll=True,
-                    nll_first=0, nll_count=0, pass_rows=0, n_rows=None):
+                    nll_first=0, nll_count=0, pass_rows=0, n_rows=None, lengths=None):
         """score() with a cache beside the model: tokens int32 [R, max_len] (or a device address with n_rows), row r attending
         over group group[r] of the cache (None: group 0) -> a dict with the requested arrays: 'logprob' float32 [n_theta, n_lambda, R,
         T] (log of the (1 - lambda, lambda) mixture of the model's and the cache's probability of each token), 'cache_prob' float32
         [n_theta, R, T], 'lstm_logprob' float32 [R, T] (score()'s 'logprob'), 'row_nll' float32 [n_theta, n_lambda, R].  The whole
-        (theta, lambda) grid costs one device pass."""
+        (theta, lambda) grid costs one device pass.  lengths int32 [R]: as score(); a query behind its song's end costs no attention."""
         tp, dev, _keep, R = self._rows(tokens, n_rows)
         c = self.cache_score_config(R, thetas, lambdas, nll_first, nll_count, pass_rows, dev)
         g = None
@@ -1040,11 +1083,17 @@ class FsmgModel(object):
         if row_nll:
             out['row_nll'] = np.empty((NT, NL, R), np.float32)
         f = lambda k: _f32p(out[k]) if k in out else None
+        if lengths is not None:
+            ln = self._lengths(lengths, R)
+            self._ck(self._lib.fsmg_cache_score_masked(self._h, cache._ptr(), C.byref(c), tp, ln.ctypes.data_as(_I32P),
+                                                       g.ctypes.data_as(_I32P) if g is not None else None, f('logprob'), f('cache_prob'),
+                                                       f('lstm_logprob'), f('row_nll')))
+            return out
         self._ck(self._lib.fsmg_cache_score(self._h, cache._ptr(), C.byref(c), tp, g.ctypes.data_as(_I32P) if g is not None else None,
                                             f('logprob'), f('cache_prob'), f('lstm_logprob'), f('row_nll')))
         return out
 
-    def cache_eval_step(self, support, query, theta, lam):
+    def cache_eval_step(self, support, query, theta, lam, support_len=None, query_len=None):
         """support int32 [N, K, max_len], query int32 [N, Q, max_len] -> the mean NLL of the query tokens under the mixture, artist
         a's query songs attending over a cache built from artist a's support songs (eval_step with the support set used)"""
         s = np.ascontiguousarray(support, dtype=np.int32)
@@ -1052,6 +1101,15 @@ class FsmgModel(object):
         if s.ndim != 3 or q.ndim != 3 or s.shape[0] != q.shape[0] or s.shape[2] != self.max_len or q.shape[2] != self.max_len:
             raise ValueError('support %r / query %r must be [N, K, %d] and [N, Q, %d]' % (s.shape, q.shape, self.max_len, self.max_len))
         nll = C.c_float()
+        if (support_len is None) != (query_len is None):
+            raise ValueError('support_len and query_len go together')
+        if support_len is not None:     # the padding-masked form: ragged groups, the mean over the scored positions
+            sl = self._lengths(support_len, s.shape[0] * s.shape[1], 'support_len')
+            ql = self._lengths(query_len, q.shape[0] * q.shape[1], 'query_len')
+            self._ck(self._lib.fsmg_cache_eval_step_masked(self._h, C.c_void_p(s.ctypes.data), C.c_void_p(q.ctypes.data),
+                                                           sl.ctypes.data_as(_I32P), ql.ctypes.data_as(_I32P), s.shape[0], s.shape[1],
+                                                           q.shape[1], float(theta), float(lam), C.byref(nll)))
+            return nll.value
         self._ck(self._lib.fsmg_cache_eval_step(self._h, C.c_void_p(s.ctypes.data), C.c_void_p(q.ctypes.data), s.shape[0], s.shape[1],
                                                 q.shape[1], float(theta), float(lam), C.byref(nll)))
         return nll.value
@@ -1140,7 +1198,7 @@ class FsmgModel(object):
         return out
 
     def cache_self_score(self, tokens, thetas, lambdas, window, cache=None, group=None, logprob=True, cache_prob=False,
-                         lstm_logprob=False, row_nll=True, nll_first=0, nll_count=0, pass_rows=0, n_rows=None):
+                         lstm_logprob=False, row_nll=True, nll_first=0, nll_count=0, pass_rows=0, n_rows=None, lengths=None):
         """cache_score() with every song's own history in the set: position t also attends over the hidden states of its own
         positions max(0, t - window) .. t - 1, each with the token that followed.  cache=None: the own history alone (group is then
         ignored; position 0 is scored by the model alone).  The keywords and the result are cache_score's."""
@@ -1159,6 +1217,12 @@ class FsmgModel(object):
         if row_nll:
             out['row_nll'] = np.empty((NT, NL, R), np.float32)
         f = lambda k: _f32p(out[k]) if k in out else None
+        if lengths is not None:
+            ln = self._lengths(lengths, R)
+            self._ck(self._lib.fsmg_cache_self_score_masked(self._h, cache._ptr() if cache is not None else None, C.byref(c), C.byref(sc),
+                                                            tp, ln.ctypes.data_as(_I32P), g.ctypes.data_as(_I32P) if g is not None else None,
+                                                            f('logprob'), f('cache_prob'), f('lstm_logprob'), f('row_nll')))
+            return out
         self._ck(self._lib.fsmg_cache_self_score(self._h, cache._ptr() if cache is not None else None, C.byref(c), C.byref(sc), tp,
                                                  g.ctypes.data_as(_I32P) if g is not None else None, f('logprob'), f('cache_prob'),
                                                  f('lstm_logprob'), f('row_nll')))

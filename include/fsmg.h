@@ -737,6 +737,51 @@ int fsmg_cache_self_distribution(fsmg_handle h, fsmg_cache cache, const fsmg_cac
                                  const int32_t* self_len, int32_t S, const int32_t* group, float* out_cache_prob, float* out_logprob,
                                  float* out_lse);
 
+/* ---- per-song lengths in scoring and in the support-set cache: ragged groups (DESIGN.md "Ragged cache groups").  Songs are stored
+ * zero-padded to max_len; these calls take each row's true length (host int32, every value in [1, max_len]) so that padding is
+ * neither scored nor filed as cache entries.  Lengths are checked before any device work; a NULL or out-of-range length gives
+ * FSMG_ERR_INVALID with nothing touched.  Position t of row r is SCORED iff t < lengths[r].
+ * A RAGGED cache keeps the layout of a uniform one -- G groups of Mg slots, fsmg_cache_info reports Mg, now a capacity -- and adds a
+ * per-group entry count n_g in [1, Mg]: entries 0 .. n_g - 1 of group g exist; the slots behind them hold zero keys and value 0, read
+ * back as zeros from fsmg_cache_get and are never scored by any kernel (skipped, not scored as a zero key).  Every call that takes a
+ * cache (fsmg_cache_attend, _score, _distribution, _generate, fsmg_dstate_cache_generate, fsmg_cache_self_*) accepts a ragged one with
+ * no new argument and gives, for group g, bitwise what it gives on a uniform one-group cache made of g's first n_g entries; the
+ * size limits (rows * entries_per_group <= 2^26) keep using the capacity Mg.
+ *   fsmg_score_masked            fsmg_score with lengths [R]: every per-token output is bitwise fsmg_score's at a scored position (same
+ *                                rows, same pass_rows) and +0.0f / 0 behind a song's end; out_row_nll[r] = -(fp64 sum in increasing
+ *                                t over nll_first <= t < min(window end, lengths[r])) / (the number of those positions), rounded
+ *                                once, bitwise recomputable from out_logprob; NaN when the window holds no scored position.
+ *   fsmg_cache_build_masked      fsmg_cache_build with lengths [n_rows]: the same passes (the same hidden states), then position t of
+ *                                row r is filed iff t < lengths[r], the entries of a group packed row-major, t increasing, without
+ *                                gaps: n_g = the sum of the group's rows' lengths, Mg = (n_rows / n_groups) * max_len.  The tokens
+ *                                behind a row's length change no bit of the cache.  Full lengths give fsmg_cache_build's bits.
+ *   fsmg_cache_create_from_counts  fsmg_cache_create_from with counts [G], each in [1, Mg]: slots >= counts[g] of keys and values
+ *                                are not read (they may hold anything, NaN and out-of-range ids included).
+ *   fsmg_cache_counts            out[g] = n_g; Mg for every group of a uniform cache.
+ *   fsmg_cache_score_masked      fsmg_cache_score with lengths [R]: outputs bitwise fsmg_cache_score's at scored positions and +0.0f
+ *                                behind a song's end; out_row_nll as fsmg_score_masked, per (theta, lambda).  A query behind its
+ *                                song's end costs no attention work.
+ *   fsmg_cache_self_score_masked the same for fsmg_cache_self_score.
+ *   fsmg_cache_eval_step_masked  fsmg_cache_eval_step with support_len [N * K] and query_len [N * Q]: fsmg_cache_build_masked, then
+ *                                fsmg_cache_score_masked; *nll = -(fp64 sum, in storage order, of out_logprob over the scored
+ *                                positions) / (their number), rounded once.
+ * Further errors, FSMG_ERR_INVALID: a count outside [1, entries_per_group], NULL lengths / counts / out. */
+int fsmg_score_masked(fsmg_handle h, const fsmg_score_config* c, const int32_t* tokens, const int32_t* lengths, float* out_logprob,
+                      int32_t* out_rank, float* out_entropy, int32_t* out_argmax, float* out_row_nll);
+int fsmg_cache_build_masked(fsmg_handle h, const fsmg_cache_config* c, const int32_t* tokens, const int32_t* lengths, fsmg_cache* out);
+/* counts host [G], keys host [G][Mg][H], values host [G][Mg] */
+int fsmg_cache_create_from_counts(fsmg_handle h, int32_t n_groups, int32_t entries_per_group, const int32_t* counts, const float* keys,
+                                  const int32_t* values, fsmg_cache* out);
+int fsmg_cache_counts(fsmg_handle h, fsmg_cache cache, int32_t* out /* [G] */);
+int fsmg_cache_score_masked(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const int32_t* tokens,
+                            const int32_t* lengths, const int32_t* group, float* out_logprob, float* out_cache_prob,
+                            float* out_lstm_logprob, float* out_row_nll);
+int fsmg_cache_self_score_masked(fsmg_handle h, fsmg_cache cache, const fsmg_cache_score_config* c, const fsmg_cache_self_config* sc,
+                                 const int32_t* tokens, const int32_t* lengths, const int32_t* group, float* out_logprob,
+                                 float* out_cache_prob, float* out_lstm_logprob, float* out_row_nll);
+int fsmg_cache_eval_step_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len,
+                                const int32_t* query_len, int32_t N, int32_t K, int32_t Q, float theta, float lambda, float* nll);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
