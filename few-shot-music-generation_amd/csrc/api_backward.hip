@@ -101,6 +101,8 @@ int backward(fsmg_model* h, int B, int part) {
     const bool aside = h->tail_aside && defer_ok && h->eager_call && h->aux != nullptr && !h->timing && !ov;
     h->side_pending = false;
     if (part != 2) GEMMCK(fills.add(h->G + h->off_emb, 0u, (long long)h->V1 * h->Ep));
+    // (the chunk counter of a deferred softmax half of this step's update, should there be one: same launch)
+    if (part == 0 && h->upd_defer && h->xov_call && h->d_upd_ctr != nullptr) { GEMMCK(fills.add(h->d_upd_ctr, 0u, 4)); h->upd_ctr_zeroed = true; }
     if (ov) GEMMCK(fills.flush());          // (two-stream order: the auxiliary stream forks right below)
     if (part == 2) {
     } else if (ov) {

@@ -37,7 +37,8 @@ int fsmg_debug_dims(fsmg_handle h, int32_t dims[5]) {
 
 int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count) {
     if (!h || !what || !host || count <= 0) return FSMG_ERR_INVALID;
-    BEGIN_CALL(h);
+    const int upd_state = h->upd_deferred ? 2 : h->upd_pending ? 1 : 0;
+    BEGIN_CALL(h, !std::strcmp(what, "upd_defer"));       // (a host-side fact about the pending half: reading it must not settle it)
     const int64_t B = h->lastB, T = h->T, Hp = h->Hp, G4 = h->G4, rows = T * B;
     const float* src = nullptr; int64_t cap = 0;
     auto layer_of = [&](const char* prefix) -> int {
@@ -49,6 +50,11 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
     int l;
     if (!std::strcmp(what, "aux_tries")) { host[0] = (float)h->aux_tries; return FSMG_OK; }       // streams drawn until one ran beside the handle's (-1: none did)
     if (!std::strcmp(what, "fused_softmax")) { host[0] = h->fused_softmax ? 1.0f : 0.0f; if (count > 1) host[1] = h->fs_call ? 1.0f : 0.0f; return FSMG_OK; }   // [0] the knob, [1] whether the last train pass took it
+    if (!std::strcmp(what, "upd_defer")) {            // [0] the knob, [1] the softmax half when this call began: 0 nothing pending, 1 in flight, 2 not launched yet,
+        const float v[4] = {h->upd_defer ? 1.0f : 0.0f, (float)upd_state, (float)h->n_upd_placed, (float)h->n_upd_settled};     // [2] halves placed beside a chain, [3] launched by settle_pending
+        for (int64_t i = 0; i < count && i < 4; ++i) host[i] = v[i];
+        return FSMG_OK;
+    }
     if (!std::strcmp(what, "xcd_bx3")) { host[0] = h->xcd_bx3 ? 1.0f : 0.0f; return FSMG_OK; }      // a host-side fact: which XCD-local kernel family this handle runs
     if (!std::strcmp(what, "gemm_kinds")) {           // GEMM launches the host enqueued, by kernel (fsmg_model::gemm_kinds; a replayed hipGraph does not count again)
         for (int64_t i = 0; i < count && i < 4; ++i) host[i] = (float)h->gemm_kinds[i];

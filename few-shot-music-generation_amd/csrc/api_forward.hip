@@ -199,9 +199,14 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
             if (xcd) {       // the same for the XCD-local hand-off buffer, and fresh ticket counters for this layer's launches
                 GEMMCK(fills.add(h->tickets, 0u, (long long)8 * fsmg_model::TICKET_LAUNCHES));
                 h->ticket_next = 0;
-                const long long step_f = lstm_xcd_hx_floats(B, 0, Hp, h->xcd_bx3, xov && top ? rpx : 0);
+                // "not written" in the XCD slices this launch uses and no others: a packed chain (rpx > 0) leaves the slices of the XCDs
+                // without rows untouched -- at cfg-B five of eight, 31 MB of a 50 MB fill on the critical path -- and a later pass on more
+                // XCDs refills its own (lstm_xcd_used_slices is what the kernels' row0 >= B test comes to)
+                const int rpx_l = xov && top ? rpx : 0;
+                const long long step_f = lstm_xcd_hx_floats(B, 0, Hp, h->xcd_bx3, rpx_l);
+                const long long used_f = step_f / lstm_xcd_slices(Hp) * lstm_xcd_used_slices(B, rpx_l, Hp);
                 GEMMCK(fills.add(h->HX, 0u, step_f));
-                GEMMCK(fills.add(h->HX + step_f, 0xFFFFFFFFu, step_f * T));
+                GEMMCK(fills.add_strided(h->HX + step_f, 0xFFFFFFFFu, used_f, step_f, T));
                 if (xov && top) {
                     GEMMCK(fills.add(h->xov_ctl, 0u, 4 + gemm_items(ghead)));
                     GEMMCK(fills.add(h->xov_prog, 0u, T));
@@ -209,10 +214,16 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
             }
             return fills.flush();
         };
+        // a softmax half of the previous update that has not been launched yet (fsmg_model::upd_deferred) goes to the auxiliary stream
+        // here, behind the x-part GEMM and in front of the fills: its blocks are placed on the free XCDs while the chip is empty, and
+        // the projection's restricted launch below follows it in stream order
+        const bool place = l == 0 && h->upd_deferred && xov && top && xfree >= 1 && xfree <= 7;
+        if (place) GEMMCK(place_deferred_half(h, xfree));
         GEMMCK(chain_fills());
         // the softmax half of the previous update may still be running on the auxiliary stream (apply_update): what has been issued
         // so far -- token_prep, the bottom layer's x-part GEMM, the fills -- reads none of it; everything from here on may
-        if (l == 0) GEMMCK(settle_pending(h));
+        // (a half placed above: the chain reads none of it either, the main stream waits in front of the clean-up launch)
+        if (l == 0 && !place) GEMMCK(settle_pending(h));
         if (xov && top) {         // the projection's queue launch on the auxiliary stream, confined to the XCDs the chain leaves free
             HIPCK(h, hipEventRecord(h->ev_fork, s));
             HIPCK(h, hipStreamWaitEvent(h->aux, h->ev_fork, 0));
@@ -277,6 +288,7 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
     } else if (xov) {
         {
             ScopedTimer tm(h, "gemm_logits");      // (what is left of the queue when the chain is over, on the whole chip)
+            GEMMCK(settle_pending(h));             // (a half placed beside the chain: done long ago)
             GEMMCK(gemm_cleanup(h, s, OP_KC, OP_XC, ghead, h->xov_ctl));
             HIPCK(h, hipStreamWaitEvent(s, h->ev_join, 0));    // the restricted launch and its tiles in flight
         }

@@ -67,10 +67,40 @@ static int pick_concurrent_aux(fsmg_model* h, int priority, int max_tries) {
 
 // The second launch of the last clip + Adam update (softmax_w, softmax_b and their moments, on the auxiliary stream) may still be in
 // flight: order the main stream behind it.  One event wait, no host synchronisation.
+// A half that has not been launched yet (upd_deferred: the fused train step left it for the next pass's forward pair) is launched
+// here, unrestricted, on the main stream: stream order, no event.  It consumes the (go, clip scale, alpha) its first half published,
+// so a skipped step leaves the softmax parameters and moments alone like the rest.
 int settle_pending(fsmg_model* h) {
+    if (h->upd_deferred) {
+        h->upd_deferred = false;
+        UpdateArgs b = h->upd_half;
+        b.xcd_first = 0; b.chunk_ctr = nullptr;
+        HIPCK(h, launch_adam_update(h->stream, b));
+        ++h->n_upd_settled;
+    }
     if (!h->upd_pending) return FSMG_OK;
     h->upd_pending = false;
     HIPCK(h, hipStreamWaitEvent(h->stream, h->ev_upd, 0));
+    return FSMG_OK;
+}
+
+// forward() under the XCD-partitioned order, right behind the x-part GEMM: the waiting half on the auxiliary stream, on the XCDs the
+// chain leaves free, placed while the chip is empty (the main stream's fills follow, then the chain).  The projection's restricted
+// launch comes behind it on the same stream and finds softmax_w / softmax_b updated; the main stream waits for ev_upd in front of
+// its first reader of them (settle_pending in front of the clean-up launch).
+int place_deferred_half(fsmg_model* h, int xcd_first) {
+    if (!h->upd_deferred) return FSMG_OK;
+    if (h->aux == nullptr || h->d_upd_ctr == nullptr || !h->upd_ctr_zeroed || xcd_first < 1 || xcd_first > 7) return settle_pending(h);
+    h->upd_deferred = false;
+    h->upd_ctr_zeroed = false;
+    UpdateArgs b = h->upd_half;
+    b.xcd_first = xcd_first; b.chunk_ctr = h->d_upd_ctr;
+    HIPCK(h, hipEventRecord(h->ev_upd_fork, h->stream));
+    HIPCK(h, hipStreamWaitEvent(h->aux, h->ev_upd_fork, 0));
+    HIPCK(h, launch_adam_update(h->aux, b));
+    HIPCK(h, hipEventRecord(h->ev_upd, h->aux));
+    h->upd_pending = true;
+    ++h->n_upd_placed;
     return FSMG_OK;
 }
 
@@ -187,6 +217,7 @@ int fsmg_create(const fsmg_config* cfg, fsmg_handle* out) {
         if (const char* e = std::getenv("FSMG_EAGER")) h->eager = (e[0] != '0');
         if (const char* e = std::getenv("FSMG_MERGE_DK")) h->merge_dk = (e[0] != '0');
         if (const char* e = std::getenv("FSMG_UPD_SPLIT")) h->upd_split = (e[0] != '0');
+        if (const char* e = std::getenv("FSMG_UPD_DEFER")) h->upd_defer = (e[0] != '0');
         if (const char* e = std::getenv("FSMG_TAIL_ASIDE")) h->tail_aside = (e[0] != '0');
         if (const char* e = std::getenv("FSMG_LAZY_CS")) h->lazy_cs = (e[0] != '0');
         if (const char* e = std::getenv("FSMG_FUSED_SOFTMAX")) h->fused_softmax = (e[0] != '0');
@@ -255,6 +286,7 @@ int fsmg_create(const fsmg_config* cfg, fsmg_handle* out) {
     h->d_step = (long long*)small; h->d_err = (int*)(small + 256); h->d_gnorm = (float*)(small + 512);
     h->d_inbox_dirty = (int*)(small + 768);
     h->d_decided = (float*)(small + 896);
+    h->d_upd_ctr = (int*)(small + 960);
     { static const int one = 1; hipStreamSynchronize(h->stream); hipMemcpy(h->d_inbox_dirty, &one, sizeof(int), hipMemcpyHostToDevice); }
     h->d_ring = (float*)(small + 1024);
     if (hipHostMalloc((void**)&h->host_counters, 64, hipHostMallocMapped) != hipSuccess ||
@@ -408,6 +440,7 @@ int fsmg_debug_set(fsmg_handle h, const char* what, int64_t value) {
     else if (!std::strcmp(what, "persistent")) { h->persist = h->persist_cfg = value != 0; h->fallback_left = 0; }
     else if (!std::strcmp(what, "inplace_dlogits")) h->inplace_dlogits = value != 0;
     else if (!std::strcmp(what, "upd_split")) h->upd_split = value != 0;
+    else if (!std::strcmp(what, "upd_defer")) h->upd_defer = value != 0;
     else if (!std::strcmp(what, "reprobe_aux")) {
         // the create-time probe found no stream running beside the handle's own (aux_stream_tries = -1), possibly because the device was
         // busy with somebody else's work at that moment: ask again.  On success the overlapped tails come back; the XCD-partitioned order

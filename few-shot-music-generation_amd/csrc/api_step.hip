@@ -58,7 +58,7 @@ int forward_backward_core(fsmg_model* h, int32_t N, int32_t K, int32_t Q, Stage&
             int r = token_prep(h, n_sup, n_qry, true);
             if (r == FSMG_OK) r = forward(h, B, B, 1, h->G + h->n_flat + 1, true);
             if (r == FSMG_OK) r = backward(h, B);
-            if (r == FSMG_OK && with_update) r = apply_update(h, 1.0f);
+            if (r == FSMG_OK && with_update) r = apply_update(h, 1.0f, true);
             return r;
         });
     }

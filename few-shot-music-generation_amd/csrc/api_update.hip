@@ -66,7 +66,7 @@ int ensure_cs(fsmg_model* h) {
     return FSMG_OK;
 }
 
-int apply_update(fsmg_model* h, float grad_scale) {
+int apply_update(fsmg_model* h, float grad_scale, bool may_defer) {
     ScopedRange rng_("fsmg.clip+adam");
     hipStream_t s = h->stream;
     ScopedTimer tm(h, "update");
@@ -87,7 +87,21 @@ int apply_update(fsmg_model* h, float grad_scale) {
     // flags.  Same arithmetic on the same values: bit-identical to the single launch.  Whoever reads or writes the softmax
     // parameters / moments / gradients next goes through settle_pending() first (fsmg_model.h).
     const bool split = h->upd_split && h->eager_call && h->aux != nullptr && !h->timing && h->off_w > 0 && h->off_w < h->n_flat;
-    if (split) {
+    // Deferred form of the same two launches (fsmg_model::upd_defer): where this step ran in the XCD-partitioned eager order, the second
+    // half is not launched at all -- the next train pass puts it on the XCDs its forward chain leaves free (place_deferred_half), anybody
+    // else launches it in stream order (settle_pending).  One half per run of train steps is paid by the first call that is not one.
+    const bool defer = !split && may_defer && h->upd_defer && h->xov_call && (h->xov_parts & 1) && h->eager_call && h->aux != nullptr && !h->timing &&
+                       h->Hp == 512 && h->L == 1 && h->comm == nullptr && h->d_upd_ctr != nullptr && h->off_w > 0 && h->off_w < h->n_flat;
+    if (defer) {
+        GEMMCK(settle_pending(h));
+        a.n = h->off_w; a.publish = h->d_decided;
+        HIPCK(h, launch_adam_update(s, a));
+        UpdateArgs b = a;
+        b.p = h->P + h->off_w; b.m = h->M + h->off_w; b.v = h->Vv + h->off_w; b.g = h->G + h->off_w; b.n = h->n_flat - h->off_w;
+        b.publish = nullptr; b.consume = h->d_decided; b.gnorm_out = nullptr;
+        h->upd_half = b;
+        h->upd_deferred = true;
+    } else if (split) {
         GEMMCK(settle_pending(h));           // (an earlier update's second half: cannot be pending here, but costs nothing to rule out)
         a.n = h->off_w; a.publish = h->d_decided;
         HIPCK(h, launch_adam_update(s, a));

@@ -61,6 +61,22 @@ __global__ __launch_bounds__(256) void k_multi_op(const MultiOps r) {
         const uint32_t word = o.word;
         const long long n = o.n, n4 = n >> 2;
         const uint4 w4 = make_uint4(word, word, word, word);
+        if (o.piece > 0) {          // strided: piece j of o.piece words at p + j * o.stride (both multiples of 4, n = piece * count)
+            const long long piece4 = o.piece >> 2, stride4 = o.stride >> 2;
+            if (n4 < (1LL << 31)) {             // (a 32-bit division per store: the 64-bit one is a hundred instructions)
+                const unsigned pc = (unsigned)piece4, nn = (unsigned)n4;
+                for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < nn; i += gridDim.x * 256u) {
+                    const unsigned j = i / pc;
+                    reinterpret_cast<uint4*>(p)[(long long)j * stride4 + (i - j * pc)] = w4;
+                }
+                return;
+            }
+            for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+                const long long j = i / piece4;
+                reinterpret_cast<uint4*>(p)[j * stride4 + (i - j * piece4)] = w4;
+            }
+            return;
+        }
         for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256)
             reinterpret_cast<uint4*>(p)[i] = w4;
         if (blockIdx.x == 0 && threadIdx.x < (n & 3)) p[(n4 << 2) + threadIdx.x] = word;
@@ -812,6 +828,21 @@ __global__ __launch_bounds__(256) void k_sqnorm_partials(const float* __restrict
     if (tid == 0) partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
+// One element of the update.  The kernel has two loops over it (grid-stride, and chunks drawn from a counter) that must give the same
+// bits, so which products are fused is spelled out here instead of left to the compiler's contraction, which decides per loop:
+//   gc = g * scale;  m <- fma(gc, 1 - b1, b1 * m);  v <- fma((1 - b2) * gc, gc, b2 * v);  p <- p - (alpha * m) / (sqrt(v) + eps)
+// (the fusions the single grid-stride loop was compiled to before the second loop existed: same bits as then)
+__device__ __forceinline__ void adam_element(float g, float& m, float& v, float& p, float scale, float alpha) {
+#pragma clang fp contract(off)
+    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+    const float gc = g * scale;
+    const float m_old = b1 * m, v_old = b2 * v, u = (1.0f - b2) * gc;
+    m = __builtin_fmaf(gc, 1.0f - b1, m_old);
+    v = __builtin_fmaf(u, gc, v_old);
+    const float num = alpha * m, den = sqrtf(v) + eps;
+    p = p - num / den;
+}
+
 // clip_by_global_norm + exponential_decay + TF AdamOptimizer (reference
 // src/models/lstm_baseline.py:77-87; SURVEY.md A.4: epsilon added to the un-corrected sqrt(v)).
 // Every block re-derives the scalars from the same partials in the same order, so all blocks
@@ -851,26 +882,50 @@ __global__ __launch_bounds__(256) void k_adam_update(const UpdateArgs a) {
     }
     __syncthreads();
     const float scale = s_scale, alpha = s_alpha;
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
     const long long n4 = a.n >> 2;
+#define FSMG_ADAM1(g, m, v, p, c) adam_element(g.c, m.c, v.c, p.c, scale, alpha);
+#define FSMG_ADAM4(g, m, v, p) FSMG_ADAM1(g, m, v, p, x) FSMG_ADAM1(g, m, v, p, y) FSMG_ADAM1(g, m, v, p, z) FSMG_ADAM1(g, m, v, p, w)
+    if (a.xcd_first > 0) {
+        // restricted form: the XCDs a packed recurrent chain holds take nothing; a block elsewhere draws chunks of ADAM_CHUNK4 float4
+        // (thread t: float4 t and t + 256 of the chunk, both loaded before either is updated) until the counter runs past the range
+        __shared__ long long s_chunk;
+        int xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        if ((xcc & 7) < a.xcd_first) return;
+        const long long nchunks = (n4 + ADAM_CHUNK4 - 1) / ADAM_CHUNK4;
+        for (;;) {
+            __syncthreads();                                  // (the last round's readers of s_chunk are through)
+            if (tid == 0) s_chunk = (long long)atomicAdd(a.chunk_ctr, 1);
+            __syncthreads();
+            const long long c = s_chunk;
+            if (c >= nchunks) return;
+            const long long i0 = c * ADAM_CHUNK4 + tid, i1 = i0 + 256;
+            const bool h0 = i0 < n4, h1 = i1 < n4;
+            float4 g0, m0, v0, p0, g1, m1, v1, p1;
+            if (h0) { g0 = reinterpret_cast<const float4*>(a.g)[i0]; m0 = reinterpret_cast<float4*>(a.m)[i0]; v0 = reinterpret_cast<float4*>(a.v)[i0]; p0 = reinterpret_cast<float4*>(a.p)[i0]; }
+            if (h1) { g1 = reinterpret_cast<const float4*>(a.g)[i1]; m1 = reinterpret_cast<float4*>(a.m)[i1]; v1 = reinterpret_cast<float4*>(a.v)[i1]; p1 = reinterpret_cast<float4*>(a.p)[i1]; }
+            if (h0) {
+                FSMG_ADAM4(g0, m0, v0, p0)
+                reinterpret_cast<float4*>(a.m)[i0] = m0; reinterpret_cast<float4*>(a.v)[i0] = v0; reinterpret_cast<float4*>(a.p)[i0] = p0;
+            }
+            if (h1) {
+                FSMG_ADAM4(g1, m1, v1, p1)
+                reinterpret_cast<float4*>(a.m)[i1] = m1; reinterpret_cast<float4*>(a.v)[i1] = v1; reinterpret_cast<float4*>(a.p)[i1] = p1;
+            }
+        }
+    }
     for (long long i = (long long)blockIdx.x * 256 + tid; i < n4; i += (long long)gridDim.x * 256) {
         float4 g = reinterpret_cast<const float4*>(a.g)[i];
         float4 m = reinterpret_cast<float4*>(a.m)[i];
         float4 v = reinterpret_cast<float4*>(a.v)[i];
         float4 p = reinterpret_cast<float4*>(a.p)[i];
-#define FSMG_ADAM1(c)                                         \
-        {                                                     \
-            const float gc = g.c * scale;                     \
-            m.c = b1 * m.c + (1.0f - b1) * gc;                \
-            v.c = b2 * v.c + (1.0f - b2) * gc * gc;           \
-            p.c = p.c - alpha * m.c / (sqrtf(v.c) + eps);     \
-        }
-        FSMG_ADAM1(x) FSMG_ADAM1(y) FSMG_ADAM1(z) FSMG_ADAM1(w)
-#undef FSMG_ADAM1
+        FSMG_ADAM4(g, m, v, p)
         reinterpret_cast<float4*>(a.m)[i] = m;
         reinterpret_cast<float4*>(a.v)[i] = v;
         reinterpret_cast<float4*>(a.p)[i] = p;
     }
+#undef FSMG_ADAM4
+#undef FSMG_ADAM1
 }
 
 // Inner-loop update of the MAML-style step (cfg-E; oracle/lstm_oracle.py maml_adapt): p <- p - lr * clip_by_global_norm(g).
@@ -1222,6 +1277,13 @@ hipError_t launch_adam_update(hipStream_t s, const UpdateArgs& a) {
     int blocks = (int)((n4 + 255) / 256);
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
+    if (a.xcd_first > 0) {
+        // blocks go round the eight XCDs: four per CU of the chip (8 x 32 CUs) are four per CU of the free XCDs, all of them placed at
+        // once -- the others leave at their first instruction -- and no more blocks than the free XCDs' share of them has chunks
+        if (a.consume == nullptr || a.chunk_ctr == nullptr || a.xcd_first > 7) return hipErrorInvalidValue;
+        const long long nchunks = (n4 + ADAM_CHUNK4 - 1) / ADAM_CHUNK4;
+        blocks = (int)std::max<long long>(8, std::min<long long>(4 * 8 * 32, (nchunks * 8 + (8 - a.xcd_first) - 1) / (8 - a.xcd_first)));
+    }
     hipLaunchKernelGGL(k_adam_update, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }

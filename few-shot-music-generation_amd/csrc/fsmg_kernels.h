@@ -238,6 +238,13 @@ int lstm_xcd_max_rows(int Hp);                 // 128 / 64 / 0
 long long lstm_xcd_hx_floats(int B, int T, int Hp = 512, bool bx3 = false, int rpx = 0);   // bx3: for the bf16-split kernels (hidden 512); rpx: rows packed per XCD
 long long lstm_xcd_inbox_floats(int B, int Hp = 512, int rpx = 0);
 int lstm_xcd16_packed_rows(int B, int Hp = 512);      // bf16-split kernels: rows per XCD (hidden 1024: per XCD pair) that put B rows on the fewest (up to 16 each)
+// XCD slices (hidden 1024: XCD-pair slices) of the hand-off buffer a launch with rows packed rpx per slice reads and writes -- the kernels'
+// `row0 = slice * rpx >= B: return` -- out of 8 (4); rpx == 0: the rows are spread over all of them.  The forward pass refills exactly these
+inline int lstm_xcd_slices(int Hp = 512) { return Hp == 1024 ? 4 : 8; }
+inline int lstm_xcd_used_slices(int B, int rpx, int Hp = 512) {
+    const int all = lstm_xcd_slices(Hp);
+    return rpx > 0 && (B + rpx - 1) / rpx < all ? (B + rpx - 1) / rpx : all;
+}
 inline int lstm_xcd_active_blocks(int B, int rpx, int Hp = 512) { return (Hp == 1024 ? 64 : 32) * ((B + rpx - 1) / rpx); }     // blocks of a packed launch that own rows
 long long lstm_xcd_weight_floats(int Hp = 512, bool bx3 = false);   // floats per register image
 bool lstm_xcd_bx3_pays(int B, int Hp);         // the bf16-split kernels are the faster ones at this row count
@@ -257,6 +264,8 @@ hipError_t launch_lstm_bwd_xcd(hipStream_t s, const LstmBwdXcdArgs& a);
 // ---------------------------------------------------------------- everything else (elementwise.hip)
 // up to MULTI_MAX_OPS small memory passes in ONE launch (every pointer 16-byte aligned):
 //   MULTI_FILL    dst[0 .. n) = word (32-bit pattern); cond != nullptr: only when *cond != 0 (read on the device when the launch runs)
+//                 piece > 0: strided -- n = piece * count words, piece j (of `piece` words, a multiple of 4) starts at dst + j * stride
+//                 (stride a multiple of 4): the pieces of a buffer a launch really uses, without a launch per piece
 //   MULTI_REDUCE  dst[i] = sum_z src[z * stride + i] for i < n, slabs added in order z = 0 .. nslab - 1 (deterministic split-K);
 //                 sq != nullptr: also the squared-norm partials of dst, one double per SQ_CHUNK (= sqnorm_blocks) elements, bit-equal
 //                 to launch_sqnorm_partials(dst, n, sq)
@@ -265,7 +274,8 @@ hipError_t launch_lstm_bwd_xcd(hipStream_t s, const LstmBwdXcdArgs& a);
 enum { MULTI_FILL = 0, MULTI_REDUCE = 1, MULTI_MEAN = 2 };
 constexpr int MULTI_MAX_OPS = 16;
 struct MultiOp { int kind; void* dst; const void* src; long long n; long long stride; int nslab; uint32_t word; const int* cond; double* sq;
-                 const float* row_scale; int row_len; /* REDUCE without sq: dst[i] = row_scale[i / row_len] * sum (row_len % 4 == 0) */ };
+                 const float* row_scale; int row_len; /* REDUCE without sq: dst[i] = row_scale[i / row_len] * sum (row_len % 4 == 0) */
+                 long long piece; /* FILL: words per piece of a strided fill (0: one contiguous range) */ };
 struct MultiOps { MultiOp op[MULTI_MAX_OPS]; int count; };
 hipError_t launch_multi_op(hipStream_t s, const MultiOps& r);
 // out[r][0..T) = table[idx[r]][0..T) for r < n_rows (device-resident split table -> the token staging buffer)
@@ -353,7 +363,12 @@ struct UpdateArgs {
     // writes publish[0..2] = (go ? 1 : 0, clip scale, alpha) from thread 0 of block 0, the second (consume != nullptr) reads them
     // instead of deriving them -- flags, tail and step counter may have moved on by then
     float* publish; const float* consume;
+    // restricted form (xcd_first > 0; with consume only): blocks on an XCD below xcd_first return at once, the others draw contiguous
+    // chunks of ADAM_CHUNK4 float4 from *chunk_ctr (zero before the launch) until the range is done -- the same operations on the same
+    // values per element, on the XCDs a packed recurrent chain leaves free (launch_adam_update sizes the grid for them)
+    int xcd_first; int* chunk_ctr;
 };
+constexpr int ADAM_CHUNK4 = 512;                  // float4 per drawn chunk: two per thread, eight 16-byte loads in flight
 hipError_t launch_adam_update(hipStream_t s, const UpdateArgs& a);
 // p <- p - a.lr * clip_by_global_norm(g): the inner-loop step of cfg-E (m, v, step, n_decay, grad_scale unused)
 hipError_t launch_sgd_update(hipStream_t s, const UpdateArgs& a);

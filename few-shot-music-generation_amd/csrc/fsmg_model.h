@@ -282,6 +282,19 @@ struct fsmg_model {
     bool upd_pending = false;
     hipEvent_t ev_upd_fork = nullptr, ev_upd = nullptr;
     float* d_decided = nullptr;         // [4]: go (1 / 0), clip scale, alpha, unused
+    // Deferred softmax half: under the XCD-partitioned eager order (hidden 512, one layer) the fused train step launches
+    // the first half only and leaves the second one NOT LAUNCHED (upd_deferred, its arguments in upd_half).  The next train pass under
+    // that order launches it on the auxiliary stream right behind the x-part GEMM, restricted to the XCDs the forward chain leaves free
+    // (UpdateArgs::xcd_first) -- they idle until the projection's first row tile is through its gate -- with the restricted projection
+    // launch behind it in stream order; from there it is an in-flight half like upd_split's (upd_pending, ev_upd).  Anybody else goes
+    // through settle_pending(), which launches a half that is still waiting unrestricted on the main stream.
+    // FSMG_UPD_DEFER=0 / fsmg_debug_set("upd_defer", 0): the single in-line launch.
+    bool upd_defer = true;
+    bool upd_deferred = false;
+    fsmg::UpdateArgs upd_half{};
+    int* d_upd_ctr = nullptr;           // [4] chunk counter of the restricted launch: zeroed by the backward pass's first fills launch ...
+    bool upd_ctr_zeroed = false;        // ... of this step (a restricted launch uses it once)
+    long long n_upd_placed = 0, n_upd_settled = 0;      // halves launched restricted beside a forward chain / unrestricted by settle_pending (fsmg_debug_read("upd_defer"))
     // the split-K slabs of the main lane hold a GEMM's partial sums whose REDUCE op is still waiting in this batch (the XCD-partitioned
     // order's dW): gemm() flushes it before anything else writes those slabs
     fsmg_host::OpBatch* slabs_owner = nullptr;
@@ -417,8 +430,9 @@ inline void drain_timers(fsmg_model* h) {
 
 // ------------------------------------------------------------------ one prologue for every C entry point that takes a handle
 // begin_call: selects the handle's device and settles what an earlier call left in flight on another stream (settle_pending: the
-// softmax half of the last clip + Adam update runs on the auxiliary stream beside the NEXT step's input phase -- any other reader
-// or writer of the parameters, the optimizer state or the gradient buffer must be ordered behind it first).  The train-step entry
+// softmax half of the last clip + Adam update runs on the auxiliary stream beside the NEXT step's input phase, or has not been
+// launched yet (upd_deferred) -- any other reader or writer of the parameters, the optimizer state or the gradient buffer must be
+// ordered behind it first).  The train-step entry
 // points pass keep_pending: their forward pass orders itself behind the update where it first reads the softmax parameters.
 int begin_call(fsmg_model* h, bool keep_pending = false);
 int settle_pending(fsmg_model* h);
@@ -498,6 +512,16 @@ struct OpBatch {
         const int rc = room(1); if (rc != FSMG_OK) return rc;
         MultiOp& o = r.op[r.count++];
         o = MultiOp{}; o.kind = MULTI_FILL; o.dst = p; o.word = word; o.n = n_words; o.cond = cond;
+        return FSMG_OK;
+    }
+    // `count` pieces of `piece` words each, piece j at p + j * stride (piece and stride multiples of 4 words)
+    int add_strided(void* p, uint32_t word, long long piece, long long stride, long long count) {
+        if (piece <= 0 || count <= 0) return FSMG_OK;
+        if (piece == stride || count == 1) return add(p, word, piece * count);
+        if (((piece | stride) & 3) != 0 || piece > stride) return fail(h, FSMG_ERR_STATE, "internal: a strided fill needs piece <= stride, both multiples of 4 words");
+        const int rc = room(1); if (rc != FSMG_OK) return rc;
+        MultiOp& o = r.op[r.count++];
+        o = MultiOp{}; o.kind = MULTI_FILL; o.dst = p; o.word = word; o.n = piece * count; o.piece = piece; o.stride = stride;
         return FSMG_OK;
     }
     // out[i] = sum over the nslab slabs (fixed order); sq: squared-norm partials of out as a by-product
@@ -641,7 +665,8 @@ int ensure_cs(fsmg_model* h);           // the column-split copies of K_h are cu
 inline bool pass_reads_cs(const fsmg_model* h, int B, bool train) {
     return !use_xcd(h, B) || (train && !use_xcd(h, B, true));
 }
-int apply_update(fsmg_model* h, float grad_scale);
+int apply_update(fsmg_model* h, float grad_scale, bool may_defer = false);      // may_defer: the fused single-GPU train step (the softmax half may wait for the next pass)
+int place_deferred_half(fsmg_model* h, int xcd_first);     // forward(): the waiting half on the auxiliary stream, on the XCDs >= xcd_first
 int sgd_update(fsmg_model* h, float lr);
 int save_theta(fsmg_model* h);
 int restore_theta(fsmg_model* h);

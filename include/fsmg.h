@@ -862,6 +862,11 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
  *                       0: the cross-entropy pass
  *   "upd_split"         1: clip + Adam of an eager pass as two launches, the softmax half on the auxiliary stream beside the next
  *                       step's input phase (bit-identical; measured slower), 0 (default): one launch
+ *   "upd_defer"         1 (default): under the XCD-partitioned eager order (hidden 512, one layer) the fused train step leaves the softmax
+ *                       half of clip + Adam unlaunched; the next train pass runs it on the XCDs its forward chain leaves free, any other
+ *                       call launches it in stream order first (bit-identical), 0: one launch.  fsmg_debug_read("upd_defer", 4)
+ *                       = [knob, the half when the read began: 0 none / 1 in flight / 2 not launched, halves placed, halves launched in line]
+ *                       and, alone among the reads, leaves a waiting half waiting
  *   "tail_aside"        1 (default): the bandwidth-bound tail of an eager backward pass (deferred slab sums, embedding gradient) on
  *                       the auxiliary stream beside the bottom layer's weight-gradient GEMM (bit-identical), 0: in line
  *   "xov_selfcheck"     XCD-partitioned order: the next `value` train passes recompute the gated projection on the serial path and
