@@ -71,6 +71,10 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
         if (count > 2) host[2] = h->xov_last ? 1.0f : 0.0f;       // [2] whether the LAST train pass took it (its row count decides per call)
         return FSMG_OK;
     }
+    if (!std::strncmp(what, "adapted:", 8)) {         // theta' of the last MAML-style call, reference layout like fsmg_get_param (fsmg_debug_set("keep_adapted", 1))
+        if (!h->have_adapted) return fail(h, FSMG_ERR_STATE, "no adapted parameters kept: fsmg_debug_set(\"keep_adapted\", 1), then a MAML-style call");
+        return download_tensor(h, h->P_adapted, what + 8, host, count);
+    }
     if (!std::strcmp(what, "logits")) { src = h->logits; cap = rows * h->V1p; }
     else if (!std::strcmp(what, "dlogits")) { src = dlogits_buf(h); cap = rows * h->V1p; }
     else if (!std::strcmp(what, "lse")) { src = h->lse; cap = rows; }

@@ -359,6 +359,7 @@ int fsmg_destroy(fsmg_handle h) {
     if (h->khf) hipFree(h->khf);
     if (h->khx) hipFree(h->khx);
     if (h->P_saved) hipFree(h->P_saved);
+    if (h->P_adapted) hipFree(h->P_adapted);
     for (int* t : h->table) if (t) hipFree(t);
     for (int* t : h->table_len) if (t) hipFree(t);
     if (h->d_idx) hipFree(h->d_idx);
@@ -461,7 +462,7 @@ int fsmg_debug_set(fsmg_handle h, const char* what, int64_t value) {
     }
     else if (!std::strcmp(what, "tail_aside")) h->tail_aside = value != 0;
     else if (!std::strcmp(what, "fused_softmax")) h->fused_softmax = value != 0;
-
+    else if (!std::strcmp(what, "keep_adapted")) h->keep_adapted = value != 0;
     else if (!std::strcmp(what, "xov_selfcheck")) h->xov_selfcheck_left = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
     else if (!std::strcmp(what, "xov_selfcheck_fault")) h->xov_selfcheck_fault = value != 0;
     else if (!std::strcmp(what, "xov_selfcheck_every")) h->xov_selfcheck_every = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));

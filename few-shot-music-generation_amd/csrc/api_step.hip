@@ -327,7 +327,9 @@ int fsmg_maml_forward_backward(fsmg_handle h, const int32_t* support, const int3
     BEGIN_CALL(h);
     int rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, tokens_on_device);
     if (rc == FSMG_OK) rc = fsmg_forward_backward(h, query, query, N, Q, 0, tokens_on_device);     // query rows at theta'
-    const int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;                                         // theta comes back whatever happened
+    const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
+    int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;                                               // theta comes back whatever happened
+    if (rc2 == FSMG_OK) rc2 = rc_keep;
     return rc != FSMG_OK ? rc : rc2;
 }
 
@@ -387,6 +389,9 @@ int fsmg_maml_step_indexed(fsmg_handle h, int32_t table_id, const int32_t* suppo
     return fsmg_maml_step(h, h->d_gather, h->d_gather + (size_t)N * K * h->T, N, K, Q, inner_steps, inner_lr, 1, loss);
 }
 
+static int eval_batch_core(fsmg_handle h, const int32_t* queries, const int32_t* query_len, int32_t n_episodes, int32_t N, int32_t Q,
+                           int32_t tokens_on_device, float* nll, bool masked, bool repeat_chunk = true);
+
 int fsmg_maml_eval(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q,
                    int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* nll) {
     if (!h || !support || !query || !nll) return FSMG_ERR_INVALID;
@@ -395,9 +400,14 @@ int fsmg_maml_eval(fsmg_handle h, const int32_t* support, const int32_t* query, 
     int rc = FSMG_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
         rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, tokens_on_device);
-        // the flag of a time-out / token error inside the adaptation is still set: fsmg_eval_step reads and reports it
-        if (rc == FSMG_OK) rc = fsmg_eval_step(h, query, N, Q, tokens_on_device, nll);
-        const int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
+        // the flag of a time-out / token error inside the adaptation is still set: the query pass reads and reports it.  It must not
+        // repeat its chunk on its own as fsmg_eval_step does: the inner updates of a timed-out adaptation were skipped, the repeated
+        // chunk would succeed at the UNADAPTED theta and its NLL would be returned as if nothing had happened -- the adaptation is
+        // repeated with it, below
+        if (rc == FSMG_OK) rc = eval_batch_core(h, query, nullptr, 1, N, Q, tokens_on_device, nll, false, false);
+        const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
+        int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
+        if (rc2 == FSMG_OK) rc2 = rc_keep;
         h->have_grads = false;
         if (rc == FSMG_OK) rc = rc2;
         if (!(is_retry(rc) && h->retry_armed)) break;
@@ -434,7 +444,9 @@ int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_
         rc = maml_adapt(h, support, 1, n_support_rows, inner_steps, inner_lr, support_on_device);
         if (rc == FSMG_OK) rc = adapt_flag(h);           // a time-out / token error inside the adaptation: theta' is not usable
         if (rc == FSMG_OK) rc = at_theta_prime();
-        const int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
+        const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
+        int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
+        if (rc2 == FSMG_OK) rc2 = rc_keep;
         h->have_grads = false;
         if (rc == FSMG_OK) rc = rc2;
         if (!(is_retry(rc) && h->retry_armed)) break;
@@ -447,8 +459,10 @@ int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_
 extern "C" {
 
 // query_len != nullptr: the padding-masked form -- each episode's NLL over its own n_valid
+// repeat_chunk: a chunk whose persistent kernel timed out is repeated here on per-step launches (false: the caller repeats -- fsmg_maml_eval,
+// whose adaptation has to be repeated with it)
 static int eval_batch_core(fsmg_handle h, const int32_t* queries, const int32_t* query_len, int32_t n_episodes, int32_t N, int32_t Q,
-                           int32_t tokens_on_device, float* nll, bool masked) {
+                           int32_t tokens_on_device, float* nll, bool masked, bool repeat_chunk) {
     if (!h || !queries || !nll || n_episodes <= 0) return FSMG_ERR_INVALID;
     int rc = validate_shape(h, N, 0, Q);
     if (rc != FSMG_OK) return rc;
@@ -492,7 +506,7 @@ static int eval_batch_core(fsmg_handle h, const int32_t* queries, const int32_t*
         if (rc != FSMG_OK) return rc;
         h->lastB = B;
         rc = check_tokens_and_read(h, h->d_eval, 1.0f, nll + e0, ne);
-        if (is_retry(rc) && h->retry_armed && !retried) {
+        if (repeat_chunk && is_retry(rc) && h->retry_armed && !retried) {
             // a persistent kernel could not get its blocks resident: the handle has switched to one launch per time
             // step; repeat this chunk that way (validation must not abort a training run, nor leave peer ranks hanging)
             h->retry_armed = false;

@@ -154,6 +154,19 @@ int save_theta(fsmg_model* h) {
     HIPCK(h, launch_copy_words(h->stream, h->P_saved, h->P, h->n_flat));        // (n_flat is a multiple of FLAT_ALIGN = 64 floats)
     return FSMG_OK;
 }
+// the parameters as they are right now (theta' where the adaptation ran, theta where it failed before its first step) for
+// fsmg_debug_read("adapted:<name>"): one copy in stream order.  Knob off: no allocation, no launch.
+int keep_theta_prime(fsmg_model* h) {
+    if (!h->keep_adapted) return FSMG_OK;
+    if (!h->P_adapted) {
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        if (hipMalloc((void**)&h->P_adapted, sizeof(float) * (size_t)h->n_flat) != hipSuccess)
+            return fail(h, FSMG_ERR_NOMEM, "hipMalloc(kept adapted parameters) failed");
+    }
+    HIPCK(h, launch_copy_words(h->stream, h->P_adapted, h->P, h->n_flat));
+    h->have_adapted = true;
+    return FSMG_OK;
+}
 int restore_theta(fsmg_model* h) {
     HIPCK(h, launch_copy_words(h->stream, h->P, h->P_saved, h->n_flat));
     h->khf_dirty = true;

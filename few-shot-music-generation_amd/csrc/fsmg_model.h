@@ -144,6 +144,9 @@ struct fsmg_model {
     bool persist = true;                // FSMG_PERSISTENT=0: one launch per time step instead of one persistent launch per chain chunk
     float* khf = nullptr;               // fragment-ordered recurrent weights: per layer fwd copy, bwd copy
     float* P_saved = nullptr;           // cfg-E: theta while the handle computes at the adapted theta'
+    float* P_adapted = nullptr;         // fsmg_debug_set("keep_adapted", 1): the last theta', copied right before theta came back (tests read it:
+    bool keep_adapted = false;          // fsmg_debug_read("adapted:<parameter name>")); never allocated, never written while the knob is 0
+    bool have_adapted = false;
     static constexpr int MAX_TABLES = 4;
     int* table[MAX_TABLES] = {};        // device-resident packed splits [n_songs][T] (fsmg_upload_table)
     int64_t table_rows[MAX_TABLES] = {};
@@ -670,6 +673,7 @@ int place_deferred_half(fsmg_model* h, int xcd_first);     // forward(): the wai
 int sgd_update(fsmg_model* h, float lr);
 int save_theta(fsmg_model* h);
 int restore_theta(fsmg_model* h);
+int keep_theta_prime(fsmg_model* h);      // before every restore_theta: P -> P_adapted where fsmg_debug_set("keep_adapted", 1) asks for it
 void on_timeout(fsmg_model* h);
 void on_softmax_range(fsmg_model* h);
 inline bool is_retry(int rc) { return rc == FSMG_ERR_TIMEOUT || rc == FSMG_ERR_SOFTMAX_RANGE; }

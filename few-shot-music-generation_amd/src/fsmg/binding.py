@@ -1291,7 +1291,7 @@ class FsmgModel(object):
 
     def debug_set(self, what, value):
         """run-time knob of the handle (include/fsmg.h: chain_spin_limit, fallback_steps, persistent, eager, inplace_dlogits,
-        upd_split, upd_defer, xov_selfcheck, xov_selfcheck_fault)"""
+        upd_split, upd_defer, xov_selfcheck, xov_selfcheck_fault, keep_adapted)"""
         self._ck(self._lib.fsmg_debug_set(self._h, what.encode(), int(value)))
 
     def clock_begin(self, microseconds):
@@ -1307,6 +1307,11 @@ class FsmgModel(object):
         out = np.empty(int(count), np.float32)
         self._ck(self._lib.fsmg_debug_read(self._h, what.encode(), _f32p(out), out.size))
         return out
+
+    def get_adapted(self, name):
+        """theta' of the last MAML-style call, shaped like get_param(name); needs debug_set('keep_adapted', 1) before that call"""
+        shape = self._shape(name)
+        return self.debug_read('adapted:' + name, int(np.prod(shape))).reshape(shape)
 
     def step_profile(self, which):
         """-> uint64 [n_blocks, n_waves, 8] s_memtime stamps of one instrumented recurrent step kernel"""

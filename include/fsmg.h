@@ -846,7 +846,10 @@ int fsmg_get_stats(fsmg_handle h, fsmg_stats* out);
  *   "gemm_kinds" [4]: GEMM launches the host has enqueued through this handle since fsmg_create, by kernel: [0] fp32 MFMA (k_gemm,
  *   k_gemm_staged, k_gemm_queue), [1] k_gemm_bx3, [2] k_gemm_bx3w (wave-specialised), [3] k_gemm_bx3h (256 x 256 tile).  A launch
  *   captured into a hipGraph counts once, when it is captured; a replay of the graph does not count again.  Which kernel a GEMM takes
- *   follows FSMG_GEMM_H / FSMG_GEMM_WS, how many K slabs FSMG_MAX_SPLIT: all three are read by fsmg_create, per handle */
+ *   follows FSMG_GEMM_H / FSMG_GEMM_WS, how many K slabs FSMG_MAX_SPLIT: all three are read by fsmg_create, per handle
+ *   "adapted:<parameter name>" [rows*cols]: the adapted parameters theta' of the last MAML-style call (fsmg_maml_forward_backward /
+ *   _step / _eval, their _indexed forms, fsmg_maml_generate / _beam_search / _score), in the reference layout like fsmg_get_param;
+ *   count must be rows*cols.  Needs fsmg_debug_set("keep_adapted", 1) before that call: FSMG_ERR_STATE if nothing has been kept */
 int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count);
 /* run-time knobs of a handle that used to be create-time environment variables (tests, diagnostics):
  *   "chain_spin_limit"  polls before a persistent recurrent kernel gives up (0 forces the time-out path)
@@ -878,6 +881,9 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
  *   "reprobe_aux"       1: a handle whose create-time probe found no second stream running beside its own (fsmg_stats.aux_stream_tries = -1)
  *                       probes again (300 us, then 5 ms per candidate); on success the overlapped tails -- and the XCD-partitioned order where the
  *                       handle was created in the format it needs -- come back
+ *   "keep_adapted"      1: every MAML-style call copies its adapted parameters theta' into a buffer of the handle's own (allocated on first
+ *                       use, one copy kernel in stream order) right before it puts theta back; fsmg_debug_read("adapted:<name>") reads it
+ *                       (tests).  0 (default): no buffer, no launch, results bit-identical either way
  * Synchronises the stream and drops the captured graphs. */
 int fsmg_debug_set(fsmg_handle h, const char* what, int64_t value);
 /* shader clock the chip sustains while the handle works: _begin starts a one-wave probe on a stream of its own that compares the

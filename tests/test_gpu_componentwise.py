@@ -22,8 +22,10 @@ the packed [unit block][gate][unit % 4] column order that gpu_utils.read_states 
 weight-gradient GEMM of api_backward.hip (dk_gemm: `m.B = h->Z[l]; m.ldb = G4`) could contract with.  So dz is compared for
 every family.
 
-The parameters after the inner SGD step of the MAML-style pass are not readable (fsmg_maml_forward_backward restores theta
-before it returns, api_step.hip), so k_sgd_update has no elementwise check here.
+The parameters after the inner SGD step of the MAML-style pass are read through fsmg_debug_set("keep_adapted", 1) /
+fsmg_debug_read("adapted:<name>") (fsmg_maml_forward_backward restores theta before it returns, api_step.hip; the knob keeps a
+copy of theta' first): k_sgd_update and the query pass at theta' have their elementwise checks in
+tests/test_gpu_maml_componentwise.py, which takes M, device_tensors and check_all from here.
 """
 import os
 
