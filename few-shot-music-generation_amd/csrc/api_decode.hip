@@ -406,6 +406,18 @@ int fsmg_maml_generate_filtered(fsmg_handle h, const fsmg_gen_config* g, const f
                               [&] { return generate_core(h, g, f, primer, out_tokens, out_logprob); });
 }
 
+// the adaptation over the positions inside a support song only; the generation at theta' is fsmg_maml_generate_filtered's
+int fsmg_maml_generate_filtered_masked(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* support,
+                                       const int32_t* support_len, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
+                                       int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    int rc = check_gen_config(h, g, primer, out_tokens);
+    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    if (rc != FSMG_OK) return rc;
+    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
+                              [&] { return generate_core(h, g, f, primer, out_tokens, out_logprob); }, support_len, true);
+}
+
 int fsmg_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_t* primer, int32_t* out_tokens, float* out_scores,
                      float* out_logprob) {
     if (!h) return FSMG_ERR_INVALID;
@@ -423,6 +435,16 @@ int fsmg_maml_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_
     if (rc != FSMG_OK) return rc;
     return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
                               [&] { return beam_core(h, b, primer, out_tokens, out_scores, out_logprob); });
+}
+
+int fsmg_maml_beam_search_masked(fsmg_handle h, const fsmg_beam_config* b, const int32_t* support, const int32_t* support_len,
+                                 int32_t n_support_rows, int32_t inner_steps, float inner_lr, int32_t support_on_device,
+                                 const int32_t* primer, int32_t* out_tokens, float* out_scores, float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    const int rc = check_beam_config(h, b, primer, out_tokens, out_scores);
+    if (rc != FSMG_OK) return rc;
+    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
+                              [&] { return beam_core(h, b, primer, out_tokens, out_scores, out_logprob); }, support_len, true);
 }
 
 // ---- decode states

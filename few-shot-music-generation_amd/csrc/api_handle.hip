@@ -364,6 +364,7 @@ int fsmg_destroy(fsmg_handle h) {
     for (int* t : h->table_len) if (t) hipFree(t);
     if (h->d_idx) hipFree(h->d_idx);
     if (h->d_gather) hipFree(h->d_gather);
+    if (h->d_gather_len) hipFree(h->d_gather_len);
     if (h->d_eval) hipFree(h->d_eval);
     if (h->host_counters) hipHostFree(h->host_counters);
     if (h->own_state && h->state) hipFree(h->state);

@@ -177,4 +177,19 @@ int fsmg_maml_score(fsmg_handle h, const fsmg_score_config* c, const int32_t* su
                               [&] { return score_core(h, c, tokens, out_logprob, out_rank, out_entropy, out_argmax, out_row_nll); });
 }
 
+// the adaptation over the positions inside a support song only; `lengths` (host, NULL: none) are the scored songs' own
+// and treat the outputs as fsmg_score_masked does
+int fsmg_maml_score_masked(fsmg_handle h, const fsmg_score_config* c, const int32_t* support, const int32_t* support_len, int32_t n_support_rows,
+                           int32_t inner_steps, float inner_lr, int32_t support_on_device, const int32_t* tokens, const int32_t* lengths,
+                           float* out_logprob, int32_t* out_rank, float* out_entropy, int32_t* out_argmax, float* out_row_nll) {
+    if (!h) return FSMG_ERR_INVALID;
+    const void* outs[5] = {out_logprob, out_rank, out_entropy, out_argmax, out_row_nll};
+    int rc = check_score_config(h, c, tokens, outs);
+    if (rc == FSMG_OK && lengths) rc = check_host_lengths(h, lengths, (size_t)c->n_rows);
+    if (rc != FSMG_OK) return rc;
+    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
+                              [&] { return score_core(h, c, tokens, out_logprob, out_rank, out_entropy, out_argmax, out_row_nll, lengths); },
+                              support_len, true);
+}
+
 }  // extern "C"

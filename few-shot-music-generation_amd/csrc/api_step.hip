@@ -311,10 +311,27 @@ int fsmg_forward_backward_indexed_masked(fsmg_handle h, int32_t table_id, const 
 }
 
 // ---- cfg-E (BASELINE.json configs[4]): MAML-style inner / outer loop, first order.  DESIGN.md "cfg-E".
-static int maml_adapt(fsmg_handle h, const int32_t* support, int32_t N, int32_t K, int32_t inner_steps, float inner_lr, int32_t on_device) {
+// one padding-masked forward + backward over `rows` [N*R][T] with their lengths, as one group of N*R rows.  The public
+// fsmg_forward_backward_masked cannot stand in for it inside a MAML call as fsmg_forward_backward does for the unmasked pass: the
+// flag is set here, behind the prologue that clears it, and the pass's own lengths are staged by its own `stage` (a repeat restages them)
+static int masked_rows_pass(fsmg_handle h, const int32_t* rows, const int32_t* len, int32_t N, int32_t R, int32_t on_device) {
+    BEGIN_CALL(h, true);        // fsmg_forward_backward's prologue
+    begin_masked(h, N * R, 1);
+    const int rc = forward_backward_core(h, N, R, 0, [&]() {
+        const int r = stage_tokens(h, rows, N * R, rows, 0, on_device);
+        return r != FSMG_OK ? r : stage_lengths(h, len, N * R, len, 0, on_device);
+    });
+    h->masked_call = false;     // what runs next at theta' (the update, a decode) is not a masked pass
+    return rc;
+}
+
+// support_len != nullptr: every inner step's loss over the positions inside a song only (masked_rows_pass)
+static int maml_adapt(fsmg_handle h, const int32_t* support, int32_t N, int32_t K, int32_t inner_steps, float inner_lr, int32_t on_device,
+                      const int32_t* support_len = nullptr) {
     int rc = save_theta(h);
     for (int i = 0; rc == FSMG_OK && i < inner_steps; ++i) {
-        rc = fsmg_forward_backward(h, support, support, N, K, 0, on_device);       // support rows only
+        rc = support_len ? masked_rows_pass(h, support, support_len, N, K, on_device)
+                         : fsmg_forward_backward(h, support, support, N, K, 0, on_device);       // support rows only
         if (rc == FSMG_OK) rc = sgd_update(h, inner_lr);
     }
     return rc;
@@ -350,24 +367,79 @@ int fsmg_maml_step(fsmg_handle h, const int32_t* support, const int32_t* query, 
     return rc;
 }
 
+// ---- cfg-E with per-song lengths: every inner step over the support rows' valid positions, the outer pass over the query rows'
+static int validate_maml_masked_args(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                                     int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t on_device) {
+    if (!support || !query) return fail(h, FSMG_ERR_INVALID, "null token pointer");
+    if (inner_steps < 0 || inner_steps > 64 || !(inner_lr >= 0.f) || K <= 0 || Q <= 0) return fail(h, FSMG_ERR_INVALID, "bad inner_steps / inner_lr / K / Q");
+    return validate_masked_args(h, support_len, query_len, N, K, Q, on_device);
+}
+
+static int maml_forward_backward_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                                        int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t on_device) {
+    int rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, on_device, support_len);
+    if (rc == FSMG_OK) rc = masked_rows_pass(h, query, query_len, N, Q, on_device);                  // query rows at theta'
+    const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
+    int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;                                               // theta comes back whatever happened
+    if (rc2 == FSMG_OK) rc2 = rc_keep;
+    return rc != FSMG_OK ? rc : rc2;
+}
+
+int fsmg_maml_forward_backward_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                                      int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t tokens_on_device) {
+    if (!h) return FSMG_ERR_INVALID;
+    const int rcv = validate_maml_masked_args(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
+    if (rcv != FSMG_OK) return rcv;
+    BEGIN_CALL(h);
+    return maml_forward_backward_masked(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
+}
+
+int fsmg_maml_step_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                          int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* loss) {
+    if (!h) return FSMG_ERR_INVALID;
+    const int rcv = validate_maml_masked_args(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
+    if (rcv != FSMG_OK) return rcv;
+    BEGIN_CALL(h);
+    auto fb = [&]() { return maml_forward_backward_masked(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device); };
+    if (h->comm != nullptr)           // each rank normalises by its own n_valid; 1 / world takes the mean
+        return dp_train_step(h, loss, fb);
+    int rc = fb();
+    if (rc != FSMG_OK) return rc;
+    rc = fsmg_apply_update(h, 1.0f, loss);
+    if (is_retry(rc) && h->retry_armed) {        // same recovery as fsmg_maml_step: nothing was updated, repeat per step -- with the lengths
+        h->retry_armed = false;
+        rc = fb();
+        if (rc == FSMG_OK) rc = fsmg_apply_update(h, 1.0f, loss);
+    }
+    return rc;
+}
+
 // cfg-E on the device-resident split table: the episode's rows are gathered ONCE into a buffer of the handle's own and the
 // inner / outer passes read them there (an index outside the table raises the token-range flag like any bad token)
-static int gather_episode(fsmg_handle h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry) {
+// with_len: the rows' lengths are gathered in the same launch into d_gather_len (the masked forms; a table without lengths: FSMG_ERR_STATE)
+static int gather_episode(fsmg_handle h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry, bool with_len = false) {
     if (table_id < 0 || table_id >= fsmg_model::MAX_TABLES || !h->table[table_id]) return fail(h, FSMG_ERR_STATE, "no token table uploaded under this id");
+    if (with_len && !h->table_len[table_id]) return fail(h, FSMG_ERR_STATE, "the table under this id has no lengths (fsmg_upload_table_lengths)");
     const int n = n_sup + n_qry;
     if (h->idx_cap < n || h->gather_cap < (int64_t)n * h->T) {
         HIPCK(h, hipStreamSynchronize(h->stream));
         if (h->d_idx) hipFree(h->d_idx);
         if (h->d_gather) hipFree(h->d_gather);
-        h->d_idx = nullptr; h->d_gather = nullptr; h->idx_cap = 0; h->gather_cap = 0;
+        if (h->d_gather_len) hipFree(h->d_gather_len);
+        h->d_idx = nullptr; h->d_gather = nullptr; h->d_gather_len = nullptr; h->idx_cap = 0; h->gather_cap = 0;
         const int cap = std::max(n, 4096);
-        if (hipMalloc((void**)&h->d_idx, sizeof(int) * cap) != hipSuccess || hipMalloc((void**)&h->d_gather, sizeof(int) * (size_t)cap * h->T) != hipSuccess)
+        if (hipMalloc((void**)&h->d_idx, sizeof(int) * cap) != hipSuccess || hipMalloc((void**)&h->d_gather, sizeof(int) * (size_t)cap * h->T) != hipSuccess ||
+            hipMalloc((void**)&h->d_gather_len, sizeof(int) * cap) != hipSuccess)
             return fail(h, FSMG_ERR_NOMEM, "hipMalloc(episode gather buffers) failed");
         h->idx_cap = cap; h->gather_cap = (int64_t)cap * h->T;
     }
     if (n_sup > 0) HIPCK(h, hipMemcpyAsync(h->d_idx, sup_idx, sizeof(int) * n_sup, hipMemcpyHostToDevice, h->stream));
     if (n_qry > 0) HIPCK(h, hipMemcpyAsync(h->d_idx + n_sup, qry_idx, sizeof(int) * n_qry, hipMemcpyHostToDevice, h->stream));
-    HIPCK(h, launch_gather_rows(h->stream, h->table[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id], h->d_gather, h->d_err));
+    if (with_len)
+        HIPCK(h, launch_gather_rows_len(h->stream, h->table[table_id], h->table_len[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id],
+                                        h->d_gather, h->d_gather_len, h->d_err));
+    else
+        HIPCK(h, launch_gather_rows(h->stream, h->table[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id], h->d_gather, h->d_err));
     return FSMG_OK;
 }
 
@@ -387,6 +459,27 @@ int fsmg_maml_step_indexed(fsmg_handle h, int32_t table_id, const int32_t* suppo
     const int rc = gather_episode(h, table_id, support_idx, N * K, query_idx, N * Q);
     if (rc != FSMG_OK) return rc;
     return fsmg_maml_step(h, h->d_gather, h->d_gather + (size_t)N * K * h->T, N, K, Q, inner_steps, inner_lr, 1, loss);
+}
+
+// the masked forms: the rows' lengths come out of the same gather (fsmg_upload_table_lengths) and reach the token forms as device lengths
+int fsmg_maml_forward_backward_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                                              int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr) {
+    if (!h || !support_idx || !query_idx || N <= 0 || K <= 0 || Q <= 0) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h);
+    const int rc = gather_episode(h, table_id, support_idx, N * K, query_idx, N * Q, true);
+    if (rc != FSMG_OK) return rc;
+    return fsmg_maml_forward_backward_masked(h, h->d_gather, h->d_gather + (size_t)N * K * h->T, h->d_gather_len, h->d_gather_len + N * K,
+                                             N, K, Q, inner_steps, inner_lr, 1);
+}
+
+int fsmg_maml_step_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                                  int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, float* loss) {
+    if (!h || !support_idx || !query_idx || N <= 0 || K <= 0 || Q <= 0) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h);
+    const int rc = gather_episode(h, table_id, support_idx, N * K, query_idx, N * Q, true);
+    if (rc != FSMG_OK) return rc;
+    return fsmg_maml_step_masked(h, h->d_gather, h->d_gather + (size_t)N * K * h->T, h->d_gather_len, h->d_gather_len + N * K,
+                                 N, K, Q, inner_steps, inner_lr, 1, loss);
 }
 
 static int eval_batch_core(fsmg_handle h, const int32_t* queries, const int32_t* query_len, int32_t n_episodes, int32_t N, int32_t Q,
@@ -416,6 +509,30 @@ int fsmg_maml_eval(fsmg_handle h, const int32_t* support, const int32_t* query, 
     return rc;
 }
 
+int fsmg_maml_eval_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                          int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* nll) {
+    if (!h || !nll) return FSMG_ERR_INVALID;
+    const int rcv = validate_maml_masked_args(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
+    if (rcv != FSMG_OK) return rcv;
+    BEGIN_CALL(h);
+    int rc = FSMG_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, tokens_on_device, support_len);
+        // as in fsmg_maml_eval: the query pass reports the adaptation's flag and must not repeat its chunk at the unadapted theta on its
+        // own -- the adaptation is repeated with it, lengths and all
+        if (rc == FSMG_OK) rc = eval_batch_core(h, query, query_len, 1, N, Q, tokens_on_device, nll, true, false);
+        h->masked_call = false;
+        const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
+        int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
+        if (rc2 == FSMG_OK) rc2 = rc_keep;
+        h->have_grads = false;
+        if (rc == FSMG_OK) rc = rc2;
+        if (!(is_retry(rc) && h->retry_armed)) break;
+        h->retry_armed = false;                        // adapted with garbage (skipped) steps: repeat on per-step launches
+    }
+    return rc;
+}
+
 // the device error flag the adaptation's passes left (fsmg_maml_eval's query pass reads it in check_tokens_and_read)
 static int adapt_flag(fsmg_handle h) {
     int err = 0;
@@ -434,14 +551,20 @@ namespace fsmg_host {
 // adapt on the support rows like fsmg_maml_eval, run the body at theta', restore theta whatever happened; one repeat on per-step
 // launches when the adaptation ran garbage (skipped) steps.  The MAML decode entry points (api_decode.hip) run through here.
 int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
-                       int32_t support_on_device, const std::function<int()>& at_theta_prime) {
+                       int32_t support_on_device, const std::function<int()>& at_theta_prime, const int32_t* support_len, bool masked) {
+    if (masked && !support_len) return fail(h, FSMG_ERR_INVALID, "null length pointer");
     if (!support || n_support_rows <= 0 || inner_steps < 0 || inner_steps > 64 || !(inner_lr >= 0.f) || !std::isfinite(inner_lr) ||
         (support_on_device != 0 && support_on_device != 1))
         return fail(h, FSMG_ERR_INVALID, "bad support / n_support_rows / inner_steps / inner_lr");
+    if (masked) {         // host lengths before any device work; device lengths meet the range check of the kernel that builds the weights
+        int rcv = validate_shape(h, 1, n_support_rows, 0);
+        if (rcv == FSMG_OK && !support_on_device) rcv = validate_lengths(h, support_len, n_support_rows);
+        if (rcv != FSMG_OK) return rcv;
+    }
     BEGIN_CALL(h);
     int rc = FSMG_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        rc = maml_adapt(h, support, 1, n_support_rows, inner_steps, inner_lr, support_on_device);
+        rc = maml_adapt(h, support, 1, n_support_rows, inner_steps, inner_lr, support_on_device, masked ? support_len : nullptr);
         if (rc == FSMG_OK) rc = adapt_flag(h);           // a time-out / token error inside the adaptation: theta' is not usable
         if (rc == FSMG_OK) rc = at_theta_prime();
         const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;

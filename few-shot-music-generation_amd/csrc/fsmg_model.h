@@ -161,6 +161,7 @@ struct fsmg_model {
     bool masked_call = false;           // the call in progress is a masked one (begin_call clears it, the masked entry points set it)
     int mask_rpg = 0, mask_groups = 0;  // rows per group / groups of the masked pass in progress
     int last_mask_groups = 0;           // ... and of the last one that ran (fsmg_debug_read("n_valid"))
+    int* d_gather_len = nullptr;        // ... and their lengths (the masked forms; grown and freed with d_gather)
     int* d_gather = nullptr; int64_t gather_cap = 0;     // episode rows gathered from a table for the MAML-style step (its two passes take device token buffers)
     // XCD-local recurrence (lstm_xcd.hip; hidden size 512): per layer the forward and backward register images of K_h,
     // the h hand-off buffer, the dh-partial inboxes and the per-launch ticket counters
@@ -680,7 +681,8 @@ inline bool is_retry(int rc) { return rc == FSMG_ERR_TIMEOUT || rc == FSMG_ERR_S
 // adapt on the support rows like fsmg_maml_eval, run `at_theta_prime` there, restore theta whatever happened (api_step.hip; the MAML
 // decode entry points in api_decode.hip)
 int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
-                       int32_t support_on_device, const std::function<int()>& at_theta_prime);
+                       int32_t support_on_device, const std::function<int()>& at_theta_prime, const int32_t* support_len = nullptr,
+                       bool masked = false);      // masked: every inner step over the positions t < support_len[b] only
 int poll_skipped(fsmg_model* h);
 int report(fsmg_model* h, int what);
 int check_tokens_and_read(fsmg_model* h, const float* d_src, float scale, float* host_out, int n, bool train_tail = false);

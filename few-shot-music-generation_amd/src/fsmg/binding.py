@@ -161,6 +161,11 @@ SIGNATURES = {
     'fsmg_maml_eval': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _F32P]),
     'fsmg_maml_forward_backward_indexed': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
     'fsmg_maml_step_indexed': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _F32P]),
+    'fsmg_maml_forward_backward_masked': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32]),
+    'fsmg_maml_step_masked': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _F32P]),
+    'fsmg_maml_eval_masked': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _F32P]),
+    'fsmg_maml_forward_backward_indexed_masked': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
+    'fsmg_maml_step_indexed_masked': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _F32P]),
     'fsmg_eval_step': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _F32P]),
     'fsmg_eval_batch': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F32P]),
     'fsmg_train_step_masked': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F32P]),
@@ -176,10 +181,16 @@ SIGNATURES = {
     'fsmg_generate_filtered': (C.c_int, [_P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _P, _I32P, _F32P]),
     'fsmg_maml_generate_filtered': (C.c_int, [_P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _P, C.c_int32, C.c_int32, C.c_float,
                                               C.c_int32, _P, _I32P, _F32P]),
+    'fsmg_maml_generate_filtered_masked': (C.c_int, [_P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _P, _P, C.c_int32, C.c_int32,
+                                                     C.c_float, C.c_int32, _P, _I32P, _F32P]),
     'fsmg_beam_search': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, _I32P, _F32P, _F32P]),
     'fsmg_maml_beam_search': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P, _F32P,
                                         _F32P]),
+    'fsmg_maml_beam_search_masked': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P,
+                                               _F32P, _F32P]),
     'fsmg_score': (C.c_int, [_P, C.POINTER(FsmgScoreConfig), _P, _F32P, _I32P, _F32P, _I32P, _F32P]),
+    'fsmg_maml_score_masked': (C.c_int, [_P, C.POINTER(FsmgScoreConfig), _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P,
+                                         _F32P, _I32P, _F32P, _I32P, _F32P]),
     'fsmg_maml_score': (C.c_int, [_P, C.POINTER(FsmgScoreConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _F32P, _I32P,
                                   _F32P, _I32P, _F32P]),
     'fsmg_dstate_create': (C.c_int, [_P, C.POINTER(FsmgDstateConfig), C.POINTER(_P)]),
@@ -735,6 +746,46 @@ class FsmgModel(object):
         self._ck(self._lib.fsmg_maml_eval(self._h, sp, qp, n, k, q, int(inner_steps), float(inner_lr), dev, C.byref(nll)))
         return nll.value
 
+    # -- cfg-E with per-song lengths (include/fsmg.h "cfg-E with per-song lengths") -----------
+    def _maml_masked_args(self, support, query, support_len, query_len, shape):
+        n, k, q = self._episode_shape(support, query, shape)
+        sp, dev, k1 = _tok_ptr(support)
+        qp, _, k2 = _tok_ptr(query)
+        sl, k3 = self._len_ptr(support_len, n * k, dev)
+        ql, k4 = self._len_ptr(query_len, n * q, dev)
+        return (sp, qp, sl, ql, n, k, q), dev, (k1, k2, k3, k4)
+
+    def maml_forward_backward_masked(self, support, query, support_len, query_len, inner_steps, inner_lr, shape=None):
+        """maml_forward_backward with support_len [N,K] / query_len [N,Q] int32 (host arrays, or device addresses with device tokens)"""
+        a, dev, _keep = self._maml_masked_args(support, query, support_len, query_len, shape)
+        self._ck(self._lib.fsmg_maml_forward_backward_masked(self._h, *a, int(inner_steps), float(inner_lr), dev))
+
+    def maml_step_masked(self, support, query, support_len, query_len, inner_steps, inner_lr, shape=None, want_loss=True):
+        a, dev, _keep = self._maml_masked_args(support, query, support_len, query_len, shape)
+        loss = C.c_float()
+        self._ck(self._lib.fsmg_maml_step_masked(self._h, *a, int(inner_steps), float(inner_lr), dev, C.byref(loss) if want_loss else None))
+        return loss.value if want_loss else None
+
+    def maml_eval_masked(self, support, query, support_len, query_len, inner_steps, inner_lr, shape=None):
+        a, dev, _keep = self._maml_masked_args(support, query, support_len, query_len, shape)
+        nll = C.c_float()
+        self._ck(self._lib.fsmg_maml_eval_masked(self._h, *a, int(inner_steps), float(inner_lr), dev, C.byref(nll)))
+        return nll.value
+
+    def maml_forward_backward_indexed_masked(self, table_id, support_idx, query_idx, inner_steps, inner_lr):
+        """the rows' lengths come from the table's own (upload_table(..., lengths=))"""
+        s, q = self._idx(support_idx, query_idx)
+        self._ck(self._lib.fsmg_maml_forward_backward_indexed_masked(self._h, int(table_id), C.c_void_p(s.ctypes.data), C.c_void_p(q.ctypes.data),
+                                                                     s.shape[0], s.shape[1], q.shape[1], int(inner_steps), float(inner_lr)))
+
+    def maml_step_indexed_masked(self, table_id, support_idx, query_idx, inner_steps, inner_lr, want_loss=True):
+        s, q = self._idx(support_idx, query_idx)
+        loss = C.c_float()
+        self._ck(self._lib.fsmg_maml_step_indexed_masked(self._h, int(table_id), C.c_void_p(s.ctypes.data), C.c_void_p(q.ctypes.data),
+                                                         s.shape[0], s.shape[1], q.shape[1], int(inner_steps), float(inner_lr),
+                                                         C.byref(loss) if want_loss else None))
+        return loss.value if want_loss else None
+
     def eval_step(self, query, shape=None):
         if shape is None:
             n, q, t = query.shape
@@ -793,6 +844,15 @@ class FsmgModel(object):
         s = np.ascontiguousarray(support, dtype=np.int32).reshape(-1, self.max_len)
         return C.c_void_p(s.ctypes.data), s.shape[0], 0, s
 
+    def _adapt(self, support, n_support_rows, inner_steps, inner_lr, support_len):
+        """the support arguments of a MAML decode / score call -> (masked, argument tuple, keepalive); support_len (host int32
+        [rows], or a device address with a device support): the _masked entry point"""
+        sp, rows, dev, keep = self._support(support, n_support_rows)
+        if support_len is None:
+            return False, (sp, rows, int(inner_steps), float(inner_lr), dev), keep
+        sl, keep_len = self._len_ptr(support_len, rows, dev)
+        return True, (sp, sl, rows, int(inner_steps), float(inner_lr), dev), (keep, keep_len)
+
     def _gen_args(self, n_seq, num, temperature, top_k, seed, primer):
         P, on_device, pp, keep = self._primer(primer, n_seq, ('n_seq', 'sequence'))
         return self.gen_config(n_seq, num, temperature, top_k, seed, P, on_device), pp, keep
@@ -805,15 +865,17 @@ class FsmgModel(object):
         return FsmgGenFilters(version=FSMG_GEN_FILTERS_VERSION, top_p=float(top_p), min_p=float(min_p),
                               repetition_penalty=float(repetition_penalty), repeat_window=int(repeat_window))
 
-    def _generate(self, adapt, n_seq, num, temperature, top_k, seed, primer, logprobs, filters):
+    def _generate(self, adapt, n_seq, num, temperature, top_k, seed, primer, logprobs, filters, masked=False):
         """fsmg_generate (adapt = ()) or fsmg_maml_generate (adapt = its support arguments), the _filtered entry point when a
-        filter is on"""
+        filter is on; masked: fsmg_maml_generate_filtered_masked (adapt holds the support lengths; a NULL filter struct: none)"""
         g, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
         f = self.gen_filters(*filters)
         toks = np.empty((int(n_seq), int(num)), np.int32)
         lp = np.empty((int(n_seq), int(num)), np.float32) if logprobs else None
         name = ('fsmg_maml_generate' if adapt else 'fsmg_generate') + ('' if f is None else '_filtered')
         head = (C.byref(g),) if f is None else (C.byref(g), C.byref(f))
+        if masked:
+            name, head = 'fsmg_maml_generate_filtered_masked', (C.byref(g), C.byref(f) if f is not None else None)
         self._ck(getattr(self._lib, name)(self._h, *head, *adapt, pp, toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None))
         return (toks, lp) if logprobs else toks
 
@@ -861,11 +923,16 @@ class FsmgModel(object):
         return lp
 
     def maml_generate(self, support, num, inner_steps, inner_lr, n_seq=1, temperature=1.0, top_k=0, seed=0, primer=None,
-                      logprobs=False, n_support_rows=None, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
-        """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), generate at theta', restore theta"""
-        sp, rows, dev, _keep = self._support(support, n_support_rows)
-        return self._generate((sp, rows, int(inner_steps), float(inner_lr), dev), n_seq, num, temperature, top_k, seed, primer,
-                              logprobs, (top_p, min_p, repetition_penalty, repeat_window))
+                      logprobs=False, n_support_rows=None, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0,
+                      support_len=None):
+        """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), generate at theta', restore theta.
+        support_len int32 [rows]: adapt over the positions inside each support song only (fsmg_maml_generate_filtered_masked)"""
+        masked, adapt, _keep = self._adapt(support, n_support_rows, inner_steps, inner_lr, support_len)
+        if not masked:
+            return self._generate(adapt, n_seq, num, temperature, top_k, seed, primer, logprobs,
+                                  (top_p, min_p, repetition_penalty, repeat_window))
+        return self._generate(adapt, n_seq, num, temperature, top_k, seed, primer, logprobs,
+                              (top_p, min_p, repetition_penalty, repeat_window), masked=True)
 
     # -- batched on-device beam search (include/fsmg.h fsmg_beam_search) ----------------------------------------
     @staticmethod
@@ -873,8 +940,8 @@ class FsmgModel(object):
         return FsmgBeamConfig(version=FSMG_BEAM_CONFIG_VERSION, n_groups=int(n_groups), beam_width=int(beam_width), num=int(num),
                               primer_len=int(primer_len), primer_on_device=int(primer_on_device))
 
-    def _beam_search(self, adapt, num, beam_width, n_groups, primer, logprobs):
-        """fsmg_beam_search (adapt = ()) or fsmg_maml_beam_search (adapt = its support arguments)"""
+    def _beam_search(self, adapt, num, beam_width, n_groups, primer, logprobs, masked=False):
+        """fsmg_beam_search (adapt = ()) or fsmg_maml_beam_search (adapt = its support arguments; masked: with their lengths)"""
         P, on_device, pp, _keep = self._primer(primer, n_groups, ('n_groups', 'group'))
         b = self.beam_config(n_groups, beam_width, num, P, on_device)
         G, W, num = int(n_groups), int(beam_width), int(num)
@@ -882,6 +949,8 @@ class FsmgModel(object):
         scores = np.empty((G, W), np.float32)
         lp = np.empty((G, W, num), np.float32) if logprobs else None
         fn = self._lib.fsmg_maml_beam_search if adapt else self._lib.fsmg_beam_search
+        if masked:
+            fn = self._lib.fsmg_maml_beam_search_masked
         self._ck(fn(self._h, C.byref(b), *adapt, pp, toks.ctypes.data_as(_I32P), _f32p(scores), _f32p(lp) if logprobs else None))
         return (toks, scores, lp) if logprobs else (toks, scores)
 
@@ -906,10 +975,13 @@ class FsmgModel(object):
         return (toks, scores, lp) if logprobs else (toks, scores)
 
     def maml_beam_search(self, support, num, inner_steps, inner_lr, beam_width, n_groups=1, primer=None, logprobs=False,
-                         n_support_rows=None):
-        """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), beam search at theta', restore theta"""
-        sp, rows, dev, _keep = self._support(support, n_support_rows)
-        return self._beam_search((sp, rows, int(inner_steps), float(inner_lr), dev), num, beam_width, n_groups, primer, logprobs)
+                         n_support_rows=None, support_len=None):
+        """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), beam search at theta', restore theta.
+        support_len int32 [rows]: adapt over the positions inside each support song only (fsmg_maml_beam_search_masked)"""
+        masked, adapt, _keep = self._adapt(support, n_support_rows, inner_steps, inner_lr, support_len)
+        if not masked:
+            return self._beam_search(adapt, num, beam_width, n_groups, primer, logprobs)
+        return self._beam_search(adapt, num, beam_width, n_groups, primer, logprobs, masked=True)
 
     # -- scoring of given songs (include/fsmg.h fsmg_score) -----------------------------------------------------
     @staticmethod
@@ -926,8 +998,10 @@ class FsmgModel(object):
             raise ValueError('every value of %s must be in [1, %d]' % (what, self.max_len))
         return a
 
-    def _score(self, adapt, tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows, lengths=None):
-        """fsmg_score (adapt = ()), fsmg_maml_score (adapt = its support arguments) or fsmg_score_masked (lengths)"""
+    def _score(self, adapt, tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows, lengths=None,
+               masked=False):
+        """fsmg_score (adapt = ()), fsmg_maml_score (adapt = its support arguments), fsmg_score_masked (lengths) or
+        fsmg_maml_score_masked (masked: adapt holds the support lengths; lengths: the scored songs' own, or None)"""
         if isinstance(tokens, (int, np.integer)):
             tp, dev, _keep, R = C.c_void_p(int(tokens)), 1, None, int(n_rows)
         else:
@@ -951,6 +1025,11 @@ class FsmgModel(object):
             out['row_nll'] = np.empty(R, np.float32)
         f = lambda k: _f32p(out[k]) if k in out else None
         i = lambda k: out[k].ctypes.data_as(_I32P) if k in out else None
+        if masked:
+            ln = self._lengths(lengths, R) if lengths is not None else None
+            self._ck(self._lib.fsmg_maml_score_masked(self._h, C.byref(c), *adapt, tp, ln.ctypes.data_as(_I32P) if ln is not None else None,
+                                                      f('logprob'), i('rank'), f('entropy'), i('argmax'), f('row_nll')))
+            return out
         if lengths is not None:
             ln = self._lengths(lengths, R)
             self._ck(self._lib.fsmg_score_masked(self._h, C.byref(c), tp, ln.ctypes.data_as(_I32P), f('logprob'), i('rank'), f('entropy'),
@@ -971,11 +1050,17 @@ class FsmgModel(object):
         return self._score((), tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows, lengths)
 
     def maml_score(self, support, tokens, inner_steps, inner_lr, logprob=True, rank=False, entropy=False, argmax=False, row_nll=True,
-                   nll_first=0, nll_count=0, pass_rows=0, n_rows=None, n_support_rows=None):
-        """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), score at theta', restore theta"""
-        sp, rows, dev, _keep = self._support(support, n_support_rows)
-        return self._score((sp, rows, int(inner_steps), float(inner_lr), dev), tokens, n_rows, logprob, rank, entropy, argmax,
-                           row_nll, nll_first, nll_count, pass_rows)
+                   nll_first=0, nll_count=0, pass_rows=0, n_rows=None, n_support_rows=None, support_len=None, lengths=None):
+        """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), score at theta', restore theta.
+        support_len int32 [rows]: adapt over the positions inside each support song only; lengths int32 [R]: the scored songs' own,
+        as in score() -- either one selects fsmg_maml_score_masked"""
+        if support_len is None and lengths is not None:
+            raise ValueError('maml_score(lengths=) goes with support_len= (the masked adaptation)')
+        masked, adapt, _keep = self._adapt(support, n_support_rows, inner_steps, inner_lr, support_len)
+        if not masked:
+            return self._score(adapt, tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows)
+        return self._score(adapt, tokens, n_rows, logprob, rank, entropy, argmax, row_nll, nll_first, nll_count, pass_rows, lengths,
+                           masked=True)
 
     # -- support-set neural cache (include/fsmg.h fsmg_cache_*) ---------------------------------------------------
     @staticmethod

@@ -58,7 +58,10 @@ class EpisodeParallel(object):
         table; maml=(inner_steps, inner_lr) selects the cfg-E step (per-rank
         inner SGD on the support rows, no communication; the query-set gradients are exchanged exactly like a plain step's);
         lengths=(support_len, query_len): the padding-masked step (with table=id: lengths=True, the table's own lengths) -- each
-        rank normalises by its own n_valid and grad_scale = 1 / world takes the mean of those, as for the unmasked step"""
+        rank normalises by its own n_valid and grad_scale = 1 / world takes the mean of those, as for the unmasked step;
+        maml_lengths=(support_len, query_len), only with maml=: the cfg-E step with per-song lengths (with table=id:
+        maml_lengths=True, the table's own lengths) -- every inner step over the support rows' valid positions, the outer gradient
+        over the query rows', each rank by its own n_valid"""
         try:
             return self._train_step_once(support, query, want_loss, **kw)
         except Exception as e:
@@ -70,26 +73,33 @@ class EpisodeParallel(object):
                 raise
             return self._train_step_once(support, query, want_loss, **kw)
 
-    def _train_step_once(self, support, query, want_loss=True, maml=None, table=None, lengths=None, **kw):
+    def _train_step_once(self, support, query, want_loss=True, maml=None, table=None, lengths=None, maml_lengths=None, **kw):
         if lengths is not None:
             if maml is not None:
                 raise ValueError('the MAML-style step takes no lengths')
             kw['lengths'] = lengths          # (only a masked step hands the keyword to the engine)
+        mkw = {}
+        if maml_lengths is not None:
+            if maml is None:
+                raise ValueError('maml_lengths goes with maml=(inner_steps, inner_lr) only')
+            if (maml_lengths is True) != (table is not None):
+                raise ValueError('maml_lengths is (support_len, query_len) for tokens and True for table= (the table\'s own lengths)')
+            mkw['maml_lengths'] = maml_lengths      # (only a masked MAML-style step hands the keyword to the engine)
         if self.world == 1 and maml is None and hasattr(self.engine, 'fused_train_step'):
             return self.engine.fused_train_step(support, query, want_loss=want_loss, table=table, **kw)
         if self.world == 1 and maml is not None and table is not None and hasattr(self.engine, 'fused_maml_step'):
-            return self.engine.fused_maml_step(support, query, maml[0], maml[1], want_loss=want_loss, table=table)
+            return self.engine.fused_maml_step(support, query, maml[0], maml[1], want_loss=want_loss, table=table, **mkw)
         if getattr(self.engine, 'library_comm', False):
             # the library owns the exchange (fsmg_comm_init): one call per step and rank, collectives issued by libfsmg
             if maml is not None:
-                return self.engine.fused_maml_step(support, query, maml[0], maml[1], want_loss=want_loss, table=table, **kw)
+                return self.engine.fused_maml_step(support, query, maml[0], maml[1], want_loss=want_loss, table=table, **mkw, **kw)
             return self.engine.fused_train_step(support, query, want_loss=want_loss, table=table, **kw)
         if table is not None and maml is not None:      # cfg-E on the device-resident table: per-rank inner loop, then the exchange below
-            self.engine.maml_forward_backward_indexed(table, support, query, maml[0], maml[1])
+            self.engine.maml_forward_backward_indexed(table, support, query, maml[0], maml[1], **mkw)
         elif table is not None:               # support / query are [N,K] / [N,Q] row indices into a device-resident split table
             self.engine.forward_backward_indexed(table, support, query, **kw)
         elif maml is not None:
-            self.engine.maml_forward_backward(support, query, maml[0], maml[1], **kw)
+            self.engine.maml_forward_backward(support, query, maml[0], maml[1], **mkw, **kw)
         else:
             self.engine.forward_backward(support, query, **kw)
         buckets = getattr(self.engine, 'grad_buckets', None)

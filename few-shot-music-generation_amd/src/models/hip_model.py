@@ -90,7 +90,10 @@ class HIPModel(BaseModel):
             return self._model.forward_backward_indexed_masked(table_id, support_idx, query_idx)
         self._model.forward_backward_indexed(table_id, support_idx, query_idx)
 
-    def maml_forward_backward(self, support, query, inner_steps, inner_lr, **kw):
+    # (maml_lengths: the cfg-E step with per-song lengths -- (support_len, query_len), or True for the lengths uploaded with a table)
+    def maml_forward_backward(self, support, query, inner_steps, inner_lr, maml_lengths=None, **kw):
+        if maml_lengths is not None:
+            return self._model.maml_forward_backward_masked(support, query, maml_lengths[0], maml_lengths[1], inner_steps, inner_lr, **kw)
         self._model.maml_forward_backward(support, query, inner_steps, inner_lr, **kw)
 
     def fused_train_step(self, support, query, want_loss=True, table=None, **kw):
@@ -108,11 +111,19 @@ class HIPModel(BaseModel):
         return self._model.apply_update(grad_scale, want_loss=want_loss)
 
     def fused_maml_step(self, support, query, inner_steps, inner_lr, want_loss=True, table=None, **kw):
+        maml_lengths = kw.pop('maml_lengths', None)
+        if table is not None and maml_lengths is not None:
+            return self._model.maml_step_indexed_masked(table, support, query, inner_steps, inner_lr, want_loss=want_loss)
         if table is not None:       # support / query are row indices into the device-resident split table
             return self._model.maml_step_indexed(table, support, query, inner_steps, inner_lr, want_loss=want_loss)
+        if maml_lengths is not None:
+            return self._model.maml_step_masked(support, query, maml_lengths[0], maml_lengths[1], inner_steps, inner_lr,
+                                                want_loss=want_loss, **kw)
         return self._model.maml_step(support, query, inner_steps, inner_lr, want_loss=want_loss, **kw)
 
-    def maml_forward_backward_indexed(self, table_id, support_idx, query_idx, inner_steps, inner_lr):
+    def maml_forward_backward_indexed(self, table_id, support_idx, query_idx, inner_steps, inner_lr, maml_lengths=None):
+        if maml_lengths is not None:
+            return self._model.maml_forward_backward_indexed_masked(table_id, support_idx, query_idx, inner_steps, inner_lr)
         self._model.maml_forward_backward_indexed(table_id, support_idx, query_idx, inner_steps, inner_lr)
 
     # -- the gradient exchange inside the library (fsmg_comm_*: RCCL calls issued by libfsmg on its own stream) ----------

@@ -17,24 +17,58 @@ adaptation of deep networks") as the direction the project was heading.  This pl
   score(s, songs, ...)  per-token log-probabilities, ranks, entropies and per-song NLLs of given songs at theta' adapted on the
                   support set s (fsmg_maml_score); theta is restored.
 
-Extra config keys: inner_steps (default 1), inner_lr (default 0.1).
+Extra config keys: inner_steps (default 1), inner_lr (default 0.1), maml_lengths (default false: every path is what it was;
+true: per-song lengths, DESIGN.md 22 -- every inner step averages over the positions inside a support song, the outer gradient and
+the NLL over the positions inside a query song: train / train_indexed / eval read Episode.support_len / query_len or the lengths
+handed to attach_table, generate / beam_search / score take support_len=, and a missing length is a ValueError).
 """
+import numpy as np
+
 from models.lstm_baseline import LSTMBaseline
 
 
 class MAMLLSTM(LSTMBaseline):
-    MASKS_PADDING = False        # fsmg_maml_* take no lengths: `mask_padding: true` is refused at construction
+    MASKS_PADDING = False        # `mask_padding: true` (the baseline's one-pass loss) is refused at construction; cfg-E's key is maml_lengths
     def __init__(self, config):
         super(MAMLLSTM, self).__init__(config)
+        self.maml_lengths = bool(config.get('maml_lengths', False))
         self._inner_steps = int(config.get('inner_steps', 1))
         self._inner_lr = float(config.get('inner_lr', 0.1))
         if self._inner_steps < 0 or self._inner_lr < 0:
             raise RuntimeError('inner_steps and inner_lr must be >= 0')
 
+    def _episode_lengths(self, episode, which):
+        """the episode's lengths as int32 [N, K] / [N, Q], checked against its tokens (maml_lengths)"""
+        for name in which:
+            if getattr(episode, name + '_len', None) is None:
+                raise ValueError('maml_lengths is on and the episode has no %s_len: lengths come from EpisodeSampler.gather '
+                                 '(or Episode(support, query, support_len, query_len))' % name)
+        return self._lengths(episode, which)
+
+    def _support_lengths(self, support, support_len):
+        """support_len of generate / beam_search / score as int32 [rows] (maml_lengths: required; off: refused)"""
+        if not self.maml_lengths:
+            if support_len is not None:
+                raise ValueError('support_len needs maml_lengths: true in the model config')
+            return {}
+        if support_len is None:
+            raise ValueError('maml_lengths is on: the support set needs its lengths (support_len=)')
+        ln = np.ascontiguousarray(support_len, dtype=np.int32).reshape(-1)
+        if ln.size != support.shape[0]:
+            raise ValueError('support_len %r does not match the %d support songs' % (np.shape(support_len), support.shape[0]))
+        return dict(support_len=ln)
+
+    def attach_table(self, split, table, lengths=None):
+        """like LSTMBaseline.attach_table; with maml_lengths the table's lengths (Dataset.length_table) are needed and uploaded"""
+        if self.maml_lengths and lengths is None:
+            raise ValueError('maml_lengths is on: attach_table needs the lengths of the table (Dataset.length_table)')
+        self._model.upload_table(self.TABLE_IDS[split], table, lengths if self.maml_lengths else None)
+
     def train(self, episode):
         self._require_init()
+        kw = dict(maml_lengths=tuple(self._episode_lengths(episode, ('support', 'query')))) if self.maml_lengths else {}
         loss = self._parallel.train_step(self._tokens(episode.support, 3), self._tokens(episode.query, 3),
-                                         maml=(self._inner_steps, self._inner_lr))
+                                         maml=(self._inner_steps, self._inner_lr), **kw)
         self._log_scalar('Train/loss', loss, self._train_calls)
         self._train_calls += 1
         return loss
@@ -48,7 +82,8 @@ class MAMLLSTM(LSTMBaseline):
         self._require_init()
         loss = self._parallel.train_step(np.ascontiguousarray(support_idx, dtype=np.int32),
                                          np.ascontiguousarray(query_idx, dtype=np.int32), want_loss=want_loss,
-                                         table=self.TABLE_IDS[split], maml=(self._inner_steps, self._inner_lr))
+                                         table=self.TABLE_IDS[split], maml=(self._inner_steps, self._inner_lr),
+                                         **(dict(maml_lengths=True) if self.maml_lengths else {}))
         if want_loss:
             self._log_scalar('Train/loss', loss, self._train_calls)
         self._train_calls += 1
@@ -56,32 +91,44 @@ class MAMLLSTM(LSTMBaseline):
 
     def eval(self, episode):
         self._require_init()
-        nll = self._model.maml_eval(self._tokens(episode.support, 3), self._tokens(episode.query, 3),
-                                    self._inner_steps, self._inner_lr)
+        if self.maml_lengths:
+            sl, ql = self._episode_lengths(episode, ('support', 'query'))
+            nll = self._model.maml_eval_masked(self._tokens(episode.support, 3), self._tokens(episode.query, 3), sl, ql,
+                                               self._inner_steps, self._inner_lr)
+        else:
+            nll = self._model.maml_eval(self._tokens(episode.support, 3), self._tokens(episode.query, 3),
+                                        self._inner_steps, self._inner_lr)
         self._log_scalar('Eval/Avg_NLL', nll, self._eval_calls)
         self._eval_calls += 1
         return nll
 
-    def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
-        """like LSTMBaseline.generate, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored"""
+    def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0,
+                 support_len=None):
+        """like LSTMBaseline.generate, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored.
+        support_len [rows]: the support songs' lengths (maml_lengths)"""
         self._require_init()
         support = self._tokens(support_set, 2)
         return self._model.maml_generate(support, int(num), self._inner_steps, self._inner_lr, n_seq=int(n),
                                          temperature=temperature, top_k=top_k, seed=seed,
                                          primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs,
-                                         top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window)
+                                         top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window,
+                                         **self._support_lengths(support, support_len))
 
-    def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False):
-        """like LSTMBaseline.beam_search, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored"""
+    def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False, support_len=None):
+        """like LSTMBaseline.beam_search, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored.
+        support_len [rows]: the support songs' lengths (maml_lengths)"""
         self._require_init()
         support = self._tokens(support_set, 2)
         return self._model.maml_beam_search(support, int(num), self._inner_steps, self._inner_lr, int(beam_width), n_groups=int(n),
-                                            primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs)
+                                            primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs,
+                                            **self._support_lengths(support, support_len))
 
-    def score(self, support_set, songs, **kw):
-        """like LSTMBaseline.score, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored"""
+    def score(self, support_set, songs, support_len=None, **kw):
+        """like LSTMBaseline.score, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored.
+        support_len [rows]: the support songs' lengths (maml_lengths); lengths= then gives the scored songs' own"""
         self._require_init()
-        return self._model.maml_score(self._tokens(support_set, 2), songs, self._inner_steps, self._inner_lr, **kw)
+        support = self._tokens(support_set, 2)
+        return self._model.maml_score(support, songs, self._inner_steps, self._inner_lr, **self._support_lengths(support, support_len), **kw)
 
     def eval_many(self, episodes):
         """adaptation is per episode, so there is nothing to batch: one maml_eval per episode"""

@@ -156,7 +156,7 @@ def main(argv=None):
     train_sampler = episode_sampler['train']
     fast = (hasattr(model, 'attach_table') and hasattr(model, 'train_indexed') and hasattr(model, 'recent_losses')
             and hasattr(train_sampler, 'next_indices') and os.environ.get('FSMG_TRAIN_SYNC', '0') == '0')
-    if fast and getattr(model, 'mask_padding', False):      # the padding-masked loss: the songs' lengths travel with the table
+    if fast and (getattr(model, 'mask_padding', False) or getattr(model, 'maml_lengths', False)):      # the padding-masked loss: the songs' lengths travel with the table
         model.attach_table('train', train_sampler.token_table(), train_sampler.length_table())
     elif fast:
         model.attach_table('train', train_sampler.token_table())

@@ -275,6 +275,43 @@ int fsmg_maml_forward_backward_indexed(fsmg_handle h, int32_t table_id, const in
 int fsmg_maml_step_indexed(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
                            int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, float* loss);
 
+/* ---- cfg-E with per-song lengths: the padding-masked loss of DESIGN.md 20 in every pass of the MAML-style step.
+ * support_len [N*K] and query_len [N*Q], every one in [1, T]; position t of row b is scored iff t < len[b].  Inner step i:
+ *   theta'_{i+1} = theta'_i - inner_lr * clip_by_global_norm(grad of L_sup(theta'_i), max_grad_norm),
+ *   L_sup = sum over support (b, t < len[b]) of ce / (n_valid_sup + 1e-12),  n_valid_sup = the sum of the support lengths
+ * (one group of N*K rows; both clip-norm modes as in the unmasked call).  The outer gradient is the gradient of L_qry, the same sum
+ * over the query rows / (n_valid_qry + 1e-12), with respect to theta', first order; the loss / NLL returned is L_qry(theta'); theta
+ * is restored whatever happens.  Two laws, as in DESIGN.md 20: with every length T a call has its unmasked twin's bits (loss,
+ * gradients, tail, theta', updated state, NLL); and the tokens at t >= len[b] never matter (fixed ids stand in for them on the
+ * device) -- they must still be in range.
+ * The lengths live where the tokens do (tokens_on_device covers all four pointers).  Host lengths are checked before any device
+ * work: one outside [1, T] or a NULL pointer gives FSMG_ERR_INVALID with nothing touched -- theta, the saved copy of theta, the
+ * gradient buffer.  Device lengths are checked by the kernel that builds each pass's weights, which raises the token-range flag:
+ * every update of the call is skipped on the device and the call returns FSMG_ERR_TOKEN_RANGE.
+ * Everything the unmasked twins promise holds: theta, Adam slots, global_step and the loss ring are untouched by
+ * _forward_backward_masked / _eval_masked; the gradient buffer and the recurrent-launch counters are used as they use them;
+ * fsmg_apply_update follows _forward_backward_masked; a time-out repeats the whole call -- adaptation, lengths and all -- on
+ * per-step launches; fsmg_debug_set("keep_adapted") / "adapted:<name>" work.  With a communicator attached fsmg_maml_step_masked is
+ * the episode-parallel step: each rank normalises by its OWN n_valid_qry and grad_scale = 1 / world takes the mean.
+ * Each of the inner_steps + 1 train passes costs the two launches and the one length copy a masked train pass adds (the row
+ * weights, the masked loss sum), the query pass of _eval_masked one launch (the row weights).
+ * The _indexed_masked forms gather each row's length with the row (fsmg_upload_table_lengths; a table without lengths:
+ * FSMG_ERR_STATE, nothing touched). */
+int fsmg_maml_forward_backward_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len,
+                                      const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int32_t inner_steps,
+                                      float inner_lr, int32_t tokens_on_device);
+int fsmg_maml_step_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len,
+                          const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr,
+                          int32_t tokens_on_device, float* loss);
+int fsmg_maml_eval_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len,
+                          const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr,
+                          int32_t tokens_on_device, float* nll);
+int fsmg_maml_forward_backward_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx,
+                                              const int32_t* query_idx, int32_t N, int32_t K, int32_t Q, int32_t inner_steps,
+                                              float inner_lr);
+int fsmg_maml_step_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                                  int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, float* loss);
+
 /* replaces LSTMBaseline.sample (src/models/lstm_baseline.py:135-156): greedy argmax decode of
  * `num` tokens from the start word and a zero state (the support set is ignored there; a carried state: fsmg_dstate_*). */
 int fsmg_sample(fsmg_handle h, int32_t num, int32_t* out_tokens);
@@ -357,6 +394,15 @@ int fsmg_generate_filtered(fsmg_handle h, const fsmg_gen_config* g, const fsmg_g
 int fsmg_maml_generate_filtered(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f,
                                 const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
                                 int32_t support_on_device, const int32_t* primer, int32_t* out_tokens, float* out_logprob);
+/* fsmg_maml_generate_filtered with per-song support lengths: support_len [n_support_rows], every one in [1, max_len],
+ * where the support tokens are (support_on_device covers both); every inner step is fsmg_maml_eval_masked's, over the positions
+ * t < support_len[b] only, and the generation at theta' is fsmg_maml_generate_filtered's, launch for launch.  A NULL support_len or a
+ * host length out of range: FSMG_ERR_INVALID before any device work; a device length out of range raises the token-range flag in
+ * the kernel that builds the weights: FSMG_ERR_TOKEN_RANGE, outputs unwritten.  Side effects and the time-out repeat: the twin's. */
+int fsmg_maml_generate_filtered_masked(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f,
+                                       const int32_t* support, const int32_t* support_len, int32_t n_support_rows,
+                                       int32_t inner_steps, float inner_lr, int32_t support_on_device, const int32_t* primer,
+                                       int32_t* out_tokens, float* out_logprob);
 
 /* ---- batched on-device beam search (DESIGN.md "Beam search").  G independent searches of width W.  Every hypothesis of group g
  * reads [start, primer[g][0..P-1], y_0, y_1, ...] from a zero state, exactly as a row of fsmg_generate does, and the logits are
@@ -393,6 +439,11 @@ int fsmg_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_t* pr
 int fsmg_maml_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_t* support, int32_t n_support_rows,
                           int32_t inner_steps, float inner_lr, int32_t support_on_device, const int32_t* primer,
                           int32_t* out_tokens, float* out_scores, float* out_logprob);
+/* fsmg_maml_beam_search with per-song support lengths: support_len as in fsmg_maml_generate_filtered_masked (same checks, same
+ * errors); the search at theta' is fsmg_maml_beam_search's */
+int fsmg_maml_beam_search_masked(fsmg_handle h, const fsmg_beam_config* b, const int32_t* support, const int32_t* support_len,
+                                 int32_t n_support_rows, int32_t inner_steps, float inner_lr, int32_t support_on_device,
+                                 const int32_t* primer, int32_t* out_tokens, float* out_scores, float* out_logprob);
 
 /* ---- scoring of given songs (DESIGN.md "Scoring").  Row r of tokens [R, max_len] is read exactly as an eval row: the inputs are
  * [start, x_0 .. x_{T-2}] (start = input_size, T = max_len) from a zero state, z the V1 = input_size + 1 logits after input t -- the
@@ -438,6 +489,13 @@ int fsmg_score(fsmg_handle h, const fsmg_score_config* c, const int32_t* tokens,
 int fsmg_maml_score(fsmg_handle h, const fsmg_score_config* c, const int32_t* support, int32_t n_support_rows,
                     int32_t inner_steps, float inner_lr, int32_t support_on_device, const int32_t* tokens,
                     float* out_logprob, int32_t* out_rank, float* out_entropy, int32_t* out_argmax, float* out_row_nll);
+/* fsmg_maml_score with per-song support lengths: support_len as in fsmg_maml_generate_filtered_masked (same checks, same errors).
+ * lengths (host [R], every one in [1, max_len]; NULL: fsmg_maml_score's outputs) are the SCORED songs' own and shape the outputs as
+ * fsmg_score_masked does: 0 behind a song's end, out_row_nll over the positions inside the song. */
+int fsmg_maml_score_masked(fsmg_handle h, const fsmg_score_config* c, const int32_t* support, const int32_t* support_len,
+                           int32_t n_support_rows, int32_t inner_steps, float inner_lr, int32_t support_on_device,
+                           const int32_t* tokens, const int32_t* lengths, float* out_logprob, int32_t* out_rank,
+                           float* out_entropy, int32_t* out_argmax, float* out_row_nll);
 
 /* ---- decode states (DESIGN.md "Decode states"): the LSTM state of R decode rows as a device-resident object the handle owns, so
  * that every decode entry point can start from it and leave it advanced -- continue a piece, read something longer than max_len in
@@ -848,7 +906,7 @@ int fsmg_get_stats(fsmg_handle h, fsmg_stats* out);
  *   captured into a hipGraph counts once, when it is captured; a replay of the graph does not count again.  Which kernel a GEMM takes
  *   follows FSMG_GEMM_H / FSMG_GEMM_WS, how many K slabs FSMG_MAX_SPLIT: all three are read by fsmg_create, per handle
  *   "adapted:<parameter name>" [rows*cols]: the adapted parameters theta' of the last MAML-style call (fsmg_maml_forward_backward /
- *   _step / _eval, their _indexed forms, fsmg_maml_generate / _beam_search / _score), in the reference layout like fsmg_get_param;
+ *   _step / _eval, their _indexed and _masked forms, fsmg_maml_generate / _beam_search / _score), in the reference layout like fsmg_get_param;
  *   count must be rows*cols.  Needs fsmg_debug_set("keep_adapted", 1) before that call: FSMG_ERR_STATE if nothing has been kept */
 int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count);
 /* run-time knobs of a handle that used to be create-time environment variables (tests, diagnostics):
