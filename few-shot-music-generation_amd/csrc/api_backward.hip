@@ -92,6 +92,24 @@ int backward(fsmg_model* h, int B, int part) {
     const bool defer_ok = part == 0 && (cut || xov);
     if (part != 2) h->arena_off = 0;
     h->last_bwd_xcd = xcd;
+    // the merged dKx + dKh GEMM of layer l (see dk_gemm below) and whether the layer takes it
+    auto dk_merged_args = [&](int l, GemmArgs& m) -> bool {
+        const int in_p = h->in_dim[l];
+        if (l == 0) { m.A = h->P + h->off_emb; m.lda = h->Ep; m.gather = h->X; }
+        else { m.A = h->Hs[l - 1] + (size_t)B * Hp; m.lda = Hp; }
+        m.A2 = h->Hs[l]; m.lda2 = Hp; m.m_split = in_p;
+        m.B = h->Z[l]; m.ldb = G4; m.C = h->G + h->off_kx[l]; m.ldc = G4; m.M = in_p + Hp; m.N = G4; m.K = (int)rows;
+        m.colsum = h->G + h->off_b[l]; m.ksplit = 1;
+        return h->merge_dk && in_p % 256 == 0 && Hp % 4 == 0 && h->off_kh[l] == h->off_kx[l] + (int64_t)in_p * G4 &&
+               (l > 0 || 4LL * h->V1 * h->Ep < 0xfffff000LL) && 4LL * Hp * rows < 0xfffff000LL && 4LL * G4 * rows < 0xfffff000LL &&
+               (((uintptr_t)m.A | (uintptr_t)m.A2 | (uintptr_t)m.B) & 15) == 0 && gemm_dma_enabled() && use_h_gemm(h, OP_XC, OP_XC, m, mainl);
+    };
+    // Backward pair at hidden 512, one layer (fsmg_model::xov_dk_tail): the merged dK -- it reads dZ, the inputs and h, nothing of dW -- is
+    // prepared in front of the pair (its K split what gemm() would pick, its slabs in the arena) and its items are the tail of the work list
+    // that dW's clean-up launch drains behind the chain: no launch of its own, no kernel boundary between the two.
+    bool dk_tail = false;
+    GemmArgs gdk{};
+    QueuedSums dk_sums{};
     FillBatch fills(h);                     // embedding-gradient zero + the top layer's BPTT buffers: one launch
     OpBatch late(h);
     OpBatch late2(h);                       // tail_aside beside a 128-tile dK: the bottom layer's weight-gradient sums, on the main stream behind the join
@@ -119,9 +137,18 @@ int backward(fsmg_model* h, int B, int part) {
         HIPCK(h, hipEventRecord(h->ev_bucket[0], h->aux));
         h->bucket0_recorded = true;
     } else if (xov) {
-        GEMMCK(fills.add(h->xov_ctl + fsmg_model::XOV_CTL, 0u, 4 + gemm_items(gdw)));
+        int dk_split = 1, dk_items = 0;
+        if (h->xov_dk_tail != 0 && d_late != nullptr && h->L == 1 && Hp == 512 && dk_merged_args(0, gdk)) {
+            dk_split = pick_split(h->max_split, gdk.M, gdk.N, gdk.K, 256, true, 256);       // gemm()'s choice for it on the 256-tile kernel
+            dk_items = ((gdk.M + 255) / 256) * ((gdk.N + 255) / 256) * dk_split;
+            dk_tail = dk_split > 1 && gemm_pair_supported(gdw, gdk) && 4 + gemm_items(gdw) + dk_items <= fsmg_model::XOV_CTL;
+        }
+        GEMMCK(fills.add(h->xov_ctl + fsmg_model::XOV_CTL, 0u, 4 + gemm_items(gdw) + (dk_tail ? dk_items : 0)));     // dK's claim words behind dW's
         GEMMCK(fills.flush());                // (the queue words must be zero before the auxiliary stream forks)
         GEMMCK(dhout_chunk(h, mainl, B, 0, T, d_now));
+        // (arena order as without the tail: dH, dK, dx; the slab sums wait in dk_sums and enter `late` behind dW's.  No room: the two launches)
+        if (dk_tail) GEMMCK(gemm_prepare_queue(h, gdk, dk_split, d_late, &dk_tail, &dk_sums));
+        if (dk_tail) { h->joint_items[0] = gemm_items(gdw); h->joint_items[1] = gemm_items(gdk); }
         HIPCK(h, hipEventRecord(h->ev_fork, s));
         HIPCK(h, hipStreamWaitEvent(h->aux, h->ev_fork, 0));
         GEMMCK(gemm_restricted(h, h->aux, OP_XC, OP_XC, gdw, xov_first_free(B, Hp), h->xov_ctl + fsmg_model::XOV_CTL));
@@ -234,7 +261,10 @@ int backward(fsmg_model* h, int B, int part) {
         }
         if (xov && top) {                     // the rest of dW chip-wide, then the fixed-order slab sum
             ScopedTimer tm(h, "gemm_dw");
-            GEMMCK(gemm_cleanup(h, s, OP_XC, OP_XC, gdw, h->xov_ctl + fsmg_model::XOV_CTL));
+            // with dK's items behind dW's (dk_tail): dZ is complete and visible behind the chain's kernel boundary, which this launch is behind
+            if (dk_tail && h->xov_dk_tail == 2) {}        // (tests: what the restricted launch alone claimed)
+            else if (dk_tail) GEMMCK(gemm_cleanup_pair(h, s, gdw, gdk, h->xov_ctl + fsmg_model::XOV_CTL));
+            else GEMMCK(gemm_cleanup(h, s, OP_XC, OP_XC, gdw, h->xov_ctl + fsmg_model::XOV_CTL));
             HIPCK(h, hipStreamWaitEvent(s, h->ev_join, 0));
             if (dw_split > 1) {
                 const int64_t mn = (int64_t)gdw.M * gdw.N;
@@ -250,6 +280,7 @@ int backward(fsmg_model* h, int B, int part) {
                     h->bucket0_recorded = true;
                 }
             }
+            if (dk_tail) GEMMCK(gemm_queue_sums(&late, dk_sums));       // where dk_gemm would have queued them
         }
         if (pend_on) {                        // the rest of the waiting weight gradient chip-wide (its slab sums ride in `late`)
             ScopedTimer tm(h, "gemm_dk");
@@ -272,14 +303,7 @@ int backward(fsmg_model* h, int B, int part) {
                 // same rows: where the 256 x 256-tile kernel takes the shape they are ONE GEMM with a two-part A (GemmArgs::m_split) --
                 // one K split and one set of slabs instead of two (cfg-B: 63 MB of slabs instead of 100), no 128-tile launch for dKx
                 GemmArgs m{};
-                if (l == 0) { m.A = h->P + h->off_emb; m.lda = h->Ep; m.gather = h->X; }
-                else { m.A = h->Hs[l - 1] + (size_t)B * Hp; m.lda = Hp; }
-                m.A2 = h->Hs[l]; m.lda2 = Hp; m.m_split = in_p;
-                m.B = h->Z[l]; m.ldb = G4; m.C = h->G + h->off_kx[l]; m.ldc = G4; m.M = in_p + Hp; m.N = G4; m.K = (int)rows;
-                m.colsum = h->G + h->off_b[l]; m.ksplit = 1;
-                const bool merged = h->merge_dk && in_p % 256 == 0 && Hp % 4 == 0 && h->off_kh[l] == h->off_kx[l] + (int64_t)in_p * G4 &&
-                                    (l > 0 || 4LL * h->V1 * h->Ep < 0xfffff000LL) && 4LL * Hp * rows < 0xfffff000LL && 4LL * G4 * rows < 0xfffff000LL &&
-                                    (((uintptr_t)m.A | (uintptr_t)m.A2 | (uintptr_t)m.B) & 15) == 0 && gemm_dma_enabled() && use_h_gemm(h, OP_XC, OP_XC, m, mainl);
+                const bool merged = dk_merged_args(l, m);
                 if (merged && wait_for_chain != nullptr) {       // leave it to the queue beside the next chain
                     GEMMCK(gemm_prepare_queue(h, m, h->xov_dw_split, dk_defer, wait_for_chain));
                     if (*wait_for_chain) { pend = m; return FSMG_OK; }
@@ -325,7 +349,10 @@ int backward(fsmg_model* h, int B, int part) {
         // = nothing, so those passes keep the tail in line.
         bool dk_h = false;
         if (aside && l == 0) GEMMCK(dk_gemm(&dk_h));
-        if (aside && l == 0 && dk_h) {
+        if (dk_tail && l == 0) {              // dK ran in the clean-up launch behind the chain
+            GEMMCK(dx_gemm());
+            if (aside) GEMMCK(tail_kernels(s));
+        } else if (aside && l == 0 && dk_h) {
             GEMMCK(dk_gemm(nullptr));
             GEMMCK(dx_gemm());
             GEMMCK(tail_kernels(s));

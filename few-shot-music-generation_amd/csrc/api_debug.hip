@@ -60,6 +60,20 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
         for (int64_t i = 0; i < count && i < 4; ++i) host[i] = (float)h->gemm_kinds[i];
         return FSMG_OK;
     }
+    if (!std::strcmp(what, "xov_dk_tail")) {          // [0] the knob, [1] joint clean-up launches enqueued so far, [2] / [3] dW's / dK's items in the last one
+        const float v[4] = {(float)h->xov_dk_tail, (float)h->n_joint_launches, (float)h->joint_items[0], (float)h->joint_items[1]};
+        for (int64_t i = 0; i < count && i < 4; ++i) host[i] = v[i];
+        return FSMG_OK;
+    }
+    if (!std::strcmp(what, "xov_bwd_queue")) {        // the backward pair's queue words as the last pass left them: [0..1] draw counters, [2] stop, [3] unused, [4 ..] claim words
+        if (count > fsmg_model::XOV_CTL) return fail(h, FSMG_ERR_SIZE, "debug read larger than the buffer");
+        std::vector<int> w((size_t)count);
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        if (h->aux) HIPCK(h, hipStreamSynchronize(h->aux));
+        HIPCK(h, hipMemcpy(w.data(), h->xov_ctl + fsmg_model::XOV_CTL, sizeof(int) * count, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < count; ++i) host[i] = (float)w[(size_t)i];
+        return FSMG_OK;
+    }
     if (!std::strcmp(what, "xov_selfcheck")) {        // [0] passes that recomputed and compared the gated projection, [1] passes that took the XCD-partitioned order, [2] the period
         const float v[3] = {(float)h->xov_selfcheck_runs, (float)h->xov_passes, (float)h->xov_selfcheck_every};
         for (int64_t i = 0; i < count && i < 3; ++i) host[i] = v[i];

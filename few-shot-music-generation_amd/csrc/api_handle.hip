@@ -216,6 +216,7 @@ int fsmg_create(const fsmg_config* cfg, fsmg_handle* out) {
         if (const char* e = std::getenv("FSMG_XOV_PARTS")) h->xov_parts = std::max(1, std::min(7, std::atoi(e)));
         if (const char* e = std::getenv("FSMG_EAGER")) h->eager = (e[0] != '0');
         if (const char* e = std::getenv("FSMG_MERGE_DK")) h->merge_dk = (e[0] != '0');
+        if (const char* e = std::getenv("FSMG_XOV_DK_TAIL")) h->xov_dk_tail = (e[0] != '0') ? 1 : 0;
         if (const char* e = std::getenv("FSMG_UPD_SPLIT")) h->upd_split = (e[0] != '0');
         if (const char* e = std::getenv("FSMG_UPD_DEFER")) h->upd_defer = (e[0] != '0');
         if (const char* e = std::getenv("FSMG_TAIL_ASIDE")) h->tail_aside = (e[0] != '0');
@@ -462,6 +463,7 @@ int fsmg_debug_set(fsmg_handle h, const char* what, int64_t value) {
         }
     }
     else if (!std::strcmp(what, "tail_aside")) h->tail_aside = value != 0;
+    else if (!std::strcmp(what, "xov_dk_tail")) h->xov_dk_tail = value == 2 ? 2 : value != 0;     // 2: tests only (fsmg_model::xov_dk_tail)
     else if (!std::strcmp(what, "fused_softmax")) h->fused_softmax = value != 0;
     else if (!std::strcmp(what, "keep_adapted")) h->keep_adapted = value != 0;
     else if (!std::strcmp(what, "xov_selfcheck")) h->xov_selfcheck_left = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));

@@ -158,7 +158,7 @@ int gemm_restricted(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs
 }
 // A split-K GEMM for the work queue: slabs in the pass arena, the fixed-order slab sums (same order as gemm()'s) queued in `defer`;
 // the launches are the caller's (gemm_restricted beside a chain, gemm_cleanup behind it).  *ok = false: no room, nothing changed.
-int gemm_prepare_queue(fsmg_model* h, GemmArgs& g, int split, OpBatch* defer, bool* ok) {
+int gemm_prepare_queue(fsmg_model* h, GemmArgs& g, int split, OpBatch* defer, bool* ok, QueuedSums* hold) {
     *ok = false;
     const int S = std::max(1, std::min(std::min(split, MAX_SPLIT), g.K / 256));
     const int64_t mn = (int64_t)g.M * g.N;
@@ -170,15 +170,29 @@ int gemm_prepare_queue(fsmg_model* h, GemmArgs& g, int split, OpBatch* defer, bo
     g.C = slabs; g.c_slab = mn; g.ksplit = S; g.bx3 = 3;
     if (colsum) { g.colsum = cslabs; g.colsum_slab = g.N; }
     if (!xov_fits(g)) { h->arena_off -= need; g.C = C; g.colsum = colsum; g.ksplit = 1; return FSMG_OK; }
-    GEMMCK(defer->room(colsum ? 2 : 1));
-    GEMMCK(defer->reduce(slabs, mn, S, C, mn));
-    if (colsum) GEMMCK(defer->reduce(cslabs, g.N, S, colsum, g.N));
+    const QueuedSums q{slabs, colsum ? cslabs : nullptr, C, colsum, mn, S, g.N};
+    if (hold != nullptr) *hold = q;
+    else GEMMCK(gemm_queue_sums(defer, q));
     *ok = true;
+    return FSMG_OK;
+}
+int gemm_queue_sums(OpBatch* defer, const QueuedSums& q) {
+    GEMMCK(defer->room(q.colsum ? 2 : 1));
+    GEMMCK(defer->reduce(q.slabs, q.mn, q.S, q.C, q.mn));
+    if (q.colsum) GEMMCK(defer->reduce(q.cslabs, q.N, q.S, q.colsum, q.N));
     return FSMG_OK;
 }
 int gemm_cleanup(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs g, int* ctl) {
     g.bx3 = 3; g.xcd_first = -1; g.work = ctl; g.claim = ctl + 4;
     HIPCK(h, launch_gemm(h, s, amode, bmode, g, 0));
+    return FSMG_OK;
+}
+int gemm_cleanup_pair(fsmg_model* h, hipStream_t s, GemmArgs g0, GemmArgs g1, int* ctl) {
+    g0.bx3 = g1.bx3 = 3; g0.xcd_first = g1.xcd_first = -1; g0.work = ctl; g0.claim = ctl + 4;
+    g0.gate_err = h->d_err;                   // a chain that gave up: the step is skipped, nobody draws
+    HIPCK(h, launch_gemm_pair_cleanup(s, g0, g1));
+    ++h->gemm_kinds[3];                       // one launch of the 256 x 256-tile family
+    ++h->n_joint_launches;
     return FSMG_OK;
 }
 

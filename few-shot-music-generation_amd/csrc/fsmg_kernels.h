@@ -73,6 +73,15 @@ struct GemmArgs {
 };
 // amode/bmode in {OP_KC, OP_XC}. Supported combinations: (KC,XC) (XC,XC) (KC,KC)
 hipError_t launch_gemm(hipStream_t s, int amode, int bmode, const GemmArgs& g, int lds_pad = 0);
+// The clean-up launch of a work-queue GEMM g0 (XC x XC, 256 x 256 tiles, LDS-DMA staged) with the items of a second one, g1 (the same with a
+// two-part A, GemmArgs::m_split), as the tail of its list: joint item j < n0 is item j of g0, j >= n0 item j - n0 of g1.  g0.work[1] is the
+// draw counter, g0.claim[0 .. n0 + n1) the taken marks (zeroed by the caller; the restricted launch of g0 ALONE marks what it took in
+// [0, n0) and cannot draw from g1).  Blocks draw g1's items first, then what is left of g0's (k_gemm_bx3h_pair says why).  Ordered behind
+// everything either GEMM reads; g1's queue words are not used.
+// g0.gate_err != nullptr: a block that finds 2 there leaves before it draws.
+struct GemmPairArgs { GemmArgs g0, g1; int n0, n1; };
+bool gemm_pair_supported(const GemmArgs& g0, const GemmArgs& g1);
+hipError_t launch_gemm_pair_cleanup(hipStream_t s, const GemmArgs& g0, const GemmArgs& g1);
 // dynamic-LDS padding that caps a GEMM at `blocks_per_cu` resident blocks per CU
 int gemm_lds_pad_for(int blocks_per_cu);
 // resident 128x128 blocks the chip holds at once (256 CUs x blocks per CU): the split-K policy's slot count

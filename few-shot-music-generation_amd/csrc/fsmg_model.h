@@ -254,6 +254,13 @@ struct fsmg_model {
     // forward projection / dW: [0..1] draw counters, [2] stop flag, [3] items, [4 ..] claim words (gemm_restricted)
     static constexpr int XOV_CTL = 8192;
     int* xov_ctl = nullptr;             // [2][XOV_CTL]
+    // Backward pair, hidden 512, one layer: the merged dK's items are the tail of the work list dW's clean-up launch drains
+    // behind the BPTT chain -- ONE launch (k_gemm_bx3h_pair) where there were two with a kernel boundary in between; same K split, same
+    // slabs, same slab sums in the same order.  FSMG_XOV_DK_TAIL=0 / fsmg_debug_set("xov_dk_tail", 0): the two launches.
+    // 2 (tests only, gradients are WRONG): no clean-up launch at all, so that the claim words show what the restricted launch alone took
+    int xov_dk_tail = 1;
+    long long n_joint_launches = 0;     // joint clean-up launches enqueued, and the last one's item counts (fsmg_debug_read("xov_dk_tail"))
+    int joint_items[2] = {0, 0};
     int64_t slab_cap = 0;
     // whole-phase hipGraphs, keyed by the shape of the call; dropped when scratch moves
     std::map<std::string, hipGraphExec_t> graphs;
@@ -642,7 +649,12 @@ inline int gemm_items(const GemmArgs& g) { return ((g.M + 255) / 256) * ((g.N + 
 inline bool xov_fits(const GemmArgs& g) { return 4 + gemm_items(g) <= fsmg_model::XOV_CTL; }
 void choose_schedule(fsmg_model* h, int B, bool train = false);
 void xov_gate(fsmg_model* h, GemmArgs& g, int B);
-int gemm_prepare_queue(fsmg_model* h, GemmArgs& g, int split, OpBatch* defer, bool* ok);
+// hold != nullptr: the slab sums are described there instead of being queued in `defer` (the caller queues them later: gemm_queue_sums)
+struct QueuedSums { const float* slabs = nullptr; const float* cslabs = nullptr; float* C = nullptr; float* colsum = nullptr; int64_t mn = 0; int S = 0; int N = 0; };
+int gemm_prepare_queue(fsmg_model* h, GemmArgs& g, int split, OpBatch* defer, bool* ok, QueuedSums* hold = nullptr);
+int gemm_queue_sums(OpBatch* defer, const QueuedSums& q);
+// the clean-up launch of g0's queue with g1's items as its tail (GemmPairArgs); ctl: g0's queue words, 4 + both item counts of them zeroed
+int gemm_cleanup_pair(fsmg_model* h, hipStream_t s, GemmArgs g0, GemmArgs g1, int* ctl);
 int select_xcd_format(fsmg_model* h, int B);
 int gemm_restricted(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs g, int first, int* ctl);
 int gemm_cleanup(fsmg_model* h, hipStream_t s, int amode, int bmode, GemmArgs g, int* ctl);

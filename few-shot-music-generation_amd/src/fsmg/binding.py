@@ -1376,7 +1376,7 @@ class FsmgModel(object):
 
     def debug_set(self, what, value):
         """run-time knob of the handle (include/fsmg.h: chain_spin_limit, fallback_steps, persistent, eager, inplace_dlogits,
-        upd_split, upd_defer, xov_selfcheck, xov_selfcheck_fault, keep_adapted)"""
+        upd_split, upd_defer, xov_dk_tail, xov_selfcheck, xov_selfcheck_fault, keep_adapted)"""
         self._ck(self._lib.fsmg_debug_set(self._h, what.encode(), int(value)))
 
     def clock_begin(self, microseconds):

@@ -930,6 +930,12 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
  *                       and, alone among the reads, leaves a waiting half waiting
  *   "tail_aside"        1 (default): the bandwidth-bound tail of an eager backward pass (deferred slab sums, embedding gradient) on
  *                       the auxiliary stream beside the bottom layer's weight-gradient GEMM (bit-identical), 0: in line
+ *   "xov_dk_tail"       1 (default): XCD-partitioned order, hidden 512, one layer: the merged dKx + dKh GEMM's items are the tail of the work
+ *                       list that the projection weight gradient's clean-up launch drains behind the BPTT chain -- one launch instead of two
+ *                       (bit-identical), 0: two launches.  2 (tests only, the pass's gradients are NOT computed): no clean-up
+ *                       launch.  fsmg_debug_read("xov_dk_tail", 4) = [knob, joint launches enqueued, dW's items, dK's items of the last such
+ *                       pass]; fsmg_debug_read("xov_bwd_queue", n) = the backward pair's queue words as the last pass left them ([0..1] draw
+ *                       counters, [4 + i] claim word of joint item i: dW's items, then dK's)
  *   "xov_selfcheck"     XCD-partitioned order: the next `value` train passes recompute the gated projection on the serial path and
  *                       compare the words (default: the first 2 passes of a handle)
  *   "xov_selfcheck_fault" 1: the comparison runs against a buffer that is NOT the recomputed logits (tests of the recovery path)
