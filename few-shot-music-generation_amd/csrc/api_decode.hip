@@ -418,6 +418,17 @@ int fsmg_maml_generate_filtered_masked(fsmg_handle h, const fsmg_gen_config* g, 
                               [&] { return generate_core(h, g, f, primer, out_tokens, out_logprob); }, support_len, true);
 }
 
+// the adaptation by dynamic evaluation over the support stream; the generation at theta_l is fsmg_generate_filtered's
+int fsmg_dyneval_generate(fsmg_handle h, const fsmg_dyneval_config* cfg, const int32_t* support, const int32_t* support_len,
+                          int32_t n_support_rows, const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* primer,
+                          int32_t* out_tokens, float* out_logprob) {
+    if (!h) return FSMG_ERR_INVALID;
+    int rc = check_gen_config(h, g, primer, out_tokens);
+    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    if (rc != FSMG_OK) return rc;
+    return with_dyneval_theta(h, cfg, support, support_len, n_support_rows, [&] { return generate_core(h, g, f, primer, out_tokens, out_logprob); });
+}
+
 int fsmg_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_t* primer, int32_t* out_tokens, float* out_scores,
                      float* out_logprob) {
     if (!h) return FSMG_ERR_INVALID;

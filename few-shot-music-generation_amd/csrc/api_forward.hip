@@ -43,6 +43,13 @@ int reset_tok_table(fsmg_model* h) {
 // train: the pass ends in k_embed_grad, which wants the occurrence table of the input ids
 int token_prep(fsmg_model* h, int n_sup, int n_qry, bool train) {
     const bool table = train && h->tok_first != nullptr;
+    if (h->masked_call && h->window_call) {     // window pass: weights on [lo, e[b]) with (lo, hi) read on the device, fixed ids from e[b] on
+        HIPCK(h, launch_window_weights(h->stream, h->cur_len, n_sup + n_qry, h->T, h->d_win, h->roww, h->d_nvalid, h->d_elen, h->d_err));
+        HIPCK(h, launch_token_prep_len(h->stream, h->cur_sup, n_sup, h->cur_qry, n_qry, h->T, h->V, h->V,
+                                       h->X, h->Y, h->d_err, table ? h->tok_first : nullptr, table ? h->tok_count : nullptr, h->d_elen));
+        h->last_mask_groups = 1;
+        return FSMG_OK;
+    }
     if (h->masked_call) {      // padding-masked pass: the row weights + n_valid, and fixed ids behind every song's end
         HIPCK(h, launch_row_weights(h->stream, h->cur_len, n_sup + n_qry, h->T, h->mask_rpg, h->mask_groups, h->roww, h->d_nvalid, h->d_err));
         HIPCK(h, launch_token_prep_len(h->stream, h->cur_sup, n_sup, h->cur_qry, n_qry, h->T, h->V, h->V,

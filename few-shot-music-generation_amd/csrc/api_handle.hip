@@ -141,6 +141,7 @@ static void forget_turn(fsmg_model* h) {          // fsmg_destroy: nobody may wa
 int begin_call(fsmg_model* h, bool keep_pending) {
     HIPCK(h, hipSetDevice(h->device));
     h->masked_call = false;
+    h->window_call = false;
     const int rc = take_turn(h);
     if (rc != FSMG_OK) return rc;
     return keep_pending ? FSMG_OK : settle_pending(h);
@@ -361,6 +362,8 @@ int fsmg_destroy(fsmg_handle h) {
     if (h->khx) hipFree(h->khx);
     if (h->P_saved) hipFree(h->P_saved);
     if (h->P_adapted) hipFree(h->P_adapted);
+    if (h->dyn_stats) hipFree(h->dyn_stats);
+    if (h->dyn_out) hipFree(h->dyn_out);
     for (int* t : h->table) if (t) hipFree(t);
     for (int* t : h->table_len) if (t) hipFree(t);
     if (h->d_idx) hipFree(h->d_idx);

@@ -128,6 +128,7 @@ int ensure_scratch(fsmg_model* h, int B) {
     const int64_t o_arena = place(4 * std::max<int64_t>(arena_need, 64));
     const int64_t o_score = place(4 * 4 * rows);        // fsmg_score's four per-position outputs (last: nothing else moves)
     const int64_t o_len = place(4 * (int64_t)B), o_roww = place(4 * rows), o_nvalid = place(4 * std::max<int64_t>(B, 64));     // padding-masked passes
+    const int64_t o_win = place(16), o_elen = place(4 * (int64_t)B);      // window passes (dynamic evaluation)
     hipError_t e = hipMalloc((void**)&h->scratch, off);
     if (e != hipSuccess) {
         h->Bcap = 0;
@@ -161,6 +162,7 @@ int ensure_scratch(fsmg_model* h, int B) {
     h->slabs2 = (float*)(s + o_slab2); h->colsum_slabs2 = (float*)(s + o_cslab2);
     h->score_out = (float*)(s + o_score);
     h->d_len = (int*)(s + o_len); h->roww = (float*)(s + o_roww); h->d_nvalid = (int*)(s + o_nvalid);
+    h->d_win = (int*)(s + o_win); h->d_elen = (int*)(s + o_elen);
     h->arena = (float*)(s + o_arena); h->arena_cap = arena_need; h->arena_off = 0;
     h->Bcap = B;
     return FSMG_OK;

@@ -40,7 +40,7 @@ int forward_backward_core(fsmg_model* h, int32_t N, int32_t K, int32_t Q, Stage&
     const int n_sup = N * K, n_qry = N * Q;
     h->bucket0_recorded = false;
     // (a padding-masked pass has launches of its own -- the row weights, the weighted cross entropy, the masked loss: its own graphs)
-    const std::string shape_key = std::to_string(n_sup) + ":" + std::to_string(n_qry) + (h->masked_call ? ":m" : "");
+    const std::string shape_key = std::to_string(n_sup) + ":" + std::to_string(n_qry) + (h->masked_call ? (h->window_call ? ":w" : ":m") : "");      // (a window pass: the weights' kernel differs)
     if (h->dp_split && !with_update) {
         // episode-parallel order: bucket 0 (softmax gradients, 56 % of the bytes at cfg-B) is final when the first graph ends and
         // travels while the second one (BPTT, weight / input gradients, embedding gradient) runs
@@ -548,6 +548,24 @@ static int adapt_flag(fsmg_handle h) {
 }  // extern "C"
 
 namespace fsmg_host {
+// masked_rows_pass over host rows with the loss window [lo, hi) (dynamic evaluation): the window is written to its fixed
+// address in stream order before the pass, outside any capture, so a replayed graph reads the window of THIS call
+int window_rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t n, int lo, int hi) {
+    BEGIN_CALL(h, true);
+    begin_masked(h, n, 1);
+    h->window_call = true;
+    const int rc = forward_backward_core(h, 1, n, 0, [&]() {
+        int r = stage_tokens(h, rows, n, rows, 0, 0);
+        if (r == FSMG_OK) r = stage_lengths(h, len, n, len, 0, 0);
+        if (r == FSMG_OK) HIPCK(h, launch_set_window(h->stream, h->d_win, lo, hi));
+        return r;
+    });
+    h->masked_call = false;
+    h->window_call = false;
+    return rc;
+}
+int pass_flag(fsmg_model* h) { return adapt_flag(h); }
+
 // adapt on the support rows like fsmg_maml_eval, run the body at theta', restore theta whatever happened; one repeat on per-step
 // launches when the adaptation ran garbage (skipped) steps.  The MAML decode entry points (api_decode.hip) run through here.
 int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,

@@ -381,6 +381,30 @@ constexpr int ADAM_CHUNK4 = 512;                  // float4 per drawn chunk: two
 hipError_t launch_adam_update(hipStream_t s, const UpdateArgs& a);
 // p <- p - a.lr * clip_by_global_norm(g): the inner-loop step of cfg-E (m, v, step, n_decay, grad_scale unused)
 hipError_t launch_sgd_update(hipStream_t s, const UpdateArgs& a);
+
+// ---------------------------------------------------------------- dynamic evaluation (dyneval.hip)
+// win[0..1] = (lo, hi): the window the next window pass reads from its fixed address
+hipError_t launch_set_window(hipStream_t s, int* win, int lo, int hi);
+// launch_row_weights with the window [win[0], win[1]) and one group of B rows: e[b] = min(hi, len[b]), *n_valid = sum_b max(0, e[b] - lo),
+// w[t * B + b] = lo <= t < e[b] ? (float)(1 / ((double)n_valid + 1e-12)) : 0, elen[b] = e[b] (the length launch_token_prep_len is given)
+hipError_t launch_window_weights(hipStream_t s, const int* len, int B, int T, const int* win, float* w, int* n_valid, int* elen, int* err_flag);
+// out[(row0 + b) * T + t] = -ce[t * B + b] for the positions with w[t * B + b] != 0; nothing else is written
+hipError_t launch_dyneval_collect(hipStream_t s, const float* ce, const float* w, int B, int T, long long row0, float* out);
+// theta_l <- theta_l - lr c g [/ (sqrt(ms / count) + eps)] + decay (theta_g - theta_l) [min(1 / decay, sqrt(ms / count) / *mean_rms)]
+// c = clip > 0 ? clip / max(gnorm, clip) : 1 from the partials / tail as launch_sgd_update derives gnorm; no update when *err_flag != 0
+// or tail[2..5] != 0.  decay == 0: no pull-back term (pg unread); rms == 0: ms / mean_rms unread.  n a multiple of 4.
+struct DynUpdateArgs {
+    float* p; const float* pg; const float* g; const float* ms; long long n;
+    const double* partials; int n_partials; const float* tail; int use_slices;
+    int rms; float lr, decay, eps, clip, count; const float* mean_rms;
+    float* gnorm_out; const int* err_flag;
+};
+hipError_t launch_dyneval_update(hipStream_t s, const DynUpdateArgs& a);
+// ms[i] <- ms[i] + g[i] * g[i] (fp32, two roundings), n a multiple of 4
+hipError_t launch_dyneval_accumulate(hipStream_t s, float* ms, const float* g, long long n);
+// *out = (float)(sum_i sqrt((double)ms[i] / count) / n_logical): fp64, fixed order; partials holds dyneval_rms_blocks(n) doubles
+int dyneval_rms_blocks(long long n);
+hipError_t launch_dyneval_mean_rms(hipStream_t s, const float* ms, long long n, long long count, long long n_logical, double* partials, float* out);
 // last kernel of a train step: counts the step (ring[step % cap] = loss, ++step) or, when *err_flag != 0 or the
 // all-reduced time-out indicator tail[2] is set, tallies it in counters ([0] time-outs, [1] token-range rejections;
 // host-mapped memory) and clears the flag

@@ -161,6 +161,17 @@ struct fsmg_model {
     bool masked_call = false;           // the call in progress is a masked one (begin_call clears it, the masked entry points set it)
     int mask_rpg = 0, mask_groups = 0;  // rows per group / groups of the masked pass in progress
     int last_mask_groups = 0;           // ... and of the last one that ran (fsmg_debug_read("n_valid"))
+    // dynamic evaluation (fsmg_dyneval_*): a window pass is a masked pass whose weights come from launch_window_weights
+    bool window_call = false;           // the masked pass in progress is a window pass (begin_call clears it)
+    int* d_win = nullptr;               // [4] (lo, hi, -, -) at a fixed address in the scratch: a captured window pass replays with the next window
+    int* d_elen = nullptr;              // [Bcap] e[b] = min(hi, len[b]) of the window pass in flight
+    char* dyn_stats = nullptr;          // the gradient statistics, one allocation on first use: [ms_sum | rms partials | mean_rms]
+    float* dyn_ms = nullptr;            // [n_flat] running sum of g * g, pads exact zeros
+    double* dyn_part = nullptr;
+    float* d_mean_rms = nullptr;
+    int64_t dyn_count = 0;              // accumulated passes
+    bool dyn_rms_dirty = true;          // ms_sum or count changed since d_mean_rms was computed
+    float* dyn_out = nullptr; int64_t dyn_out_cap = 0;      // [R][T] scores of the call in progress
     int* d_gather_len = nullptr;        // ... and their lengths (the masked forms; grown and freed with d_gather)
     int* d_gather = nullptr; int64_t gather_cap = 0;     // episode rows gathered from a table for the MAML-style step (its two passes take device token buffers)
     // XCD-local recurrence (lstm_xcd.hip; hidden size 512): per layer the forward and backward register images of K_h,
@@ -695,6 +706,16 @@ inline bool is_retry(int rc) { return rc == FSMG_ERR_TIMEOUT || rc == FSMG_ERR_S
 int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
                        int32_t support_on_device, const std::function<int()>& at_theta_prime, const int32_t* support_len = nullptr,
                        bool masked = false);      // masked: every inner step over the positions t < support_len[b] only
+// api_step.hip, for the dynamic-evaluation driver (api_dyneval.hip): one window pass -- forward + backward over `rows` [n][T] with their
+// lengths, weights on [lo, min(hi, len[b])) only -- and the read-back of the error word the passes so far have left (cleared; a
+// time-out switches the handle to per-step launches and is reported as FSMG_ERR_TIMEOUT)
+int window_rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t n, int lo, int hi);
+int pass_flag(fsmg_model* h);
+int validate_shape(fsmg_model* h, int N, int K, int Q);
+// api_dyneval.hip: adapt on the support stream by dynamic evaluation (nothing reported), run `at_theta_l` there, restore theta whatever
+// happened -- with_adapted_theta's twin (fsmg_dyneval_generate, api_decode.hip)
+int with_dyneval_theta(fsmg_model* h, const fsmg_dyneval_config* c, const int32_t* support, const int32_t* support_len, int32_t n_support_rows,
+                       const std::function<int()>& at_theta_l);
 int poll_skipped(fsmg_model* h);
 int report(fsmg_model* h, int what);
 int check_tokens_and_read(fsmg_model* h, const float* d_src, float scale, float* host_out, int n, bool train_tail = false);

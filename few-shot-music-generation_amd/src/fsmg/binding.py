@@ -121,6 +121,15 @@ class FsmgCacheSelfConfig(C.Structure):
     _fields_ = [('version', C.c_int32), ('window', C.c_int32), ('reserved', C.c_int32 * 14)]
 
 
+DYNEVAL_RULES = {'sgd': 0, 'rms': 1}
+
+
+class FsmgDynevalConfig(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('rule', C.c_int32), ('seg_len', C.c_int32), ('rows_per_step', C.c_int32),
+                ('lr', C.c_float), ('decay', C.c_float), ('eps', C.c_float), ('clip_norm', C.c_float),
+                ('adapt_reported', C.c_int32), ('reserved', C.c_int32)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -252,6 +261,16 @@ SIGNATURES = {
     'fsmg_timing_select': (C.c_int, [_P, C.c_char_p]),
     'fsmg_timing_read': (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'fsmg_timing_reset': (C.c_int, [_P]),
+    'fsmg_dyneval_stats_reset': (C.c_int, [_P]),
+    'fsmg_dyneval_stats_accumulate': (C.c_int, [_P]),
+    'fsmg_dyneval_stats_info': (C.c_int, [_P, C.POINTER(C.c_int64), _F32P]),
+    'fsmg_dyneval_stats_get': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
+    'fsmg_dyneval_stats_set': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
+    'fsmg_dyneval_stats_set_count': (C.c_int, [_P, C.c_int64]),
+    'fsmg_dyneval_score': (C.c_int, [_P, C.POINTER(FsmgDynevalConfig), _P, _P, C.c_int32, C.c_int32, _F32P, _F32P, _F32P]),
+    'fsmg_dyneval_eval_step': (C.c_int, [_P, C.POINTER(FsmgDynevalConfig), _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _F32P]),
+    'fsmg_dyneval_generate': (C.c_int, [_P, C.POINTER(FsmgDynevalConfig), _P, _P, C.c_int32, C.POINTER(FsmgGenConfig),
+                                        C.POINTER(FsmgGenFilters), _P, _I32P, _F32P]),
 }
 
 _lib = None
@@ -1354,6 +1373,97 @@ class FsmgModel(object):
                                                         k.shape[1], g.ctypes.data_as(_I32P) if g is not None else None,
                                                         _f32p(out['cache_prob']), _f32p(out['logprob']), _f32p(out['lse'])))
         return out
+
+    # -- dynamic evaluation (include/fsmg.h "dynamic evaluation") --------------------------------------------------
+    @staticmethod
+    def dyneval_config(rule='sgd', seg_len=1, rows_per_step=1, lr=0.0, decay=0.0, eps=1e-3, clip_norm=0.0, adapt_reported=True):
+        """the fsmg_dyneval_config struct; rule: 'sgd' / 'rms' (or the enum value)"""
+        if rule not in DYNEVAL_RULES and rule not in DYNEVAL_RULES.values():
+            raise ValueError("rule must be 'sgd' or 'rms', got %r" % (rule,))
+        return FsmgDynevalConfig(struct_size=C.sizeof(FsmgDynevalConfig), rule=DYNEVAL_RULES.get(rule, rule), seg_len=int(seg_len),
+                                 rows_per_step=int(rows_per_step), lr=float(lr), decay=float(decay), eps=float(eps),
+                                 clip_norm=float(clip_norm), adapt_reported=int(bool(adapt_reported)), reserved=0)
+
+    def _dyn_cfg(self, cfg):
+        return cfg if isinstance(cfg, FsmgDynevalConfig) else self.dyneval_config(**cfg)
+
+    @staticmethod
+    def _opt_len(lengths, count):
+        """optional host lengths of `count` rows -> (pointer or None, keepalive)"""
+        if lengths is None:
+            return None, None
+        a = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        if a.size != count:
+            raise ValueError('%d lengths for %d sequences' % (a.size, count))
+        return C.c_void_p(a.ctypes.data), a
+
+    def dyneval_stats_reset(self):
+        self._ck(self._lib.fsmg_dyneval_stats_reset(self._h))
+
+    def dyneval_stats_accumulate(self):
+        """ms_sum += g * g of the gradient the last forward_backward* left; count += 1"""
+        self._ck(self._lib.fsmg_dyneval_stats_accumulate(self._h))
+
+    def dyneval_stats_info(self):
+        """-> (count, mean_rms)"""
+        count, mean = C.c_int64(), C.c_float()
+        self._ck(self._lib.fsmg_dyneval_stats_info(self._h, C.byref(count), C.byref(mean)))
+        return int(count.value), float(mean.value)
+
+    def dyneval_stats_get(self, name):
+        out = np.empty(self._shape(name), np.float32)
+        self._ck(self._lib.fsmg_dyneval_stats_get(self._h, name.encode(), _f32p(out), out.size))
+        return out
+
+    def dyneval_stats_set(self, name, value):
+        a = np.ascontiguousarray(value, dtype=np.float32)
+        self._ck(self._lib.fsmg_dyneval_stats_set(self._h, name.encode(), _f32p(a), a.size))
+
+    def dyneval_stats_set_count(self, count):
+        self._ck(self._lib.fsmg_dyneval_stats_set_count(self._h, int(count)))
+
+    def dyneval_score(self, cfg, tokens, lengths=None, first_reported=0):
+        """one stream: tokens int32 [R, max_len], lengths int32 [R] or None, rows [first_reported, R) reported
+        -> dict(logprob float32 [R, max_len], row_nll float32 [R], nll float)"""
+        c = self._dyn_cfg(cfg)
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        if t.ndim != 2 or t.shape[1] != self.max_len:
+            raise ValueError('tokens %r do not match [R, max_len=%d]' % (t.shape, self.max_len))
+        lp_, _keep = self._opt_len(lengths, t.shape[0])
+        lp = np.empty(t.shape, np.float32)
+        row = np.empty(t.shape[0], np.float32)
+        nll = C.c_float()
+        self._ck(self._lib.fsmg_dyneval_score(self._h, C.byref(c), C.c_void_p(t.ctypes.data), lp_, t.shape[0], int(first_reported),
+                                              _f32p(lp), _f32p(row), C.byref(nll)))
+        return dict(logprob=lp, row_nll=row, nll=float(nll.value))
+
+    def dyneval_eval_step(self, cfg, support, query, support_len=None, query_len=None):
+        """support [N,K,T], query [N,Q,T] int32, optional lengths [N,K] / [N,Q] -> the NLL over all artists' scored query positions"""
+        c = self._dyn_cfg(cfg)
+        n, k, q = self._episode_shape(support, query, None)
+        s = np.ascontiguousarray(support, dtype=np.int32)
+        qq = np.ascontiguousarray(query, dtype=np.int32)
+        sl, _k1 = self._opt_len(support_len, n * k)
+        ql, _k2 = self._opt_len(query_len, n * q)
+        nll = C.c_float()
+        self._ck(self._lib.fsmg_dyneval_eval_step(self._h, C.byref(c), C.c_void_p(s.ctypes.data), C.c_void_p(qq.ctypes.data), sl, ql,
+                                                  n, k, q, C.byref(nll)))
+        return float(nll.value)
+
+    def dyneval_generate(self, cfg, support, num, support_len=None, n_seq=1, temperature=1.0, top_k=0, seed=0, primer=None,
+                         logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0):
+        """adapt on the support stream [rows, max_len] by dynamic evaluation, generate at theta_l, restore theta"""
+        c = self._dyn_cfg(cfg)
+        s = np.ascontiguousarray(support, dtype=np.int32).reshape(-1, self.max_len)
+        sl, _k1 = self._opt_len(support_len, s.shape[0])
+        g, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
+        f = self.gen_filters(top_p, min_p, repetition_penalty, repeat_window)
+        toks = np.empty((int(n_seq), int(num)), np.int32)
+        lp = np.empty((int(n_seq), int(num)), np.float32) if logprobs else None
+        self._ck(self._lib.fsmg_dyneval_generate(self._h, C.byref(c), C.c_void_p(s.ctypes.data), sl, s.shape[0], C.byref(g),
+                                                 C.byref(f) if f is not None else None, pp, toks.ctypes.data_as(_I32P),
+                                                 _f32p(lp) if logprobs else None))
+        return (toks, lp) if logprobs else toks
 
     def read_losses(self, n):
         out = np.empty(n, np.float32)

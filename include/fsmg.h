@@ -840,6 +840,92 @@ int fsmg_cache_self_score_masked(fsmg_handle h, fsmg_cache cache, const fsmg_cac
 int fsmg_cache_eval_step_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len,
                                 const int32_t* query_len, int32_t N, int32_t K, int32_t Q, float theta, float lambda, float* nll);
 
+/* ---- dynamic evaluation (Krause et al., "Dynamic evaluation of neural sequence models", arXiv 1709.07432): the model
+ * adapts on the songs it scores.  While it reads a stream of songs it takes a small gradient step on every segment it has just
+ * scored, pulled back towards the trained parameters theta by a decay term and, under the RMS rule, scaled per parameter by gradient
+ * statistics collected once on training data.  Every reported position is scored BEFORE the model has adapted on it.
+ *
+ * A stream is an ordered list of n_rows rows `tokens` [n_rows][T] (host int32, one song per row, T = max_len) with optional host
+ * `lengths` [n_rows] (NULL: every row has T positions).  Rows [0, first_reported) adapt only; rows [first_reported, n_rows) are
+ * reported.  Rows are consumed in blocks: block boundaries stand at every multiple of rows_per_step, at first_reported (a block is
+ * never half reported) and at n_rows.  A block of rows is walked in windows [lo, hi) = [i S, min((i + 1) S, T)), S = seg_len,
+ * i = 0, 1, ...  theta_l starts as a copy of theta; theta_g is the saved copy of theta.  Per (block, window), with
+ * e[b] = min(hi, len[b]) and n_valid = sum_b max(0, e[b] - lo):
+ *   1. n_valid == 0: the window is skipped -- no pass, no update.
+ *   2. One forward + backward over the block's rows from position 0, zero initial state, at the current theta_l.  Position t of row
+ *      b carries the weight fl32(1 / ((double)n_valid + 1e-12)) iff lo <= t < e[b], else an exact 0;
+ *      loss = sum of ce over the weighted positions / (n_valid + 1e-12).  Inputs at t < lo are the real tokens (the window's context:
+ *      BPTT runs through them); positions t >= e[b] get fixed ids (input: the start word, target: 0), so whatever the caller put
+ *      behind a song's end never matters, exactly.
+ *   3. A reported block: out_logprob[row][t] = -ce of the weighted positions of this window -- the score under the parameters BEFORE
+ *      this window's update.  Every other element of out_logprob is 0.
+ *   4. The update, g = the gradient of that pass, c = clip_norm > 0 ? clip_norm / max(gnorm, clip_norm) : 1 with gnorm by the handle's
+ *      norm convention (fsmg_config.clip_norm_mode), derived as the MAML inner step derives it:
+ *        FSMG_DYNEVAL_SGD: theta_l <- theta_l - lr c g + decay (theta_g - theta_l)
+ *        FSMG_DYNEVAL_RMS: theta_l <- theta_l - lr c g / (sqrt(MS) + eps) + decay (theta_g - theta_l) min(1 / decay, sqrt(MS) / mean_rms)
+ *      MS = ms_sum / count per parameter (the statistics below); mean_rms = the mean of sqrt(MS) over the logical elements of the
+ *      fsmg_num_params tensors (pad elements of the flat buffer are not counted).  decay == 0: the last term is absent.
+ *      adapt_reported == 0: a reported block is scored with ONE window [0, T) and no update.
+ *   5. Pads stay exact zeros (g, theta_g and ms_sum are 0 there; eps > 0 is required for RMS).
+ * On return, whatever happened: theta is back, bitwise; the Adam slots and global_step are untouched; no gradient is pending
+ * (fsmg_apply_update returns FSMG_ERR_STATE); a handle with a communicator has made no collective call.
+ * out_row_nll [n_rows]: for a reported row minus the fp64 sum of the row's out_logprob in position order, rounded once, computed on
+ * the host from the returned array (0 for a row that only adapts); out_nll = minus the fp64 sum of every reported row's out_logprob in (row, position) order, divided by
+ * the count of scored positions, rounded once (NaN when nothing is reported).  out_logprob [n_rows][T] holds zeros in the rows that
+ * only adapt.  Any output pointer may be NULL.
+ * A persistent kernel's time-out anywhere puts theta back and repeats the whole call once on per-step launches, as fsmg_maml_eval does.
+ *
+ * DELIBERATE DIFFERENCE from the paper, which carries the hidden state across segments and truncates BPTT at the segment start: here
+ * every window's pass recomputes the prefix [0, lo) at the current theta_l from the zero state and differentiates through it.  The
+ * library's passes start from the zero state, songs are at most max_len positions, and this variant is exactly differentiable (it has
+ * a plain fp64 restatement: tests/dyneval_ref.py).  Its cost is ceil(T / S) full passes per block.  A carried initial state is not
+ * offered.
+ *
+ * Statistics: ms_sum (one float per parameter element, fsmg_get_param's layout) and count.  fsmg_dyneval_stats_accumulate adds g * g
+ * (fp32: ms_sum <- ms_sum + g * g, two roundings) of the gradient the last fsmg_forward_backward* call left and increments count;
+ * FSMG_ERR_STATE without a pending gradient or when that pass was skipped on the device.  _reset zeroes both.  _get / _set move one
+ * tensor's ms_sum (count = rows * cols; _set refuses a negative or non-finite value), _set_count sets count (>= 0), _info returns
+ * count and mean_rms (0 while count == 0), recomputed on the device in a fixed order whenever the statistics have changed.
+ *
+ * fsmg_dyneval_eval_step: per artist n of the episode (support [N][K][T], query [N][Q][T], lengths [N][K] / [N][Q], either may be
+ * NULL) a fresh theta_l and the stream (support rows of n, then query rows of n) with first_reported = K; *nll = minus the fp64 sum of
+ * all artists' reported log-probs in (artist, row, position) order over the count of scored query positions, rounded once.
+ * fsmg_dyneval_generate: adapts on the support stream (n_support_rows rows, nothing reported), runs what fsmg_generate_filtered runs at
+ * theta_l (filters may be NULL), then restores theta.
+ *
+ * Errors, all before any device work and with nothing touched: FSMG_ERR_INVALID for a NULL handle / config / tokens, struct_size not
+ * sizeof(fsmg_dyneval_config), nonzero reserved, rule not SGD / RMS, seg_len outside [1, T], rows_per_step outside [1, 2^20] (a pass's
+ * capacity; the activation scratch grows on demand), lr negative or not finite, decay outside [0, 1], eps not > 0 or not finite (RMS),
+ * clip_norm negative or not finite, adapt_reported not 0 / 1, n_rows outside [1, 2^20], first_reported outside [0, n_rows], a length
+ * outside [1, T], K < 1 or Q < 1 (eval_step), what fsmg_generate_filtered refuses (generate); FSMG_ERR_TOKEN_RANGE for a token outside
+ * [0, input_size); FSMG_ERR_STATE for RMS with count == 0.  Host tokens and lengths only. */
+enum { FSMG_DYNEVAL_SGD = 0, FSMG_DYNEVAL_RMS = 1 };
+typedef struct {
+    int32_t struct_size;      /* sizeof(fsmg_dyneval_config), else FSMG_ERR_INVALID  */
+    int32_t rule;             /* FSMG_DYNEVAL_SGD / FSMG_DYNEVAL_RMS                  */
+    int32_t seg_len;          /* S in [1, T]                                          */
+    int32_t rows_per_step;    /* rows per block, >= 1                                 */
+    float lr;
+    float decay;              /* in [0, 1]                                            */
+    float eps;                /* > 0 for RMS                                          */
+    float clip_norm;          /* 0: no clipping                                       */
+    int32_t adapt_reported;   /* 1: adapt on the reported rows too (after scoring)    */
+    int32_t reserved;         /* 0                                                    */
+} fsmg_dyneval_config;
+int fsmg_dyneval_stats_reset(fsmg_handle h);
+int fsmg_dyneval_stats_accumulate(fsmg_handle h);
+int fsmg_dyneval_stats_info(fsmg_handle h, int64_t* count, float* mean_rms);
+int fsmg_dyneval_stats_get(fsmg_handle h, const char* name, float* sum, int64_t n);
+int fsmg_dyneval_stats_set(fsmg_handle h, const char* name, const float* sum, int64_t n);
+int fsmg_dyneval_stats_set_count(fsmg_handle h, int64_t count);
+int fsmg_dyneval_score(fsmg_handle h, const fsmg_dyneval_config* cfg, const int32_t* tokens, const int32_t* lengths, int32_t n_rows,
+                       int32_t first_reported, float* out_logprob, float* out_row_nll, float* out_nll);
+int fsmg_dyneval_eval_step(fsmg_handle h, const fsmg_dyneval_config* cfg, const int32_t* support, const int32_t* query,
+                           const int32_t* support_len, const int32_t* query_len, int32_t N, int32_t K, int32_t Q, float* nll);
+int fsmg_dyneval_generate(fsmg_handle h, const fsmg_dyneval_config* cfg, const int32_t* support, const int32_t* support_len,
+                          int32_t n_support_rows, const fsmg_gen_config* gen_config, const fsmg_gen_filters* filters,
+                          const int32_t* primer, int32_t* out_tokens, float* out_logprob);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
