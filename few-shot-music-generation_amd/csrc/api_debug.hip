@@ -89,6 +89,10 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
         if (!h->have_adapted) return fail(h, FSMG_ERR_STATE, "no adapted parameters kept: fsmg_debug_set(\"keep_adapted\", 1), then a MAML-style call");
         return download_tensor(h, h->P_adapted, what + 8, host, count);
     }
+    if (!std::strncmp(what, "msgd_sum:", 9)) {        // S of the last train-form adaptation with Meta-SGD enabled, reference layout like fsmg_get_param
+        if (!h->msgd_state) return fail(h, FSMG_ERR_STATE, "no Meta-SGD state: fsmg_msgd_enable first");
+        return download_tensor(h, h->msgd_S, what + 9, host, count);
+    }
     if (!std::strcmp(what, "logits")) { src = h->logits; cap = rows * h->V1p; }
     else if (!std::strcmp(what, "dlogits")) { src = dlogits_buf(h); cap = rows * h->V1p; }
     else if (!std::strcmp(what, "lse")) { src = h->lse; cap = rows; }

@@ -364,6 +364,7 @@ int fsmg_destroy(fsmg_handle h) {
     if (h->P_adapted) hipFree(h->P_adapted);
     if (h->dyn_stats) hipFree(h->dyn_stats);
     if (h->dyn_out) hipFree(h->dyn_out);
+    if (h->msgd_state) hipFree(h->msgd_state);
     for (int* t : h->table) if (t) hipFree(t);
     for (int* t : h->table_len) if (t) hipFree(t);
     if (h->d_idx) hipFree(h->d_idx);

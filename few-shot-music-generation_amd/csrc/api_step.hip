@@ -74,6 +74,7 @@ int forward_backward_core(fsmg_model* h, int32_t N, int32_t K, int32_t Q, Stage&
     }
     h->lastB = B;
     h->have_grads = !with_update;
+    h->msgd_pending = false;            // (a rate gradient belongs to the pass it was formed from: msgd_rate_gradient sets it behind the query pass)
     return FSMG_OK;
 }
 
@@ -255,7 +256,11 @@ int fsmg_apply_update(fsmg_handle h, float grad_scale, float* loss) {
     if (!h->have_grads) return fail(h, FSMG_ERR_STATE, "fsmg_apply_update without a preceding fsmg_forward_backward");
     if (!(grad_scale > 0.f)) return fail(h, FSMG_ERR_INVALID, "grad_scale must be > 0");
     uint32_t bits; std::memcpy(&bits, &grad_scale, 4);
-    int rc = run_graphed(h, "up:" + std::to_string(bits) + (h->last_bwd_xcd ? "x" : "s"), [&]() -> int { return apply_update(h, grad_scale); });
+    // a pending Meta-SGD rate gradient: the rates' two launches ride in the update (a graph of its own; fsmg_msgd_enable drops the graphs)
+    const bool rates = msgd_rates_due(h);
+    int rc = run_graphed(h, (rates ? "upr:" : "up:") + std::to_string(bits) + (h->last_bwd_xcd ? "x" : "s"),
+                         [&]() -> int { return apply_update(h, grad_scale, false, rates); });
+    h->msgd_pending = false;
     if (rc != FSMG_OK) return rc;
     return after_update(h, grad_scale, loss);
 }
@@ -326,13 +331,15 @@ static int masked_rows_pass(fsmg_handle h, const int32_t* rows, const int32_t* l
 }
 
 // support_len != nullptr: every inner step's loss over the positions inside a song only (masked_rows_pass)
+// train: the adaptation of a train form -- with Meta-SGD enabled S starts from zero and collects every applied step
 static int maml_adapt(fsmg_handle h, const int32_t* support, int32_t N, int32_t K, int32_t inner_steps, float inner_lr, int32_t on_device,
-                      const int32_t* support_len = nullptr) {
+                      const int32_t* support_len = nullptr, bool train = false) {
     int rc = save_theta(h);
+    if (rc == FSMG_OK && h->msgd_on && train) rc = msgd_begin_sum(h);
     for (int i = 0; rc == FSMG_OK && i < inner_steps; ++i) {
         rc = support_len ? masked_rows_pass(h, support, support_len, N, K, on_device)
                          : fsmg_forward_backward(h, support, support, N, K, 0, on_device);       // support rows only
-        if (rc == FSMG_OK) rc = sgd_update(h, inner_lr);
+        if (rc == FSMG_OK) rc = h->msgd_on ? msgd_inner_update(h, inner_lr, train) : sgd_update(h, inner_lr);
     }
     return rc;
 }
@@ -342,8 +349,9 @@ int fsmg_maml_forward_backward(fsmg_handle h, const int32_t* support, const int3
     if (!h || !support || !query) return FSMG_ERR_INVALID;
     if (inner_steps < 0 || inner_steps > 64 || !(inner_lr >= 0.f) || K <= 0 || Q <= 0) return fail(h, FSMG_ERR_INVALID, "bad inner_steps / inner_lr / K / Q");
     BEGIN_CALL(h);
-    int rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, tokens_on_device);
+    int rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, tokens_on_device, nullptr, true);
     if (rc == FSMG_OK) rc = fsmg_forward_backward(h, query, query, N, Q, 0, tokens_on_device);     // query rows at theta'
+    if (rc == FSMG_OK && h->msgd_on) rc = msgd_rate_gradient(h);
     const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
     int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;                                               // theta comes back whatever happened
     if (rc2 == FSMG_OK) rc2 = rc_keep;
@@ -377,8 +385,9 @@ static int validate_maml_masked_args(fsmg_handle h, const int32_t* support, cons
 
 static int maml_forward_backward_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
                                         int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t on_device) {
-    int rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, on_device, support_len);
+    int rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, on_device, support_len, true);
     if (rc == FSMG_OK) rc = masked_rows_pass(h, query, query_len, N, Q, on_device);                  // query rows at theta'
+    if (rc == FSMG_OK && h->msgd_on) rc = msgd_rate_gradient(h);
     const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
     int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;                                               // theta comes back whatever happened
     if (rc2 == FSMG_OK) rc2 = rc_keep;

@@ -66,7 +66,7 @@ int ensure_cs(fsmg_model* h) {
     return FSMG_OK;
 }
 
-int apply_update(fsmg_model* h, float grad_scale, bool may_defer) {
+int apply_update(fsmg_model* h, float grad_scale, bool may_defer, bool with_rates) {
     ScopedRange rng_("fsmg.clip+adam");
     hipStream_t s = h->stream;
     ScopedTimer tm(h, "update");
@@ -116,6 +116,8 @@ int apply_update(fsmg_model* h, float grad_scale, bool may_defer) {
     } else {
         HIPCK(h, launch_adam_update(s, a));
     }
+    // the Meta-SGD rates move with theta: before the launch below counts the step and clears the flags they read
+    if (with_rates) GEMMCK(msgd_update_rates(h, grad_scale));
     // refresh the fragment-ordered recurrent weights and close the step (ring[step] = loss, ++step, or the skip tallies) -- one launch
     StepIncArgs inc{};
     inc.step = h->d_step; inc.loss_src = h->G + h->n_flat + 1; inc.loss_scale = grad_scale; inc.ring = h->d_ring; inc.ring_cap = RING_CAP;
@@ -139,7 +141,10 @@ int sgd_update(fsmg_model* h, float lr) {
     a.p = h->P; a.g = h->G; a.n = h->n_flat;
     a.partials = h->partials; a.n_partials = sqnorm_blocks(n); a.tail = h->G + h->n_flat; a.use_slices = slices ? 1 : 0;
     a.lr = lr; a.clip = h->cfg.max_grad_norm; a.gnorm_out = h->d_gnorm; a.err_flag = h->d_err;
-    HIPCK(h, launch_sgd_update(s, a));
+    {
+        ScopedTimer tk(h, "sgd_update");    // the kernel alone, inside "update" (tools/msgd_bench.py reads it beside the rates' kernels)
+        HIPCK(h, launch_sgd_update(s, a));
+    }
     h->khf_dirty = true;
     h->have_grads = false;
     return ensure_khf(h);

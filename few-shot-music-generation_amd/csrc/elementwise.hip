@@ -4,6 +4,7 @@
 // __shfl_xor over 64 lanes.
 #include <algorithm>
 #include "fsmg_kernels.h"
+#include "adam_element.h"
 #include <cstdlib>
 
 namespace fsmg {
@@ -828,21 +829,7 @@ __global__ __launch_bounds__(256) void k_sqnorm_partials(const float* __restrict
     if (tid == 0) partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-// One element of the update.  The kernel has two loops over it (grid-stride, and chunks drawn from a counter) that must give the same
-// bits, so which products are fused is spelled out here instead of left to the compiler's contraction, which decides per loop:
-//   gc = g * scale;  m <- fma(gc, 1 - b1, b1 * m);  v <- fma((1 - b2) * gc, gc, b2 * v);  p <- p - (alpha * m) / (sqrt(v) + eps)
-// (the fusions the single grid-stride loop was compiled to before the second loop existed: same bits as then)
-__device__ __forceinline__ void adam_element(float g, float& m, float& v, float& p, float scale, float alpha) {
-#pragma clang fp contract(off)
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-    const float gc = g * scale;
-    const float m_old = b1 * m, v_old = b2 * v, u = (1.0f - b2) * gc;
-    m = __builtin_fmaf(gc, 1.0f - b1, m_old);
-    v = __builtin_fmaf(u, gc, v_old);
-    const float num = alpha * m, den = sqrtf(v) + eps;
-    p = p - num / den;
-}
-
+// One element of the update: adam_element (adam_element.h; the rates' update of msgd.hip runs the same element).
 // clip_by_global_norm + exponential_decay + TF AdamOptimizer (reference
 // src/models/lstm_baseline.py:77-87; SURVEY.md A.4: epsilon added to the un-corrected sqrt(v)).
 // Every block re-derives the scalars from the same partials in the same order, so all blocks

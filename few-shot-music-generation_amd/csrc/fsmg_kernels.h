@@ -405,6 +405,30 @@ hipError_t launch_dyneval_accumulate(hipStream_t s, float* ms, const float* g, l
 // *out = (float)(sum_i sqrt((double)ms[i] / count) / n_logical): fp64, fixed order; partials holds dyneval_rms_blocks(n) doubles
 int dyneval_rms_blocks(long long n);
 hipError_t launch_dyneval_mean_rms(hipStream_t s, const float* ms, long long n, long long count, long long n_logical, double* partials, float* out);
+
+// ---------------------------------------------------------------- Meta-SGD: learned per-parameter inner rates (msgd.hip)
+// The inner step of the MAML-style pass with a rate per element.  step = (float)(clip / max(gnorm, clip)) * lr and the conditions under
+// which nothing is written are launch_sgd_update's, from the same partials / tail / error word.  Per element: st = step * alpha (one
+// rounding), p -= st * g (launch_sgd_update's element line).  sum != nullptr (the train forms): sum <- fma(step, g, sum) as well -- 24 B
+// per element against 16 B without it.  n a multiple of 4.
+struct MsgdUpdateArgs {
+    float* p; const float* g; const float* alpha; float* sum; long long n;
+    const double* partials; int n_partials; const float* tail; int use_slices;
+    float lr, clip; float* gnorm_out; const int* err_flag;
+};
+hipError_t launch_msgd_update(hipStream_t s, const MsgdUpdateArgs& a);
+// ga[i] = -(g[i] * sum[i]), one rounding: the first-order gradient of the query loss with respect to the rates.  n a multiple of 4.
+hipError_t launch_msgd_alpha_grad(hipStream_t s, float* ga, const float* g, const float* sum, long long n);
+// clip + Adam + clamp of the rates from ga: skipped where launch_adam_update skips (err_flag, tail[2..5]);
+//   gnorm = sqrt(sum of partials) * grad_scale;  scale = clip > 0 ? clip / max(gnorm, clip) * grad_scale : grad_scale
+//   step size: launch_adam_update's schedule with `lr`, from *step (the launch that counts the step comes later in the stream)
+//   adam_element, then alpha <- min(max(alpha, lo), hi).  partials: launch_sqnorm_partials(ga, n, partials).  n a multiple of 4.
+struct MsgdAlphaArgs {
+    float* alpha; float* m; float* v; const float* ga; long long n;
+    const double* partials; int n_partials; const float* tail; const int* err_flag;
+    float grad_scale, lr, n_decay, clip, lo, hi; const long long* step;
+};
+hipError_t launch_msgd_alpha_update(hipStream_t s, const MsgdAlphaArgs& a);
 // last kernel of a train step: counts the step (ring[step % cap] = loss, ++step) or, when *err_flag != 0 or the
 // all-reduced time-out indicator tail[2] is set, tallies it in counters ([0] time-outs, [1] token-range rejections;
 // host-mapped memory) and clears the flag

@@ -172,6 +172,14 @@ struct fsmg_model {
     int64_t dyn_count = 0;              // accumulated passes
     bool dyn_rms_dirty = true;          // ms_sum or count changed since d_mean_rms was computed
     float* dyn_out = nullptr; int64_t dyn_out_cap = 0;      // [R][T] scores of the call in progress
+    // Meta-SGD (fsmg_msgd_*): learned per-element multipliers of the MAML-style step's inner_lr.  One allocation on the first
+    // fsmg_msgd_enable, kept until fsmg_destroy: [A | AM | AV | S | GA | norm partials], the float buffers laid out like P (pads: S, GA exact 0)
+    bool msgd_on = false;               // every adaptation takes launch_msgd_update in place of launch_sgd_update
+    bool msgd_pending = false;          // GA belongs to the gradient that is pending (have_grads): fsmg_apply_update moves the rates with it
+    char* msgd_state = nullptr;
+    float *msgd_A = nullptr, *msgd_AM = nullptr, *msgd_AV = nullptr, *msgd_S = nullptr, *msgd_GA = nullptr;
+    double* msgd_part = nullptr;        // [sqnorm_blocks(n_flat)] squared-norm partials of GA (the theta update's live in `partials`)
+    fsmg_msgd_config msgd_cfg{};        // the scalars of the last fsmg_msgd_enable
     int* d_gather_len = nullptr;        // ... and their lengths (the masked forms; grown and freed with d_gather)
     int* d_gather = nullptr; int64_t gather_cap = 0;     // episode rows gathered from a table for the MAML-style step (its two passes take device token buffers)
     // XCD-local recurrence (lstm_xcd.hip; hidden size 512): per layer the forward and backward register images of K_h,
@@ -692,7 +700,16 @@ int ensure_cs(fsmg_model* h);           // the column-split copies of K_h are cu
 inline bool pass_reads_cs(const fsmg_model* h, int B, bool train) {
     return !use_xcd(h, B) || (train && !use_xcd(h, B, true));
 }
-int apply_update(fsmg_model* h, float grad_scale, bool may_defer = false);      // may_defer: the fused single-GPU train step (the softmax half may wait for the next pass)
+// may_defer: the fused single-GPU train step (the softmax half may wait for the next pass); with_rates: the Meta-SGD rates move too (update_rates)
+int apply_update(fsmg_model* h, float grad_scale, bool may_defer = false, bool with_rates = false);
+// api_msgd.hip.  msgd_inner_update: sgd_update with the rates (with_sum: the train forms, S collects the applied gradients);
+// msgd_begin_sum: S <- 0 where an adaptation of a train form begins; msgd_rate_gradient: GA from the query pass's gradient and S, marks it
+// pending; msgd_rates_due: fsmg_apply_update has rates to move; msgd_update_rates: the two launches inside apply_update
+int msgd_inner_update(fsmg_model* h, float lr, bool with_sum);
+int msgd_begin_sum(fsmg_model* h);
+int msgd_rate_gradient(fsmg_model* h);
+inline bool msgd_rates_due(const fsmg_model* h) { return h->msgd_on && h->msgd_pending && h->msgd_cfg.alpha_lr > 0.f; }
+int msgd_update_rates(fsmg_model* h, float grad_scale);
 int place_deferred_half(fsmg_model* h, int xcd_first);     // forward(): the waiting half on the auxiliary stream, on the XCDs >= xcd_first
 int sgd_update(fsmg_model* h, float lr);
 int save_theta(fsmg_model* h);

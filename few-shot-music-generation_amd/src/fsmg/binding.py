@@ -130,6 +130,11 @@ class FsmgDynevalConfig(C.Structure):
                 ('adapt_reported', C.c_int32), ('reserved', C.c_int32)]
 
 
+class FsmgMsgdConfig(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('alpha_init', C.c_float), ('alpha_lr', C.c_float), ('alpha_min', C.c_float),
+                ('alpha_max', C.c_float), ('alpha_clip_norm', C.c_float), ('reserved', C.c_int32)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -269,6 +274,16 @@ SIGNATURES = {
     'fsmg_dyneval_stats_set_count': (C.c_int, [_P, C.c_int64]),
     'fsmg_dyneval_score': (C.c_int, [_P, C.POINTER(FsmgDynevalConfig), _P, _P, C.c_int32, C.c_int32, _F32P, _F32P, _F32P]),
     'fsmg_dyneval_eval_step': (C.c_int, [_P, C.POINTER(FsmgDynevalConfig), _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _F32P]),
+    'fsmg_msgd_enable': (C.c_int, [_P, C.POINTER(FsmgMsgdConfig)]),
+    'fsmg_msgd_disable': (C.c_int, [_P]),
+    'fsmg_msgd_info': (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    'fsmg_msgd_fill': (C.c_int, [_P, C.c_float]),
+    'fsmg_msgd_get_alpha': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
+    'fsmg_msgd_set_alpha': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
+    'fsmg_msgd_get_opt_state': (C.c_int, [_P, C.c_char_p, _F32P, _F32P, C.c_int64]),
+    'fsmg_msgd_set_opt_state': (C.c_int, [_P, C.c_char_p, _F32P, _F32P, C.c_int64]),
+    'fsmg_msgd_get_grad': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
+    'fsmg_msgd_grad_buffer': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
     'fsmg_dyneval_generate': (C.c_int, [_P, C.POINTER(FsmgDynevalConfig), _P, _P, C.c_int32, C.POINTER(FsmgGenConfig),
                                         C.POINTER(FsmgGenFilters), _P, _I32P, _F32P]),
 }
@@ -1483,6 +1498,71 @@ class FsmgModel(object):
         d = (C.c_int32 * 5)()
         self._ck(self._lib.fsmg_debug_dims(self._h, d))
         return dict(Ep=d[0], Hp=d[1], V1p=d[2], B=d[3], T=d[4])
+
+    # -- Meta-SGD: learned per-parameter inner rates (include/fsmg.h "Meta-SGD") ------------------------------------
+    @staticmethod
+    def msgd_config(alpha_init=1.0, alpha_lr=0.0, alpha_min=0.0, alpha_max=float('inf'), alpha_clip_norm=0.0):
+        """the fsmg_msgd_config struct"""
+        return FsmgMsgdConfig(struct_size=C.sizeof(FsmgMsgdConfig), alpha_init=float(alpha_init), alpha_lr=float(alpha_lr),
+                              alpha_min=float(alpha_min), alpha_max=float(alpha_max), alpha_clip_norm=float(alpha_clip_norm), reserved=0)
+
+    def msgd_enable(self, cfg=None, **kw):
+        """every adaptation of this handle takes the rates from here on; cfg: FsmgMsgdConfig, a dict of msgd_config's keywords, or keywords"""
+        c = cfg if isinstance(cfg, FsmgMsgdConfig) else self.msgd_config(**dict(cfg or {}, **kw))
+        self._ck(self._lib.fsmg_msgd_enable(self._h, C.byref(c)))
+
+    def msgd_disable(self):
+        self._ck(self._lib.fsmg_msgd_disable(self._h))
+
+    def msgd_info(self):
+        """-> dict(enabled, allocated, count, pending)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.fsmg_msgd_info(self._h, out))
+        return dict(enabled=bool(out[0]), allocated=bool(out[1]), count=int(out[2]), pending=bool(out[3]))
+
+    def msgd_fill(self, value):
+        """A = value everywhere, Adam slots of the rates zero"""
+        self._ck(self._lib.fsmg_msgd_fill(self._h, float(value)))
+
+    def msgd_get_alpha(self, name):
+        out = np.empty(self._shape(name), np.float32)
+        self._ck(self._lib.fsmg_msgd_get_alpha(self._h, name.encode(), _f32p(out), out.size))
+        return out
+
+    def msgd_set_alpha(self, name, value):
+        a = np.ascontiguousarray(value, dtype=np.float32)
+        self._ck(self._lib.fsmg_msgd_set_alpha(self._h, name.encode(), _f32p(a), a.size))
+
+    def msgd_get_alphas(self):
+        return {k: self.msgd_get_alpha(k) for k in self.param_shapes}
+
+    def msgd_get_opt_state(self, name):
+        m = np.empty(self._shape(name), np.float32)
+        v = np.empty(self._shape(name), np.float32)
+        self._ck(self._lib.fsmg_msgd_get_opt_state(self._h, name.encode(), _f32p(m), _f32p(v), m.size))
+        return m, v
+
+    def msgd_set_opt_state(self, name, m, v):
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        self._ck(self._lib.fsmg_msgd_set_opt_state(self._h, name.encode(), _f32p(m), _f32p(v), m.size))
+
+    def msgd_get_grad(self, name):
+        """GA of the pending rate gradient (a maml_forward_backward* on an enabled handle, before apply_update)"""
+        out = np.empty(self._shape(name), np.float32)
+        self._ck(self._lib.fsmg_msgd_get_grad(self._h, name.encode(), _f32p(out), out.size))
+        return out
+
+    def msgd_grad_buffer(self):
+        """-> (device pointer, float count) of GA: what a data-parallel wrapper all-reduces next to grad_buffer()"""
+        ptr, count = _P(), C.c_int64()
+        self._ck(self._lib.fsmg_msgd_grad_buffer(self._h, C.byref(ptr), C.byref(count)))
+        return ptr.value, count.value
+
+    def msgd_get_sum(self, name):
+        """S of the last train-form adaptation, shaped like get_param(name)"""
+        shape = self._shape(name)
+        return self.debug_read('msgd_sum:' + name, int(np.prod(shape))).reshape(shape)
 
     def debug_set(self, what, value):
         """run-time knob of the handle (include/fsmg.h: chain_spin_limit, fallback_steps, persistent, eager, inplace_dlogits,

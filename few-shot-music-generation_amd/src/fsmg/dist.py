@@ -122,6 +122,17 @@ class EpisodeParallel(object):
                     dist.all_reduce(self.engine.grad_tensor, op=dist.ReduceOp.SUM, group=self.group)
             else:
                 dist.all_reduce(self.engine.grad_tensor, op=dist.ReduceOp.SUM, group=self.group)
+        # Meta-SGD: the gradient with respect to the learned inner rates was formed on every rank from ITS query
+        # gradient and ITS applied support steps, before any exchange (a product of means is not a mean of products); it is summed
+        # like the flat gradient buffer and apply_update(1 / world) takes the mean
+        rate_grad = getattr(self.engine, 'rate_grad_tensor', None) if maml is not None else None
+        if self.exchange and self.world > 1 and rate_grad is not None:
+            ctx = getattr(self.engine, 'stream_context', None)
+            if ctx is not None:
+                with ctx():
+                    dist.all_reduce(rate_grad, op=dist.ReduceOp.SUM, group=self.group)
+            else:
+                dist.all_reduce(rate_grad, op=dist.ReduceOp.SUM, group=self.group)
         return self.engine.apply_update(1.0 / self.world, want_loss=want_loss)
 
     def mean_scalar(self, value):

@@ -926,6 +926,68 @@ int fsmg_dyneval_generate(fsmg_handle h, const fsmg_dyneval_config* cfg, const i
                           int32_t n_support_rows, const fsmg_gen_config* gen_config, const fsmg_gen_filters* filters,
                           const int32_t* primer, int32_t* out_tokens, float* out_logprob);
 
+/* ---- Meta-SGD: learned per-parameter inner rates for the MAML-style step (Li et al. 2017, first order).
+ * The MAML-style step learns the initialisation theta; its fine-tuning procedure is one hand-set scalar inner_lr on a clipped SGD
+ * step.  With Meta-SGD enabled the handle also holds a rate per parameter element, A, a MULTIPLIER of the call's inner_lr, trained
+ * with theta by the outer update.  While enabled, EVERY adaptation in the library takes step 1 below in place of the plain inner
+ * step: the train, eval, masked and indexed forms of fsmg_maml_*, and fsmg_maml_generate* / fsmg_maml_beam_search* / fsmg_maml_score*.
+ * No existing signature changes; disabled (or never enabled), every path is bit for bit what it was.
+ *
+ * State, created by the first fsmg_msgd_enable and kept until fsmg_destroy, five buffers laid out like the flat parameter buffer
+ * (fsmg_get_param's layout by name; not counted by fsmg_state_bytes): A the rates, AM / AV their Adam slots, S the sum of the applied
+ * support gradients of the last train-form adaptation, GA the gradient with respect to A.  Pad elements of A never matter (g is an
+ * exact 0 there, so the pads of theta' stay 0 whatever A holds); the pads of S and GA are zeros.
+ *
+ *   1. Inner step i.  The pass, the norm, the conditions under which the step is skipped and the fp32 scalar
+ *      step = (float)(clip / max(gnorm, clip)) * inner_lr are those of the plain inner step.  Per element j:
+ *        st = step * A[j]                      (one rounding)
+ *        p[j] <- p[j] - st * g[j]              (the plain step's expression with st for step: A == 1 gives the plain step's bits)
+ *        S[j] <- fma(step, g[j], S[j])         (the train forms only: fsmg_maml_forward_backward* / fsmg_maml_step*)
+ *      S is zeroed when the adaptation of a train form begins (a pass repeated after a time-out starts from zero again).  The eval
+ *      and decoding forms neither read nor write S.
+ *   2. Rate gradient.  After the query pass of a train form, GA[j] = -(G[j] * S[j]), one rounding: the first-order gradient of
+ *      L_query(theta') with respect to A, the support gradients and their clip scales taken as constants.  For inner_steps == 1 it is
+ *      the exact gradient.  It is pending until the next fsmg_apply_update or backward pass.
+ *   3. Outer update, in fsmg_apply_update while a rate gradient is pending.  theta's clip + Adam runs exactly as without Meta-SGD.
+ *      The rates: gnorm_a = sqrt(sum GA^2) * grad_scale, a plain global norm whatever clip_norm_mode;
+ *      scale = alpha_clip_norm > 0 ? alpha_clip_norm / max(gnorm_a, alpha_clip_norm) * grad_scale : grad_scale; the step size is
+ *      theta's schedule (exponential decay, Adam bias correction) with alpha_lr in place of lr at the same global_step; the element
+ *      update is theta's Adam element, then A <- min(max(A, alpha_min), alpha_max).  A step that is skipped for theta (a time-out, a
+ *      token out of range) is skipped for A, AM and AV too; global_step counts once.  alpha_lr == 0: A, AM and AV stay bitwise.
+ *   4. Data-parallel.  GA is formed per rank BEFORE any exchange (a product of means is not a mean of products): all-reduce the
+ *      buffer of fsmg_msgd_grad_buffer next to fsmg_grad_buffer, then fsmg_apply_update(1 / world).  The library's own exchange does
+ *      not carry GA: fsmg_msgd_enable on a handle with a communicator, and fsmg_comm_init / _attach on an enabled handle, return
+ *      FSMG_ERR_STATE.
+ *
+ * fsmg_msgd_enable: the first call allocates and sets A = alpha_init, AM = AV = 0; a later call keeps the state and takes the new
+ * scalars (alpha_init is then unused).  fsmg_msgd_disable: every path is the old one; the state is kept.  fsmg_msgd_info: out =
+ * {enabled, allocated, elements per buffer (the flat count, pads included), rate gradient pending}.  fsmg_msgd_fill: A = value, AM =
+ * AV = 0.  _get_alpha / _set_alpha, _get_opt_state / _set_opt_state, _get_grad move one tensor by name (count = rows * cols);
+ * _get_grad returns FSMG_ERR_STATE without a pending rate gradient.  fsmg_debug_read("msgd_sum:<name>") reads S.
+ * Errors, before any device work: FSMG_ERR_INVALID for a NULL handle / config, struct_size not sizeof(fsmg_msgd_config), nonzero
+ * reserved, a NaN anywhere, alpha_init not finite, alpha_lr or alpha_clip_norm negative or not finite, alpha_min > alpha_max (an
+ * infinite alpha_min / alpha_max is an open end of the clamp), a non-finite value given to _fill / _set_alpha; FSMG_ERR_STATE for the calls that need the state before the
+ * first fsmg_msgd_enable. */
+typedef struct {
+    int32_t struct_size;      /* sizeof(fsmg_msgd_config), else FSMG_ERR_INVALID     */
+    float alpha_init;         /* A of the first enable                               */
+    float alpha_lr;           /* >= 0; 0: the rates are not trained                  */
+    float alpha_min;          /* clamp after every update of A                       */
+    float alpha_max;
+    float alpha_clip_norm;    /* 0: no clipping of GA                                */
+    int32_t reserved;         /* 0                                                   */
+} fsmg_msgd_config;
+int fsmg_msgd_enable(fsmg_handle h, const fsmg_msgd_config* cfg);
+int fsmg_msgd_disable(fsmg_handle h);
+int fsmg_msgd_info(fsmg_handle h, int64_t out[4]);
+int fsmg_msgd_fill(fsmg_handle h, float value);
+int fsmg_msgd_get_alpha(fsmg_handle h, const char* name, float* host, int64_t count);
+int fsmg_msgd_set_alpha(fsmg_handle h, const char* name, const float* host, int64_t count);
+int fsmg_msgd_get_opt_state(fsmg_handle h, const char* name, float* m, float* v, int64_t count);
+int fsmg_msgd_set_opt_state(fsmg_handle h, const char* name, const float* m, const float* v, int64_t count);
+int fsmg_msgd_get_grad(fsmg_handle h, const char* name, float* host, int64_t count);
+int fsmg_msgd_grad_buffer(fsmg_handle h, void** device_ptr, int64_t* count);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
