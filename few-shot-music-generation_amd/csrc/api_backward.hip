@@ -19,7 +19,7 @@ int dhout_chunk(fsmg_model* h, const Lane& ln, int B, int t0, int t1, OpBatch* d
 
 GemmArgs dw_args(fsmg_model* h, int B) {      // dW = Hout^T * dlogits, dd = colsum(dlogits)
     GemmArgs g{};
-    g.A = h->Hs[h->L - 1] + (size_t)B * h->Hp; g.lda = h->Hp; g.B = dlogits_buf(h); g.ldb = h->V1p;
+    g.A = drop_up(h, h->L - 1, B); g.lda = h->Hp; g.B = dlogits_buf(h); g.ldb = h->V1p;      // (a dropped pass: the masked copy)
     g.C = h->G + h->off_w; g.ldc = h->V1p; g.M = h->Hp; g.N = h->V1p; g.K = (int)((int64_t)h->T * B);
     g.colsum = h->G + h->off_d; g.ksplit = 1;
     if (h->fs_call) { g.A = h->Hsc; g.colsum_w = h->crow; }      // fused softmax: (diag(c) Hout)^T E', dd = sum_r c_r E'[r]
@@ -95,13 +95,15 @@ int backward(fsmg_model* h, int B, int part) {
     // the merged dKx + dKh GEMM of layer l (see dk_gemm below) and whether the layer takes it
     auto dk_merged_args = [&](int l, GemmArgs& m) -> bool {
         const int in_p = h->in_dim[l];
-        if (l == 0) { m.A = h->P + h->off_emb; m.lda = h->Ep; m.gather = h->X; }
-        else { m.A = h->Hs[l - 1] + (size_t)B * Hp; m.lda = Hp; }
+        const bool emb_copy = l == 0 && drop_emb(h) != nullptr;       // a dropped pass: the masked rows, no gather
+        if (emb_copy) { m.A = drop_emb(h); m.lda = h->Ep; }
+        else if (l == 0) { m.A = h->P + h->off_emb; m.lda = h->Ep; m.gather = h->X; }
+        else { m.A = drop_up(h, l - 1, B); m.lda = Hp; }
         m.A2 = h->Hs[l]; m.lda2 = Hp; m.m_split = in_p;
         m.B = h->Z[l]; m.ldb = G4; m.C = h->G + h->off_kx[l]; m.ldc = G4; m.M = in_p + Hp; m.N = G4; m.K = (int)rows;
         m.colsum = h->G + h->off_b[l]; m.ksplit = 1;
         return h->merge_dk && in_p % 256 == 0 && Hp % 4 == 0 && h->off_kh[l] == h->off_kx[l] + (int64_t)in_p * G4 &&
-               (l > 0 || 4LL * h->V1 * h->Ep < 0xfffff000LL) && 4LL * Hp * rows < 0xfffff000LL && 4LL * G4 * rows < 0xfffff000LL &&
+               (l > 0 || (emb_copy ? 4LL * h->Ep * rows : 4LL * h->V1 * h->Ep) < 0xfffff000LL) && 4LL * Hp * rows < 0xfffff000LL && 4LL * G4 * rows < 0xfffff000LL &&
                (((uintptr_t)m.A | (uintptr_t)m.A2 | (uintptr_t)m.B) & 15) == 0 && gemm_dma_enabled() && use_h_gemm(h, OP_XC, OP_XC, m, mainl);
     };
     // Backward pair at hidden 512, one layer (fsmg_model::xov_dk_tail): the merged dK -- it reads dZ, the inputs and h, nothing of dW -- is
@@ -116,7 +118,7 @@ int backward(fsmg_model* h, int B, int part) {
     OpBatch* const d_now = defer_ok ? &fills : nullptr;
     OpBatch* const d_late = defer_ok ? &late : nullptr;
     // (eager passes only: a captured pass would have to join the auxiliary stream inside the graph; event timing wants one stream)
-    const bool aside = h->tail_aside && defer_ok && h->eager_call && h->aux != nullptr && !h->timing && !ov;
+    const bool aside = h->tail_aside && defer_ok && h->eager_call && h->aux != nullptr && !h->timing && !ov && !h->drop_call;      // (a dropped pass: one stream)
     h->side_pending = false;
     if (part != 2) GEMMCK(fills.add(h->G + h->off_emb, 0u, (long long)h->V1 * h->Ep));
     // (the chunk counter of a deferred softmax half of this step's update, should there be one: same launch)
@@ -179,6 +181,8 @@ int backward(fsmg_model* h, int B, int part) {
         const bool loss_in_batch = late.r.count > 0 && !masked;
         if (loss_in_batch) GEMMCK(late.mean(h->ce, rows, h->G + h->n_flat + 1));
         GEMMCK(late.flush());
+        // a dropped pass: the gradient that flows back through site 0, in place, before the embedding gradient and its squared-norm partials
+        GEMMCK(drop_backward_site(h, 0, B, h->dXemb));
         // tail[0] = squared norm of the embedding-slice gradients, tail[1] = mean loss of the pass, tail[2] / tail[3] = time-out /
         // token-range indicators: one block's work, which rides in the embedding gradient's first launch where the partials are there already
         const int nb = sqnorm_blocks(rows * h->Ep);
@@ -214,6 +218,8 @@ int backward(fsmg_model* h, int B, int part) {
             GEMMCK(bptt_fills(h, fills, B, xcd, rs, chain, packed ? rpx : 0));
             GEMMCK(fills.flush());
         }
+        // a dropped pass: dH is complete here (its slab sum went out with the fills) -- the gradient that flows back through site l + 1, in place
+        GEMMCK(drop_backward_site(h, l + 1, B, h->dH));
         for (int c = nch - 1; c >= 0; --c) {
             const int t0 = chunk_begin(h, c, nch), t1 = chunk_begin(h, c + 1, nch);
             if (top && ov) HIPCK(h, hipStreamWaitEvent(s, h->ev_chunk[c], 0));
@@ -319,8 +325,9 @@ int backward(fsmg_model* h, int B, int part) {
                 if (probe) { *probe = use_h_gemm(h, OP_XC, OP_XC, g, mainl); return FSMG_OK; }
                 GEMMCK(gemm(h, mainl, OP_XC, OP_XC, g, dk_defer));
                 GemmArgs k{};                     // dKx = in^T * dZ
-                if (l == 0) { k.A = h->P + h->off_emb; k.lda = h->Ep; k.gather = h->X; }
-                else { k.A = h->Hs[l - 1] + (size_t)B * Hp; k.lda = Hp; }
+                if (l == 0 && drop_emb(h) != nullptr) { k.A = drop_emb(h); k.lda = h->Ep; }
+                else if (l == 0) { k.A = h->P + h->off_emb; k.lda = h->Ep; k.gather = h->X; }
+                else { k.A = drop_up(h, l - 1, B); k.lda = Hp; }
                 k.B = h->Z[l]; k.ldb = G4; k.C = h->G + h->off_kx[l]; k.ldc = G4;
                 k.M = in_p; k.N = G4; k.K = (int)rows; k.ksplit = 1;
                 GEMMCK(gemm(h, mainl, OP_XC, OP_XC, k, dk_defer));
@@ -337,7 +344,9 @@ int backward(fsmg_model* h, int B, int part) {
                 g.M = (int)rows; g.N = in_p; g.K = G4; g.ksplit = 1;
                 // layer 0: the sum rides with the weight gradients' and leaves the squared-norm partials of dXemb behind;
                 // above: the layer below reads dH next, the sum goes out with that layer's fills
-                if (l == 0) GEMMCK(gemm(h, mainl, OP_KC, OP_KC, g, d_late, h->partials, &dx_sq_done));
+                // (a dropped pass masks dXemb behind the sum: the partials must be the masked gradient's, they come from launch_sqnorm_partials)
+                if (l == 0 && drop_site_on(h, 0)) GEMMCK(gemm(h, mainl, OP_KC, OP_KC, g, d_late));
+                else if (l == 0) GEMMCK(gemm(h, mainl, OP_KC, OP_KC, g, d_late, h->partials, &dx_sq_done));
                 else GEMMCK(gemm(h, mainl, OP_KC, OP_KC, g, d_now));
             }
             return FSMG_OK;

@@ -47,6 +47,13 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
         const int l = std::atoi(what + n);
         return (l >= 0 && l < h->L && std::strlen(what) > n) ? l : -1;
     };
+    auto drop_site_of = [&](const char* w) -> int {
+        if (std::strncmp(w, "drop", 4) != 0 || !w[4]) return -1;
+        if (std::strlen(w + 4) > 3) return -1;                  // (no site has more digits; nothing longer reaches atol)
+        for (const char* p = w + 4; *p; ++p) if (*p < '0' || *p > '9') return -1;
+        const long s = std::atol(w + 4);
+        return s <= h->L ? (int)s : -1;
+    };
     int l;
     if (!std::strcmp(what, "aux_tries")) { host[0] = (float)h->aux_tries; return FSMG_OK; }       // streams drawn until one ran beside the handle's (-1: none did)
     if (!std::strcmp(what, "fused_softmax")) { host[0] = h->fused_softmax ? 1.0f : 0.0f; if (count > 1) host[1] = h->fs_call ? 1.0f : 0.0f; return FSMG_OK; }   // [0] the knob, [1] whether the last train pass took it
@@ -105,6 +112,10 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
         HIPCK(h, hipMemcpy(nv.data(), h->d_nvalid, sizeof(int) * count, hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < count; ++i) host[i] = (float)nv[(size_t)i];
         return FSMG_OK;
+    }
+    else if ((l = drop_site_of(what)) >= 0) {          // the masked activations of the last dropped pass at that site
+        if (h->drop_buf.empty() || h->drop_lastB[(size_t)l] <= 0) return fail(h, FSMG_ERR_STATE, "no dropped pass has written this site");
+        src = h->drop_buf[(size_t)l]; cap = T * h->drop_lastB[(size_t)l] * (l == 0 ? h->Ep : Hp);
     }
     else if (!std::strcmp(what, "dx")) { src = h->dXemb; cap = rows * h->Ep; }
     else if (!std::strcmp(what, "dh")) { src = h->dH; cap = rows * Hp; }

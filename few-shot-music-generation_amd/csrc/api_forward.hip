@@ -67,7 +67,7 @@ GemmArgs logits_args(fsmg_model* h, int B, int t0, int t1) {
     const int Hp = h->Hp;
     const int64_t r0 = (int64_t)t0 * B, m = (int64_t)(t1 - t0) * B;
     GemmArgs g{};
-    g.A = h->Hs[h->L - 1] + (size_t)B * Hp + (size_t)r0 * Hp; g.lda = Hp;
+    g.A = drop_up(h, h->L - 1, B) + (size_t)r0 * Hp; g.lda = Hp;        // (a dropped pass: the masked copy)
     g.B = h->P + h->off_w; g.ldb = h->V1p;
     g.C = h->logits + (size_t)r0 * h->V1p; g.ldc = h->V1p; g.M = (int)m; g.N = h->V1p; g.K = Hp;
     g.bias = h->P + h->off_d; g.ksplit = 1; g.nt_store = 1;      // streaming stores: read back by the cross entropy much later (A/B: profiles/r03t_ntp_*)
@@ -82,11 +82,11 @@ int ce_finish(fsmg_model* h, hipStream_t s, int B, int64_t rows) {
     ScopedTimer tm(h, "ce");
     if (h->masked_call) {
         HIPCK(h, launch_ce_finish_w(s, h->ce_part, h->ce_nparts, h->Y, (int)rows, h->roww, h->logits, h->V1p,
-                                    h->lse, h->ce, h->crow, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Hsc, h->Hp, h->d_err, h->d_counters + 4));
+                                    h->lse, h->ce, h->crow, drop_up(h, h->L - 1, B), h->Hsc, h->Hp, h->d_err, h->d_counters + 4));
         return FSMG_OK;
     }
     HIPCK(h, launch_ce_finish(s, h->ce_part, h->ce_nparts, h->Y, (int)rows, (float)(1.0 / ((double)rows + 1e-12)), h->logits, h->V1p,
-                              h->lse, h->ce, h->crow, h->Hs[h->L - 1] + (size_t)B * h->Hp, h->Hsc, h->Hp, h->d_err, h->d_counters + 4));
+                              h->lse, h->ce, h->crow, drop_up(h, h->L - 1, B), h->Hsc, h->Hp, h->d_err, h->d_counters + 4));
     return FSMG_OK;
 }
 int ce_rows(fsmg_model* h, hipStream_t s, int B, int t0, int t1, int64_t rows_total) {
@@ -190,11 +190,13 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
         GEMMCK(fills.add(h->Hs[l], 0u, (long long)B * Hp));
         GEMMCK(fills.add(h->Cs[l], 0u, (long long)B * Hp));
         if (!xcd) GEMMCK(fills.add(h->HF[l], 0u, (long long)Bp16 * Hp));
+        if (l == 0) GEMMCK(drop_forward_site(h, 0, B));        // a dropped pass: the masked embedding rows, gathered once
         {
             ScopedTimer tm(h, "gemm_zx");
             GemmArgs g{};
-            if (l == 0) { g.A = h->P + h->off_emb; g.lda = h->Ep; g.gather = h->X; g.K = h->Ep; }
-            else { g.A = h->Hs[l - 1] + (size_t)B * Hp; g.lda = Hp; g.K = Hp; }
+            if (l == 0 && drop_emb(h) != nullptr) { g.A = drop_emb(h); g.lda = h->Ep; g.K = h->Ep; }
+            else if (l == 0) { g.A = h->P + h->off_emb; g.lda = h->Ep; g.gather = h->X; g.K = h->Ep; }
+            else { g.A = drop_up(h, l - 1, B); g.lda = Hp; g.K = Hp; }
             g.B = h->P + h->off_kx[l]; g.ldb = G4;
             g.C = h->Z[l]; g.ldc = G4; g.M = (int)rows; g.N = G4;
             g.bias = h->P + h->off_b[l]; g.ksplit = 1;
@@ -280,6 +282,7 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
                 GEMMCK(logits_and_ce(h, aux_lane(h, !want_dlogits, chain || xcd), B, t0, t1, rows, want_dlogits));
             }
         }
+        GEMMCK(drop_forward_site(h, l + 1, B));                // a dropped pass: layer l's output on its way up
     }
     if (head == HEAD_NONE) {
         // the hidden states are the product

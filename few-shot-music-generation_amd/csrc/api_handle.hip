@@ -142,6 +142,7 @@ int begin_call(fsmg_model* h, bool keep_pending) {
     HIPCK(h, hipSetDevice(h->device));
     h->masked_call = false;
     h->window_call = false;
+    h->drop_call = false;
     const int rc = take_turn(h);
     if (rc != FSMG_OK) return rc;
     return keep_pending ? FSMG_OK : settle_pending(h);
@@ -365,6 +366,7 @@ int fsmg_destroy(fsmg_handle h) {
     if (h->dyn_stats) hipFree(h->dyn_stats);
     if (h->dyn_out) hipFree(h->dyn_out);
     if (h->msgd_state) hipFree(h->msgd_state);
+    drop_destroy(h);
     for (int* t : h->table) if (t) hipFree(t);
     for (int* t : h->table_len) if (t) hipFree(t);
     if (h->d_idx) hipFree(h->d_idx);

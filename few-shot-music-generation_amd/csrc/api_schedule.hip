@@ -142,6 +142,10 @@ void choose_schedule(fsmg_model* h, int B, bool train) {
         h->xov_call = rpx > 0 && xov_first_free(B, h->Hp) <= (h->Hp == 1024 ? 6 : 5);          // at least three XCDs (hidden 1024: a pair) for the GEMMs
         if (h->xov_call) h->eager_call = true;
     }
+    // a dropped pass: serial, single-stream, eager -- the gated projection of the XCD-partitioned order would read the top
+    // layer's rows before a masked copy of them exists; the kernel choices inside the order stay the handle's
+    if (!train) h->drop_call = false;
+    if (h->drop_call) { h->ov_call = false; h->xov_call = false; h->eager_call = true; }
 }
 void xov_gate(fsmg_model* h, GemmArgs& g, int B) {     // the projection's A rows arrive time step by time step
     const int rpx = lstm_xcd16_packed_rows(B, h->Hp);

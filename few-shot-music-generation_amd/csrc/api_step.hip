@@ -27,6 +27,8 @@ int forward_backward_core(fsmg_model* h, int32_t N, int32_t K, int32_t Q, Stage&
     }
     if ((rc = ensure_scratch(h, B)) != FSMG_OK) return rc;
     if ((rc = select_xcd_format(h, B)) != FSMG_OK) return rc;
+    if ((rc = drop_begin_pass(h, B)) != FSMG_OK) return rc;
+    struct DropScope { fsmg_model* m; ~DropScope() { m->drop_call = false; } } drop_scope{h};      // whatever way the pass ends, it is over
     choose_schedule(h, B, true);
     h->xov_last = h->xov_call;
     // an eager pass orders itself behind a pending update half inside forward(); a pass that is captured or replayed cannot hold
@@ -37,6 +39,7 @@ int forward_backward_core(fsmg_model* h, int32_t N, int32_t K, int32_t Q, Stage&
     if (h->tok_table_open && (rc = reset_tok_table(h)) != FSMG_OK) return rc;     // a pass that never reached its embed_grad
     h->tok_table_open = true;
     if ((rc = stage()) != FSMG_OK) return rc;
+    drop_take_index(h);                 // (a call refused up to here has used up no pass index)
     const int n_sup = N * K, n_qry = N * Q;
     h->bucket0_recorded = false;
     // (a padding-masked pass has launches of its own -- the row weights, the weighted cross entropy, the masked loss: its own graphs)
@@ -81,7 +84,9 @@ int forward_backward_core(fsmg_model* h, int32_t N, int32_t K, int32_t Q, Stage&
 // the episode-parallel step with the exchange inside the library: forward + backward, all-reduce, clip + Adam (1 / world)
 template <class FB>
 int dp_train_step(fsmg_model* h, float* loss, FB&& forward_backward) {
+    const uint64_t drop_p0 = h->drop_next;      // a repeated step draws the masks of the passes it repeats
     for (int attempt = 0; attempt < 2; ++attempt) {
+        h->drop_next = drop_p0;
         int rc = forward_backward();
         int local_rc = FSMG_OK; std::string local_msg;
         if (rc != FSMG_OK) {
@@ -133,6 +138,7 @@ inline void begin_masked(fsmg_model* h, int rows_per_group, int groups) {
 template <class Stage>
 int fused_train_step(fsmg_model* h, int32_t N, int32_t K, int32_t Q, float* loss, Stage&& stage) {
     if (h->comm != nullptr) return dp_train_step(h, loss, [&]() { return forward_backward_core(h, N, K, Q, stage, false); });
+    const uint64_t drop_p0 = h->drop_next;
     int rc = forward_backward_core(h, N, K, Q, stage, true);
     if (rc == FSMG_OK) rc = after_update(h, 1.0f, loss);
     if (is_retry(rc) && h->retry_armed) {
@@ -140,6 +146,7 @@ int fused_train_step(fsmg_model* h, int32_t N, int32_t K, int32_t Q, float* loss
         // update kernels saw the flag and left parameters, Adam state and step counter alone, and the handle has
         // fallen back to one launch per time step -- repeat the step that way
         h->retry_armed = false;
+        h->drop_next = drop_p0;             // the repeated pass draws the masks of the pass it repeats
         rc = forward_backward_core(h, N, K, Q, stage, true);
         if (rc == FSMG_OK) rc = after_update(h, 1.0f, loss);
     }
@@ -336,11 +343,14 @@ static int maml_adapt(fsmg_handle h, const int32_t* support, int32_t N, int32_t 
                       const int32_t* support_len = nullptr, bool train = false) {
     int rc = save_theta(h);
     if (rc == FSMG_OK && h->msgd_on && train) rc = msgd_begin_sum(h);
+    const bool suppress0 = h->drop_suppress;
+    if (!train) h->drop_suppress = true;        // the adaptation of an eval / decode / score form is never dropped
     for (int i = 0; rc == FSMG_OK && i < inner_steps; ++i) {
         rc = support_len ? masked_rows_pass(h, support, support_len, N, K, on_device)
                          : fsmg_forward_backward(h, support, support, N, K, 0, on_device);       // support rows only
         if (rc == FSMG_OK) rc = h->msgd_on ? msgd_inner_update(h, inner_lr, train) : sgd_update(h, inner_lr);
     }
+    h->drop_suppress = suppress0;
     return rc;
 }
 
@@ -364,11 +374,13 @@ int fsmg_maml_step(fsmg_handle h, const int32_t* support, const int32_t* query, 
     BEGIN_CALL(h);
     if (h->comm != nullptr)           // per-rank inner loop (no communication), query gradients exchanged like a plain step's
         return dp_train_step(h, loss, [&]() { return fsmg_maml_forward_backward(h, support, query, N, K, Q, inner_steps, inner_lr, tokens_on_device); });
+    const uint64_t drop_p0 = h->drop_next;
     int rc = fsmg_maml_forward_backward(h, support, query, N, K, Q, inner_steps, inner_lr, tokens_on_device);
     if (rc != FSMG_OK) return rc;
     rc = fsmg_apply_update(h, 1.0f, loss);
     if (is_retry(rc) && h->retry_armed) {        // same recovery as fsmg_train_step: nothing was updated, repeat per step
         h->retry_armed = false;
+        h->drop_next = drop_p0;
         rc = fsmg_maml_forward_backward(h, support, query, N, K, Q, inner_steps, inner_lr, tokens_on_device);
         if (rc == FSMG_OK) rc = fsmg_apply_update(h, 1.0f, loss);
     }
@@ -412,11 +424,13 @@ int fsmg_maml_step_masked(fsmg_handle h, const int32_t* support, const int32_t* 
     auto fb = [&]() { return maml_forward_backward_masked(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device); };
     if (h->comm != nullptr)           // each rank normalises by its own n_valid; 1 / world takes the mean
         return dp_train_step(h, loss, fb);
+    const uint64_t drop_p0 = h->drop_next;
     int rc = fb();
     if (rc != FSMG_OK) return rc;
     rc = fsmg_apply_update(h, 1.0f, loss);
     if (is_retry(rc) && h->retry_armed) {        // same recovery as fsmg_maml_step: nothing was updated, repeat per step -- with the lengths
         h->retry_armed = false;
+        h->drop_next = drop_p0;
         rc = fb();
         if (rc == FSMG_OK) rc = fsmg_apply_update(h, 1.0f, loss);
     }
@@ -563,12 +577,15 @@ int window_rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int
     BEGIN_CALL(h, true);
     begin_masked(h, n, 1);
     h->window_call = true;
+    const bool suppress0 = h->drop_suppress;
+    h->drop_suppress = true;                    // dynamic evaluation is never dropped
     const int rc = forward_backward_core(h, 1, n, 0, [&]() {
         int r = stage_tokens(h, rows, n, rows, 0, 0);
         if (r == FSMG_OK) r = stage_lengths(h, len, n, len, 0, 0);
         if (r == FSMG_OK) HIPCK(h, launch_set_window(h->stream, h->d_win, lo, hi));
         return r;
     });
+    h->drop_suppress = suppress0;
     h->masked_call = false;
     h->window_call = false;
     return rc;

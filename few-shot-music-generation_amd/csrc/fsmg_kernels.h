@@ -429,6 +429,19 @@ struct MsgdAlphaArgs {
     float grad_scale, lr, n_decay, clip, lo, hi; const long long* step;
 };
 hipError_t launch_msgd_alpha_update(hipStream_t s, const MsgdAlphaArgs& a);
+
+// ---------------------------------------------------------------- dropout of the train passes (dropout.hip)
+// One site of one pass: element (r, j), r a device row (t * B + b), j < W of a row of ld floats (ld a multiple of 4), is kept iff
+// (word >> 8) < thr, word = output j & 3 of Philox4x32-10(counter (j >> 2, variational ? r % B : r, site, pass), key (key0, key1));
+// kept elements are multiplied by scale, dropped ones and the pad columns j >= W are +0.0.  8 B per element out of place, 8 in place.
+struct DropArgs {
+    uint32_t key0, key1, site, pass, thr; float scale;
+    int variational, B, W, ld; long long rows;
+};
+hipError_t launch_dropout_fwd(hipStream_t s, const DropArgs& a, const float* src, float* dst);                         // dst[r] = mask(src[r])
+hipError_t launch_dropout_embed_fwd(hipStream_t s, const DropArgs& a, const float* emb, const int* ids, float* dst);   // dst[r] = mask(emb[ids[r]])
+hipError_t launch_dropout_bwd(hipStream_t s, const DropArgs& a, float* g);                                             // in place
+hipError_t launch_dropout_mask(hipStream_t s, const DropArgs& a, unsigned char* out);                                 // 0 / 1 bytes [rows][W]
 // last kernel of a train step: counts the step (ring[step % cap] = loss, ++step) or, when *err_flag != 0 or the
 // all-reduced time-out indicator tail[2] is set, tallies it in counters ([0] time-outs, [1] token-range rejections;
 // host-mapped memory) and clears the flag

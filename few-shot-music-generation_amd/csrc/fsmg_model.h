@@ -180,6 +180,20 @@ struct fsmg_model {
     float *msgd_A = nullptr, *msgd_AM = nullptr, *msgd_AV = nullptr, *msgd_S = nullptr, *msgd_GA = nullptr;
     double* msgd_part = nullptr;        // [sqnorm_blocks(n_flat)] squared-norm partials of GA (the theta update's live in `partials`)
     fsmg_msgd_config msgd_cfg{};        // the scalars of the last fsmg_msgd_enable
+    // dropout of the train passes (fsmg_dropout_*): masks regenerated from (seed, pass, site, row, unit), never stored
+    bool drop_on = false;               // fsmg_dropout_enable / _disable
+    bool drop_ever = false;             // enabled at least once (fsmg_dropout_mask / _set_pass need the scalars)
+    bool drop_suppress = false;         // the gradient passes in progress are not a train form's (maml_adapt of the eval / decode forms, dynamic evaluation)
+    bool drop_call = false;             // the pass in progress is a dropped one (forward_backward_core): serial, single-stream, eager
+    fsmg_dropout_config drop_cfg{};
+    uint64_t drop_next = 0;             // the index the next dropped pass takes
+    int64_t drop_last = -1;             // ... and the one the last dropped pass took
+    uint32_t drop_pass = 0;             // drop_last mod 2^32: what the kernels of the pass in progress take
+    char* drop_state = nullptr;         // the masked copies, one allocation: [T * drop_cap][Ep] | L x [T * drop_cap][Hp]
+    int drop_cap = 0;                   // sequences the copies hold
+    int64_t drop_bytes = 0;
+    std::vector<float*> drop_buf;       // [L + 1] by site
+    std::vector<int> drop_lastB;        // [L + 1] rows / T of the last dropped pass that wrote the site's copy (0: none; "drop<site>")
     int* d_gather_len = nullptr;        // ... and their lengths (the masked forms; grown and freed with d_gather)
     int* d_gather = nullptr; int64_t gather_cap = 0;     // episode rows gathered from a table for the MAML-style step (its two passes take device token buffers)
     // XCD-local recurrence (lstm_xcd.hip; hidden size 512): per layer the forward and backward register images of K_h,
@@ -710,6 +724,23 @@ int msgd_begin_sum(fsmg_model* h);
 int msgd_rate_gradient(fsmg_model* h);
 inline bool msgd_rates_due(const fsmg_model* h) { return h->msgd_on && h->msgd_pending && h->msgd_cfg.alpha_lr > 0.f; }
 int msgd_update_rates(fsmg_model* h, float grad_scale);
+// api_dropout.hip.  drop_begin_pass: forward_backward_core, before choose_schedule -- decides drop_call and makes sure the
+// masked copies hold B sequences; drop_take_index: behind the staging, where nothing host-side can refuse the pass any more -- a dropped
+// pass takes its index.  drop_site_on: the site is masked in the pass in progress (its keep is below 1).
+// drop_up: "layer l's output going up" -- the masked copy in a dropped pass, Hs[l] + B * Hp otherwise; drop_emb: the masked embedding
+// rows [T * B][Ep] of a dropped pass (layer 0 then reads them without the gather), nullptr otherwise.  drop_forward_site: the site's
+// forward launch; drop_backward_site: the same factors, in place, on the gradient g [T * B][ld] that flows back through the site.
+int drop_begin_pass(fsmg_model* h, int B);
+void drop_take_index(fsmg_model* h);
+inline float drop_keep(const fsmg_model* h, int site) { return site == 0 ? h->drop_cfg.keep_input : h->drop_cfg.keep_output; }
+inline bool drop_site_on(const fsmg_model* h, int site) { return h->drop_call && drop_keep(h, site) < 1.0f; }
+inline const float* drop_up(const fsmg_model* h, int l, int B) {
+    return drop_site_on(h, l + 1) ? h->drop_buf[l + 1] : h->Hs[l] + (size_t)B * h->Hp;
+}
+inline const float* drop_emb(const fsmg_model* h) { return drop_site_on(h, 0) ? h->drop_buf[0] : nullptr; }
+int drop_forward_site(fsmg_model* h, int site, int B);
+int drop_backward_site(fsmg_model* h, int site, int B, float* g);
+void drop_destroy(fsmg_model* h);
 int place_deferred_half(fsmg_model* h, int xcd_first);     // forward(): the waiting half on the auxiliary stream, on the XCDs >= xcd_first
 int sgd_update(fsmg_model* h, float lr);
 int save_theta(fsmg_model* h);

@@ -135,6 +135,11 @@ class FsmgMsgdConfig(C.Structure):
                 ('alpha_max', C.c_float), ('alpha_clip_norm', C.c_float), ('reserved', C.c_int32)]
 
 
+class FsmgDropoutConfig(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('keep_input', C.c_float), ('keep_output', C.c_float), ('variational', C.c_int32),
+                ('seed', C.c_uint64)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -284,6 +289,11 @@ SIGNATURES = {
     'fsmg_msgd_set_opt_state': (C.c_int, [_P, C.c_char_p, _F32P, _F32P, C.c_int64]),
     'fsmg_msgd_get_grad': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
     'fsmg_msgd_grad_buffer': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    'fsmg_dropout_enable': (C.c_int, [_P, C.POINTER(FsmgDropoutConfig)]),
+    'fsmg_dropout_disable': (C.c_int, [_P]),
+    'fsmg_dropout_info': (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    'fsmg_dropout_set_pass': (C.c_int, [_P, C.c_int64]),
+    'fsmg_dropout_mask': (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     'fsmg_dyneval_generate': (C.c_int, [_P, C.POINTER(FsmgDynevalConfig), _P, _P, C.c_int32, C.POINTER(FsmgGenConfig),
                                         C.POINTER(FsmgGenFilters), _P, _I32P, _F32P]),
 }
@@ -1498,6 +1508,44 @@ class FsmgModel(object):
         d = (C.c_int32 * 5)()
         self._ck(self._lib.fsmg_debug_dims(self._h, d))
         return dict(Ep=d[0], Hp=d[1], V1p=d[2], B=d[3], T=d[4])
+
+    # -- dropout of the train passes (include/fsmg.h "Dropout") -----------------------------------------------------
+    @staticmethod
+    def dropout_config(keep_input=1.0, keep_output=1.0, variational=False, seed=0):
+        """the fsmg_dropout_config struct"""
+        return FsmgDropoutConfig(struct_size=C.sizeof(FsmgDropoutConfig), keep_input=float(keep_input), keep_output=float(keep_output),
+                                 variational=int(variational), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    def dropout_enable(self, cfg=None, **kw):
+        """the gradient passes of the train forms are dropped from here on; cfg: FsmgDropoutConfig, a dict of dropout_config's keywords, or keywords"""
+        c = cfg if isinstance(cfg, FsmgDropoutConfig) else self.dropout_config(**dict(cfg or {}, **kw))
+        self._ck(self._lib.fsmg_dropout_enable(self._h, C.byref(c)))
+
+    def dropout_disable(self):
+        self._ck(self._lib.fsmg_dropout_disable(self._h))
+
+    def dropout_info(self):
+        """-> dict(enabled, last_pass (-1: none yet), next_pass, bytes)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.fsmg_dropout_info(self._h, out))
+        return dict(enabled=bool(out[0]), last_pass=int(out[1]), next_pass=int(out[2]), bytes=int(out[3]))
+
+    def dropout_set_pass(self, next_pass):
+        self._ck(self._lib.fsmg_dropout_set_pass(self._h, int(next_pass)))
+
+    def dropout_mask(self, pass_index, site, B):
+        """-> uint8 [T, B, width]: the 0 / 1 mask of `site` in pass `pass_index` for B sequences (device row order t * B + b)"""
+        W = self.cfg.embedding_size if site == 0 else self.cfg.hidden_size
+        out = np.zeros((self.max_len, max(int(B), 1), W), np.uint8)        # (a bad site / B: the library refuses before it writes)
+        self._ck(self._lib.fsmg_dropout_mask(self._h, int(pass_index), int(site), int(B), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def dropout_read(self, site, B=None):
+        """-> float32 [T, B, Ep or Hp]: the masked activations of the last dropped pass at `site` (pads included)"""
+        d = self.debug_dims()
+        B = d['B'] if B is None else int(B)
+        ld = d['Ep'] if site == 0 else d['Hp']
+        return self.debug_read('drop%d' % site, d['T'] * B * ld).reshape(d['T'], B, ld)
 
     # -- Meta-SGD: learned per-parameter inner rates (include/fsmg.h "Meta-SGD") ------------------------------------
     @staticmethod

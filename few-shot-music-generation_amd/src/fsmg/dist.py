@@ -19,6 +19,15 @@ import torch.distributed as dist
 RETRY_CODES = (-9, -10)        # FSMG_ERR_TIMEOUT, FSMG_ERR_SOFTMAX_RANGE (fsmg.binding.RETRY_CODES; repeated here: no import of the binding on CPU-only ranks)
 
 
+GOLDEN64 = 0x9E3779B97F4A7C15
+
+
+def rank_seed(seed, rank):
+    """the dropout seed of rank r (include/fsmg.h "Dropout"): seed + r * 0x9E3779B97F4A7C15 mod 2^64 -- every rank draws its own masks
+    for its own episode, rank 0 the single-process run's"""
+    return (int(seed) + int(rank) * GOLDEN64) % (1 << 64)
+
+
 def init_from_env(backend=None):
     """Initialise torch.distributed from RANK / WORLD_SIZE / MASTER_* (torchrun); returns (rank, world)."""
     import os

@@ -23,13 +23,59 @@ Optional config keys beyond the reference's: device, clip_norm_mode ('tf1_slices
 max_sequences, use_graph, gemm / schedule / recurrence / dp_split_backward (fsmg_config), dp_exchange ('torch': the
 all-reduce is issued through torch.distributed; 'library': libfsmg issues the RCCL calls itself), mask_padding (default false; true:
 train / train_indexed / eval / eval_many score position t of a song iff t < its length -- Episode.support_len / query_len, the
-lengths handed to attach_table -- and average over the scored positions, include/fsmg.h "per-song lengths").  When torch.distributed is initialised, train() runs episode-parallel
-(one episode per rank, one gradient all-reduce per step, see fsmg/dist.py).
+lengths handed to attach_table -- and average over the scored positions, include/fsmg.h "per-song lengths"),
+keep_prob_input / keep_prob_output / dropout_variational / dropout_seed (config/lstm_dropout.yaml; all absent by default = never
+enabled: dropout of the train passes on the non-recurrent connections, include/fsmg.h "Dropout"; eval, sample, generate, score never
+drop; rank r of an episode-parallel run draws its masks from fsmg.dist.rank_seed(dropout_seed, r); the index of the next dropped pass
+is saved and restored next to the native checkpoint, <name>.dropout.npz -- ONE file holding the index at the latest save, while the
+native checkpoints are kept per step: recovering from an older checkpoint than the newest restores the newest index, i.e. the run
+continues with masks of later passes, not the ones it drew the first time; every rank of an episode-parallel run writes the same
+file with the same counter, atomically).  When torch.distributed is initialised, train() runs
+episode-parallel (one episode per rank, one gradient all-reduce per step, see fsmg/dist.py).
 """
+import os
+
 import numpy as np
 
-from fsmg.dist import EpisodeParallel
+from fsmg.dist import EpisodeParallel, rank_seed
 from models.hip_model import HIPModel
+
+DROPOUT_KEYS = ('keep_prob_input', 'keep_prob_output', 'dropout_variational', 'dropout_seed')
+
+
+def dropout_settings(config, rank=0):
+    """the dropout keys of a model config -> the keyword arguments of FsmgModel.dropout_enable for rank `rank`, or None when none of the
+    keys is there (the handle is then never enabled)"""
+    if not any(config.get(k) is not None for k in DROPOUT_KEYS):
+        return None
+    keep_in = float(config['keep_prob_input']) if config.get('keep_prob_input') is not None else 1.0
+    keep_out = float(config['keep_prob_output']) if config.get('keep_prob_output') is not None else 1.0
+    for name, k in (('keep_prob_input', keep_in), ('keep_prob_output', keep_out)):
+        if not (0.0 < k <= 1.0):
+            raise RuntimeError('%s must be in (0, 1], got %r' % (name, k))
+    seed = int(config.get('dropout_seed') or 0)
+    if seed < 0:
+        raise RuntimeError('dropout_seed must be >= 0')
+    return dict(keep_input=keep_in, keep_output=keep_out, variational=bool(config.get('dropout_variational') or False),
+                seed=rank_seed(seed, rank))
+
+
+def save_dropout(engine, path):
+    """the index the engine's next dropped pass takes -> one small .npz beside the native checkpoint (which stays byte-identical)"""
+    tmp = path + '.tmp.npz'
+    np.savez(tmp, next_pass=np.int64(engine.dropout_info()['next_pass']))
+    os.replace(tmp, path)
+
+
+def load_dropout(engine, path):
+    """-> True when the file exists and holds an index (the engine's next dropped pass then takes it), else False with nothing set"""
+    if not os.path.isfile(path):
+        return False
+    with np.load(path) as blob:
+        if 'next_pass' not in blob or int(blob['next_pass']) < 0:
+            return False
+        engine.dropout_set_pass(int(blob['next_pass']))
+    return True
 
 
 class LSTMBaseline(HIPModel):
@@ -50,11 +96,24 @@ class LSTMBaseline(HIPModel):
         self._parallel = EpisodeParallel(self)
         if config.get('dp_exchange', 'torch') == 'library' and self._parallel.world > 1:
             self.attach_library_comm()
+        self._dropout = dropout_settings(config, self._parallel.rank)
+
+    def _dropout_path(self, checkpt_path):
+        return os.path.join(checkpt_path, self.name, self.name + '.dropout.npz')
+
+    def save(self, checkpt_path):
+        super(LSTMBaseline, self).save(checkpt_path)
+        if self._dropout is not None:
+            save_dropout(self._model, self._dropout_path(checkpt_path))
 
     def recover_or_init(self, init_path):
         super(LSTMBaseline, self).recover_or_init(init_path)
         if self._parallel.world > 1:                     # replicas start from rank 0's state
             self._parallel.broadcast_parameters(self._arena)
+        if self._dropout is not None:                    # the gradient passes of the train forms are dropped from here on
+            self._model.dropout_enable(**self._dropout)
+            if init_path and load_dropout(self._model, self._dropout_path(init_path)):
+                print('recovered the dropout pass index')
 
     @staticmethod
     def _tokens(arr, ndim):

@@ -988,6 +988,57 @@ int fsmg_msgd_set_opt_state(fsmg_handle h, const char* name, const float* m, con
 int fsmg_msgd_get_grad(fsmg_handle h, const char* name, float* host, int64_t count);
 int fsmg_msgd_grad_buffer(fsmg_handle h, void** device_ptr, int64_t* count);
 
+/* ---- Dropout for the train passes (Zaremba et al. 2014: non-recurrent connections only).  Never enabled, or
+ * disabled, every path is what it was, bit for bit.  The masks are never stored: forward and backward regenerate them from a
+ * counter-based generator (Philox4x32-10, Salmon et al. 2011), so a test can rebuild every mask on the host.
+ *
+ * Sites.  Site 0 is the embedding rows that enter layer 0 (width embedding_size).  Site l + 1 is the output h^l_t of layer l on its
+ * way UP (width hidden_size): for l < n_layers - 1 to layer l + 1's input product, for the top layer to the projection.  The
+ * recurrent path h^l_t -> h^l_{t+1} and the cell state are never masked.  Site 0 uses keep_input, every other site keep_output.
+ * A site whose keep is exactly 1 launches nothing and is bit-identical to the undropped path.
+ *
+ * Mask of element (row, j) at `site` in pass p: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (j >> 2, row, site, p mod 2^32); element j takes output word j & 3.  row = t * B + b, the device's time-major row order of the
+ * pass (B = its sequences, support rows first); with variational = 1, row = b: one mask per song shared by all time steps (Gal &
+ * Ghahramani 2016).  The element is kept iff (word >> 8) < thr, thr = (uint32)(keep * 16777216.0f) (truncation).  Kept elements
+ * are multiplied by scale = 1.0f / keep (one fp32 rounding of the quotient, one of the product), dropped elements are +0.0, pad
+ * columns stay zero.  Backward: the gradient that flows back through a site is multiplied by the same mask * scale, regenerated.
+ *
+ * Which passes.  Dropout is on in the gradient passes of the train forms: fsmg_train_step*, fsmg_forward_backward*, and
+ * fsmg_maml_step* / fsmg_maml_forward_backward* (the inner support passes and the query pass).  It is never on in fsmg_eval_*,
+ * fsmg_score*, any decoding, fsmg_cache_*, fsmg_dyneval_*, nor in the adaptation passes of fsmg_maml_eval* and the MAML decode /
+ * score entry points.
+ *
+ * Pass index.  A 64-bit counter of the handle gives every dropped gradient pass its own p (a MAML-style step uses inner_steps + 1
+ * of them); a pass repeated inside one call after a time-out draws the masks of the pass it repeats.  fsmg_dropout_info: out =
+ * {enabled, index of the last dropped pass (-1: none yet), index the next one takes, bytes of the masked copies}.
+ * fsmg_dropout_set_pass sets the next index (checkpoint restore, tests).
+ *
+ * Order.  A dropped pass runs in the serial, single-stream, eager order (the XCD-partitioned order's gated projection would read
+ * the top layer's rows before a masked copy of them can exist); inside it every kernel choice stays the handle's.  A handle that
+ * is enabled with both keeps 1 takes that order too and launches nothing else.
+ *
+ * fsmg_dropout_enable takes the scalars (a later call replaces them; the pass counter is kept) and allocates the masked copies
+ * ([T * B][Ep] + n_layers x [T * B][Hp] floats, outside fsmg_state_bytes, freed by fsmg_destroy).  fsmg_dropout_mask writes the
+ * 0 / 1 bytes [T * B][width] (device row order) of `site` in pass `pass` for B sequences with the enabled scalars, keep 1 included.
+ * fsmg_debug_read("drop<site>") returns the masked activations [T * B][Ep or Hp] of the last dropped pass.
+ * Errors, before any device work: FSMG_ERR_INVALID for a NULL handle / config / out, struct_size not
+ * sizeof(fsmg_dropout_config), a keep outside (0, 1] or NaN, variational not 0 / 1, pass < 0, a site outside [0, n_layers], B < 1;
+ * FSMG_ERR_STATE for fsmg_dropout_mask / _set_pass before the first fsmg_dropout_enable and for "drop<site>" without a dropped
+ * pass at that site. */
+typedef struct {
+    int32_t struct_size;      /* sizeof(fsmg_dropout_config), else FSMG_ERR_INVALID  */
+    float keep_input;         /* site 0, in (0, 1]                                   */
+    float keep_output;        /* sites 1 .. n_layers, in (0, 1]                      */
+    int32_t variational;      /* 1: one mask per song, shared by all time steps      */
+    uint64_t seed;
+} fsmg_dropout_config;
+int fsmg_dropout_enable(fsmg_handle h, const fsmg_dropout_config* cfg);
+int fsmg_dropout_disable(fsmg_handle h);
+int fsmg_dropout_info(fsmg_handle h, int64_t out[4]);
+int fsmg_dropout_set_pass(fsmg_handle h, int64_t next_pass);
+int fsmg_dropout_mask(fsmg_handle h, int64_t pass, int32_t site, int32_t B, uint8_t* out);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
