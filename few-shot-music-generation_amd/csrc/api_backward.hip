@@ -118,7 +118,7 @@ int backward(fsmg_model* h, int B, int part) {
     OpBatch* const d_now = defer_ok ? &fills : nullptr;
     OpBatch* const d_late = defer_ok ? &late : nullptr;
     // (eager passes only: a captured pass would have to join the auxiliary stream inside the graph; event timing wants one stream)
-    const bool aside = h->tail_aside && defer_ok && h->eager_call && h->aux != nullptr && !h->timing && !ov && !h->drop_call;      // (a dropped pass: one stream)
+    const bool aside = h->tail_aside && defer_ok && h->eager_call && h->aux != nullptr && !h->timing && !ov && !h->drop_call && h->state_cur == nullptr;      // (a dropped pass, a state pass: one stream)
     h->side_pending = false;
     if (part != 2) GEMMCK(fills.add(h->G + h->off_emb, 0u, (long long)h->V1 * h->Ep));
     // (the chunk counter of a deferred softmax half of this step's update, should there be one: same launch)

@@ -67,6 +67,10 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
         for (int64_t i = 0; i < count && i < 4; ++i) host[i] = (float)h->gemm_kinds[i];
         return FSMG_OK;
     }
+    if (!std::strcmp(what, "state_imports")) {        // state passes' imports so far by hand-off copy: [1] HF, [2] fp32 HX, [3] bf16 HX (STATE_HAND_*)
+        for (int64_t i = 0; i < count && i < 4; ++i) host[i] = (float)h->n_state_imports[i];
+        return FSMG_OK;
+    }
     if (!std::strcmp(what, "xov_dk_tail")) {          // [0] the knob, [1] joint clean-up launches enqueued so far, [2] / [3] dW's / dK's items in the last one
         const float v[4] = {(float)h->xov_dk_tail, (float)h->n_joint_launches, (float)h->joint_items[0], (float)h->joint_items[1]};
         for (int64_t i = 0; i < count && i < 4; ++i) host[i] = v[i];

@@ -43,6 +43,10 @@ int reset_tok_table(fsmg_model* h) {
 // train: the pass ends in k_embed_grad, which wants the occurrence table of the input ids
 int token_prep(fsmg_model* h, int n_sup, int n_qry, bool train) {
     const bool table = train && h->tok_first != nullptr;
+    if (h->state_cur != nullptr) {              // state pass: one group's weights, the state's pending token at position 0
+        h->last_mask_groups = 1;
+        return state_token_prep(h, n_sup + n_qry, table);
+    }
     if (h->masked_call && h->window_call) {     // window pass: weights on [lo, e[b]) with (lo, hi) read on the device, fixed ids from e[b] on
         HIPCK(h, launch_window_weights(h->stream, h->cur_len, n_sup + n_qry, h->T, h->d_win, h->roww, h->d_nvalid, h->d_elen, h->d_err));
         HIPCK(h, launch_token_prep_len(h->stream, h->cur_sup, n_sup, h->cur_qry, n_qry, h->T, h->V, h->V,
@@ -187,9 +191,13 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
         const size_t Bp16 = (size_t)(B + 15) / 16 * 16;
         const bool top = l == h->L - 1;
         FillBatch fills(h);                 // zero states + hand-off patterns of this layer: ONE launch, issued ahead of the chain
+        if (h->state_cur != nullptr) {      // state pass: slot 0 and the hand-off copy of index 0 hold the carried state of this layer
+            GEMMCK(state_import(h, l, B, xcd));
+        } else {
         GEMMCK(fills.add(h->Hs[l], 0u, (long long)B * Hp));
         GEMMCK(fills.add(h->Cs[l], 0u, (long long)B * Hp));
         if (!xcd) GEMMCK(fills.add(h->HF[l], 0u, (long long)Bp16 * Hp));
+        }
         if (l == 0) GEMMCK(drop_forward_site(h, 0, B));        // a dropped pass: the masked embedding rows, gathered once
         {
             ScopedTimer tm(h, "gemm_zx");
@@ -214,7 +222,7 @@ int forward(fsmg_model* h, int B, int rows_per_group, int ngroups, float* loss_o
                 const int rpx_l = xov && top ? rpx : 0;
                 const long long step_f = lstm_xcd_hx_floats(B, 0, Hp, h->xcd_bx3, rpx_l);
                 const long long used_f = step_f / lstm_xcd_slices(Hp) * lstm_xcd_used_slices(B, rpx_l, Hp);
-                GEMMCK(fills.add(h->HX, 0u, step_f));
+                if (h->state_cur == nullptr) GEMMCK(fills.add(h->HX, 0u, step_f));      // (a state pass: state_import wrote index 0)
                 GEMMCK(fills.add_strided(h->HX + step_f, 0xFFFFFFFFu, used_f, step_f, T));
                 if (xov && top) {
                     GEMMCK(fills.add(h->xov_ctl, 0u, 4 + gemm_items(ghead)));

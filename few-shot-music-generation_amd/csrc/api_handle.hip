@@ -143,6 +143,7 @@ int begin_call(fsmg_model* h, bool keep_pending) {
     h->masked_call = false;
     h->window_call = false;
     h->drop_call = false;
+    h->state_cur = nullptr;
     const int rc = take_turn(h);
     if (rc != FSMG_OK) return rc;
     return keep_pending ? FSMG_OK : settle_pending(h);

@@ -146,6 +146,9 @@ void choose_schedule(fsmg_model* h, int B, bool train) {
     // layer's rows before a masked copy of them exists; the kernel choices inside the order stay the handle's
     if (!train) h->drop_call = false;
     if (h->drop_call) { h->ov_call = false; h->xov_call = false; h->eager_call = true; }
+    // a state pass: the same order -- the import and the export sit in stream order around the chains, and the state
+    // must not depend on which graph a pass was captured into; the kernel choices inside the order stay the handle's
+    if (h->state_cur != nullptr) { h->ov_call = false; h->xov_call = false; h->eager_call = true; }
 }
 void xov_gate(fsmg_model* h, GemmArgs& g, int B) {     // the projection's A rows arrive time step by time step
     const int rpx = lstm_xcd16_packed_rows(B, h->Hp);

@@ -55,12 +55,19 @@ int forward_backward_core(fsmg_model* h, int32_t N, int32_t K, int32_t Q, Stage&
         });
         if (rc != FSMG_OK) return rc;
         if (!h->bucket0_recorded) { HIPCK(h, hipEventRecord(h->ev_bucket[0], h->stream)); h->bucket0_recorded = true; }
-        rc = run_graphed(h, "fb2:" + shape_key, [&]() -> int { return backward(h, B, 2); });
+        rc = run_graphed(h, "fb2:" + shape_key, [&]() -> int {
+            int r = backward(h, B, 2);
+            if (r == FSMG_OK && h->state_cur != nullptr) r = state_export(h, B);
+            return r;
+        });
     } else {
         rc = run_graphed(h, (with_update ? "fbu:" : "fb:") + shape_key, [&]() -> int {
             int r = token_prep(h, n_sup, n_qry, true);
             if (r == FSMG_OK) r = forward(h, B, B, 1, h->G + h->n_flat + 1, true);
             if (r == FSMG_OK) r = backward(h, B);
+            // a state pass: the state advances behind the last reader of Hs / Cs and in front of the update, whose
+            // k_step_increment clears the error word the export looks at -- a skipped step leaves the state where it was
+            if (r == FSMG_OK && h->state_cur != nullptr) r = state_export(h, B);
             if (r == FSMG_OK && with_update) r = apply_update(h, 1.0f, true);
             return r;
         });
@@ -151,6 +158,19 @@ int fused_train_step(fsmg_model* h, int32_t N, int32_t K, int32_t Q, float* loss
         if (rc == FSMG_OK) rc = after_update(h, 1.0f, loss);
     }
     return rc;
+}
+
+// fsmg_forward_backward_state / fsmg_train_step_state behind their argument checks (api_state.hip, which has set state_cur, masked_call and
+// the lengths): the R rows as one group, fsmg_*_masked's passes and retries
+int state_train_pass(fsmg_model* h, int R, const int32_t* tokens, const int32_t* len, int on_device, bool with_update, float* loss) {
+    auto stage = [&]() {
+        int r = stage_tokens(h, tokens, 0, tokens, R, on_device);
+        if (r == FSMG_OK) r = stage_lengths(h, len, 0, len, R, 0);
+        h->state_len = h->d_len;
+        return r;
+    };
+    if (with_update) return fused_train_step(h, 1, 0, R, loss, stage);
+    return forward_backward_core(h, 1, 0, R, stage);
 }
 
 }  // namespace fsmg_host

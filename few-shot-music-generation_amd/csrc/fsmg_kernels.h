@@ -721,4 +721,33 @@ struct CacheMixSelfArgs {
 };
 hipError_t launch_cache_mix_self(hipStream_t s, int R, const CacheMixSelfArgs& a);
 
+// ---- carried state of the batched passes (state.hip, fsmg_*_state).  No allocation, no synchronisation.
+// launch_state_import: layer l of a decode state (h, c [B][Hp]) into slot 0 of Hs[l] / Cs[l] (row-major) and into the hand-off copy the
+// layer's recurrence reads at time index 0.  kind / ng / nq / rows describe that copy:
+//   STATE_HAND_HF    HF[l] index 0, fragment order [ceil(B / 16)][Hp / 16][64][4] (per-step and column-split kernels)
+//   STATE_HAND_HX32  HX index 0 of the fp32 XCD-local kernels: ng weight copies (8 XCDs at hidden 512, 4 XCD pairs at 1024, 16 slices at
+//                    256), nq fragments of 64 units per wave (2 / 4 / 1), rows = 4 x the row groups the launch is instantiated for
+//   STATE_HAND_HX16  HX index 0 of the bf16-split kernels: ng copies (8 / 4), nq k steps of 32 units per wave (4 / 8), rows = HXR
+// Pad rows and pad units of every copy are exact zeros; every word of the copy is written.
+enum { STATE_HAND_NONE = 0, STATE_HAND_HF = 1, STATE_HAND_HX32 = 2, STATE_HAND_HX16 = 3 };
+struct StateImportArgs {
+    const float* h; const float* c;
+    float* Hs0; float* Cs0;
+    float* hand;
+    int B, Hp, kind, ng, nq, rows;
+};
+hipError_t launch_state_import(hipStream_t s, const StateImportArgs& a);
+// launch_token_prep_len for one block of B rows whose position 0 reads the state's pending token ctx[b * ldctx + kept] (a row of length
+// 0: the start word); len (device, [B], values clamped to [0, T]) may be null = all T.  The occurrence table counts what X holds.
+hipError_t launch_state_token_prep(hipStream_t s, const int* tokens, int B, int T, int vocab, int start_word, const int* len, const int* ctx,
+                                   int ldctx, int kept, int* X, int* Y, int* err_flag, int* tok_first, int* tok_count);
+// launch_row_weights for one group of B rows with lengths in [0, T]
+hipError_t launch_state_weights(hipStream_t s, const int* len, int B, int T, float* w, int* n_valid);
+// one layer of the state after the pass: h / c row b = slot len[b] of Hs / Cs ([T + 1][B][Hp]); nothing when *err_flag != 0
+hipError_t launch_state_export(hipStream_t s, const float* Hs, const float* Cs, int B, int Hp, int T, const int* len, float* h, float* c,
+                               const int* err_flag);
+// the ring after the pass (ctx [B][ldctx], `kept` context tokens before, `keep` after); nothing when *err_flag != 0
+hipError_t launch_state_export_ctx(hipStream_t s, const int* tokens, int B, int T, int vocab, const int* len, int* ctx, int ldctx, int kept,
+                                   int keep, const int* err_flag);
+
 }  // namespace fsmg

@@ -12,6 +12,8 @@
 //   api_score.hip     scoring of given songs: fsmg_score, fsmg_maml_score; the pass driver of every score-style call (run_passes)
 //   api_cache.hip     support-set neural cache: fsmg_cache_* (build, attend, score and eval against a cache; the cache side of
 //                     cache-conditioned generation, whose entry points sit beside the decode driver in api_decode.hip)
+//   api_state.hip     batched passes from a carried state: fsmg_score_state, fsmg_eval_step_state, fsmg_forward_backward_state,
+//                     fsmg_train_step_state (the hooks of a state pass: import, token prep, export)
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
@@ -194,6 +196,12 @@ struct fsmg_model {
     int64_t drop_bytes = 0;
     std::vector<float*> drop_buf;       // [L + 1] by site
     std::vector<int> drop_lastB;        // [L + 1] rows / T of the last dropped pass that wrote the site's copy (0: none; "drop<site>")
+    // carried state of a batched pass (fsmg_*_state): the pass in progress starts every layer from this decode state, reads its
+    // pending token at position 0 and leaves it advanced (begin_call clears it, the state entry points set it).  Such a pass is a masked
+    // pass of one group (masked_call is set with it) in the serial order: single-stream, eager
+    fsmg_dstate_s* state_cur = nullptr;
+    const int* state_len = nullptr;     // device lengths [R] of the state pass in progress (d_len)
+    int64_t n_state_imports[4] = {};    // imports by hand-off kind (STATE_HAND_*): fsmg_debug_read("state_imports")
     int* d_gather_len = nullptr;        // ... and their lengths (the masked forms; grown and freed with d_gather)
     int* d_gather = nullptr; int64_t gather_cap = 0;     // episode rows gathered from a table for the MAML-style step (its two passes take device token buffers)
     // XCD-local recurrence (lstm_xcd.hip; hidden size 512): per layer the forward and backward register images of K_h,
@@ -741,6 +749,15 @@ inline const float* drop_emb(const fsmg_model* h) { return drop_site_on(h, 0) ? 
 int drop_forward_site(fsmg_model* h, int site, int B);
 int drop_backward_site(fsmg_model* h, int site, int B, float* g);
 void drop_destroy(fsmg_model* h);
+// api_state.hip, the hooks of a state pass (fsmg_model::state_cur != nullptr):
+// state_token_prep: token_prep's launches -- one group's weights with lengths in [0, T], the pending token at position 0
+// state_import: forward(), per layer in place of the zero fills of slot 0 (xcd: the layer's chain takes the XCD-local kernels)
+// state_export: behind the pass's last reader of Hs / Cs and in front of whatever clears the error word: slot len[b] and the ring
+// state_train_pass (api_step.hip): forward + backward (+ update) of the state's rows, the masked train forms' contract
+int state_token_prep(fsmg_model* h, int B, bool table);
+int state_import(fsmg_model* h, int l, int B, bool xcd);
+int state_export(fsmg_model* h, int B);
+int state_train_pass(fsmg_model* h, int R, const int32_t* tokens, const int32_t* len, int on_device, bool with_update, float* loss);
 int place_deferred_half(fsmg_model* h, int xcd_first);     // forward(): the waiting half on the auxiliary stream, on the XCDs >= xcd_first
 int sgd_update(fsmg_model* h, float lr);
 int save_theta(fsmg_model* h);

@@ -140,6 +140,14 @@ class FsmgDropoutConfig(C.Structure):
                 ('seed', C.c_uint64)]
 
 
+FSMG_STATE_CONFIG_VERSION = 1
+FSMG_STATE_PASS_ROWS = 1024
+
+
+class FsmgStateConfig(C.Structure):
+    _fields_ = [('version', C.c_int32), ('tokens_on_device', C.c_int32), ('reserved', C.c_int32 * 6)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _F32P = C.POINTER(C.c_float)
@@ -296,6 +304,10 @@ SIGNATURES = {
     'fsmg_dropout_mask': (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     'fsmg_dyneval_generate': (C.c_int, [_P, C.POINTER(FsmgDynevalConfig), _P, _P, C.c_int32, C.POINTER(FsmgGenConfig),
                                         C.POINTER(FsmgGenFilters), _P, _I32P, _F32P]),
+    'fsmg_score_state': (C.c_int, [_P, _P, C.POINTER(FsmgStateConfig), _P, _I32P, _F32P, _I32P, _F32P, _I32P, _F32P]),
+    'fsmg_eval_step_state': (C.c_int, [_P, _P, C.POINTER(FsmgStateConfig), _P, _I32P, _F32P, _I32P]),
+    'fsmg_forward_backward_state': (C.c_int, [_P, _P, C.POINTER(FsmgStateConfig), _P, _I32P]),
+    'fsmg_train_step_state': (C.c_int, [_P, _P, C.POINTER(FsmgStateConfig), _P, _I32P, _F32P]),
 }
 
 _lib = None
@@ -965,6 +977,62 @@ class FsmgModel(object):
         lp = np.empty((state.rows, n), np.float32) if logprobs else None
         state._call(self._lib.fsmg_dstate_feed, tp, n, dev, _f32p(lp) if logprobs else None)
         return lp
+
+    # -- batched passes from a carried state (include/fsmg.h fsmg_*_state) ---------------------------------
+    def _state_args(self, state, tokens, lengths):
+        """-> (config, token pointer, length pointer or None, keepalives): tokens int32 [rows, max_len] (or a device address), lengths
+        host int32 [rows] in [0, max_len] or None = every position"""
+        if not isinstance(state, DecodeState) or state._model is not self:
+            raise ValueError('state must be a DecodeState of this model')
+        tp, dev, keep = _tok_ptr(tokens)
+        if keep is not None and keep.shape != (state.rows, self.max_len):
+            raise ValueError('tokens must be [%d, %d], got %r' % (state.rows, self.max_len, keep.shape))
+        ln = None
+        if lengths is not None:
+            ln = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+            if ln.size != state.rows:
+                raise ValueError('%d lengths for %d rows' % (ln.size, state.rows))
+        c = FsmgStateConfig(version=FSMG_STATE_CONFIG_VERSION, tokens_on_device=dev)
+        return c, tp, (ln.ctypes.data_as(_I32P) if ln is not None else None), (keep, ln)
+
+    def score_state(self, state, tokens, lengths=None, rank=False, entropy=False, argmax=False):
+        """fsmg_score's outputs for one segment read from `state`, which is left advanced: dict of 'logprob' float32 [rows, max_len],
+        'row_nll' [rows] (over the scored positions; NaN for a row of length 0) and, on request, 'rank', 'entropy', 'argmax';
+        everything behind a row's length is 0"""
+        c, tp, lp, _keep = self._state_args(state, tokens, lengths)
+        n = (state.rows, self.max_len)
+        out = dict(logprob=np.empty(n, np.float32), row_nll=np.empty(state.rows, np.float32))
+        if rank:
+            out['rank'] = np.empty(n, np.int32)
+        if entropy:
+            out['entropy'] = np.empty(n, np.float32)
+        if argmax:
+            out['argmax'] = np.empty(n, np.int32)
+        state._call(self._lib.fsmg_score_state, C.byref(c), tp, lp, _f32p(out['logprob']),
+                    out['rank'].ctypes.data_as(_I32P) if rank else None, _f32p(out['entropy']) if entropy else None,
+                    out['argmax'].ctypes.data_as(_I32P) if argmax else None, _f32p(out['row_nll']))
+        return out
+
+    def eval_step_state(self, state, tokens, lengths=None):
+        """-> (nll, n_valid): the segment's NLL over its n_valid scored positions; advances the state.  Segments of one stream combine
+        as sum(nll_i * n_i) / sum(n_i)."""
+        c, tp, lp, _keep = self._state_args(state, tokens, lengths)
+        nll, nv = C.c_float(), C.c_int32()
+        state._call(self._lib.fsmg_eval_step_state, C.byref(c), tp, lp, C.byref(nll), C.byref(nv))
+        return nll.value, int(nv.value)
+
+    def forward_backward_state(self, state, tokens, lengths=None):
+        """loss and gradients of the segment with the incoming state held constant (truncated BPTT); apply_update follows, as after
+        forward_backward_masked.  Advances the state."""
+        c, tp, lp, _keep = self._state_args(state, tokens, lengths)
+        state._call(self._lib.fsmg_forward_backward_state, C.byref(c), tp, lp)
+
+    def train_step_state(self, state, tokens, lengths=None):
+        """the fused step on one segment -> its loss; advances the state"""
+        c, tp, lp, _keep = self._state_args(state, tokens, lengths)
+        loss = C.c_float()
+        state._call(self._lib.fsmg_train_step_state, C.byref(c), tp, lp, C.byref(loss))
+        return loss.value
 
     def maml_generate(self, support, num, inner_steps, inner_lr, n_seq=1, temperature=1.0, top_k=0, seed=0, primer=None,
                       logprobs=False, n_support_rows=None, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0,

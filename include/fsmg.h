@@ -1039,6 +1039,68 @@ int fsmg_dropout_info(fsmg_handle h, int64_t out[4]);
 int fsmg_dropout_set_pass(fsmg_handle h, int64_t next_pass);
 int fsmg_dropout_mask(fsmg_handle h, int64_t pass, int32_t site, int32_t B, uint8_t* out);
 
+/* ---- batched passes from a carried LSTM state: truncated BPTT, scoring and evaluation over segments.
+ * Every batched pass above starts each row from a zero state and reads [start word, x_0 .. x_{T-2}].  A STATE PASS starts from a decode
+ * state (fsmg_dstate_*, above) and leaves it advanced, on the train path's kernels: one persistent launch per layer and direction and
+ * one projection GEMM per pass, where fsmg_dstate_feed pays a launch per position and layer.  A song longer than max_len is walked in
+ * segments of T = max_len tokens on one state: scored or evaluated under its full context, trained with truncated BPTT.
+ * A state pass over tokens [R][T] (R == the state's rows, ids in [0, input_size); host, or device with c->tokens_on_device) takes
+ * optional HOST lengths [R], each in [0, T], NULL = all T, at least one > 0 (host memory even with device tokens: the host must know them).
+ *   Inputs     row b reads [pending_b, x_0 .. x_{T-2}], pending_b the state's pending token (the start word on a fresh state), against
+ *              the targets x_0 .. x_{T-1}.  Layer l starts from the state's h[l][b], c[l][b] instead of zeros.
+ *   Scored     position t iff t < len[b].  Weights, n_valid, loss and dlogits are those of the masked passes with one
+ *              group over all R rows; positions t >= len[b] get the masked passes' fixed ids (input: the start word, target: 0), so
+ *              nothing depends on what the caller put behind a row's end.  A row with len[b] == 0 reads the start word at position 0 too.
+ *   Gradients  those of the segment with the incoming state held CONSTANT (truncated BPTT): nothing flows into the previous segment --
+ *              dh, dc arriving at slot 0 are dropped -- and the recurrent weight gradient includes h_{-1}^T dZ_0 with the imported h.
+ *              The embedding gradient of position 0 goes to the pending token's row.
+ *   State      after a successful call h[l][b], c[l][b] are slot len[b] of the pass's hidden / cell states, bit for bit (len[b] == T: the
+ *              end of the segment; len[b] == 0: the row's state as it was).  The context gains the T tokens y[b][t] = x[b][t] for
+ *              t < len[b] and, behind them, the last real token repeated (x[b][len[b]-1], or the old pending token when len[b] == 0): the
+ *              rows stay in lockstep, n_ctx += T, n_gen is unchanged, the last context token -- x[b][len[b]-1] -- is pending.  The
+ *              repetition penalty counts distinct ids, so the repeats add nothing to its set.
+ *   Untouched  an argument error, a token-range error and a skipped step leave the state exactly as it was (host tokens are checked
+ *              before any device work; device tokens and time-outs by the flag the pass raises on the device: the export reads it).
+ *   Time-out   a persistent kernel's time-out repeats the pass on per-step launches as everywhere else; the repeat imports the same
+ *              state again and the state advances once.
+ *   Order      a state pass runs the serial order -- single-stream, eager, no XCD-partitioned or two-stream order, no graph replay --
+ *              and inside it every kernel choice (recurrence family, GEMM kernels, fused softmax) is the handle's.  Enabled dropout
+ *              composes (non-recurrent sites only); a dropped state pass takes a pass index like any dropped train pass.
+ * On a fresh state every call is bitwise its masked twin over one pass of R rows (fsmg_score_masked, fsmg_eval_step_masked,
+ * fsmg_forward_backward_masked, fsmg_train_step_masked with N = 1, K = 0, Q = R).  Every stateless entry point returns the bits it
+ * returned before state passes existed.
+ *   fsmg_score_state             fsmg_score's five outputs ([R][T], out_row_nll [R]; any may be NULL, not all) treated as fsmg_score_masked
+ *                                treats them: 0 behind a row's end, out_row_nll over the scored positions (NaN for a row of length 0).
+ *                                Advances st; changes nothing else that fsmg_score does not change.
+ *   fsmg_eval_step_state         *nll = the segment's summed NLL over its n_valid (fsmg_eval_step_masked's number for one group);
+ *                                *n_valid (may be NULL) = the sum of the lengths, so that segments combine as sum(nll_i n_i) / sum(n_i).
+ *                                Advances st.
+ *   fsmg_forward_backward_state  loss and gradients as above, then fsmg_apply_update -- fsmg_forward_backward_masked's contract (loss
+ *                                ring, buckets, fsmg/dist.py's forward/backward + all-reduce + apply route).  Advances st; synchronises
+ *                                the stream once to learn whether the device advanced it.
+ *   fsmg_train_step_state        the fused step, fsmg_train_step_masked's contract with a non-NULL loss (the read-back is how the call
+ *                                learns that the step and the state went through; a timed-out step is repeated inside).  Advances st.
+ * MAML-style, Meta-SGD, cache and dynamic-evaluation calls stay stateless.
+ * Errors, before any device work and with nothing touched: FSMG_ERR_INVALID for a state this handle does not own, more rows than
+ * FSMG_STATE_PASS_ROWS, a length outside [0, T] or all lengths 0, a wrong version or nonzero reserved fields, tokens_on_device not
+ * 0 / 1, NULL tokens (or config, or the outputs named above); FSMG_ERR_TOKEN_RANGE for a host id outside [0, input_size);
+ * FSMG_ERR_STATE for the two gradient calls on a handle with a library communicator (fsmg_comm_*): a step that a peer rank makes every
+ * rank skip would leave this rank's state advanced -- exchange the gradients outside the library (fsmg/dist.py). */
+#define FSMG_STATE_CONFIG_VERSION 1
+#define FSMG_STATE_PASS_ROWS 1024          /* rows of one state pass at the most */
+typedef struct fsmg_state_config {
+    int32_t version;            /* FSMG_STATE_CONFIG_VERSION                                   */
+    int32_t tokens_on_device;   /* 0 / 1                                                       */
+    int32_t reserved[6];        /* must be 0                                                   */
+} fsmg_state_config;
+int fsmg_score_state(fsmg_handle h, fsmg_dstate st, const fsmg_state_config* c, const int32_t* tokens, const int32_t* lengths,
+                     float* out_logprob, int32_t* out_rank, float* out_entropy, int32_t* out_argmax, float* out_row_nll);
+int fsmg_eval_step_state(fsmg_handle h, fsmg_dstate st, const fsmg_state_config* c, const int32_t* tokens, const int32_t* lengths,
+                         float* nll, int32_t* n_valid);
+int fsmg_forward_backward_state(fsmg_handle h, fsmg_dstate st, const fsmg_state_config* c, const int32_t* tokens, const int32_t* lengths);
+int fsmg_train_step_state(fsmg_handle h, fsmg_dstate st, const fsmg_state_config* c, const int32_t* tokens, const int32_t* lengths,
+                          float* loss);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
@@ -1163,7 +1225,7 @@ int fsmg_debug_step_profile(fsmg_handle h, int32_t which, uint64_t* stamps, int6
                             int32_t* n_waves);
 /* per-kernel-class HIP-event timing on the handle's stream (disables graph replay while on).
  * classes: "gemm_zx","lstm_fwd","gemm_logits","ce","gemm_dhout","gemm_dw","lstm_bwd",
- * "gemm_dk","gemm_dx","embed_grad","update" */
+ * "gemm_dk","gemm_dx","embed_grad","update","state_import","state_export" (the last two: state passes only) */
 int fsmg_timing_enable(fsmg_handle h, int32_t on);
 /* restrict event timing to ONE kernel class (NULL or "" = all classes): two event records per
  * launch of that class, cheap enough to leave on inside a throughput measurement */
