@@ -125,6 +125,7 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
     else if (!std::strcmp(what, "dh")) { src = h->dH; cap = rows * Hp; }
     else if (!std::strcmp(what, "gnorm")) { src = h->d_gnorm; cap = 1; }
     else if (!std::strcmp(what, "tail")) { src = h->G + h->n_flat; cap = FSMG_GRAD_TAIL; }
+    else if (!std::strcmp(what, "task_loss")) { src = h->d_task_loss; cap = h->task_loss_n; }      // L_n of the last per-artist train call
     else if ((l = layer_of("gates")) >= 0) { src = h->Z[l]; cap = rows * G4; }
     else if ((l = layer_of("h")) >= 0) { src = h->Hs[l]; cap = (T + 1) * B * Hp; }
     else if ((l = layer_of("c")) >= 0) { src = h->Cs[l]; cap = (T + 1) * B * Hp; }

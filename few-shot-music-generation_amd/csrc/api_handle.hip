@@ -364,6 +364,8 @@ int fsmg_destroy(fsmg_handle h) {
     if (h->khx) hipFree(h->khx);
     if (h->P_saved) hipFree(h->P_saved);
     if (h->P_adapted) hipFree(h->P_adapted);
+    if (h->task_acc) hipFree(h->task_acc);
+    if (h->d_task_loss) hipFree(h->d_task_loss);
     if (h->dyn_stats) hipFree(h->dyn_stats);
     if (h->dyn_out) hipFree(h->dyn_out);
     if (h->msgd_state) hipFree(h->msgd_state);

@@ -611,6 +611,17 @@ int window_rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int
     return rc;
 }
 int pass_flag(fsmg_model* h) { return adapt_flag(h); }
+int dp_train_step_fn(fsmg_model* h, float* loss, const std::function<int()>& forward_backward) { return dp_train_step(h, loss, forward_backward); }
+int maml_adapt_rows(fsmg_model* h, const int32_t* support, int32_t N, int32_t K, int32_t inner_steps, float inner_lr, int32_t on_device,
+                    const int32_t* support_len, bool train) {
+    return maml_adapt(h, support, N, K, inner_steps, inner_lr, on_device, support_len, train);
+}
+int masked_query_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t N, int32_t R, int32_t on_device) {
+    return masked_rows_pass(h, rows, len, N, R, on_device);
+}
+int gather_episode_rows(fsmg_model* h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry, bool with_len) {
+    return gather_episode(h, table_id, sup_idx, n_sup, qry_idx, n_qry, with_len);
+}
 
 // adapt on the support rows like fsmg_maml_eval, run the body at theta', restore theta whatever happened; one repeat on per-step
 // launches when the adaptation ran garbage (skipped) steps.  The MAML decode entry points (api_decode.hip) run through here.

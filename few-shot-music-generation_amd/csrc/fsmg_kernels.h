@@ -430,6 +430,19 @@ struct MsgdAlphaArgs {
 };
 hipError_t launch_msgd_alpha_update(hipStream_t s, const MsgdAlphaArgs& a);
 
+// ---------------------------------------------------------------- per-artist MAML: the fold behind an artist's query pass (tasks.hip)
+// g holds the artist's gradient [n] and its tail (g + n: [0] slice sum of squares, [1] loss, [2..5] indicators), acc [n + FSMG_GRAD_TAIL]
+// the running fold.  first: acc = w * g; otherwise fma(w, g, acc), written to acc or -- last -- to g.  first && last: g is left alone.
+// Tail: [0] folds with w * w, [1] with w, [2..5] are 1.0f where any artist's was non-zero, the other words are left alone.
+// s != nullptr (Meta-SGD): r = -(g * s), one rounding, folded by the same rule in place in ga (first && last: ga = r).
+// p = p_saved in the same pass; *task_loss = g[n + 1] (may be null).  20 B per element without the rates (first: 16), 32 with them.
+// n a multiple of 4.
+struct TaskFoldArgs {
+    float* g; float* acc; float* p; const float* p_saved; const float* s; float* ga; long long n;
+    float w; int first, last; float* task_loss;
+};
+hipError_t launch_task_fold(hipStream_t s, const TaskFoldArgs& a);
+
 // ---------------------------------------------------------------- dropout of the train passes (dropout.hip)
 // One site of one pass: element (r, j), r a device row (t * B + b), j < W of a row of ld floats (ld a multiple of 4), is kept iff
 // (word >> 8) < thr, word = output j & 3 of Philox4x32-10(counter (j >> 2, variational ? r % B : r, site, pass), key (key0, key1));

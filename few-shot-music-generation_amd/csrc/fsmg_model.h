@@ -147,6 +147,10 @@ struct fsmg_model {
     float* khf = nullptr;               // fragment-ordered recurrent weights: per layer fwd copy, bwd copy
     float* P_saved = nullptr;           // cfg-E: theta while the handle computes at the adapted theta'
     float* P_adapted = nullptr;         // fsmg_debug_set("keep_adapted", 1): the last theta', copied right before theta came back (tests read it:
+    // per-artist MAML, allocated by the first fsmg_maml_tasks_* train call and kept until fsmg_destroy; not part of fsmg_state_bytes
+    float* task_acc = nullptr;          // [n_flat + FSMG_GRAD_TAIL]: the fold of the artists so far
+    float* d_task_loss = nullptr;       // [task_loss_cap]: L_n of the last tasks train call
+    int task_loss_cap = 0, task_loss_n = 0;
     bool keep_adapted = false;          // fsmg_debug_read("adapted:<parameter name>")); never allocated, never written while the knob is 0
     bool have_adapted = false;
     static constexpr int MAX_TABLES = 4;
@@ -781,6 +785,14 @@ int validate_shape(fsmg_model* h, int N, int K, int Q);
 // happened -- with_adapted_theta's twin (fsmg_dyneval_generate, api_decode.hip)
 int with_dyneval_theta(fsmg_model* h, const fsmg_dyneval_config* c, const int32_t* support, const int32_t* support_len, int32_t n_support_rows,
                        const std::function<int()>& at_theta_l);
+// api_step.hip, for the per-artist driver (api_tasks.hip): the adaptation, the masked K = 0 pass and the episode gather of the
+// fsmg_maml_* entry points as they stand
+int maml_adapt_rows(fsmg_model* h, const int32_t* support, int32_t N, int32_t K, int32_t inner_steps, float inner_lr, int32_t on_device,
+                    const int32_t* support_len, bool train);
+int masked_query_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t N, int32_t R, int32_t on_device);
+int gather_episode_rows(fsmg_model* h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry, bool with_len);
+int validate_masked_args(fsmg_model* h, const int32_t* support_len, const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int32_t on_device);
+int dp_train_step_fn(fsmg_model* h, float* loss, const std::function<int()>& forward_backward);     // the library-owned exchange around it
 int poll_skipped(fsmg_model* h);
 int report(fsmg_model* h, int what);
 int check_tokens_and_read(fsmg_model* h, const float* d_src, float scale, float* host_out, int n, bool train_tail = false);

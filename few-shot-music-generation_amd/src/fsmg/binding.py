@@ -140,6 +140,11 @@ class FsmgDropoutConfig(C.Structure):
                 ('seed', C.c_uint64)]
 
 
+class FsmgMamlTasksConfig(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('inner_steps', C.c_int32), ('inner_lr', C.c_float), ('tokens_on_device', C.c_int32),
+                ('table_id', C.c_int32), ('use_table_lengths', C.c_int32), ('reserved', C.c_int32 * 2)]
+
+
 FSMG_STATE_CONFIG_VERSION = 1
 FSMG_STATE_PASS_ROWS = 1024
 
@@ -308,6 +313,9 @@ SIGNATURES = {
     'fsmg_eval_step_state': (C.c_int, [_P, _P, C.POINTER(FsmgStateConfig), _P, _I32P, _F32P, _I32P]),
     'fsmg_forward_backward_state': (C.c_int, [_P, _P, C.POINTER(FsmgStateConfig), _P, _I32P]),
     'fsmg_train_step_state': (C.c_int, [_P, _P, C.POINTER(FsmgStateConfig), _P, _I32P, _F32P]),
+    'fsmg_maml_tasks_forward_backward': (C.c_int, [_P, C.POINTER(FsmgMamlTasksConfig), _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    'fsmg_maml_tasks_step': (C.c_int, [_P, C.POINTER(FsmgMamlTasksConfig), _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _F32P, _F32P]),
+    'fsmg_maml_tasks_eval': (C.c_int, [_P, C.POINTER(FsmgMamlTasksConfig), _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _F32P, _F32P]),
 }
 
 _lib = None
@@ -841,6 +849,59 @@ class FsmgModel(object):
                                                          s.shape[0], s.shape[1], q.shape[1], int(inner_steps), float(inner_lr),
                                                          C.byref(loss) if want_loss else None))
         return loss.value if want_loss else None
+
+    # -- per-artist MAML (include/fsmg.h "per-artist MAML"): one adaptation per artist -----------
+    def _maml_tasks_args(self, support, query, inner_steps, inner_lr, support_len, query_len, table, table_lengths, shape):
+        """(config, support, query, support_len, query_len, N, K, Q) of a tasks call and what must stay alive behind it.
+        table=None: support [N,K,T] / query [N,Q,T] tokens (or device addresses with shape=), lengths optional and together;
+        table=id: support [N,K] / query [N,Q] row indices into that table, table_lengths says whether its lengths mask the passes"""
+        cfg = FsmgMamlTasksConfig()
+        cfg.struct_size = C.sizeof(FsmgMamlTasksConfig)
+        cfg.inner_steps, cfg.inner_lr, cfg.table_id, cfg.use_table_lengths = int(inner_steps), float(inner_lr), -1, 0
+        if table is not None:
+            if support_len is not None or query_len is not None:
+                raise ValueError('a table call takes the table\'s lengths (table_lengths=True), not length arrays')
+            s, q = self._idx(support, query)
+            cfg.table_id, cfg.use_table_lengths = int(table), 1 if table_lengths else 0
+            return (cfg, C.c_void_p(s.ctypes.data), C.c_void_p(q.ctypes.data), None, None, s.shape[0], s.shape[1], q.shape[1]), (s, q)
+        if table_lengths:
+            raise ValueError('table_lengths needs table=')
+        if (support_len is None) != (query_len is None):
+            raise ValueError('support_len and query_len go together')
+        n, k, q = self._episode_shape(support, query, shape)
+        sp, dev, k1 = _tok_ptr(support)
+        qp, _, k2 = _tok_ptr(query)
+        cfg.tokens_on_device = dev
+        sl = ql = k3 = k4 = None
+        if support_len is not None:
+            sl, k3 = self._len_ptr(support_len, n * k, dev)
+            ql, k4 = self._len_ptr(query_len, n * q, dev)
+        return (cfg, sp, qp, sl, ql, n, k, q), (k1, k2, k3, k4)
+
+    def maml_tasks_forward_backward(self, support, query, inner_steps, inner_lr, support_len=None, query_len=None, table=None,
+                                    table_lengths=False, shape=None):
+        a, _keep = self._maml_tasks_args(support, query, inner_steps, inner_lr, support_len, query_len, table, table_lengths, shape)
+        self._ck(self._lib.fsmg_maml_tasks_forward_backward(self._h, C.byref(a[0]), *a[1:]))
+
+    def maml_tasks_step(self, support, query, inner_steps, inner_lr, support_len=None, query_len=None, table=None, table_lengths=False,
+                        shape=None, want_loss=True, task_loss=False):
+        """the mean of the per-artist query losses (None without want_loss); task_loss=True: (loss, [N] float32 array of L_n)"""
+        a, _keep = self._maml_tasks_args(support, query, inner_steps, inner_lr, support_len, query_len, table, table_lengths, shape)
+        loss = C.c_float()
+        per = np.empty(a[5], dtype=np.float32) if task_loss else None
+        self._ck(self._lib.fsmg_maml_tasks_step(self._h, C.byref(a[0]), *a[1:], C.byref(loss) if want_loss else None,
+                                                _f32p(per) if task_loss else None))
+        out = loss.value if want_loss else None
+        return (out, per) if task_loss else out
+
+    def maml_tasks_eval(self, support, query, inner_steps, inner_lr, support_len=None, query_len=None, table=None, table_lengths=False,
+                        shape=None, task_nll=False):
+        """the mean over the artists of the query NLL at that artist's theta'; task_nll=True: (nll, [N] float32 array)"""
+        a, _keep = self._maml_tasks_args(support, query, inner_steps, inner_lr, support_len, query_len, table, table_lengths, shape)
+        nll = C.c_float()
+        per = np.empty(a[5], dtype=np.float32) if task_nll else None
+        self._ck(self._lib.fsmg_maml_tasks_eval(self._h, C.byref(a[0]), *a[1:], C.byref(nll), _f32p(per) if task_nll else None))
+        return (nll.value, per) if task_nll else nll.value
 
     def eval_step(self, query, shape=None):
         if shape is None:

@@ -70,7 +70,9 @@ class EpisodeParallel(object):
         rank normalises by its own n_valid and grad_scale = 1 / world takes the mean of those, as for the unmasked step;
         maml_lengths=(support_len, query_len), only with maml=: the cfg-E step with per-song lengths (with table=id:
         maml_lengths=True, the table's own lengths) -- every inner step over the support rows' valid positions, the outer gradient
-        over the query rows', each rank by its own n_valid"""
+        over the query rows', each rank by its own n_valid;
+        maml_tasks=True, only with maml=: the per-artist form of the cfg-E step -- one adaptation per artist of the
+        episode, the mean of the artists' query gradients; every combination maml= takes (tokens, table=, maml_lengths) is taken"""
         try:
             return self._train_step_once(support, query, want_loss, **kw)
         except Exception as e:
@@ -82,7 +84,7 @@ class EpisodeParallel(object):
                 raise
             return self._train_step_once(support, query, want_loss, **kw)
 
-    def _train_step_once(self, support, query, want_loss=True, maml=None, table=None, lengths=None, maml_lengths=None, **kw):
+    def _train_step_once(self, support, query, want_loss=True, maml=None, table=None, lengths=None, maml_lengths=None, maml_tasks=False, **kw):
         if lengths is not None:
             if maml is not None:
                 raise ValueError('the MAML-style step takes no lengths')
@@ -94,6 +96,10 @@ class EpisodeParallel(object):
             if (maml_lengths is True) != (table is not None):
                 raise ValueError('maml_lengths is (support_len, query_len) for tokens and True for table= (the table\'s own lengths)')
             mkw['maml_lengths'] = maml_lengths      # (only a masked MAML-style step hands the keyword to the engine)
+        if maml_tasks:
+            if maml is None:
+                raise ValueError('maml_tasks goes with maml=(inner_steps, inner_lr) only')
+            mkw['maml_tasks'] = True                # (only a per-artist step hands the keyword to the engine)
         if self.world == 1 and maml is None and hasattr(self.engine, 'fused_train_step'):
             return self.engine.fused_train_step(support, query, want_loss=want_loss, table=table, **kw)
         if self.world == 1 and maml is not None and table is not None and hasattr(self.engine, 'fused_maml_step'):

@@ -91,7 +91,11 @@ class HIPModel(BaseModel):
         self._model.forward_backward_indexed(table_id, support_idx, query_idx)
 
     # (maml_lengths: the cfg-E step with per-song lengths -- (support_len, query_len), or True for the lengths uploaded with a table)
-    def maml_forward_backward(self, support, query, inner_steps, inner_lr, maml_lengths=None, **kw):
+    # (maml_tasks: the per-artist form, DESIGN.md 27 -- one entry point for tokens, lengths and the table)
+    def maml_forward_backward(self, support, query, inner_steps, inner_lr, maml_lengths=None, maml_tasks=False, **kw):
+        if maml_tasks:
+            sl, ql = maml_lengths if maml_lengths is not None else (None, None)
+            return self._model.maml_tasks_forward_backward(support, query, inner_steps, inner_lr, support_len=sl, query_len=ql, **kw)
         if maml_lengths is not None:
             return self._model.maml_forward_backward_masked(support, query, maml_lengths[0], maml_lengths[1], inner_steps, inner_lr, **kw)
         self._model.maml_forward_backward(support, query, inner_steps, inner_lr, **kw)
@@ -112,6 +116,12 @@ class HIPModel(BaseModel):
 
     def fused_maml_step(self, support, query, inner_steps, inner_lr, want_loss=True, table=None, **kw):
         maml_lengths = kw.pop('maml_lengths', None)
+        if kw.pop('maml_tasks', False):
+            if table is not None:
+                return self._model.maml_tasks_step(support, query, inner_steps, inner_lr, table=table, table_lengths=maml_lengths is not None,
+                                                   want_loss=want_loss)
+            sl, ql = maml_lengths if maml_lengths is not None else (None, None)
+            return self._model.maml_tasks_step(support, query, inner_steps, inner_lr, support_len=sl, query_len=ql, want_loss=want_loss, **kw)
         if table is not None and maml_lengths is not None:
             return self._model.maml_step_indexed_masked(table, support, query, inner_steps, inner_lr, want_loss=want_loss)
         if table is not None:       # support / query are row indices into the device-resident split table
@@ -121,7 +131,10 @@ class HIPModel(BaseModel):
                                                 want_loss=want_loss, **kw)
         return self._model.maml_step(support, query, inner_steps, inner_lr, want_loss=want_loss, **kw)
 
-    def maml_forward_backward_indexed(self, table_id, support_idx, query_idx, inner_steps, inner_lr, maml_lengths=None):
+    def maml_forward_backward_indexed(self, table_id, support_idx, query_idx, inner_steps, inner_lr, maml_lengths=None, maml_tasks=False):
+        if maml_tasks:
+            return self._model.maml_tasks_forward_backward(support_idx, query_idx, inner_steps, inner_lr, table=table_id,
+                                                           table_lengths=maml_lengths is not None)
         if maml_lengths is not None:
             return self._model.maml_forward_backward_indexed_masked(table_id, support_idx, query_idx, inner_steps, inner_lr)
         self._model.maml_forward_backward_indexed(table_id, support_idx, query_idx, inner_steps, inner_lr)

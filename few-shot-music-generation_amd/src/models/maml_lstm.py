@@ -20,7 +20,11 @@ adaptation of deep networks") as the direction the project was heading.  This pl
 Extra config keys: inner_steps (default 1), inner_lr (default 0.1), maml_lengths (default false: every path is what it was;
 true: per-song lengths, DESIGN.md 22 -- every inner step averages over the positions inside a support song, the outer gradient and
 the NLL over the positions inside a query song: train / train_indexed / eval read Episode.support_len / query_len or the lengths
-handed to attach_table, generate / beam_search / score take support_len=, and a missing length is a ValueError).
+handed to attach_table, generate / beam_search / score take support_len=, and a missing length is a ValueError),
+maml_per_artist (default false: every path is what it was; true: the episode is a meta-batch of N tasks, DESIGN.md 27 -- train /
+train_indexed / eval / eval_many adapt once per artist, on that artist's support songs alone, and report the mean over the artists of
+the query NLL at that artist's theta', which is the procedure generate / beam_search / score run for one artist; works with
+maml_lengths).
 """
 import numpy as np
 
@@ -29,9 +33,11 @@ from models.lstm_baseline import LSTMBaseline
 
 class MAMLLSTM(LSTMBaseline):
     MASKS_PADDING = False        # `mask_padding: true` (the baseline's one-pass loss) is refused at construction; cfg-E's key is maml_lengths
+    maml_per_artist = False      # config key `maml_per_artist`: one adaptation per artist in train / train_indexed / eval
     def __init__(self, config):
         super(MAMLLSTM, self).__init__(config)
         self.maml_lengths = bool(config.get('maml_lengths', False))
+        self.maml_per_artist = bool(config.get('maml_per_artist', False))
         self._inner_steps = int(config.get('inner_steps', 1))
         self._inner_lr = float(config.get('inner_lr', 0.1))
         if self._inner_steps < 0 or self._inner_lr < 0:
@@ -67,6 +73,8 @@ class MAMLLSTM(LSTMBaseline):
     def train(self, episode):
         self._require_init()
         kw = dict(maml_lengths=tuple(self._episode_lengths(episode, ('support', 'query')))) if self.maml_lengths else {}
+        if self.maml_per_artist:
+            kw['maml_tasks'] = True
         loss = self._parallel.train_step(self._tokens(episode.support, 3), self._tokens(episode.query, 3),
                                          maml=(self._inner_steps, self._inner_lr), **kw)
         self._log_scalar('Train/loss', loss, self._train_calls)
@@ -83,7 +91,8 @@ class MAMLLSTM(LSTMBaseline):
         loss = self._parallel.train_step(np.ascontiguousarray(support_idx, dtype=np.int32),
                                          np.ascontiguousarray(query_idx, dtype=np.int32), want_loss=want_loss,
                                          table=self.TABLE_IDS[split], maml=(self._inner_steps, self._inner_lr),
-                                         **(dict(maml_lengths=True) if self.maml_lengths else {}))
+                                         **(dict(maml_lengths=True) if self.maml_lengths else {}),
+                                         **(dict(maml_tasks=True) if self.maml_per_artist else {}))
         if want_loss:
             self._log_scalar('Train/loss', loss, self._train_calls)
         self._train_calls += 1
@@ -91,7 +100,11 @@ class MAMLLSTM(LSTMBaseline):
 
     def eval(self, episode):
         self._require_init()
-        if self.maml_lengths:
+        if self.maml_per_artist:
+            sl, ql = self._episode_lengths(episode, ('support', 'query')) if self.maml_lengths else (None, None)
+            nll = self._model.maml_tasks_eval(self._tokens(episode.support, 3), self._tokens(episode.query, 3),
+                                              self._inner_steps, self._inner_lr, support_len=sl, query_len=ql)
+        elif self.maml_lengths:
             sl, ql = self._episode_lengths(episode, ('support', 'query'))
             nll = self._model.maml_eval_masked(self._tokens(episode.support, 3), self._tokens(episode.query, 3), sl, ql,
                                                self._inner_steps, self._inner_lr)

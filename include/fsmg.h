@@ -1101,6 +1101,54 @@ int fsmg_forward_backward_state(fsmg_handle h, fsmg_dstate st, const fsmg_state_
 int fsmg_train_step_state(fsmg_handle h, fsmg_dstate st, const fsmg_state_config* c, const int32_t* tokens, const int32_t* lengths,
                           float* loss);
 
+/* ---- per-artist MAML: one adaptation per artist.  fsmg_maml_forward_backward adapts once, on the N * K support rows of
+ * all N artists, and takes the query gradient of all N * Q rows at that one theta'.  The calls below treat the episode as a meta-batch of
+ * N tasks: support [N][K][max_len], query [N][Q][max_len], optional lengths [N][K] / [N][Q].  For artist n = 0 .. N-1 in that order,
+ * w = (float)(1.0 / N):
+ *   1. adapt: theta' starts at theta and takes inner_steps inner steps on artist n's K support rows alone -- exactly the adaptation of
+ *      fsmg_maml_forward_backward (or _masked, with lengths) for N = 1, K: the pass, the norm of that artist's gradient, the clip, the
+ *      skip conditions, the Meta-SGD element step and its S (zeroed per artist), dropout's pass counter.
+ *   2. query pass: the K = 0 train pass over artist n's Q query rows at theta'_n: G_n, its tail, the loss L_n (masked: over artist n's
+ *      own n_valid -- a mean of per-artist means, the convention of the episode-parallel exchange).
+ *   3. fold, one launch: n == 0: ACC[j] = w * G_n[j], one rounding (N == 1: nothing is folded, G keeps its bits, -0 included);
+ *      n > 0: ACC[j] = fma(w, G_n[j], ACC[j]); the last artist's result goes to the flat gradient buffer, so fsmg_grad_buffer, the
+ *      buckets and fsmg_get_grad see the folded gradient.  Tail: [0] folds with w * w (the N IndexedSlices concatenated), [1] with w,
+ *      [2] .. [5] are non-zero if any artist's was.  Meta-SGD enabled: GA_n[j] = -(G_n[j] * S_n[j]), one rounding, folded by the same
+ *      rule into the rate gradient.  Theta comes back in the same launch; pad elements stay exact zeros.
+ *   4. afterwards theta is back bitwise whatever happened, Adam slots and global_step are untouched, a gradient (and with Meta-SGD a rate
+ *      gradient) is pending for fsmg_apply_update(grad_scale); fsmg_debug_set("keep_adapted", 1) keeps theta' of artist N - 1.
+ * N == 1: every tasks call has the bits of its fsmg_maml_* twin.  Any N: theta'_n, G_n and L_n have the bits of N separate N = 1 calls of
+ * the existing entry points on the same handle state; the returned buffer is their fold by the rule above.
+ * fsmg_maml_tasks_eval: per artist the eval-form adaptation (never dropped, S untouched) and the query NLL_n of fsmg_maml_eval / _masked
+ * for N = 1; *nll = (float)(sum_n (double)NLL_n / N), in artist order.  No gradient is pending afterwards.
+ * support_len == query_len == NULL selects the unmasked passes; one NULL and one non-NULL is FSMG_ERR_INVALID.  table_id >= 0: support /
+ * query are host row indices into that table, support_len / query_len must be NULL and use_table_lengths says whether the pass is masked.
+ * fsmg_maml_tasks_step is to fsmg_maml_tasks_forward_backward what fsmg_maml_step is to fsmg_maml_forward_backward: loss == NULL leaves
+ * the loss in the ring, an attached communicator makes it the library-owned exchange, and after a time-out the whole call is repeated
+ * once on per-step launches with dropout's pass counter put back.  task_loss / task_nll [N] are read back only when non-NULL;
+ * fsmg_debug_read("task_loss") reads the [N] losses L_n of the last tasks train call.  Timing classes "task_fold" (the fold's kernel)
+ * and "tasks" (a train call's loop over the artists).
+ * Errors, before any device work and with nothing touched: FSMG_ERR_INVALID for a NULL handle / config / token pointer, struct_size not
+ * sizeof(fsmg_maml_tasks_config), nonzero reserved words, inner_steps outside [0, 64], inner_lr negative or NaN, tokens_on_device or
+ * use_table_lengths not 0 / 1, table_id outside [-1, 4), use_table_lengths or a length pointer at odds with table_id, a bad N / K / Q,
+ * a host length outside [1, max_len].  FSMG_ERR_STATE for a table (or its lengths) that was never uploaded.  A token or length out of
+ * range in any artist skips the update on the device and returns FSMG_ERR_TOKEN_RANGE. */
+typedef struct {
+    int32_t struct_size;       /* sizeof(fsmg_maml_tasks_config), else FSMG_ERR_INVALID          */
+    int32_t inner_steps;       /* [0, 64]                                                        */
+    float   inner_lr;          /* >= 0                                                           */
+    int32_t tokens_on_device;  /* 0 / 1; covers tokens and lengths                               */
+    int32_t table_id;          /* -1: tokens; [0, 4): host row indices into that table           */
+    int32_t use_table_lengths; /* 0 / 1, only with table_id >= 0                                 */
+    int32_t reserved[2];       /* must be 0                                                      */
+} fsmg_maml_tasks_config;
+int fsmg_maml_tasks_forward_backward(fsmg_handle h, const fsmg_maml_tasks_config* c, const int32_t* support, const int32_t* query,
+                                     const int32_t* support_len, const int32_t* query_len, int32_t N, int32_t K, int32_t Q);
+int fsmg_maml_tasks_step(fsmg_handle h, const fsmg_maml_tasks_config* c, const int32_t* support, const int32_t* query,
+                         const int32_t* support_len, const int32_t* query_len, int32_t N, int32_t K, int32_t Q, float* loss, float* task_loss);
+int fsmg_maml_tasks_eval(fsmg_handle h, const fsmg_maml_tasks_config* c, const int32_t* support, const int32_t* query,
+                         const int32_t* support_len, const int32_t* query_len, int32_t N, int32_t K, int32_t Q, float* nll, float* task_nll);
+
 /* ---- unigram baseline.  Replaces the graph of UnigramModel (src/models/unigram_model.py:26-39): a
  * word_count variable initialised to alpha = 1, tf.scatter_add of ones, prob = gather(word_count) / reduce_sum(word_count),
  * loss = -mean(log prob).  Counts live on the device as unsigned integers (exact, order-independent atomics) and cross the
