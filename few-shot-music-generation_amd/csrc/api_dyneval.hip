@@ -139,32 +139,27 @@ static int ensure_dyn_out(fsmg_model* h, int64_t words) {
 // repeated once on per-step launches.  (arguments checked by the caller; no BEGIN_CALL of its own beyond the passes')
 int dyneval_stream(fsmg_model* h, const fsmg_dyneval_config* c, const int32_t* tokens, const int32_t* len, int n_rows, int first_reported,
                    float* host_out, const std::function<int()>* body) {
-    int rc = FSMG_OK;
     const int64_t words = (int64_t)n_rows * h->T;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        rc = save_theta(h);
-        if (rc == FSMG_OK && c->rule == FSMG_DYNEVAL_RMS) rc = refresh_mean_rms(h);
-        if (rc == FSMG_OK && host_out) {
-            rc = ensure_dyn_out(h, words);
-            if (rc == FSMG_OK) HIPCK(h, launch_fill32(h->stream, h->dyn_out, 0u, round_up(words, 4)));
-        }
-        if (rc == FSMG_OK) rc = run_stream(h, c, tokens, len, n_rows, first_reported, host_out ? h->dyn_out : nullptr);
-        if (rc == FSMG_OK) rc = pass_flag(h);              // a time-out / token error inside the stream: its updates were skipped
-        if (rc == FSMG_OK && body) rc = (*body)();
-        if (rc == FSMG_OK && host_out) {
-            HIPCK(h, hipMemcpyAsync(host_out, h->dyn_out, sizeof(float) * (size_t)words, hipMemcpyDeviceToHost, h->stream));
-            HIPCK(h, hipStreamSynchronize(h->stream));
-        }
-        h->masked_call = false; h->window_call = false;
-        const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
-        int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
-        if (rc2 == FSMG_OK) rc2 = rc_keep;
-        h->have_grads = false;
-        if (rc == FSMG_OK) rc = rc2;
-        if (!(is_retry(rc) && h->retry_armed)) break;
-        h->retry_armed = false;                            // adapted with skipped steps: repeat on per-step launches
-    }
-    return rc;
+    return at_adapted_theta(
+        h,
+        [&]() {             // theta is saved and the mean RMS refreshed inside each attempt: a repeat starts from what the first one started from
+            int rc = save_theta(h);
+            if (rc == FSMG_OK && c->rule == FSMG_DYNEVAL_RMS) rc = refresh_mean_rms(h);
+            if (rc == FSMG_OK && host_out) {
+                rc = ensure_dyn_out(h, words);
+                if (rc == FSMG_OK) HIPCK(h, launch_fill32(h->stream, h->dyn_out, 0u, round_up(words, 4)));
+            }
+            if (rc == FSMG_OK) rc = run_stream(h, c, tokens, len, n_rows, first_reported, host_out ? h->dyn_out : nullptr);
+            return rc != FSMG_OK ? rc : adapt_flag(h);       // a time-out / token error inside the stream: its updates were skipped
+        },
+        [&]() {
+            const int rc = body ? (*body)() : FSMG_OK;
+            if (rc == FSMG_OK && host_out) {
+                HIPCK(h, hipMemcpyAsync(host_out, h->dyn_out, sizeof(float) * (size_t)words, hipMemcpyDeviceToHost, h->stream));
+                HIPCK(h, hipStreamSynchronize(h->stream));
+            }
+            return rc;
+        });
 }
 
 // fsmg_dyneval_generate's adapt-decode-restore (the decode body lives with the decode driver, api_decode.hip)

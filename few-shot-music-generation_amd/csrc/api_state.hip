@@ -99,7 +99,7 @@ int check_state_args(fsmg_model* h, fsmg_dstate st, const int32_t* tokens, const
 // the pass begins: behind BEGIN_CALL, which clears these
 void begin_state(fsmg_model* h, fsmg_dstate_s* st) {
     h->state_cur = st; h->state_len = h->d_len;
-    h->masked_call = true; h->mask_rpg = st->R; h->mask_groups = 1;
+    begin_masked(h, st->R, 1);
 }
 
 // a forward-only state pass over the state's R rows: launch() enqueues it (token_prep, forward, what reads the result) and read_back()

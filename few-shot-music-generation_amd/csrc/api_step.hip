@@ -1,4 +1,5 @@
-// Train / eval / MAML-style step entry points and the device-resident episode table.
+// Train / eval / MAML-style step entry points and the device-resident episode table; the drivers every adapting call shares (rows_pass,
+// maml_adapt, end_adaptation, at_adapted_theta, step_with_update; the Episode a MAML call runs on: DESIGN.md 28).
 // Host-side C++ only (part of the C-ABI of libfsmg, include/fsmg.h); every kernel lives in gemm.hip / lstm_*.hip / elementwise.hip.
 #include "fsmg_model.h"
 
@@ -89,8 +90,7 @@ int forward_backward_core(fsmg_model* h, int32_t N, int32_t K, int32_t Q, Stage&
 }
 
 // the episode-parallel step with the exchange inside the library: forward + backward, all-reduce, clip + Adam (1 / world)
-template <class FB>
-int dp_train_step(fsmg_model* h, float* loss, FB&& forward_backward) {
+int dp_train_step(fsmg_model* h, float* loss, const std::function<int()>& forward_backward) {
     const uint64_t drop_p0 = h->drop_next;      // a repeated step draws the masks of the passes it repeats
     for (int attempt = 0; attempt < 2; ++attempt) {
         h->drop_next = drop_p0;
@@ -135,10 +135,6 @@ int validate_masked_args(fsmg_model* h, const int32_t* support_len, const int32_
     if (rc != FSMG_OK || on_device) return rc;
     if ((rc = validate_lengths(h, support_len, (int64_t)N * K)) != FSMG_OK) return rc;
     return validate_lengths(h, query_len, (int64_t)N * Q);
-}
-// the call in progress is a padding-masked pass over `groups` groups of `rows_per_group` sequences (behind BEGIN_CALL, which clears the flag)
-inline void begin_masked(fsmg_model* h, int rows_per_group, int groups) {
-    h->masked_call = true; h->mask_rpg = rows_per_group; h->mask_groups = groups;
 }
 
 // forward + backward + update as ONE captured graph (17 us between two graph launches at cfg-B otherwise)
@@ -217,11 +213,35 @@ int fsmg_upload_table_lengths(fsmg_handle h, int32_t table_id, const int32_t* le
     return FSMG_OK;
 }
 
-static int stage_indexed(fsmg_handle h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry) {
+// d_gather / d_gather_len hold an episode of n rows: the MAML table forms' buffers, grown together with the indices'
+static int ensure_gather_buffers(fsmg_handle h, int n) {
+    if (h->idx_cap >= n && h->gather_cap >= (int64_t)n * h->T) return FSMG_OK;
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (h->d_idx) hipFree(h->d_idx);
+    if (h->d_gather) hipFree(h->d_gather);
+    if (h->d_gather_len) hipFree(h->d_gather_len);
+    h->d_idx = nullptr; h->d_gather = nullptr; h->d_gather_len = nullptr; h->idx_cap = 0; h->gather_cap = 0;
+    const int cap = std::max(n, 4096);
+    if (hipMalloc((void**)&h->d_idx, sizeof(int) * cap) != hipSuccess || hipMalloc((void**)&h->d_gather, sizeof(int) * (size_t)cap * h->T) != hipSuccess ||
+        hipMalloc((void**)&h->d_gather_len, sizeof(int) * cap) != hipSuccess)
+        return fail(h, FSMG_ERR_NOMEM, "hipMalloc(episode gather buffers) failed");
+    h->idx_cap = cap; h->gather_cap = (int64_t)cap * h->T;
+    return FSMG_OK;
+}
+
+// The one table gather: the rows sup_idx[0 .. n_sup) then qry_idx[0 .. n_qry) of the table under `table_id`, with_len: and their lengths
+// in the same launch (a table without lengths: FSMG_ERR_STATE).  episode: into d_gather / d_gather_len, where the passes of a MAML call
+// read them; otherwise into the staging buffers d_tok / d_len of the one pass that is about to run.  An index outside the table raises
+// the token-range flag like any bad token.
+static int gather_table_rows(fsmg_handle h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry, bool with_len,
+                             bool episode) {
     if (table_id < 0 || table_id >= fsmg_model::MAX_TABLES || !h->table[table_id]) return fail(h, FSMG_ERR_STATE, "no token table uploaded under this id");
-    if (h->masked_call && !h->table_len[table_id]) return fail(h, FSMG_ERR_STATE, "the table under this id has no lengths (fsmg_upload_table_lengths)");
+    if (with_len && !h->table_len[table_id]) return fail(h, FSMG_ERR_STATE, "the table under this id has no lengths (fsmg_upload_table_lengths)");
     const int n = n_sup + n_qry;
-    if (h->idx_cap < n) {
+    if (episode) {
+        const int rc = ensure_gather_buffers(h, n);
+        if (rc != FSMG_OK) return rc;
+    } else if (h->idx_cap < n) {
         HIPCK(h, hipStreamSynchronize(h->stream));
         if (h->d_idx) hipFree(h->d_idx);
         h->idx_cap = std::max(n, 4096);
@@ -229,13 +249,20 @@ static int stage_indexed(fsmg_handle h, int32_t table_id, const int32_t* sup_idx
     }
     if (n_sup > 0) HIPCK(h, hipMemcpyAsync(h->d_idx, sup_idx, sizeof(int) * n_sup, hipMemcpyHostToDevice, h->stream));
     if (n_qry > 0) HIPCK(h, hipMemcpyAsync(h->d_idx + n_sup, qry_idx, sizeof(int) * n_qry, hipMemcpyHostToDevice, h->stream));
-    if (h->masked_call) {      // the rows' lengths travel with them
-        HIPCK(h, launch_gather_rows_len(h->stream, h->table[table_id], h->table_len[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id],
-                                        h->d_tok, h->d_len, h->d_err));
-        h->cur_len = h->d_len;
-    } else {
-        HIPCK(h, launch_gather_rows(h->stream, h->table[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id], h->d_tok, h->d_err));
-    }
+    int32_t* dst = episode ? h->d_gather : h->d_tok;
+    if (with_len)
+        HIPCK(h, launch_gather_rows_len(h->stream, h->table[table_id], h->table_len[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id], dst,
+                                        episode ? h->d_gather_len : h->d_len, h->d_err));
+    else
+        HIPCK(h, launch_gather_rows(h->stream, h->table[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id], dst, h->d_err));
+    return FSMG_OK;
+}
+
+// a one-pass call's `stage` on the table: a masked call's rows bring their lengths
+static int stage_indexed(fsmg_handle h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry) {
+    const int rc = gather_table_rows(h, table_id, sup_idx, n_sup, qry_idx, n_qry, h->masked_call, false);
+    if (rc != FSMG_OK) return rc;
+    if (h->masked_call) h->cur_len = h->d_len;
     h->cur_sup = h->d_tok; h->cur_qry = h->d_tok + (size_t)n_sup * h->T;
     return FSMG_OK;
 }
@@ -342,257 +369,30 @@ int fsmg_forward_backward_indexed_masked(fsmg_handle h, int32_t table_id, const 
     return forward_backward_core(h, N, K, Q, [&]() { return stage_indexed(h, table_id, support_idx, N * K, query_idx, N * Q); });
 }
 
-// ---- cfg-E (BASELINE.json configs[4]): MAML-style inner / outer loop, first order.  DESIGN.md "cfg-E".
-// one padding-masked forward + backward over `rows` [N*R][T] with their lengths, as one group of N*R rows.  The public
-// fsmg_forward_backward_masked cannot stand in for it inside a MAML call as fsmg_forward_backward does for the unmasked pass: the
-// flag is set here, behind the prologue that clears it, and the pass's own lengths are staged by its own `stage` (a repeat restages them)
-static int masked_rows_pass(fsmg_handle h, const int32_t* rows, const int32_t* len, int32_t N, int32_t R, int32_t on_device) {
-    BEGIN_CALL(h, true);        // fsmg_forward_backward's prologue
-    begin_masked(h, N * R, 1);
-    const int rc = forward_backward_core(h, N, R, 0, [&]() {
-        const int r = stage_tokens(h, rows, N * R, rows, 0, on_device);
-        return r != FSMG_OK ? r : stage_lengths(h, len, N * R, len, 0, on_device);
-    });
-    h->masked_call = false;     // what runs next at theta' (the update, a decode) is not a masked pass
-    return rc;
-}
-
-// support_len != nullptr: every inner step's loss over the positions inside a song only (masked_rows_pass)
-// train: the adaptation of a train form -- with Meta-SGD enabled S starts from zero and collects every applied step
-static int maml_adapt(fsmg_handle h, const int32_t* support, int32_t N, int32_t K, int32_t inner_steps, float inner_lr, int32_t on_device,
-                      const int32_t* support_len = nullptr, bool train = false) {
-    int rc = save_theta(h);
-    if (rc == FSMG_OK && h->msgd_on && train) rc = msgd_begin_sum(h);
-    const bool suppress0 = h->drop_suppress;
-    if (!train) h->drop_suppress = true;        // the adaptation of an eval / decode / score form is never dropped (DESIGN.md 25)
-    for (int i = 0; rc == FSMG_OK && i < inner_steps; ++i) {
-        rc = support_len ? masked_rows_pass(h, support, support_len, N, K, on_device)
-                         : fsmg_forward_backward(h, support, support, N, K, 0, on_device);       // support rows only
-        if (rc == FSMG_OK) rc = h->msgd_on ? msgd_inner_update(h, inner_lr, train) : sgd_update(h, inner_lr);
-    }
-    h->drop_suppress = suppress0;
-    return rc;
-}
-
-int fsmg_maml_forward_backward(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q,
-                               int32_t inner_steps, float inner_lr, int32_t tokens_on_device) {
-    if (!h || !support || !query) return FSMG_ERR_INVALID;
-    if (inner_steps < 0 || inner_steps > 64 || !(inner_lr >= 0.f) || K <= 0 || Q <= 0) return fail(h, FSMG_ERR_INVALID, "bad inner_steps / inner_lr / K / Q");
-    BEGIN_CALL(h);
-    int rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, tokens_on_device, nullptr, true);
-    if (rc == FSMG_OK) rc = fsmg_forward_backward(h, query, query, N, Q, 0, tokens_on_device);     // query rows at theta'
-    if (rc == FSMG_OK && h->msgd_on) rc = msgd_rate_gradient(h);
-    const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
-    int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;                                               // theta comes back whatever happened
-    if (rc2 == FSMG_OK) rc2 = rc_keep;
-    return rc != FSMG_OK ? rc : rc2;
-}
-
-int fsmg_maml_step(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q,
-                   int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* loss) {
-    if (!h) return FSMG_ERR_INVALID;
-    BEGIN_CALL(h);
-    if (h->comm != nullptr)           // per-rank inner loop (no communication), query gradients exchanged like a plain step's
-        return dp_train_step(h, loss, [&]() { return fsmg_maml_forward_backward(h, support, query, N, K, Q, inner_steps, inner_lr, tokens_on_device); });
-    const uint64_t drop_p0 = h->drop_next;
-    int rc = fsmg_maml_forward_backward(h, support, query, N, K, Q, inner_steps, inner_lr, tokens_on_device);
-    if (rc != FSMG_OK) return rc;
-    rc = fsmg_apply_update(h, 1.0f, loss);
-    if (is_retry(rc) && h->retry_armed) {        // same recovery as fsmg_train_step: nothing was updated, repeat per step
-        h->retry_armed = false;
-        h->drop_next = drop_p0;
-        rc = fsmg_maml_forward_backward(h, support, query, N, K, Q, inner_steps, inner_lr, tokens_on_device);
-        if (rc == FSMG_OK) rc = fsmg_apply_update(h, 1.0f, loss);
-    }
-    return rc;
-}
-
-// ---- cfg-E with per-song lengths (DESIGN.md 22): every inner step over the support rows' valid positions, the outer pass over the query rows'
-static int validate_maml_masked_args(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
-                                     int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t on_device) {
-    if (!support || !query) return fail(h, FSMG_ERR_INVALID, "null token pointer");
-    if (inner_steps < 0 || inner_steps > 64 || !(inner_lr >= 0.f) || K <= 0 || Q <= 0) return fail(h, FSMG_ERR_INVALID, "bad inner_steps / inner_lr / K / Q");
-    return validate_masked_args(h, support_len, query_len, N, K, Q, on_device);
-}
-
-static int maml_forward_backward_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
-                                        int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t on_device) {
-    int rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, on_device, support_len, true);
-    if (rc == FSMG_OK) rc = masked_rows_pass(h, query, query_len, N, Q, on_device);                  // query rows at theta'
-    if (rc == FSMG_OK && h->msgd_on) rc = msgd_rate_gradient(h);
-    const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
-    int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;                                               // theta comes back whatever happened
-    if (rc2 == FSMG_OK) rc2 = rc_keep;
-    return rc != FSMG_OK ? rc : rc2;
-}
-
-int fsmg_maml_forward_backward_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
-                                      int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t tokens_on_device) {
-    if (!h) return FSMG_ERR_INVALID;
-    const int rcv = validate_maml_masked_args(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
-    if (rcv != FSMG_OK) return rcv;
-    BEGIN_CALL(h);
-    return maml_forward_backward_masked(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
-}
-
-int fsmg_maml_step_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
-                          int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* loss) {
-    if (!h) return FSMG_ERR_INVALID;
-    const int rcv = validate_maml_masked_args(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
-    if (rcv != FSMG_OK) return rcv;
-    BEGIN_CALL(h);
-    auto fb = [&]() { return maml_forward_backward_masked(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device); };
-    if (h->comm != nullptr)           // each rank normalises by its own n_valid; 1 / world takes the mean
-        return dp_train_step(h, loss, fb);
-    const uint64_t drop_p0 = h->drop_next;
-    int rc = fb();
-    if (rc != FSMG_OK) return rc;
-    rc = fsmg_apply_update(h, 1.0f, loss);
-    if (is_retry(rc) && h->retry_armed) {        // same recovery as fsmg_maml_step: nothing was updated, repeat per step -- with the lengths
-        h->retry_armed = false;
-        h->drop_next = drop_p0;
-        rc = fb();
-        if (rc == FSMG_OK) rc = fsmg_apply_update(h, 1.0f, loss);
-    }
-    return rc;
-}
-
-// cfg-E on the device-resident split table: the episode's rows are gathered ONCE into a buffer of the handle's own and the
-// inner / outer passes read them there (an index outside the table raises the token-range flag like any bad token)
-// with_len: the rows' lengths are gathered in the same launch into d_gather_len (the masked forms; a table without lengths: FSMG_ERR_STATE)
-static int gather_episode(fsmg_handle h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry, bool with_len = false) {
-    if (table_id < 0 || table_id >= fsmg_model::MAX_TABLES || !h->table[table_id]) return fail(h, FSMG_ERR_STATE, "no token table uploaded under this id");
-    if (with_len && !h->table_len[table_id]) return fail(h, FSMG_ERR_STATE, "the table under this id has no lengths (fsmg_upload_table_lengths)");
-    const int n = n_sup + n_qry;
-    if (h->idx_cap < n || h->gather_cap < (int64_t)n * h->T) {
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        if (h->d_idx) hipFree(h->d_idx);
-        if (h->d_gather) hipFree(h->d_gather);
-        if (h->d_gather_len) hipFree(h->d_gather_len);
-        h->d_idx = nullptr; h->d_gather = nullptr; h->d_gather_len = nullptr; h->idx_cap = 0; h->gather_cap = 0;
-        const int cap = std::max(n, 4096);
-        if (hipMalloc((void**)&h->d_idx, sizeof(int) * cap) != hipSuccess || hipMalloc((void**)&h->d_gather, sizeof(int) * (size_t)cap * h->T) != hipSuccess ||
-            hipMalloc((void**)&h->d_gather_len, sizeof(int) * cap) != hipSuccess)
-            return fail(h, FSMG_ERR_NOMEM, "hipMalloc(episode gather buffers) failed");
-        h->idx_cap = cap; h->gather_cap = (int64_t)cap * h->T;
-    }
-    if (n_sup > 0) HIPCK(h, hipMemcpyAsync(h->d_idx, sup_idx, sizeof(int) * n_sup, hipMemcpyHostToDevice, h->stream));
-    if (n_qry > 0) HIPCK(h, hipMemcpyAsync(h->d_idx + n_sup, qry_idx, sizeof(int) * n_qry, hipMemcpyHostToDevice, h->stream));
-    if (with_len)
-        HIPCK(h, launch_gather_rows_len(h->stream, h->table[table_id], h->table_len[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id],
-                                        h->d_gather, h->d_gather_len, h->d_err));
-    else
-        HIPCK(h, launch_gather_rows(h->stream, h->table[table_id], h->d_idx, n, h->T, (int)h->table_rows[table_id], h->d_gather, h->d_err));
-    return FSMG_OK;
-}
-
-int fsmg_maml_forward_backward_indexed(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
-                                       int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr) {
-    if (!h || !support_idx || !query_idx || N <= 0 || K <= 0 || Q <= 0) return FSMG_ERR_INVALID;
-    BEGIN_CALL(h);
-    const int rc = gather_episode(h, table_id, support_idx, N * K, query_idx, N * Q);
-    if (rc != FSMG_OK) return rc;
-    return fsmg_maml_forward_backward(h, h->d_gather, h->d_gather + (size_t)N * K * h->T, N, K, Q, inner_steps, inner_lr, 1);
-}
-
-int fsmg_maml_step_indexed(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
-                           int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, float* loss) {
-    if (!h || !support_idx || !query_idx || N <= 0 || K <= 0 || Q <= 0) return FSMG_ERR_INVALID;
-    BEGIN_CALL(h);
-    const int rc = gather_episode(h, table_id, support_idx, N * K, query_idx, N * Q);
-    if (rc != FSMG_OK) return rc;
-    return fsmg_maml_step(h, h->d_gather, h->d_gather + (size_t)N * K * h->T, N, K, Q, inner_steps, inner_lr, 1, loss);
-}
-
-// the masked forms: the rows' lengths come out of the same gather (fsmg_upload_table_lengths) and reach the token forms as device lengths
-int fsmg_maml_forward_backward_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
-                                              int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr) {
-    if (!h || !support_idx || !query_idx || N <= 0 || K <= 0 || Q <= 0) return FSMG_ERR_INVALID;
-    BEGIN_CALL(h);
-    const int rc = gather_episode(h, table_id, support_idx, N * K, query_idx, N * Q, true);
-    if (rc != FSMG_OK) return rc;
-    return fsmg_maml_forward_backward_masked(h, h->d_gather, h->d_gather + (size_t)N * K * h->T, h->d_gather_len, h->d_gather_len + N * K,
-                                             N, K, Q, inner_steps, inner_lr, 1);
-}
-
-int fsmg_maml_step_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
-                                  int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, float* loss) {
-    if (!h || !support_idx || !query_idx || N <= 0 || K <= 0 || Q <= 0) return FSMG_ERR_INVALID;
-    BEGIN_CALL(h);
-    const int rc = gather_episode(h, table_id, support_idx, N * K, query_idx, N * Q, true);
-    if (rc != FSMG_OK) return rc;
-    return fsmg_maml_step_masked(h, h->d_gather, h->d_gather + (size_t)N * K * h->T, h->d_gather_len, h->d_gather_len + N * K,
-                                 N, K, Q, inner_steps, inner_lr, 1, loss);
-}
-
 static int eval_batch_core(fsmg_handle h, const int32_t* queries, const int32_t* query_len, int32_t n_episodes, int32_t N, int32_t Q,
                            int32_t tokens_on_device, float* nll, bool masked, bool repeat_chunk = true);
 
-int fsmg_maml_eval(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q,
-                   int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* nll) {
-    if (!h || !support || !query || !nll) return FSMG_ERR_INVALID;
-    if (inner_steps < 0 || inner_steps > 64 || !(inner_lr >= 0.f) || K <= 0 || Q <= 0) return fail(h, FSMG_ERR_INVALID, "bad inner_steps / inner_lr / K / Q");
-    BEGIN_CALL(h);
-    int rc = FSMG_OK;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, tokens_on_device);
-        // the flag of a time-out / token error inside the adaptation is still set: the query pass reads and reports it.  It must not
-        // repeat its chunk on its own as fsmg_eval_step does: the inner updates of a timed-out adaptation were skipped, the repeated
-        // chunk would succeed at the UNADAPTED theta and its NLL would be returned as if nothing had happened -- the adaptation is
-        // repeated with it, below
-        if (rc == FSMG_OK) rc = eval_batch_core(h, query, nullptr, 1, N, Q, tokens_on_device, nll, false, false);
-        const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
-        int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
-        if (rc2 == FSMG_OK) rc2 = rc_keep;
-        h->have_grads = false;
-        if (rc == FSMG_OK) rc = rc2;
-        if (!(is_retry(rc) && h->retry_armed)) break;
-        h->retry_armed = false;                        // adapted with garbage (skipped) steps: repeat on per-step launches
-    }
-    return rc;
-}
-
-int fsmg_maml_eval_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
-                          int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* nll) {
-    if (!h || !nll) return FSMG_ERR_INVALID;
-    const int rcv = validate_maml_masked_args(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
-    if (rcv != FSMG_OK) return rcv;
-    BEGIN_CALL(h);
-    int rc = FSMG_OK;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        rc = maml_adapt(h, support, N, K, inner_steps, inner_lr, tokens_on_device, support_len);
-        // as in fsmg_maml_eval: the query pass reports the adaptation's flag and must not repeat its chunk at the unadapted theta on its
-        // own -- the adaptation is repeated with it, lengths and all
-        if (rc == FSMG_OK) rc = eval_batch_core(h, query, query_len, 1, N, Q, tokens_on_device, nll, true, false);
-        h->masked_call = false;
-        const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
-        int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
-        if (rc2 == FSMG_OK) rc2 = rc_keep;
-        h->have_grads = false;
-        if (rc == FSMG_OK) rc = rc2;
-        if (!(is_retry(rc) && h->retry_armed)) break;
-        h->retry_armed = false;                        // adapted with garbage (skipped) steps: repeat on per-step launches
-    }
-    return rc;
-}
-
-// the device error flag the adaptation's passes left (fsmg_maml_eval's query pass reads it in check_tokens_and_read)
-static int adapt_flag(fsmg_handle h) {
-    int err = 0;
-    HIPCK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    if (!err) return FSMG_OK;
-    HIPCK(h, hipMemsetAsync(h->d_err, 0, sizeof(int), h->stream));
-    if (err == 2) on_timeout(h);
-    else if (err == 4) on_softmax_range(h);
-    return report(h, err);
-}
-
 }  // extern "C"
 
+// ---- cfg-E (BASELINE.json configs[4]): MAML-style inner / outer loop, first order.  DESIGN.md "cfg-E", 22 (per-song lengths), 28 (the drivers).
 namespace fsmg_host {
-// masked_rows_pass over host rows with the loss window [lo, hi) (dynamic evaluation): the window is written to its fixed
-// address in stream order before the pass, outside any capture, so a replayed graph reads the window of THIS call
+
+// The prologue is fsmg_forward_backward's, and it is the pass's own: a pass repeated after an update (step_with_update) orders itself
+// behind that update's pending half here.  The flag is set behind the prologue, which clears it, and the pass's own `stage` stages its
+// lengths (a repeat restages them); what runs next at theta' (the update, a decode) is not a masked pass.
+int rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t N, int32_t R, int32_t on_device) {
+    BEGIN_CALL(h, true);
+    if (len) begin_masked(h, N * R, 1);
+    const int rc = forward_backward_core(h, N, R, 0, [&]() {
+        const int r = stage_tokens(h, rows, N * R, rows, 0, on_device);
+        return r != FSMG_OK || !len ? r : stage_lengths(h, len, N * R, len, 0, on_device);
+    });
+    h->masked_call = false;
+    return rc;
+}
+
+// the window [lo, hi) is written to its fixed address in stream order before the pass, outside any capture, so a replayed graph reads
+// the window of THIS call (dynamic evaluation)
 int window_rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t n, int lo, int hi) {
     BEGIN_CALL(h, true);
     begin_masked(h, n, 1);
@@ -610,21 +410,116 @@ int window_rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int
     h->window_call = false;
     return rc;
 }
-int pass_flag(fsmg_model* h) { return adapt_flag(h); }
-int dp_train_step_fn(fsmg_model* h, float* loss, const std::function<int()>& forward_backward) { return dp_train_step(h, loss, forward_backward); }
-int maml_adapt_rows(fsmg_model* h, const int32_t* support, int32_t N, int32_t K, int32_t inner_steps, float inner_lr, int32_t on_device,
-                    const int32_t* support_len, bool train) {
-    return maml_adapt(h, support, N, K, inner_steps, inner_lr, on_device, support_len, train);
-}
-int masked_query_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t N, int32_t R, int32_t on_device) {
-    return masked_rows_pass(h, rows, len, N, R, on_device);
-}
-int gather_episode_rows(fsmg_model* h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry, bool with_len) {
-    return gather_episode(h, table_id, sup_idx, n_sup, qry_idx, n_qry, with_len);
+
+// with Meta-SGD enabled the adaptation of a train form starts S from zero and collects every applied step
+int maml_adapt(fsmg_model* h, const Episode& e, int32_t inner_steps, float inner_lr, bool train) {
+    int rc = save_theta(h);
+    if (rc == FSMG_OK && h->msgd_on && train) rc = msgd_begin_sum(h);
+    const bool suppress0 = h->drop_suppress;
+    if (!train) h->drop_suppress = true;        // the adaptation of an eval / decode / score form is never dropped (DESIGN.md 25)
+    for (int i = 0; rc == FSMG_OK && i < inner_steps; ++i) {
+        rc = rows_pass(h, e.sup, e.masked ? e.slen : nullptr, e.N, e.K, e.on_device);       // support rows only
+        if (rc == FSMG_OK) rc = h->msgd_on ? msgd_inner_update(h, inner_lr, train) : sgd_update(h, inner_lr);
+    }
+    h->drop_suppress = suppress0;
+    return rc;
 }
 
-// adapt on the support rows like fsmg_maml_eval, run the body at theta', restore theta whatever happened; one repeat on per-step
-// launches when the adaptation ran garbage (skipped) steps.  The MAML decode entry points (api_decode.hip) run through here.
+int adapt_flag(fsmg_model* h) {
+    int err = 0;
+    HIPCK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (!err) return FSMG_OK;
+    HIPCK(h, hipMemsetAsync(h->d_err, 0, sizeof(int), h->stream));
+    if (err == 2) on_timeout(h);
+    else if (err == 4) on_softmax_range(h);
+    return report(h, err);
+}
+
+// (theta was never saved where save_theta's first allocation failed: nothing to keep or to put back.  Neither copy reads the two flags.)
+int end_adaptation(fsmg_model* h) {
+    h->masked_call = false; h->window_call = false;
+    const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
+    const int rc = h->P_saved ? restore_theta(h) : FSMG_OK;        // theta comes back whatever happened
+    h->have_grads = false;
+    return rc != FSMG_OK ? rc : rc_keep;
+}
+
+int at_adapted_theta(fsmg_model* h, const std::function<int()>& adapt, const std::function<int()>& body) {
+    int rc = FSMG_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        rc = adapt();
+        if (rc == FSMG_OK) rc = body();
+        const int rc_end = end_adaptation(h);
+        if (rc == FSMG_OK) rc = rc_end;
+        if (!(is_retry(rc) && h->retry_armed)) break;
+        h->retry_armed = false;                        // adapted with garbage (skipped) steps: repeat on per-step launches
+    }
+    return rc;
+}
+
+int step_with_update(fsmg_model* h, float* loss, const std::function<int()>& forward_backward) {
+    if (h->comm != nullptr) return dp_train_step(h, loss, forward_backward);      // the gradient exchanged like a plain step's (1 / world takes the mean)
+    const uint64_t drop_p0 = h->drop_next;
+    int rc = forward_backward();
+    if (rc != FSMG_OK) return rc;
+    rc = fsmg_apply_update(h, 1.0f, loss);
+    if (is_retry(rc) && h->retry_armed) {        // same recovery as fsmg_train_step: nothing was updated, repeat per step
+        h->retry_armed = false;
+        h->drop_next = drop_p0;                  // the repeated passes draw the masks of the passes they repeat
+        rc = forward_backward();
+        if (rc == FSMG_OK) rc = fsmg_apply_update(h, 1.0f, loss);
+    }
+    return rc;
+}
+
+int gather_episode(fsmg_model* h, int32_t table_id, bool with_len, const int32_t* support_idx, const int32_t* query_idx, int32_t N, int32_t K,
+                   int32_t Q, Episode* e) {
+    const int rc = gather_table_rows(h, table_id, support_idx, N * K, query_idx, N * Q, with_len, true);
+    if (rc != FSMG_OK) return rc;
+    *e = token_episode(h->d_gather, h->d_gather + (size_t)N * K * h->T, with_len ? h->d_gather_len : nullptr,
+                       with_len ? h->d_gather_len + (size_t)N * K : nullptr, N, K, Q, 1);
+    return FSMG_OK;
+}
+
+int locate_episode(fsmg_model* h, int32_t table_id, bool with_len, const int32_t* support, const int32_t* query, const int32_t* support_len,
+                   const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int on_device, Episode* e) {
+    if (table_id >= 0) return gather_episode(h, table_id, with_len, support, query, N, K, Q, e);
+    *e = token_episode(support, query, support_len, query_len, N, K, Q, on_device);
+    return FSMG_OK;
+}
+
+// The prologue is the call's own: a repeat behind an update (step_with_update, dp_train_step) settles that update's pending half
+// before theta is saved.  The gradient of the query pass at theta' stays pending; theta comes back under it.
+int maml_forward_backward(fsmg_model* h, const Episode& e, int32_t inner_steps, float inner_lr) {
+    BEGIN_CALL(h);
+    int rc = maml_adapt(h, e, inner_steps, inner_lr, true);
+    if (rc == FSMG_OK) rc = rows_pass(h, e.qry, e.masked ? e.qlen : nullptr, e.N, e.Q, e.on_device);       // query rows at theta'
+    if (rc == FSMG_OK && h->msgd_on) rc = msgd_rate_gradient(h);
+    const bool pending = h->have_grads;
+    const int rc_end = end_adaptation(h);
+    h->have_grads = pending;
+    return rc != FSMG_OK ? rc : rc_end;
+}
+
+int maml_step(fsmg_model* h, const Episode& e, int32_t inner_steps, float inner_lr, float* loss) {
+    // per-rank inner loop (no communication); a repeat carries the lengths like the first attempt
+    return step_with_update(h, loss, [&]() { return maml_forward_backward(h, e, inner_steps, inner_lr); });
+}
+
+int maml_eval(fsmg_model* h, const Episode& e, int32_t inner_steps, float inner_lr, float* nll) {
+    BEGIN_CALL(h);
+    // The flag of a time-out / token error inside the adaptation is still set: the query pass reads and reports it (reading it here
+    // would be one more synchronisation per call).  The query pass must not repeat its chunk on its own as fsmg_eval_step does: the
+    // inner updates of a timed-out adaptation were skipped, the repeated chunk would succeed at the UNADAPTED theta and its NLL would
+    // be returned as if nothing had happened -- the adaptation is repeated with it, lengths and all.
+    return at_adapted_theta(
+        h, [&]() { return maml_adapt(h, e, inner_steps, inner_lr, false); },
+        [&]() { return eval_batch_core(h, e.qry, e.masked ? e.qlen : nullptr, 1, e.N, e.Q, e.on_device, nll, e.masked, false); });
+}
+
+// One repeat on per-step launches when the adaptation ran garbage (skipped) steps: the error word is read before the body, because the
+// body (a decode, a scoring pass) would run at a theta' that is not one.
 int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
                        int32_t support_on_device, const std::function<int()>& at_theta_prime, const int32_t* support_len, bool masked) {
     if (masked && !support_len) return fail(h, FSMG_ERR_INVALID, "null length pointer");
@@ -637,22 +532,128 @@ int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_
         if (rcv != FSMG_OK) return rcv;
     }
     BEGIN_CALL(h);
-    int rc = FSMG_OK;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        rc = maml_adapt(h, support, 1, n_support_rows, inner_steps, inner_lr, support_on_device, masked ? support_len : nullptr);
-        if (rc == FSMG_OK) rc = adapt_flag(h);           // a time-out / token error inside the adaptation: theta' is not usable
-        if (rc == FSMG_OK) rc = at_theta_prime();
-        const int rc_keep = h->P_saved ? keep_theta_prime(h) : FSMG_OK;
-        int rc2 = h->P_saved ? restore_theta(h) : FSMG_OK;
-        if (rc2 == FSMG_OK) rc2 = rc_keep;
-        h->have_grads = false;
-        if (rc == FSMG_OK) rc = rc2;
-        if (!(is_retry(rc) && h->retry_armed)) break;
-        h->retry_armed = false;                        // adapted with garbage (skipped) steps: repeat on per-step launches
-    }
+    const Episode e = token_episode(support, nullptr, masked ? support_len : nullptr, nullptr, 1, n_support_rows, 0, support_on_device);
+    return at_adapted_theta(
+        h,
+        [&]() {
+            const int rc = maml_adapt(h, e, inner_steps, inner_lr, false);
+            return rc != FSMG_OK ? rc : adapt_flag(h);           // a time-out / token error inside the adaptation: theta' is not usable
+        },
+        at_theta_prime);
+}
+
+}  // namespace fsmg_host
+
+extern "C" {
+
+static int check_inner_loop(fsmg_handle h, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr) {
+    if (inner_steps < 0 || inner_steps > 64 || !(inner_lr >= 0.f) || K <= 0 || Q <= 0) return fail(h, FSMG_ERR_INVALID, "bad inner_steps / inner_lr / K / Q");
+    return FSMG_OK;
+}
+
+int fsmg_maml_forward_backward(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q,
+                               int32_t inner_steps, float inner_lr, int32_t tokens_on_device) {
+    if (!h || !support || !query) return FSMG_ERR_INVALID;
+    const int rcv = check_inner_loop(h, K, Q, inner_steps, inner_lr);
+    if (rcv != FSMG_OK) return rcv;
+    return maml_forward_backward(h, token_episode(support, query, nullptr, nullptr, N, K, Q, tokens_on_device), inner_steps, inner_lr);
+}
+
+int fsmg_maml_step(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q,
+                   int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* loss) {
+    if (!h) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h);
+    if (!support || !query) return FSMG_ERR_INVALID;
+    const int rcv = check_inner_loop(h, K, Q, inner_steps, inner_lr);
+    if (rcv != FSMG_OK) return rcv;
+    return maml_step(h, token_episode(support, query, nullptr, nullptr, N, K, Q, tokens_on_device), inner_steps, inner_lr, loss);
+}
+
+int fsmg_maml_eval(fsmg_handle h, const int32_t* support, const int32_t* query, int32_t N, int32_t K, int32_t Q,
+                   int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* nll) {
+    if (!h || !support || !query || !nll) return FSMG_ERR_INVALID;
+    const int rcv = check_inner_loop(h, K, Q, inner_steps, inner_lr);
+    if (rcv != FSMG_OK) return rcv;
+    return maml_eval(h, token_episode(support, query, nullptr, nullptr, N, K, Q, tokens_on_device), inner_steps, inner_lr, nll);
+}
+
+// ---- cfg-E with per-song lengths (DESIGN.md 22): every inner step over the support rows' valid positions, the outer pass over the query rows'
+static int validate_maml_masked_args(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                                     int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t on_device) {
+    if (!support || !query) return fail(h, FSMG_ERR_INVALID, "null token pointer");
+    const int rc = check_inner_loop(h, K, Q, inner_steps, inner_lr);
+    return rc != FSMG_OK ? rc : validate_masked_args(h, support_len, query_len, N, K, Q, on_device);
+}
+
+int fsmg_maml_forward_backward_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                                      int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t tokens_on_device) {
+    if (!h) return FSMG_ERR_INVALID;
+    const int rcv = validate_maml_masked_args(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
+    if (rcv != FSMG_OK) return rcv;
+    return maml_forward_backward(h, token_episode(support, query, support_len, query_len, N, K, Q, tokens_on_device), inner_steps, inner_lr);
+}
+
+int fsmg_maml_step_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                          int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* loss) {
+    if (!h) return FSMG_ERR_INVALID;
+    const int rcv = validate_maml_masked_args(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
+    if (rcv != FSMG_OK) return rcv;
+    BEGIN_CALL(h);
+    return maml_step(h, token_episode(support, query, support_len, query_len, N, K, Q, tokens_on_device), inner_steps, inner_lr, loss);
+}
+
+int fsmg_maml_eval_masked(fsmg_handle h, const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len,
+                          int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, int32_t tokens_on_device, float* nll) {
+    if (!h || !nll) return FSMG_ERR_INVALID;
+    const int rcv = validate_maml_masked_args(h, support, query, support_len, query_len, N, K, Q, inner_steps, inner_lr, tokens_on_device);
+    if (rcv != FSMG_OK) return rcv;
+    return maml_eval(h, token_episode(support, query, support_len, query_len, N, K, Q, tokens_on_device), inner_steps, inner_lr, nll);
+}
+
+// cfg-E on the device-resident split table, behind the entry point's null checks: the gather (gather_episode), then what the token
+// form of the same call checks -- in the masked forms the lengths come out of the same gather and reach the passes as device lengths
+static int indexed_episode(fsmg_handle h, int32_t table_id, bool masked, const int32_t* support_idx, const int32_t* query_idx, int32_t N, int32_t K,
+                           int32_t Q, int32_t inner_steps, float inner_lr, Episode* e) {
+    BEGIN_CALL(h);
+    int rc = gather_episode(h, table_id, masked, support_idx, query_idx, N, K, Q, e);
+    if (rc == FSMG_OK) rc = check_inner_loop(h, K, Q, inner_steps, inner_lr);
+    if (rc == FSMG_OK && masked) rc = validate_masked_args(h, e->slen, e->qlen, N, K, Q, 1);
     return rc;
 }
-}  // namespace fsmg_host
+
+int fsmg_maml_forward_backward_indexed(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                                       int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr) {
+    if (!h || !support_idx || !query_idx || N <= 0 || K <= 0 || Q <= 0) return FSMG_ERR_INVALID;
+    Episode e;
+    const int rc = indexed_episode(h, table_id, false, support_idx, query_idx, N, K, Q, inner_steps, inner_lr, &e);
+    return rc != FSMG_OK ? rc : maml_forward_backward(h, e, inner_steps, inner_lr);
+}
+
+int fsmg_maml_step_indexed(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                           int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, float* loss) {
+    if (!h || !support_idx || !query_idx || N <= 0 || K <= 0 || Q <= 0) return FSMG_ERR_INVALID;
+    Episode e;
+    const int rc = indexed_episode(h, table_id, false, support_idx, query_idx, N, K, Q, inner_steps, inner_lr, &e);
+    return rc != FSMG_OK ? rc : maml_step(h, e, inner_steps, inner_lr, loss);
+}
+
+int fsmg_maml_forward_backward_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                                              int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr) {
+    if (!h || !support_idx || !query_idx || N <= 0 || K <= 0 || Q <= 0) return FSMG_ERR_INVALID;
+    Episode e;
+    const int rc = indexed_episode(h, table_id, true, support_idx, query_idx, N, K, Q, inner_steps, inner_lr, &e);
+    return rc != FSMG_OK ? rc : maml_forward_backward(h, e, inner_steps, inner_lr);
+}
+
+int fsmg_maml_step_indexed_masked(fsmg_handle h, int32_t table_id, const int32_t* support_idx, const int32_t* query_idx,
+                                  int32_t N, int32_t K, int32_t Q, int32_t inner_steps, float inner_lr, float* loss) {
+    if (!h || !support_idx || !query_idx || N <= 0 || K <= 0 || Q <= 0) return FSMG_ERR_INVALID;
+    Episode e;
+    const int rc = indexed_episode(h, table_id, true, support_idx, query_idx, N, K, Q, inner_steps, inner_lr, &e);
+    return rc != FSMG_OK ? rc : maml_step(h, e, inner_steps, inner_lr, loss);
+}
+
+}  // extern "C"
 
 extern "C" {
 

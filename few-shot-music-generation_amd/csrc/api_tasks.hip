@@ -1,5 +1,6 @@
-// Per-artist MAML (include/fsmg.h "per-artist MAML"): the episode as a meta-batch of N tasks.  The driver loops over the
-// artists around the adaptation and the query pass of the fsmg_maml_* entry points as they stand (api_step.hip) and folds behind each.
+// Per-artist MAML (include/fsmg.h "per-artist MAML"): the episode as a meta-batch of N tasks.  The train driver loops over
+// the artists around maml_adapt and rows_pass (api_step.hip) on one-artist episodes and folds behind each; the eval driver is maml_eval
+// per artist.
 // Host-side C++ only (part of the C-ABI of libfsmg, include/fsmg.h); the fold's kernel lives in tasks.hip.
 #include "fsmg_model.h"
 
@@ -7,14 +8,6 @@ using namespace fsmg;
 using namespace fsmg_host;
 
 namespace {
-
-// where the call's rows are once the arguments are checked (and, for the table form, gathered): artist n's support rows start at
-// sup + n * K * T, its lengths at slen + n * K
-struct Episode {
-    const int32_t *sup = nullptr, *qry = nullptr, *slen = nullptr, *qlen = nullptr;
-    int on_device = 0;
-    bool masked = false;
-};
 
 // every argument error of the three entry points, before any device work
 int check_tasks_args(fsmg_model* h, const fsmg_maml_tasks_config* c, const int32_t* support, const int32_t* query, const int32_t* support_len,
@@ -40,19 +33,9 @@ int check_tasks_args(fsmg_model* h, const fsmg_maml_tasks_config* c, const int32
 }
 
 // the table form gathers the episode's rows (and lengths) once; the token form is where the caller says
-int locate_episode(fsmg_model* h, const fsmg_maml_tasks_config* c, const int32_t* support, const int32_t* query, const int32_t* support_len,
-                   const int32_t* query_len, int32_t N, int32_t K, int32_t Q, Episode* e) {
-    if (c->table_id < 0) {
-        e->sup = support; e->qry = query; e->slen = support_len; e->qlen = query_len;
-        e->on_device = c->tokens_on_device; e->masked = support_len != nullptr;
-        return FSMG_OK;
-    }
-    e->masked = c->use_table_lengths != 0;
-    const int rc = gather_episode_rows(h, c->table_id, support, N * K, query, N * Q, e->masked);
-    if (rc != FSMG_OK) return rc;
-    e->sup = h->d_gather; e->qry = h->d_gather + (size_t)N * K * h->T; e->on_device = 1;
-    if (e->masked) { e->slen = h->d_gather_len; e->qlen = h->d_gather_len + (size_t)N * K; }
-    return FSMG_OK;
+int tasks_episode(fsmg_model* h, const fsmg_maml_tasks_config* c, const int32_t* support, const int32_t* query, const int32_t* support_len,
+                  const int32_t* query_len, int32_t N, int32_t K, int32_t Q, Episode* e) {
+    return locate_episode(h, c->table_id, c->use_table_lengths != 0, support, query, support_len, query_len, N, K, Q, c->tokens_on_device, e);
 }
 
 // ACC and d_task_loss: allocated on first use, kept until fsmg_destroy
@@ -88,30 +71,22 @@ int fold_artist(fsmg_model* h, int n, int N) {
     return ensure_khf(h);
 }
 
-int tasks_forward_backward(fsmg_model* h, const fsmg_maml_tasks_config* c, const Episode& e, int32_t N, int32_t K, int32_t Q) {
+int tasks_forward_backward(fsmg_model* h, const fsmg_maml_tasks_config* c, const Episode& e) {
+    const int N = e.N;
     int rc = ensure_task_buffers(h, N);
     if (rc != FSMG_OK) return rc;
     ScopedTimer tm(h, "tasks");
-    const size_t T = (size_t)h->T;
     h->task_loss_n = 0;
     for (int n = 0; n < N; ++n) {
-        const int32_t* sup = e.sup + (size_t)n * K * T;
-        const int32_t* qry = e.qry + (size_t)n * Q * T;
-        const int32_t* slen = e.masked ? e.slen + (size_t)n * K : nullptr;
-        const int32_t* qlen = e.masked ? e.qlen + (size_t)n * Q : nullptr;
-        rc = maml_adapt_rows(h, sup, 1, K, c->inner_steps, c->inner_lr, e.on_device, slen, true);
-        if (rc == FSMG_OK) rc = e.masked ? masked_query_pass(h, qry, qlen, 1, Q, e.on_device)
-                                         : fsmg_forward_backward(h, qry, qry, 1, Q, 0, e.on_device);       // query rows at theta'_n
+        const Episode a = e.artist(n, h->T);
+        rc = maml_adapt(h, a, c->inner_steps, c->inner_lr, true);
+        if (rc == FSMG_OK) rc = rows_pass(h, a.qry, a.masked ? a.qlen : nullptr, 1, a.Q, a.on_device);       // query rows at theta'_n
         if (rc == FSMG_OK && n == N - 1) rc = keep_theta_prime(h);
         if (rc == FSMG_OK) rc = fold_artist(h, n, N);
         if (rc != FSMG_OK) break;
     }
     if (rc != FSMG_OK) {                // theta comes back whatever happened; no fold is pending
-        if (h->P_saved) {
-            (void)keep_theta_prime(h);
-            (void)restore_theta(h);
-        }
-        h->have_grads = false;
+        (void)end_adaptation(h);
         h->msgd_pending = false;
         return rc;
     }
@@ -143,8 +118,8 @@ int fsmg_maml_tasks_forward_backward(fsmg_handle h, const fsmg_maml_tasks_config
     if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
     Episode e;
-    if ((rc = locate_episode(h, c, support, query, support_len, query_len, N, K, Q, &e)) != FSMG_OK) return rc;
-    return tasks_forward_backward(h, c, e, N, K, Q);
+    if ((rc = tasks_episode(h, c, support, query, support_len, query_len, N, K, Q, &e)) != FSMG_OK) return rc;
+    return tasks_forward_backward(h, c, e);
 }
 
 int fsmg_maml_tasks_step(fsmg_handle h, const fsmg_maml_tasks_config* c, const int32_t* support, const int32_t* query,
@@ -154,22 +129,9 @@ int fsmg_maml_tasks_step(fsmg_handle h, const fsmg_maml_tasks_config* c, const i
     if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
     Episode e;
-    if ((rc = locate_episode(h, c, support, query, support_len, query_len, N, K, Q, &e)) != FSMG_OK) return rc;
-    auto fb = [&]() { return tasks_forward_backward(h, c, e, N, K, Q); };
-    if (h->comm != nullptr) {           // per-rank adaptations (no communication), the folded gradient exchanged like a plain step's
-        rc = dp_train_step_fn(h, loss, fb);
-    } else {
-        const uint64_t drop_p0 = h->drop_next;
-        rc = fb();
-        if (rc != FSMG_OK) return rc;
-        rc = fsmg_apply_update(h, 1.0f, loss);
-        if (is_retry(rc) && h->retry_armed) {        // same recovery as fsmg_maml_step: nothing was updated, repeat the whole call per step
-            h->retry_armed = false;
-            h->drop_next = drop_p0;
-            rc = fb();
-            if (rc == FSMG_OK) rc = fsmg_apply_update(h, 1.0f, loss);
-        }
-    }
+    if ((rc = tasks_episode(h, c, support, query, support_len, query_len, N, K, Q, &e)) != FSMG_OK) return rc;
+    // per-rank adaptations (no communication), the folded gradient exchanged or applied like fsmg_maml_step's; a repeat is the whole call's
+    rc = step_with_update(h, loss, [&]() { return tasks_forward_backward(h, c, e); });
     if (rc == FSMG_OK && task_loss != nullptr) rc = read_task_losses(h, task_loss, N);
     return rc;
 }
@@ -182,16 +144,11 @@ int fsmg_maml_tasks_eval(fsmg_handle h, const fsmg_maml_tasks_config* c, const i
     if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
     Episode e;
-    if ((rc = locate_episode(h, c, support, query, support_len, query_len, N, K, Q, &e)) != FSMG_OK) return rc;
-    const size_t T = (size_t)h->T;
+    if ((rc = tasks_episode(h, c, support, query, support_len, query_len, N, K, Q, &e)) != FSMG_OK) return rc;
     std::vector<float> per((size_t)N);
     double sum = 0.0;
-    for (int n = 0; n < N; ++n) {       // artist n alone: fsmg_maml_eval's adaptation, query pass, restore and repeat for N = 1
-        const int32_t* sup = e.sup + (size_t)n * K * T;
-        const int32_t* qry = e.qry + (size_t)n * Q * T;
-        rc = e.masked ? fsmg_maml_eval_masked(h, sup, qry, e.slen + (size_t)n * K, e.qlen + (size_t)n * Q, 1, K, Q, c->inner_steps, c->inner_lr,
-                                              e.on_device, &per[(size_t)n])
-                      : fsmg_maml_eval(h, sup, qry, 1, K, Q, c->inner_steps, c->inner_lr, e.on_device, &per[(size_t)n]);
+    for (int n = 0; n < N; ++n) {       // artist n alone: maml_eval's prologue, adaptation, query pass, restore and repeat for N = 1
+        rc = maml_eval(h, e.artist(n, h->T), c->inner_steps, c->inner_lr, &per[(size_t)n]);
         if (rc != FSMG_OK) return rc;
         sum += (double)per[(size_t)n];
     }

@@ -770,29 +770,78 @@ int keep_theta_prime(fsmg_model* h);      // before every restore_theta: P -> P_
 void on_timeout(fsmg_model* h);
 void on_softmax_range(fsmg_model* h);
 inline bool is_retry(int rc) { return rc == FSMG_ERR_TIMEOUT || rc == FSMG_ERR_SOFTMAX_RANGE; }
-// adapt on the support rows like fsmg_maml_eval, run `at_theta_prime` there, restore theta whatever happened (api_step.hip; the MAML
-// decode entry points in api_decode.hip)
+// ---- the train / MAML drivers (api_step.hip; DESIGN.md "cfg-E", 20, 22, 23, 27), shared with api_tasks.hip, api_dyneval.hip, api_state.hip
+// and the decode / score entry points at theta'
+int validate_shape(fsmg_model* h, int N, int K, int Q);
+int validate_masked_args(fsmg_model* h, const int32_t* support_len, const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int32_t on_device);
+// the call in progress is a padding-masked pass over `groups` groups of `rows_per_group` sequences (behind begin_call, which clears the flag)
+inline void begin_masked(fsmg_model* h, int rows_per_group, int groups) {
+    h->masked_call = true; h->mask_rpg = rows_per_group; h->mask_groups = groups;
+}
+// Where a MAML call's rows are once its arguments are checked (and, for a table form, gathered): [N * K][T] support rows, [N * Q][T] query
+// rows, their lengths where the call is a padding-masked one.  Artist n's support rows start at sup + n * K * T, its lengths at slen + n * K.
+struct Episode {
+    const int32_t *sup = nullptr, *qry = nullptr, *slen = nullptr, *qlen = nullptr;
+    int32_t N = 0, K = 0, Q = 0;
+    int on_device = 0;
+    bool masked = false;
+    Episode artist(int n, int T) const {        // artist n alone, as an episode of one
+        Episode a = *this;
+        a.N = 1; a.sup += (size_t)n * K * T; a.qry += (size_t)n * Q * T;
+        if (masked) { a.slen += (size_t)n * K; a.qlen += (size_t)n * Q; }
+        return a;
+    }
+};
+// the token form: the rows are where the caller says, masked iff it gave lengths
+inline Episode token_episode(const int32_t* support, const int32_t* query, const int32_t* support_len, const int32_t* query_len, int32_t N, int32_t K,
+                             int32_t Q, int on_device) {
+    Episode e;
+    e.sup = support; e.qry = query; e.slen = support_len; e.qlen = query_len; e.N = N; e.K = K; e.Q = Q;
+    e.on_device = on_device; e.masked = support_len != nullptr;
+    return e;
+}
+// the table form: the rows under the indices (with_len: and their lengths; a table without them: FSMG_ERR_STATE) are gathered ONCE into
+// d_gather / d_gather_len and every pass of the call reads them there
+int gather_episode(fsmg_model* h, int32_t table_id, bool with_len, const int32_t* support_idx, const int32_t* query_idx, int32_t N, int32_t K,
+                   int32_t Q, Episode* e);
+// table_id >= 0: gather_episode with support / query as the indices; otherwise token_episode
+int locate_episode(fsmg_model* h, int32_t table_id, bool with_len, const int32_t* support, const int32_t* query, const int32_t* support_len,
+                   const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int on_device, Episode* e);
+// forward + backward over the N * R rows [N * R][T] as support-position rows of one group; len != nullptr: the padding-masked pass over
+// their lengths.  Its own prologue (begin_call with keep_pending), masked_call cleared behind it.
+int rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t N, int32_t R, int32_t on_device);
+// the dynamic-evaluation driver's pass: rows_pass over host rows with the loss weights on [lo, min(hi, len[b])) only, never dropped
+int window_rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t n, int lo, int hi);
+// theta saved, `inner_steps` clipped-SGD (or Meta-SGD) steps on the episode's support rows.  train: a train form's adaptation (dropout
+// applies; with Meta-SGD S collects the applied steps)
+int maml_adapt(fsmg_model* h, const Episode& e, int32_t inner_steps, float inner_lr, bool train);
+// the error word the passes so far have left, read back and cleared; a time-out switches the handle to per-step launches and is
+// reported as FSMG_ERR_TIMEOUT
+int adapt_flag(fsmg_model* h);
+// The end of an adaptation, whatever happened in it: masked_call and window_call cleared, theta' kept where the debug knob asks for it,
+// theta back, no gradient pending.  Returns the first failure of its own.
+int end_adaptation(fsmg_model* h);
+// adapt(), body() at the adapted parameters, end_adaptation; where the adaptation ran skipped steps (a time-out: the handle has switched
+// to per-step launches) all three once more
+int at_adapted_theta(fsmg_model* h, const std::function<int()>& adapt, const std::function<int()>& body);
+// the three MAML calls behind their entry points' argument checks
+int maml_forward_backward(fsmg_model* h, const Episode& e, int32_t inner_steps, float inner_lr);
+int maml_step(fsmg_model* h, const Episode& e, int32_t inner_steps, float inner_lr, float* loss);
+int maml_eval(fsmg_model* h, const Episode& e, int32_t inner_steps, float inner_lr, float* nll);
+// adapt on the support rows like maml_eval, run `at_theta_prime` there, restore theta whatever happened (the MAML decode and score
+// entry points in api_decode.hip / api_score.hip)
 int with_adapted_theta(fsmg_model* h, const int32_t* support, int32_t n_support_rows, int32_t inner_steps, float inner_lr,
                        int32_t support_on_device, const std::function<int()>& at_theta_prime, const int32_t* support_len = nullptr,
                        bool masked = false);      // masked: every inner step over the positions t < support_len[b] only
-// api_step.hip, for the dynamic-evaluation driver (api_dyneval.hip): one window pass -- forward + backward over `rows` [n][T] with their
-// lengths, weights on [lo, min(hi, len[b])) only -- and the read-back of the error word the passes so far have left (cleared; a
-// time-out switches the handle to per-step launches and is reported as FSMG_ERR_TIMEOUT)
-int window_rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t n, int lo, int hi);
-int pass_flag(fsmg_model* h);
-int validate_shape(fsmg_model* h, int N, int K, int Q);
+// the episode-parallel step with the exchange inside the library: forward_backward(), all-reduce, clip + Adam (1 / world)
+int dp_train_step(fsmg_model* h, float* loss, const std::function<int()>& forward_backward);
+// forward_backward() and the outer update of a MAML-style step: dp_train_step with a communicator, otherwise fsmg_apply_update(1) and,
+// after a time-out, both once more on per-step launches with the masks of the passes they repeat
+int step_with_update(fsmg_model* h, float* loss, const std::function<int()>& forward_backward);
 // api_dyneval.hip: adapt on the support stream by dynamic evaluation (nothing reported), run `at_theta_l` there, restore theta whatever
 // happened -- with_adapted_theta's twin (fsmg_dyneval_generate, api_decode.hip)
 int with_dyneval_theta(fsmg_model* h, const fsmg_dyneval_config* c, const int32_t* support, const int32_t* support_len, int32_t n_support_rows,
                        const std::function<int()>& at_theta_l);
-// api_step.hip, for the per-artist driver (api_tasks.hip): the adaptation, the masked K = 0 pass and the episode gather of the
-// fsmg_maml_* entry points as they stand
-int maml_adapt_rows(fsmg_model* h, const int32_t* support, int32_t N, int32_t K, int32_t inner_steps, float inner_lr, int32_t on_device,
-                    const int32_t* support_len, bool train);
-int masked_query_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int32_t N, int32_t R, int32_t on_device);
-int gather_episode_rows(fsmg_model* h, int32_t table_id, const int32_t* sup_idx, int n_sup, const int32_t* qry_idx, int n_qry, bool with_len);
-int validate_masked_args(fsmg_model* h, const int32_t* support_len, const int32_t* query_len, int32_t N, int32_t K, int32_t Q, int32_t on_device);
-int dp_train_step_fn(fsmg_model* h, float* loss, const std::function<int()>& forward_backward);     // the library-owned exchange around it
 int poll_skipped(fsmg_model* h);
 int report(fsmg_model* h, int what);
 int check_tokens_and_read(fsmg_model* h, const float* d_src, float scale, float* host_out, int n, bool train_tail = false);
