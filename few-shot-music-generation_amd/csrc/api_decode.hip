@@ -2,6 +2,8 @@
 // with_adapted_theta in api_step.hip) and fsmg_sample, the one-row greedy case of the generate driver; and the decode states
 // (fsmg_dstate_*): the same driver started from a carried LSTM state and committed back to it.
 // Host-side C++ only (part of the C-ABI of libfsmg, include/fsmg.h); the kernels live in decode.hip.  DESIGN.md 12-14, 16.
+#include <memory>
+
 #include "fsmg_model.h"
 
 using namespace fsmg;
@@ -39,6 +41,18 @@ struct Decode {
     char* extra = nullptr;                                    // (cache-conditioned generation: the cache kernels' scratch)
 };
 
+// One constrained call's constraint side: the object, the caller's state arrays, the host block
+// [state R | dead_ends R | open R * KW] the rows' states are loaded from and read back into, and the device tables with the rows'
+// working state, which begin_decode places in the call's scratch.
+struct ConRun {
+    const fsmg_constraint_s* c = nullptr;
+    fsmg_constraint_state* io = nullptr;
+    int R = 0;
+    std::vector<int32_t> host;
+    ConstraintDev dev{};
+    size_t bytes() const { return sizeof(int32_t) * host.size(); }
+};
+
 // The prologue of generate (W = 0) and beam search (W > 0: W rows per primer row): a host primer is range-checked before any device
 // work; the scratch is laid out (h->gen grown if need be); the token buffer rows get [start word, primer row]; a device primer is
 // checked once, before the token loop; the LSTM state is zeroed.
@@ -47,7 +61,7 @@ struct Decode {
 // from the state (row r from state row r / W); and `primer` is nullptr, or with `feed` the call's [R][num] given tokens (ids in
 // [0, input_size]), which go behind the tail -- a device array's range flag is d.flag, read back with the outputs.
 int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool primer_on_device, const int32_t* primer,
-                 const fsmg_dstate_s* st = nullptr, bool feed = false) {
+                 const fsmg_dstate_s* st = nullptr, bool feed = false, ConRun* cr = nullptr) {
     const bool beam = W > 0;
     const int rows_per_primer = beam ? W : 1;
     const size_t n_primer = st ? (feed ? (size_t)R * num : 0) : (size_t)(R / rows_per_primer) * P;
@@ -70,6 +84,7 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
     const size_t o_primer = cv.take(sizeof(int) * n_primer);
     const size_t o_err = cv.take(sizeof(int));
     const size_t o_extra = cv.take(d.extra_bytes);
+    const size_t o_con = cv.take(cr ? cr->bytes() : 0);
     int rc = gen_reserve(h, cv.off);
     if (rc != FSMG_OK) return rc;
     char* base = h->gen;
@@ -101,6 +116,12 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
         d_primer = (const int32_t*)(base + o_primer);
         HIPCK(h, hipMemcpyAsync((void*)d_primer, primer, sizeof(int) * n_primer, hipMemcpyHostToDevice, s));
     }
+    if (cr) {       // the rows' constraint states: loaded here, walked over the primer below
+        cr->dev.state = (int*)(base + o_con);
+        cr->dev.dead = cr->dev.state + R;
+        cr->dev.open = (unsigned*)(cr->dev.dead + R);
+        HIPCK(h, hipMemcpyAsync(cr->dev.state, cr->host.data(), cr->bytes(), hipMemcpyHostToDevice, s));
+    }
     if (st) {
         HIPCK(h, launch_dstate_rows(s, h->L, R, st->R, h->Hp, nullptr, rows_per_primer, st->h, d.h_in, st->c, d.c, st->ctx, st->history + 1, 0,
                                     d.tok, d.ldtok, 0, P + 1));
@@ -112,11 +133,13 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
     }
     HIPCK(h, hipMemsetAsync(err, 0, sizeof(int), s));
     HIPCK(h, launch_gen_primer(s, d_primer, R, P, h->V, h->V, d.tok, d.ldtok, err, rows_per_primer));
+    if (cr && P > 0) HIPCK(h, launch_constraint_advance(s, cr->dev, h->V1, R, P, d.tok, d.ldtok, err));
     if (P > 0 && primer_on_device) {
         int e = 0;
         HIPCK(h, hipMemcpyAsync(&e, err, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCK(h, hipStreamSynchronize(s));
-        if (e) return fail(h, FSMG_ERR_TOKEN_RANGE, "primer id outside [0, input_size)");
+        if (e) return fail(h, FSMG_ERR_TOKEN_RANGE, cr ? "primer id outside [0, input_size), or not allowed by the constraint where it stands"
+                                                       : "primer id outside [0, input_size)");
     }
     HIPCK(h, hipMemsetAsync(d.h_in, 0, sizeof(float) * layer, s));
     HIPCK(h, hipMemsetAsync(d.c, 0, sizeof(float) * layer, s));
@@ -215,12 +238,91 @@ int check_beam_config(fsmg_model* h, const fsmg_beam_config* b, const int32_t* p
     return FSMG_OK;
 }
 
+// ---- constrained decoding
+// the constraint `con` if this handle owns it (the registry: a destroyed or foreign pointer is never dereferenced)
+fsmg_constraint_s* find_constraint(fsmg_model* h, fsmg_constraint con) {
+    for (fsmg_constraint_s* c : h->constraints)
+        if (c == con && con != nullptr) return c;
+    fail(h, FSMG_ERR_INVALID, "not a constraint of this handle (never created here, or already destroyed)");
+    return nullptr;
+}
+
+// is token v allowed in (s, open)?  the host twin of decode.hip's con_allowed; *nx = the next state
+bool con_allowed_host(const fsmg_constraint_s& c, int s, const uint32_t* open, int v, int* nx) {
+    *nx = c.h_next[(size_t)s * c.C + c.h_cls[(size_t)v]];
+    if (!(c.h_bias[(size_t)v] > -INFINITY) || *nx < 0) return false;
+    const unsigned w = c.h_slot[(size_t)v];
+    if (w == 0u) return true;
+    const unsigned k = (w & 0x7FFFFFFFu) - 1u;
+    return ((open[k >> 5] >> (k & 31u)) & 1u) == (w >> 31);
+}
+
+// What a constrained call checks before any device work: the caller's state arrays (NULL: start state, every slot closed, zero dead
+// ends) -> cr.host, and a host primer walked from there -- an id outside [0, input_size) is the twin's FSMG_ERR_TOKEN_RANGE, a token
+// that is not allowed where it stands FSMG_ERR_INVALID.  The device walks the primer again from the same block.
+int con_prepare(fsmg_model* h, ConRun& cr, const fsmg_constraint_s* c, fsmg_constraint_state* io, int R, const int32_t* host_primer, int P) {
+    cr.c = c; cr.io = io; cr.R = R;
+    const size_t KW = (size_t)c->KW;
+    cr.host.assign((size_t)R * (2 + KW), 0);
+    int32_t* state = cr.host.data();
+    int32_t* dead = state + R;
+    uint32_t* open = (uint32_t*)(dead + R);
+    for (int b = 0; b < R; ++b) {
+        state[b] = io && io->state ? io->state[b] : c->start;
+        dead[b] = io && io->dead_ends ? io->dead_ends[b] : 0;
+        if (state[b] < 0 || state[b] >= c->S) return fail(h, FSMG_ERR_INVALID, "cstate_io.state outside [0, n_states)");
+        if (dead[b] < 0) return fail(h, FSMG_ERR_INVALID, "cstate_io.dead_ends must be >= 0");
+        for (size_t i = 0; io && io->open && i < KW; ++i) {
+            const uint32_t w = io->open[(size_t)b * KW + i];
+            const int live = c->K - 32 * (int)i;      // the slots of this word
+            if (live < 32 && (w >> live) != 0u) return fail(h, FSMG_ERR_INVALID, "cstate_io.open has a bit at or above n_slots");
+            open[(size_t)b * KW + i] = w;
+        }
+    }
+    cr.dev = ConstraintDev{c->bias, c->cls, c->slot, c->next, c->S, c->C, c->KW, nullptr, nullptr, nullptr};
+    if (!host_primer || P <= 0) return FSMG_OK;
+    std::vector<uint32_t> o(KW + 1);
+    for (int b = 0; b < R; ++b) {
+        int s = state[b];
+        std::copy(open + (size_t)b * KW, open + (size_t)(b + 1) * KW, o.begin());
+        for (int p = 0; p < P; ++p) {
+            const int v = host_primer[(size_t)b * P + p];
+            if (v < 0 || v >= h->V) return fail(h, FSMG_ERR_TOKEN_RANGE, "primer id outside [0, input_size)");
+            int nx = 0;
+            if (!con_allowed_host(*c, s, o.data(), v, &nx))
+                return fail(h, FSMG_ERR_INVALID, "primer token " + std::to_string(p) + " of row " + std::to_string(b) +
+                                                     " is not allowed by the constraint where it stands");
+            s = nx;
+            const unsigned w = c->h_slot[(size_t)v];
+            if (w != 0u) { const unsigned k = (w & 0x7FFFFFFFu) - 1u; o[k >> 5] ^= 1u << (k & 31u); }
+        }
+    }
+    return FSMG_OK;
+}
+
+// the rows' states back into cr.host (one copy, behind the token loop on the stream); done: wait for it and hand it to the caller
+void con_scatter(ConRun& cr) {
+    if (!cr.io) return;
+    const size_t R = (size_t)cr.R;
+    const int32_t* state = cr.host.data();
+    if (cr.io->state) std::memcpy(cr.io->state, state, sizeof(int32_t) * R);
+    if (cr.io->dead_ends) std::memcpy(cr.io->dead_ends, state + R, sizeof(int32_t) * R);
+    if (cr.io->open && cr.c->KW > 0) std::memcpy(cr.io->open, state + 2 * R, sizeof(uint32_t) * R * cr.c->KW);
+}
+int con_read_back(fsmg_model* h, ConRun& cr, bool done) {
+    HIPCK(h, hipMemcpyAsync(cr.host.data(), cr.dev.state, cr.bytes(), hipMemcpyDeviceToHost, h->stream));
+    if (!done) return FSMG_OK;
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    con_scatter(cr);
+    return FSMG_OK;
+}
+
 // fsmg_generate_filtered's work at the parameters the handle holds now (no BEGIN_CALL: the MAML variants call it at theta').
 // f == nullptr or neutral: fsmg_generate's pick.  st != nullptr: from that decode state (the token loop starts at the pending token,
 // the Philox position runs on from n_gen) and back into it.  cg != nullptr (fsmg_cache_generate with lambda > 0): at every generated
 // position the logits rows are overwritten with the mixed log-probabilities z'' before the unchanged pick reads them.
 int generate_core(fsmg_model* h, const fsmg_gen_config* g, const fsmg_gen_filters* f, const int32_t* primer, int32_t* out_tokens,
-                  float* out_logprob, fsmg_dstate_s* st = nullptr, CacheGen* cg = nullptr) {
+                  float* out_logprob, fsmg_dstate_s* st = nullptr, CacheGen* cg = nullptr, ConRun* cr = nullptr) {
     const bool neutral = !f || ((f->top_p == 0.f || f->top_p == 1.f) && f->min_p == 0.f &&
                                 (f->repetition_penalty == 0.f || f->repetition_penalty == 1.f));
     GenFilters pf{};
@@ -228,8 +330,9 @@ int generate_core(fsmg_model* h, const fsmg_gen_config* g, const fsmg_gen_filter
     const GenFilters* pick_f = neutral ? nullptr : &pf;      // neutral filters: exactly fsmg_generate's pick
     Decode d;
     if (cg && g->num > 0) d.extra_bytes = cache_gen_bytes(h, *cg);        // the scratch grows here, never inside the token loop
-    int rc = begin_decode(h, d, g->n_seq, 0, st ? st->kept() : g->primer_len, g->num, g->primer_on_device, primer, st);
-    if (rc != FSMG_OK || d.num == 0) return rc;
+    int rc = begin_decode(h, d, g->n_seq, 0, st ? st->kept() : g->primer_len, g->num, g->primer_on_device, primer, st, false, cr);
+    if (rc != FSMG_OK) return rc;
+    if (d.num == 0) return cr ? con_read_back(h, *cr, true) : rc;
     if (cg && (rc = cache_gen_place(h, *cg, d.extra)) != FSMG_OK) return rc;
     const int p0 = st ? d.P : 0, ctr0 = st ? (int)st->n_gen : 0;
     // position p reads tok[:, p]; primer positions (p < P) run the cells only, generated position t = p - P writes tok[:, p + 1]
@@ -241,13 +344,19 @@ int generate_core(fsmg_model* h, const fsmg_gen_config* g, const fsmg_gen_filter
             if ((rc = cache_self_file(h, *cg, top, p)) != FSMG_OK) return rc;
             if (p >= d.P && (rc = cache_self_step(h, *cg, p, top, d.logits, d.tok + 1, d.ldtok, nullptr)) != FSMG_OK) return rc;
         } else if (p >= d.P && cg && (rc = cache_gen_step(h, *cg, d.h_out + (size_t)(h->L - 1) * d.R * h->Hp, d.logits, nullptr)) != FSMG_OK) return rc;
-        if (p >= d.P)
+        if (p >= d.P && cr)
+            HIPCK(h, launch_gen_pick_constrained(h->stream, d.logits, d.ldl, h->V1, d.R, g->temperature, g->top_k, pick_f, cr->dev, g->seed,
+                                                 p - d.P, ctr0 + p - d.P, d.tok, d.ldtok, p + 1, d.out_tok, d.out_lp, d.num));
+        else if (p >= d.P)
             HIPCK(h, launch_gen_pick(h->stream, d.logits, d.ldl, h->V1, d.R, g->temperature, g->top_k, pick_f, g->seed, p - d.P,
                                      ctr0 + p - d.P, d.tok, d.ldtok, p + 1, d.out_tok, d.out_lp, d.num));
         std::swap(d.h_in, d.h_out);                 // the new state is every row's own
     }
     if (st && (rc = commit_state(h, d, st, d.num, true)) != FSMG_OK) return rc;
-    return read_outputs(h, d, out_tokens, out_logprob);
+    if (cr && (rc = con_read_back(h, *cr, false)) != FSMG_OK) return rc;
+    if ((rc = read_outputs(h, d, out_tokens, out_logprob)) != FSMG_OK) return rc;
+    if (cr) con_scatter(*cr);
+    return FSMG_OK;
 }
 
 // fsmg_beam_search's work at the parameters the handle holds now (no BEGIN_CALL, as generate_core).  st != nullptr: group g starts
@@ -416,6 +525,132 @@ int fsmg_maml_generate_filtered_masked(fsmg_handle h, const fsmg_gen_config* g, 
     if (rc != FSMG_OK) return rc;
     return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
                               [&] { return generate_core(h, g, f, primer, out_tokens, out_logprob); }, support_len, true);
+}
+
+// ---- constrained decoding
+int fsmg_constraint_create(fsmg_handle h, const fsmg_constraint_config* c, fsmg_constraint* out) {
+    if (!h) return FSMG_ERR_INVALID;
+    if (!c || !out) return fail(h, FSMG_ERR_INVALID, "null fsmg_constraint_config / out");
+    int rc = check_config_header(h, c, "fsmg_constraint_config", FSMG_CONSTRAINT_CONFIG_VERSION);
+    if (rc != FSMG_OK) return rc;
+    if (c->n_columns != h->V1) return fail(h, FSMG_ERR_INVALID, "n_columns must be input_size + 1 of this handle");
+    if (h->V1 > (1 << 19)) return fail(h, FSMG_ERR_INVALID, "a constraint needs input_size + 1 <= 2^19");   // (two bitmaps of an unstaged row in LDS)
+    const bool automaton = c->token_class || c->next_state;
+    if (automaton && !(c->token_class && c->next_state)) return fail(h, FSMG_ERR_INVALID, "token_class and next_state come together");
+    if (!automaton && (c->n_states != 0 || c->n_classes != 0 || c->start_state != 0))
+        return fail(h, FSMG_ERR_INVALID, "without an automaton n_states, n_classes and start_state must be 0");
+    const int S = automaton ? c->n_states : 1, Cn = automaton ? c->n_classes : 1, K = c->n_slots, V1 = h->V1;
+    if (S < 1 || S > CON_MAX_STATES) return fail(h, FSMG_ERR_INVALID, "n_states must be in [1, 256]");
+    if (Cn < 1 || Cn > CON_MAX_CLASSES) return fail(h, FSMG_ERR_INVALID, "n_classes must be in [1, 64]");
+    if (K < 0 || K > CON_MAX_SLOTS) return fail(h, FSMG_ERR_INVALID, "n_slots must be in [0, 4096]");
+    if (c->start_state < 0 || c->start_state >= S) return fail(h, FSMG_ERR_INVALID, "start_state outside [0, n_states)");
+    fsmg_constraint_s* con = new (std::nothrow) fsmg_constraint_s;
+    if (!con) return fail(h, FSMG_ERR_NOMEM, "out of host memory");
+    std::unique_ptr<fsmg_constraint_s> guard(con);
+    con->V1 = V1; con->S = S; con->C = Cn; con->K = K; con->KW = (K + 31) / 32; con->start = c->start_state;
+    con->h_bias.assign((size_t)V1, 0.0f);
+    con->h_cls.assign((size_t)V1, 0);
+    con->h_slot.assign((size_t)V1, 0u);
+    con->h_next.assign((size_t)S * Cn, 0);
+    for (int v = 0; v < V1; ++v) {
+        if (c->bias) {
+            const float bv = c->bias[v];
+            if (bv != bv || bv == INFINITY) return fail(h, FSMG_ERR_INVALID, "bias must be finite or -inf");
+            con->h_bias[(size_t)v] = bv;
+        }
+        if (automaton) {
+            if (c->token_class[v] < 0 || c->token_class[v] >= Cn) return fail(h, FSMG_ERR_INVALID, "token_class outside [0, n_classes)");
+            con->h_cls[(size_t)v] = (unsigned char)c->token_class[v];
+        }
+        const int so = c->slot_open ? c->slot_open[v] : -1, sc = c->slot_close ? c->slot_close[v] : -1;
+        if (so < -1 || so >= K || sc < -1 || sc >= K) return fail(h, FSMG_ERR_INVALID, "slot index outside [-1, n_slots)");
+        if (so >= 0 && sc >= 0) return fail(h, FSMG_ERR_INVALID, "a token both opens and closes a slot");
+        if (so >= 0) con->h_slot[(size_t)v] = (unsigned)(so + 1);
+        if (sc >= 0) con->h_slot[(size_t)v] = (unsigned)(sc + 1) | 0x80000000u;
+    }
+    for (size_t i = 0; automaton && i < (size_t)S * Cn; ++i) {
+        if (c->next_state[i] < -1 || c->next_state[i] >= S) return fail(h, FSMG_ERR_INVALID, "next_state outside [-1, n_states)");
+        con->h_next[i] = (short)c->next_state[i];
+    }
+    BEGIN_CALL(h);
+    Carver cv;
+    const size_t o_bias = cv.take(sizeof(float) * V1), o_slot = cv.take(sizeof(unsigned) * V1), o_next = cv.take(sizeof(short) * S * Cn),
+                 o_cls = cv.take((size_t)V1);
+    if (hipMalloc((void**)&con->mem, cv.off) != hipSuccess) return fail(h, FSMG_ERR_NOMEM, "hipMalloc(constraint) failed");
+    con->bias = (float*)(con->mem + o_bias);
+    con->slot = (unsigned*)(con->mem + o_slot);
+    con->next = (short*)(con->mem + o_next);
+    con->cls = (unsigned char*)(con->mem + o_cls);
+    hipError_t e = hipMemcpyAsync(con->bias, con->h_bias.data(), sizeof(float) * V1, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(con->slot, con->h_slot.data(), sizeof(unsigned) * V1, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(con->next, con->h_next.data(), sizeof(short) * S * Cn, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(con->cls, con->h_cls.data(), (size_t)V1, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        hipFree(con->mem);
+        return fail(h, FSMG_ERR_HIP, std::string("uploading the constraint: ") + hipGetErrorString(e));
+    }
+    h->constraints.push_back(guard.release());
+    *out = con;
+    return FSMG_OK;
+}
+
+int fsmg_constraint_destroy(fsmg_handle h, fsmg_constraint con) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_constraint_s* c = find_constraint(h, con);
+    if (!c) return FSMG_ERR_INVALID;
+    BEGIN_CALL(h);
+    HIPCK(h, hipStreamSynchronize(h->stream));      // nothing in flight reads it
+    h->constraints.erase(std::find(h->constraints.begin(), h->constraints.end(), c));
+    hipFree(c->mem);
+    delete c;
+    return FSMG_OK;
+}
+
+int fsmg_constraint_info(fsmg_handle h, fsmg_constraint con, int64_t out[4]) {
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_constraint_s* c = find_constraint(h, con);
+    if (!c) return FSMG_ERR_INVALID;
+    if (!out) return fail(h, FSMG_ERR_INVALID, "null out");
+    out[0] = c->V1; out[1] = c->S; out[2] = c->C; out[3] = c->K;
+    return FSMG_OK;
+}
+
+int fsmg_generate_constrained(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f, fsmg_constraint con,
+                              fsmg_constraint_state* cstate_io, const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
+    if (!con) return fsmg_generate_filtered(h, g, f, primer, out_tokens, out_logprob);
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_constraint_s* c = find_constraint(h, con);
+    if (!c) return FSMG_ERR_INVALID;
+    int rc = check_gen_config(h, g, primer, out_tokens);
+    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    ConRun cr;
+    if (rc == FSMG_OK) rc = con_prepare(h, cr, c, cstate_io, g->n_seq, g->primer_on_device ? nullptr : primer, g->primer_len);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return generate_core(h, g, f, primer, out_tokens, out_logprob, nullptr, nullptr, &cr);
+}
+
+int fsmg_maml_generate_constrained(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f, fsmg_constraint con,
+                                   fsmg_constraint_state* cstate_io, const int32_t* support, const int32_t* support_len,
+                                   int32_t n_support_rows, int32_t inner_steps, float inner_lr, int32_t support_on_device,
+                                   const int32_t* primer, int32_t* out_tokens, float* out_logprob) {
+    if (!con)
+        return support_len ? fsmg_maml_generate_filtered_masked(h, g, f, support, support_len, n_support_rows, inner_steps, inner_lr,
+                                                                support_on_device, primer, out_tokens, out_logprob)
+                           : fsmg_maml_generate_filtered(h, g, f, support, n_support_rows, inner_steps, inner_lr, support_on_device, primer,
+                                                         out_tokens, out_logprob);
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_constraint_s* c = find_constraint(h, con);
+    if (!c) return FSMG_ERR_INVALID;
+    int rc = check_gen_config(h, g, primer, out_tokens);
+    if (rc == FSMG_OK) rc = check_gen_filters(h, f);
+    ConRun cr;
+    if (rc == FSMG_OK) rc = con_prepare(h, cr, c, cstate_io, g->n_seq, g->primer_on_device ? nullptr : primer, g->primer_len);
+    if (rc != FSMG_OK) return rc;
+    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
+                              [&] { return generate_core(h, g, f, primer, out_tokens, out_logprob, nullptr, nullptr, &cr); }, support_len,
+                              support_len != nullptr);
 }
 
 // the adaptation by dynamic evaluation over the support stream; the generation at theta_l is fsmg_generate_filtered's
@@ -608,6 +843,23 @@ int fsmg_dstate_generate(fsmg_handle h, fsmg_dstate st, const fsmg_gen_config* g
     if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
     return generate_core(h, g, f, nullptr, out_tokens, out_logprob, s);
+}
+
+// fsmg_dstate_generate under a constraint: the caller's cstate_io is the rows' constraint state from call to call
+int fsmg_dstate_generate_constrained(fsmg_handle h, fsmg_dstate st, const fsmg_gen_config* g, const fsmg_gen_filters* f, fsmg_constraint con,
+                                     fsmg_constraint_state* cstate_io, int32_t* out_tokens, float* out_logprob) {
+    if (!con) return fsmg_dstate_generate(h, st, g, f, out_tokens, out_logprob);
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    fsmg_constraint_s* c = find_constraint(h, con);
+    if (!c) return FSMG_ERR_INVALID;
+    int rc = check_state_generate(h, s, g, f, out_tokens);
+    ConRun cr;
+    if (rc == FSMG_OK) rc = con_prepare(h, cr, c, cstate_io, g->n_seq, nullptr, 0);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return generate_core(h, g, f, nullptr, out_tokens, out_logprob, s, nullptr, &cr);
 }
 
 // ---- cache-conditioned generation: the generate calls with a support-set cache beside the model

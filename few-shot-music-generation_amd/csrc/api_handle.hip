@@ -359,6 +359,7 @@ int fsmg_destroy(fsmg_handle h) {
     if (h->gen) hipFree(h->gen);
     for (fsmg_dstate_s* st : h->dstates) { if (st->mem) hipFree(st->mem); delete st; }     // the decode states still alive
     for (fsmg_cache_s* c : h->caches) free_cache(c);                                         // ... and the caches
+    for (fsmg_constraint_s* c : h->constraints) { if (c->mem) hipFree(c->mem); delete c; }   // ... and the constraints
     if (h->cat) hipFree(h->cat);
     if (h->khf) hipFree(h->khf);
     if (h->khx) hipFree(h->khx);

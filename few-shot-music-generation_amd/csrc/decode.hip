@@ -630,6 +630,203 @@ __global__ __launch_bounds__(PICK_THREADS) void k_gen_pick_filtered(const float*
     write_pick(best, row, lse, ncols, b, t, tok, ldtok, pos_out, out_tok, out_lp, num);
 }
 
+// ---------------------------------------------------------------- the constrained pick (fsmg_generate_constrained)
+// column v in the allowed set of (nline = next[s][*], open)?  (ConstraintDev's comment has the encoding; the masks only keep the
+// LDS indices in range -- creation checked the tables)
+__device__ __forceinline__ bool con_ok(float bias, unsigned cls, unsigned w, const unsigned* open, const short* nline) {
+    const unsigned k = (w & 0x7FFFFFFFu) - 1u;
+    const bool slot_ok = w == 0u || ((open[(k >> 5) & (CON_MAX_SLOTS / 32 - 1)] >> (k & 31u)) & 1u) == (w >> 31);
+    return bias > -INFINITY && nline[cls & (CON_MAX_CLASSES - 1)] >= 0 && slot_ok;
+}
+__device__ __forceinline__ bool con_allowed(const ConstraintDev& c, const unsigned* open, const short* nline, int v) {
+    return con_ok(c.bias[v], c.cls[v], c.slot[v], open, nline);        // (three independent loads, in flight together)
+}
+
+// k_gen_pick_filtered on the constrained logits z^c; one row per workgroup.  lse and out_lp come from the raw row exactly as in
+// k_gen_pick.  z^c_v = fl(z_v + bias_v) for v in Omega (the allowed set of the row's state), -inf elsewhere; the penalty, top-k,
+// min-p, top-p and the Gumbel-max then run on z^c as they run on z in k_gen_pick_filtered.  One sweep evaluates the predicate (the
+// bias, the class byte and the slot word of a column come from global memory, four columns' loads in flight per thread): STAGED, it
+// rewrites the staged row to z^c; else it leaves Omega as a bitmap of ceil(ncols / 32) words at the head of the dynamic LDS (the
+// penalty's presence bitmap behind it), and val(v) adds the bias on the fly.  The sweep's reduction yields Omega's lowest column,
+// ncols when Omega is empty: the dead end, picked from z like
+// k_gen_pick_filtered picks it, the state left alone, dead[b] counted up.  A column outside a non-empty Omega is never picked:
+// when no allowed column compares above -inf the pick is Omega's lowest column.  Thread 0 advances the state after the pick.
+// The row's open bits and its next[s][*] line sit in static LDS (768 B) beside the staged row.
+template <bool STAGED>
+__global__ __launch_bounds__(PICK_THREADS) void k_gen_pick_constrained(const float* __restrict__ logits, int ldl, int ncols, float temperature,
+                                                                       int top_k, float top_p, float min_p, float theta, int window,
+                                                                       ConstraintDev c, unsigned seed_lo, unsigned seed_hi, int t, int ctr_t,
+                                                                       int* __restrict__ tok, int ldtok, int pos_out,
+                                                                       int* __restrict__ out_tok, float* __restrict__ out_lp, int num) {
+    extern __shared__ float srow[];
+    __shared__ PickShared sh;
+    __shared__ RadixShared<unsigned long long> fs;
+    __shared__ unsigned copen[CON_MAX_SLOTS / 32];
+    __shared__ short nline[CON_MAX_CLASSES];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* row = logits + (long long)b * ldl;
+    const int* trow = tok + (long long)b * ldtok;
+    const int nw = (ncols + 31) >> 5;
+    unsigned* abits = (unsigned*)srow;          // unstaged: Omega, then the penalty's presence bitmap
+    unsigned* bits = abits + nw;
+    const bool pen = theta != 1.0f;
+    bool dead = false;
+    auto penalise = [&](float z) -> float { return z > 0.0f ? z / theta : z * theta; };
+    auto allowed = [&](int v) -> bool {
+        return STAGED ? con_allowed(c, copen, nline, v) : ((abits[v >> 5] >> (v & 31)) & 1u) != 0u;
+    };
+    auto zc = [&](int v) -> float {       // z^c from the raw row (z itself at a dead end)
+        const float z = row[v];
+        return dead ? z : allowed(v) ? z + c.bias[v] : -INFINITY;
+    };
+    auto val = [&](int v) -> float {
+        if (STAGED) return srow[v];
+        const float z = zc(v);
+        return pen && ((bits[v >> 5] >> (v & 31)) & 1u) ? penalise(z) : z;
+    };
+
+    // the row's constraint state -> LDS (ordered before its readers by the sweep's barriers)
+    const int s0 = min(max(c.state[b], 0), c.S - 1);
+    for (int i = tid; i < c.KW && i < CON_MAX_SLOTS / 32; i += PICK_THREADS) copen[i] = c.open[(long long)b * c.KW + i];
+    if (tid < CON_MAX_CLASSES) nline[tid] = tid < c.C ? c.next[s0 * c.C + tid] : (short)-1;
+
+    float mx; int mi;
+    const float lse = row_max_lse<STAGED>(sh, row, srow, ncols, mx, mi);
+
+    // Omega's lowest column (and, STAGED, the row rewritten to z^c)
+    float any = -INFINITY; int lo = ncols;
+    for (int v0 = tid; v0 - tid < ncols; v0 += 4 * PICK_THREADS) {         // (block-uniform trip count: the ballots below)
+        float bv[4]; unsigned cw[4], sw[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v = v0 + j * PICK_THREADS;
+            const bool in = v < ncols;
+            bv[j] = in ? c.bias[v] : -INFINITY;
+            cw[j] = in ? c.cls[v] : 0u;
+            sw[j] = in ? c.slot[v] : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v = v0 + j * PICK_THREADS;
+            const bool ok = v < ncols && con_ok(bv[j], cw[j], sw[j], copen, nline);
+            if (ok && v < lo) { any = 0.0f; lo = v; }
+            if (STAGED) {
+                if (v < ncols) srow[v] = ok ? srow[v] + bv[j] : -INFINITY;
+            } else {        // a wave's 64 consecutive columns are two words of the bitmap (v - lane is a multiple of 64)
+                const unsigned long long mk = __ballot(ok);
+                const int wi = (v - (tid & 63)) >> 5;
+                if ((tid & 63) == 0 && wi < nw) {
+                    abits[wi] = (unsigned)mk;
+                    if (wi + 1 < nw) abits[wi + 1] = (unsigned)(mk >> 32);
+                }
+            }
+        }
+    }
+    block_argmax(sh, any, lo);
+    dead = !(any > -INFINITY);
+    if (dead && STAGED) {       // nothing is allowed: back to z
+        for (int v = tid; v < ncols; v += PICK_THREADS) srow[v] = row[v];
+    }
+    __syncthreads();
+
+    if (pen) {      // the context tokens in the window (tok[b][0] is the start word, not part of it)
+        const int first = window > 0 ? max(1, pos_out - window) : 1;
+        if (!STAGED) {
+            for (int i = tid; i < (ncols + 31) >> 5; i += PICK_THREADS) bits[i] = 0u;
+            __syncthreads();
+        }
+        for (int i = first + tid; i < pos_out; i += PICK_THREADS) {
+            const int v = trow[i];
+            if (v < 0 || v >= ncols) continue;
+            if (STAGED) srow[v] = penalise(zc(v));
+            else atomicOr(&bits[v >> 5], 1u << (v & 31));
+        }
+        __syncthreads();
+    }
+    // zmax and its lowest column over the comparable values; flat: none compares above -inf
+    float zm = -INFINITY; int zi = ncols;
+    for (int v = tid; v < ncols; v += PICK_THREADS) {
+        const float z = val(v);
+        if (z > zm || (z == zm && v < zi)) { zm = z; zi = v; }
+    }
+    block_argmax(sh, zm, zi);
+    const bool flat = !(zm > -INFINITY);
+    if (zi >= ncols) zi = 0;
+    if (flat && !dead) zi = lo;
+
+    int best = zi;
+    if (temperature > 0.0f && top_k != 1 && (dead || !flat)) {
+        float thr = -INFINITY;
+        if (top_k > 1 && top_k < ncols) {
+            const unsigned kk = radix_select(sh.rs, ncols, [&](int v) { return beam_key(val(v)); }, [](int) { return 1; }, [&](int) { return top_k; });
+            if (kk != 0u) thr = key_float(kk);
+        }
+        if (min_p > 0.0f) thr = fmaxf(thr, zm + temperature * logf(min_p));
+        if (top_p > 0.0f && top_p < 1.0f) {       // k_gen_pick_filtered's top-p boundary, on z^c
+            const float thr1 = thr;
+            const unsigned xp = radix_select(
+                fs, ncols, [&](int v) { return beam_key(val(v)); },
+                [&](int v) -> unsigned long long {
+                    const float z = val(v);
+                    if (!(z >= thr1)) return 0ull;
+                    const float d = z == zm ? 0.0f : (z - zm) / temperature;
+                    return (unsigned long long)(expf(d) * 0x1p32f);
+                },
+                [&](unsigned long long Z) {
+                    const double want = ceil((double)top_p * (double)Z);
+                    const unsigned long long kl = want < 1.0 ? 1ull : (unsigned long long)want;
+                    return kl > Z ? Z : kl;
+                });
+            if (xp != 0u) thr = key_float(xp);
+        }
+        best = gumbel_max(sh, ncols, thr, temperature, seed_lo, seed_hi, ctr_t, b, zi, val);
+    }
+    best = min(max(best, 0), ncols - 1);
+    write_pick(best, row, lse, ncols, b, t, tok, ldtok, pos_out, out_tok, out_lp, num);
+    if (tid == 0) {
+        if (dead) {
+            c.dead[b] += 1;
+        } else {
+            c.state[b] = nline[c.cls[best] & (CON_MAX_CLASSES - 1)];
+            const unsigned w = c.slot[best];
+            if (w != 0u) {
+                const unsigned k = (w & 0x7FFFFFFFu) - 1u, wi = (k >> 5) & (CON_MAX_SLOTS / 32 - 1);
+                if ((int)wi < c.KW) c.open[(long long)b * c.KW + wi] = copen[wi] ^ (1u << (k & 31u));
+            }
+        }
+    }
+}
+
+// One thread per row: the row's state walked over its primer tokens tok[b][1 .. P] in order (the start word at tok[b][0] advances
+// nothing).  A token that is not allowed where it stands raises *err and is stepped over.
+__global__ void k_constraint_advance(ConstraintDev c, int ncols, int B, int P, const int* __restrict__ tok, int ldtok, int* __restrict__ err) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    unsigned* open = c.open + (long long)b * c.KW;
+    int s = c.state[b];
+    bool bad = s < 0 || s >= c.S;
+    if (bad) s = 0;
+    for (int p = 1; p <= P; ++p) {
+        const int v = tok[(long long)b * ldtok + p];
+        if (v < 0 || v >= ncols) { bad = true; continue; }
+        const int nx = c.next[s * c.C + (c.cls[v] & (CON_MAX_CLASSES - 1))];
+        const unsigned w = c.slot[v];
+        const unsigned k = (w & 0x7FFFFFFFu) - 1u;
+        bool ok = c.bias[v] > -INFINITY && nx >= 0;
+        unsigned word = 0u;
+        if (w != 0u) {
+            if ((int)(k >> 5) >= c.KW) { bad = true; continue; }
+            word = open[k >> 5];
+            ok = ok && ((word >> (k & 31u)) & 1u) == (w >> 31);
+        }
+        if (!ok) { bad = true; continue; }
+        s = nx;
+        if (w != 0u) open[k >> 5] = word ^ (1u << (k & 31u));
+    }
+    c.state[b] = s;
+    if (bad) atomicOr(err, 1);
+}
+
 // ---------------------------------------------------------------- decode states (fsmg_dstate_*, DESIGN.md "Decode states")
 // The teacher-forced log-prob of fsmg_dstate_feed; one row per workgroup.  lse is the picks' (row_max_lse), so that the log-prob feed
 // returns for a token is bitwise the number a pick that chose it reports: out_lp[b][i] = logit[target] - lse, the target the token
@@ -917,6 +1114,33 @@ hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncol
     return launch_row_kernel<k_gen_pick_filtered<true>, k_gen_pick_filtered<false>>(s, B, ncols, bitmap_bytes, logits, ldl, ncols, temperature,
                                                                                     top_k, f->top_p, f->min_p, f->theta, f->window, lo, hi, t,
                                                                                     ctr_t, tok, ldtok, pos_out, out_tok, out_lp, num);
+}
+
+hipError_t launch_gen_pick_constrained(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k,
+                                       const GenFilters* f, const ConstraintDev& c, uint64_t seed, int t, int ctr_t, int* tok, int ldtok,
+                                       int pos_out, int* out_tok, float* out_lp, int num) {
+    if (B <= 0) return hipSuccess;
+    if (ncols <= 0 || ncols > ldl || t < 0 || t >= num || ctr_t < t || pos_out >= ldtok || (f && f->window < 0)) return hipErrorInvalidValue;
+    if (c.S < 1 || c.S > CON_MAX_STATES || c.C < 1 || c.C > CON_MAX_CLASSES || c.KW < 0 || c.KW > CON_MAX_SLOTS / 32 || !c.bias || !c.cls ||
+        !c.slot || !c.next || !c.state || !c.open || !c.dead)
+        return hipErrorInvalidValue;
+    const unsigned lo = (unsigned)(seed & 0xFFFFFFFFull), hi = (unsigned)(seed >> 32);
+    const GenFilters none{0.0f, 0.0f, 1.0f, 0};
+    if (!f) f = &none;
+    // an unstaged row keeps Omega as a bitmap of its columns in LDS, and with a penalty the presence bitmap behind it
+    const size_t bitmap_bytes = sizeof(unsigned) * (size_t)((ncols + 31) / 32) * (f->theta != 1.0f ? 2 : 1);
+    if (bitmap_bytes > sizeof(float) * PICK_LDS_FLOATS) return hipErrorInvalidValue;
+    return launch_row_kernel<k_gen_pick_constrained<true>, k_gen_pick_constrained<false>>(s, B, ncols, bitmap_bytes, logits, ldl, ncols,
+                                                                                          temperature, top_k, f->top_p, f->min_p, f->theta,
+                                                                                          f->window, c, lo, hi, t, ctr_t, tok, ldtok, pos_out,
+                                                                                          out_tok, out_lp, num);
+}
+
+hipError_t launch_constraint_advance(hipStream_t s, const ConstraintDev& c, int ncols, int B, int P, const int* tok, int ldtok, int* err) {
+    if (B <= 0) return hipSuccess;
+    if (P < 0 || P + 1 > ldtok || ncols <= 0 || c.S < 1 || c.C < 1 || c.KW < 0 || !tok || !err) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_constraint_advance, dim3((B + 63) / 64), dim3(64), 0, s, c, ncols, B, P, tok, ldtok, err);
+    return hipGetLastError();
 }
 
 hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err,

@@ -524,6 +524,27 @@ struct GenFilters {
 // hipErrorInvalidValue (the presence bitmap of an unstaged row lives in LDS).
 hipError_t launch_gen_pick(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k, const GenFilters* f,
                            uint64_t seed, int t, int ctr_t, int* tok, int ldtok, int pos_out, int* out_tok, float* out_lp, int num);
+// constrained decoding (decode.hip, fsmg_generate_constrained): the device tables of one fsmg_constraint and the rows'
+// constraint state.  Column v is allowed in (s, open) iff bias[v] > -inf, next[s * C + cls[v]] >= 0 and its slot rule holds:
+// slot[v] = 0: no role; else slot k = (slot[v] & 0x7fffffff) - 1, bit 31 set: v closes k (allowed while open), clear: v opens k
+// (allowed while closed).  Bit k of a row's open set is bit k & 31 of open[b * KW + (k >> 5)].
+constexpr int CON_MAX_CLASSES = 64, CON_MAX_STATES = 256, CON_MAX_SLOTS = 4096;
+struct ConstraintDev {
+    const float* bias;            // [ncols], finite or -inf (zeros when the constraint has no bias)
+    const unsigned char* cls;     // [ncols], in [0, C)
+    const unsigned* slot;         // [ncols]
+    const short* next;            // [S][C], in [-1, S)
+    int S, C, KW;                 // KW = ceil(K / 32) <= 128
+    int* state;                   // [B], in [0, S)
+    unsigned* open;               // [B][KW]
+    int* dead;                    // [B]
+};
+// launch_gen_pick under constraint c: the filtered pick on z^c (f == nullptr: no filters), then thread 0 advances row b's state
+hipError_t launch_gen_pick_constrained(hipStream_t s, const float* logits, int ldl, int ncols, int B, float temperature, int top_k,
+                                       const GenFilters* f, const ConstraintDev& c, uint64_t seed, int t, int ctr_t, int* tok, int ldtok,
+                                       int pos_out, int* out_tok, float* out_lp, int num);
+// every row's state walked over its primer tokens tok[b][1 .. P]; *err |= 1 for a token that is not allowed where it stands
+hipError_t launch_constraint_advance(hipStream_t s, const ConstraintDev& c, int ncols, int B, int P, const int* tok, int ldtok, int* err);
 // tok rows [start, primer[b / rows_per_primer][0..P-1]]; *err |= 1 for a primer id outside [0, vocab)
 hipError_t launch_gen_primer(hipStream_t s, const int* primer, int B, int P, int vocab, int start, int* tok, int ldtok, int* err,
                              int rows_per_primer = 1);

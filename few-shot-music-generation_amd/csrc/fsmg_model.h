@@ -92,6 +92,21 @@ struct fsmg_cache_s {
     int *n_seg = nullptr, *n_long = nullptr;                                            // [G]
 };
 
+// A constraint (fsmg_constraint_*, api_decode.hip): the device tables of ConstraintDev in one allocation, and host copies for the
+// host primer's walk.
+struct fsmg_constraint_s {
+    int V1 = 0, S = 1, C = 1, K = 0, KW = 0, start = 0;
+    char* mem = nullptr;
+    float* bias = nullptr;              // device [V1]
+    unsigned char* cls = nullptr;       // device [V1]
+    unsigned* slot = nullptr;           // device [V1]
+    short* next = nullptr;              // device [S][C]
+    std::vector<float> h_bias;          // the same four on the host
+    std::vector<unsigned char> h_cls;
+    std::vector<unsigned> h_slot;
+    std::vector<short> h_next;
+};
+
 struct fsmg_model {
     fsmg_config cfg{};
     int V = 0, V1 = 0, T = 0, E = 0, H = 0, L = 0, Ep = 0, Hp = 0, V1p = 0, G4 = 0;
@@ -317,6 +332,7 @@ struct fsmg_model {
     std::vector<fsmg_dstate_s*> dstates;   // the decode states this handle owns (fsmg_dstate_create): every entry point looks its state up here
     // support-set caches (api_cache.hip): the registry, and the attention calls' scratch (grown between calls after a stream sync)
     std::vector<fsmg_cache_s*> caches;
+    std::vector<fsmg_constraint_s*> constraints;   // the constraints this handle owns (fsmg_constraint_create)
     char* cat = nullptr;
     size_t cat_bytes = 0;
 

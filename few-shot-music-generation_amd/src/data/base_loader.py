@@ -41,6 +41,10 @@ class Loader(object):
     def get_num_tokens(self):
         raise NotImplementedError
 
+    def constraints(self, **kw):
+        """the decoding constraints of this vocabulary (data.constraints.Constraints), or None when it has none"""
+        return None
+
     # -- shared ------------------------------------------------------------------
     def sidecar_path(self, filepath):
         return '%s.%s.npy' % (filepath, self.max_len)

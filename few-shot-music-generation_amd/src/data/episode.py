@@ -126,6 +126,10 @@ class EpisodeSampler(object):
     def detokenize(self, numpy_data):
         return self.dataset.loader.detokenize(numpy_data)
 
+    def constraints(self, **kw):
+        """the loader's decoding constraints (Loader.constraints), or None"""
+        return self.dataset.loader.constraints(**kw)
+
 
 class ShardedEpisodeSampler(object):
     """Rank r of R sees episodes r, r+R, r+2R, ... of the wrapped sampler's stream,

@@ -283,3 +283,8 @@ class MIDILoader(Loader):
 
     def detokenize(self, numpy_data):
         return detokenize_tokens(numpy_data)
+
+    def constraints(self, instruments=None, max_silence=None):
+        """what the detokenizer keeps, as decoding constraints (data.constraints.midi_constraints)"""
+        from data.constraints import midi_constraints
+        return midi_constraints(instruments=instruments, max_silence=max_silence)

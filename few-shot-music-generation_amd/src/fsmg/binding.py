@@ -65,6 +65,19 @@ class FsmgGenFilters(C.Structure):
                 ('repeat_window', C.c_int32), ('reserved', C.c_int32 * 8)]
 
 
+FSMG_CONSTRAINT_CONFIG_VERSION = 1
+
+
+class FsmgConstraintConfig(C.Structure):
+    _fields_ = [('version', C.c_int32), ('n_columns', C.c_int32), ('n_states', C.c_int32), ('n_classes', C.c_int32),
+                ('n_slots', C.c_int32), ('start_state', C.c_int32), ('reserved', C.c_int32 * 10), ('bias', C.c_void_p),
+                ('token_class', C.c_void_p), ('next_state', C.c_void_p), ('slot_open', C.c_void_p), ('slot_close', C.c_void_p)]
+
+
+class FsmgConstraintState(C.Structure):
+    _fields_ = [('state', C.c_void_p), ('open', C.c_void_p), ('dead_ends', C.c_void_p)]
+
+
 FSMG_BEAM_CONFIG_VERSION = 1
 
 
@@ -215,6 +228,15 @@ SIGNATURES = {
                                               C.c_int32, _P, _I32P, _F32P]),
     'fsmg_maml_generate_filtered_masked': (C.c_int, [_P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _P, _P, C.c_int32, C.c_int32,
                                                      C.c_float, C.c_int32, _P, _I32P, _F32P]),
+    'fsmg_constraint_create': (C.c_int, [_P, C.POINTER(FsmgConstraintConfig), C.POINTER(_P)]),
+    'fsmg_constraint_destroy': (C.c_int, [_P, _P]),
+    'fsmg_constraint_info': (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
+    'fsmg_generate_constrained': (C.c_int, [_P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _P, C.POINTER(FsmgConstraintState),
+                                            _P, _I32P, _F32P]),
+    'fsmg_dstate_generate_constrained': (C.c_int, [_P, _P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _P,
+                                                   C.POINTER(FsmgConstraintState), _I32P, _F32P]),
+    'fsmg_maml_generate_constrained': (C.c_int, [_P, C.POINTER(FsmgGenConfig), C.POINTER(FsmgGenFilters), _P, C.POINTER(FsmgConstraintState),
+                                                 _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P, _F32P]),
     'fsmg_beam_search': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, _I32P, _F32P, _F32P]),
     'fsmg_maml_beam_search': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P, _F32P,
                                         _F32P]),
@@ -433,6 +455,50 @@ class DecodeState(object):
         if not isinstance(src, DecodeState) or not getattr(src, '_st', None):
             raise ValueError('src must be an open DecodeState')
         self._call(self._model._lib.fsmg_dstate_gather, src._st, idx.ctypes.data_as(_I32P))
+
+
+class DeviceConstraint(object):
+    """A constraint resident on the device (include/fsmg.h fsmg_constraint_*): the tables of a data.constraints.Constraints
+    (or any object with its attributes) uploaded once for one FsmgModel.  Made by FsmgModel.new_constraint; the constraints=
+    keyword of FsmgModel.generate / maml_generate takes one (or the host object, which is uploaded and cached on the model)."""
+
+    def __init__(self, model, con):
+        self._model = model
+        keep = []
+
+        def ptr(a, dtype):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            keep.append(a)
+            return C.c_void_p(a.ctypes.data)
+        nxt = getattr(con, 'next_state', None)
+        c = FsmgConstraintConfig(version=FSMG_CONSTRAINT_CONFIG_VERSION, n_columns=int(con.n_columns),
+                                 n_states=0 if nxt is None else int(np.asarray(nxt).shape[0]),
+                                 n_classes=0 if nxt is None else int(np.asarray(nxt).shape[1]), n_slots=int(con.n_slots),
+                                 start_state=int(con.start_state), bias=ptr(con.bias, np.float32),
+                                 token_class=ptr(con.token_class, np.int32), next_state=ptr(nxt, np.int32),
+                                 slot_open=ptr(con.slot_open, np.int32), slot_close=ptr(con.slot_close, np.int32))
+        h = _P()
+        model._ck(model._lib.fsmg_constraint_create(model._h, C.byref(c), C.byref(h)))
+        self._con = h
+        out = (C.c_int64 * 4)()
+        model._ck(model._lib.fsmg_constraint_info(model._h, h, out))
+        self.n_columns, self.n_states, self.n_classes, self.n_slots = (int(x) for x in out)
+        self.n_words = (self.n_slots + 31) // 32
+        self.start_state = int(con.start_state)
+
+    def close(self):
+        # (a constraint whose model is closed already went with it: fsmg_destroy frees what is left)
+        if getattr(self, '_con', None) and getattr(self._model, '_h', None):
+            self._model._lib.fsmg_constraint_destroy(self._model._h, self._con)
+        self._con = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class FsmgCache(object):
@@ -982,6 +1048,53 @@ class FsmgModel(object):
         return FsmgGenFilters(version=FSMG_GEN_FILTERS_VERSION, top_p=float(top_p), min_p=float(min_p),
                               repetition_penalty=float(repetition_penalty), repeat_window=int(repeat_window))
 
+    # -- constrained decoding (include/fsmg.h fsmg_constraint_*) -----------------------------------
+    def new_constraint(self, con):
+        """upload a data.constraints.Constraints -> DeviceConstraint"""
+        return DeviceConstraint(self, con)
+
+    def _constraint(self, con):
+        """a DeviceConstraint of this model for `con` (a host Constraints is uploaded once and kept with the model)"""
+        if isinstance(con, DeviceConstraint):
+            if con._model is not self or not getattr(con, '_con', None):
+                raise ValueError('constraints must be an open DeviceConstraint of this model')
+            return con
+        cache = self.__dict__.setdefault('_constraints', {})
+        if id(con) not in cache:
+            cache[id(con)] = (con, DeviceConstraint(self, con))       # (the host object is kept: its id stays its own)
+        return cache[id(con)][1]
+
+    def _constrained(self, call, head, tail, dc, n_seq, num, logprobs, cstate, return_cstate):
+        """one of the three *_constrained entry points: call(g, f, con, cstate*, ...); -> tokens (, log-probs) (, cstate dict)"""
+        rows = int(n_seq)
+        cs = cstate or {}
+        st = np.ascontiguousarray(cs['state'], dtype=np.int32).reshape(rows).copy() if cs.get('state') is not None else None
+        op = (np.ascontiguousarray(cs['open'], dtype=np.uint32).reshape(rows, dc.n_words).copy()
+              if cs.get('open') is not None else None)
+        de = np.ascontiguousarray(cs['dead_ends'], dtype=np.int32).reshape(rows).copy() if cs.get('dead_ends') is not None else None
+        io = None
+        if cstate is not None or return_cstate:
+            # the arrays are read at the start and written at the end; one that is not given holds the library's default for a NULL
+            # input (start state, every slot closed, zero dead ends)
+            if st is None or op is None or de is None:
+                info_state = self._default_cstate(dc, rows)
+                st = info_state['state'] if st is None else st
+                op = info_state['open'] if op is None else op
+                de = info_state['dead_ends'] if de is None else de
+            io = FsmgConstraintState(state=st.ctypes.data, open=op.ctypes.data if op.size else None, dead_ends=de.ctypes.data)
+        toks = np.empty((rows, int(num)), np.int32)
+        lp = np.empty((rows, int(num)), np.float32) if logprobs else None
+        call(*head, dc._con, C.byref(io) if io is not None else None, *tail, toks.ctypes.data_as(_I32P), _f32p(lp) if logprobs else None)
+        out = (toks, lp) if logprobs else (toks,)
+        if return_cstate:
+            out = out + (dict(state=st, open=op, dead_ends=de),)
+        return out if len(out) > 1 else out[0]
+
+    @staticmethod
+    def _default_cstate(dc, rows):
+        return dict(state=np.full(rows, dc.start_state, np.int32), open=np.zeros((rows, dc.n_words), np.uint32),
+                    dead_ends=np.zeros(rows, np.int32))
+
     def _generate(self, adapt, n_seq, num, temperature, top_k, seed, primer, logprobs, filters, masked=False):
         """fsmg_generate (adapt = ()) or fsmg_maml_generate (adapt = its support arguments), the _filtered entry point when a
         filter is on; masked: fsmg_maml_generate_filtered_masked (adapt holds the support lengths; a NULL filter struct: none)"""
@@ -997,18 +1110,35 @@ class FsmgModel(object):
         return (toks, lp) if logprobs else toks
 
     def generate(self, n_seq, num, temperature=1.0, top_k=0, seed=0, primer=None, logprobs=False, top_p=0.0, min_p=0.0,
-                 repetition_penalty=1.0, repeat_window=0, state=None):
+                 repetition_penalty=1.0, repeat_window=0, state=None, constraints=None, cstate=None, return_cstate=False):
         """n_seq independent samples of num tokens -> int32 [n_seq, num] (, float32 [n_seq, num] log-probs with logprobs=True).
         primer: int32 [n_seq, P] (or [P] for every row) continued by each row, or (device address, P).  top_p, min_p,
         repetition_penalty, repeat_window: the sampling filters of fsmg_generate_filtered (all off: fsmg_generate).
-        state: a DecodeState of n_seq rows to continue and leave advanced (fsmg_dstate_generate; no primer then: feed it)."""
+        state: a DecodeState of n_seq rows to continue and leave advanced (fsmg_dstate_generate; no primer then: feed it).
+        constraints: a data.constraints.Constraints or a DeviceConstraint (fsmg_generate_constrained /
+        fsmg_dstate_generate_constrained); cstate: the rows' constraint states to start from, a dict with any of 'state' int32
+        [n_seq], 'open' uint32 [n_seq, words], 'dead_ends' int32 [n_seq]; return_cstate: the states after the call, such a dict,
+        as the last element of the result."""
         filters = (top_p, min_p, repetition_penalty, repeat_window)
+        if constraints is None and (cstate is not None or return_cstate):
+            raise ValueError('cstate / return_cstate need constraints')
+        if state is not None and primer is not None:
+            raise ValueError('a state takes no primer: feed it first')
+        if state is not None and int(n_seq) != state.rows:
+            raise ValueError('n_seq %d is not the row count of the state (%d)' % (int(n_seq), state.rows))
+        if constraints is not None:
+            dc = self._constraint(constraints)
+            f = self.gen_filters(*filters)
+            fp = C.byref(f) if f is not None else None
+            if state is None:
+                g, pp, _keep = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
+                return self._constrained(lambda *a: self._ck(self._lib.fsmg_generate_constrained(self._h, *a)), (C.byref(g), fp), (pp,),
+                                         dc, n_seq, num, logprobs, cstate, return_cstate)
+            g = self.gen_config(n_seq, num, temperature, top_k, seed)
+            return self._constrained(lambda *a: state._call(self._lib.fsmg_dstate_generate_constrained, *a), (C.byref(g), fp), (), dc,
+                                     n_seq, num, logprobs, cstate, return_cstate)
         if state is None:
             return self._generate((), n_seq, num, temperature, top_k, seed, primer, logprobs, filters)
-        if primer is not None:
-            raise ValueError('a state takes no primer: feed it first')
-        if int(n_seq) != state.rows:
-            raise ValueError('n_seq %d is not the row count of the state (%d)' % (int(n_seq), state.rows))
         g = self.gen_config(n_seq, num, temperature, top_k, seed)
         f = self.gen_filters(*filters)
         toks = np.empty((int(n_seq), int(num)), np.int32)
@@ -1097,10 +1227,21 @@ class FsmgModel(object):
 
     def maml_generate(self, support, num, inner_steps, inner_lr, n_seq=1, temperature=1.0, top_k=0, seed=0, primer=None,
                       logprobs=False, n_support_rows=None, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0,
-                      support_len=None):
+                      support_len=None, constraints=None, cstate=None, return_cstate=False):
         """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), generate at theta', restore theta.
-        support_len int32 [rows]: adapt over the positions inside each support song only (fsmg_maml_generate_filtered_masked)"""
+        support_len int32 [rows]: adapt over the positions inside each support song only (fsmg_maml_generate_filtered_masked).
+        constraints, cstate, return_cstate: as in generate (fsmg_maml_generate_constrained)"""
         masked, adapt, _keep = self._adapt(support, n_support_rows, inner_steps, inner_lr, support_len)
+        if constraints is None and (cstate is not None or return_cstate):
+            raise ValueError('cstate / return_cstate need constraints')
+        if constraints is not None:
+            dc = self._constraint(constraints)
+            f = self.gen_filters(top_p, min_p, repetition_penalty, repeat_window)
+            g, pp, _keep_p = self._gen_args(n_seq, num, temperature, top_k, seed, primer)
+            sup = adapt if masked else (adapt[0], None) + adapt[1:]       # (support, support_len or NULL, rows, steps, lr, on device)
+            return self._constrained(lambda *a: self._ck(self._lib.fsmg_maml_generate_constrained(self._h, *a)),
+                                     (C.byref(g), C.byref(f) if f is not None else None), sup + (pp,), dc, n_seq, num, logprobs, cstate,
+                                     return_cstate)
         if not masked:
             return self._generate(adapt, n_seq, num, temperature, top_k, seed, primer, logprobs,
                                   (top_p, min_p, repetition_penalty, repeat_window))

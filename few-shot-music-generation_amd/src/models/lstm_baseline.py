@@ -261,16 +261,25 @@ class LSTMBaseline(HIPModel):
         return float(-np.mean(lp[:, 1:].astype(np.float64)))
 
     def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0,
-                 condition_on_support=False, _draw=None):
+                 condition_on_support=False, _draw=None, constraints=None, cstate=None, return_cstate=False):
         """n independent samples of num tokens (int32 [n, num]), drawn on the device (temperature, top_k, seed; include/fsmg.h
         fsmg_generate).  Each row continues the first primer_len tokens of a support song (dealt round-robin); with
         primer_len 0 the support set is not used.  top_p, min_p, repetition_penalty, repeat_window: the sampling filters
         (include/fsmg.h fsmg_generate_filtered; all off by default).
         condition_on_support=True: the support songs are read first (condition: one state row per artist, dealt round-robin over the
         n rows), then [start] and the first primer_len tokens of one of that artist's support songs, and the rows continue from
-        there.  (_draw: what stands in for FsmgModel.generate -- a subclass's own decoder with the same keywords.)"""
+        there.  (_draw: what stands in for FsmgModel.generate -- a subclass's own decoder with the same keywords.)
+        constraints: a data.constraints.Constraints (e.g. MIDILoader.constraints()) restricting what may be drawn (include/fsmg.h
+        fsmg_generate_constrained); the primer must be allowed by it.  cstate / return_cstate: FsmgModel.generate's."""
         self._require_init()
         draw = _draw if _draw is not None else self._model.generate
+        if constraints is not None:       # (only then: a stand-in decoder need not know these keywords)
+            if _draw is not None:
+                raise ValueError('constraints are not supported by this decoder')
+            base = draw
+            draw = lambda *a, **kw: base(*a, constraints=constraints, cstate=cstate, return_cstate=return_cstate, **kw)
+        elif cstate is not None or return_cstate:
+            raise ValueError('cstate / return_cstate need constraints')
         if condition_on_support:
             n, num = int(n), int(num)
             K, T = np.shape(support_set)[-2:]

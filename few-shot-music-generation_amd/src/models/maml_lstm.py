@@ -116,16 +116,20 @@ class MAMLLSTM(LSTMBaseline):
         return nll
 
     def generate(self, support_set, num, n=1, temperature=1.0, top_k=0, seed=0, primer_len=0, logprobs=False, top_p=0.0, min_p=0.0, repetition_penalty=1.0, repeat_window=0,
-                 support_len=None):
+                 support_len=None, constraints=None, cstate=None, return_cstate=False):
         """like LSTMBaseline.generate, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored.
-        support_len [rows]: the support songs' lengths (maml_lengths)"""
+        support_len [rows]: the support songs' lengths (maml_lengths).  constraints, cstate, return_cstate: LSTMBaseline.generate's
+        (include/fsmg.h fsmg_maml_generate_constrained)"""
         self._require_init()
         support = self._tokens(support_set, 2)
+        con = dict(constraints=constraints, cstate=cstate, return_cstate=return_cstate) if constraints is not None else {}
+        if constraints is None and (cstate is not None or return_cstate):
+            raise ValueError('cstate / return_cstate need constraints')
         return self._model.maml_generate(support, int(num), self._inner_steps, self._inner_lr, n_seq=int(n),
                                          temperature=temperature, top_k=top_k, seed=seed,
                                          primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs,
                                          top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window,
-                                         **self._support_lengths(support, support_len))
+                                         **self._support_lengths(support, support_len), **con)
 
     def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False, support_len=None):
         """like LSTMBaseline.beam_search, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored.

@@ -73,6 +73,16 @@ def sample_filters(config):
     return {arg: conv(config[key]) for key, arg, conv in SAMPLE_FILTER_KEYS if key in config}
 
 
+def sample_constraints(config, sampler):
+    """model YAML key sample_constraints: none (the default: nothing is passed to generate) | loader (the loader's constraints,
+    Loader.constraints(); a loader without any gives none)"""
+    mode = str(config.get('sample_constraints', 'none')).lower()
+    if mode not in ('none', 'loader'):
+        raise ValueError("sample_constraints must be 'none' or 'loader', got %r" % config.get('sample_constraints'))
+    con = sampler.constraints() if mode == 'loader' else None
+    return {} if con is None else {'constraints': con}
+
+
 def evaluate(model, episode_sampler, n_episodes):
     """Mean of model.eval over n_episodes fresh episodes (train.py:27-33)."""
     total, done = 0.0, 0
@@ -231,6 +241,7 @@ def main(argv=None):
                                  temperature=float(config['sample_temperature']), top_k=int(config.get('sample_top_k', 0)),
                                  seed=sample_seed(config.get('sample_seed', 0), i),
                                  primer_len=int(config.get('sample_primer_len', 0)), **sample_filters(config),
+                                 **sample_constraints(config, episode_sampler['test']),
                                  **({'condition_on_support': True} if config.get('sample_condition_on_support') else {}))
         for j in range(support_set.shape[0]):
             write_seq(episode_sampler['test'].detokenize(support_set[j]), curr_sample_dir, 'support_%d' % j)

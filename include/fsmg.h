@@ -404,6 +404,80 @@ int fsmg_maml_generate_filtered_masked(fsmg_handle h, const fsmg_gen_config* g, 
                                        int32_t inner_steps, float inner_lr, int32_t support_on_device, const int32_t* primer,
                                        int32_t* out_tokens, float* out_logprob);
 
+/* ---- constrained decoding: restrict what fsmg_generate_filtered may draw, on the device, inside the pick.
+ * A constraint is one immutable device object per vocabulary, made of three independent mechanisms, each of which may be absent:
+ *   bias         bias[V1] is added to the logit; -inf bans a column (+inf and NaN are refused).  NULL: zeros.
+ *   automaton    token_class[V1] in [0, C), next_state[S][C] in [-1, S) (-1 forbids every token of that class in that state),
+ *                start_state in [0, S); 1 <= S <= 256, 1 <= C <= 64.  Absent (both tables NULL, n_states = n_classes = 0):
+ *                S = C = 1 with everything allowed.
+ *   slots        slot_open[V1] and slot_close[V1] in [-1, K), 0 <= K <= 4096, a token with at most one role.  A token that opens
+ *                slot k is allowed only while k is closed and drawing it opens k; one that closes k only while k is open, and
+ *                drawing it closes k.  NULL arrays: no token has that role.
+ * A row's constraint state is (state, open[ceil(K / 32)], dead_ends); bit k of open is bit k & 31 of word k >> 5.
+ * At generated position t of row b let z be the logits row exactly as fsmg_generate computes it and (s, open) the row's state.
+ *   Omega = { v : bias_v > -inf, next_state[s][token_class[v]] >= 0, v's slot rule holds }
+ *   z^c_v = fl(z_v + bias_v) for v in Omega, -inf otherwise.
+ * Steps 1 to 5 of fsmg_generate_filtered run on z^c in place of z, unchanged: same Philox counter (v >> 2, t, b, 0), seed and tie
+ * rule.  A column outside Omega is never drawn while Omega is non-empty, at temperature 0 too; when every allowed column's z^c is
+ * -inf or NaN the pick is the lowest column of Omega.  Dead end (Omega empty): the position is picked as if no constraint were
+ * given (z^c = z over all columns), the constraint state stays as it is and the row's dead_ends goes up by one -- nothing hangs,
+ * nothing is refused, the caller reads the counter.  out_logprob is unchanged: z_tok - logsumexp(all raw z), the lse bitwise
+ * fsmg_generate's.  After the pick s <- next_state[s][token_class[tok]] and tok's slot is flipped.  Primer tokens advance the
+ * state in order before the first pick (the start word is no primer token and advances nothing); a primer token that is not
+ * allowed where it stands: a host primer gives FSMG_ERR_INVALID before any device work, a device primer raises the primer flag,
+ * FSMG_ERR_TOKEN_RANGE with the outputs unwritten.
+ * cstate_io (may be NULL, as may each of its arrays) carries the rows' states: read at the start of the call (NULL: start_state,
+ * every slot closed, zero dead ends), written at its end.  state [B], open [B][ceil(K / 32)], dead_ends [B].
+ * con == NULL: every call is bitwise its unconstrained twin and launches that twin's kernels (cstate_io is not touched).
+ * The rest of fsmg_generate_filtered's contract holds: bitwise deterministic, a row's output independent of n_seq and of the
+ * other rows, no handle state changed.  A constraint outlives the calls that use it and is freed by fsmg_constraint_destroy or with
+ * the handle.  Not covered: beam search, the cache-conditioned generators and fsmg_dyneval_generate.
+ * Errors: fsmg_constraint_create returns FSMG_ERR_INVALID for a bad version or nonzero reserved words, n_columns that is not the
+ * handle's V1 = input_size + 1, V1 > 2^19, S, C or K outside their limits, one automaton table without the other, any index out of range, a
+ * token with both slot roles, a bias of +inf or NaN.  The generate calls: what their unconstrained twins refuse; FSMG_ERR_INVALID
+ * for a constraint this handle does not own, a cstate_io state outside [0, S), negative dead_ends or an open bit at or above K. */
+#define FSMG_CONSTRAINT_CONFIG_VERSION 1
+typedef struct fsmg_constraint_s* fsmg_constraint;
+struct fsmg_dstate_s;           /* a decode state (fsmg_dstate, below) */
+typedef struct fsmg_constraint_config {
+    int32_t version;            /* FSMG_CONSTRAINT_CONFIG_VERSION                                 */
+    int32_t n_columns;          /* V1 = input_size + 1 of the handle                              */
+    int32_t n_states;           /* S in [1, 256]; 0 with NULL tables: no automaton                */
+    int32_t n_classes;          /* C in [1, 64];  0 with NULL tables: no automaton                */
+    int32_t n_slots;            /* K in [0, 4096]                                                 */
+    int32_t start_state;        /* in [0, S)                                                      */
+    int32_t reserved[10];       /* must be 0                                                      */
+    const float*   bias;        /* host [V1] or NULL                                              */
+    const int32_t* token_class; /* host [V1] or NULL                                              */
+    const int32_t* next_state;  /* host [S][C] or NULL                                            */
+    const int32_t* slot_open;   /* host [V1] or NULL                                              */
+    const int32_t* slot_close;  /* host [V1] or NULL                                              */
+} fsmg_constraint_config;
+typedef struct fsmg_constraint_state {
+    int32_t*  state;            /* host [B] or NULL                                               */
+    uint32_t* open;             /* host [B][ceil(K / 32)] or NULL                                 */
+    int32_t*  dead_ends;        /* host [B] or NULL                                               */
+} fsmg_constraint_state;
+
+int fsmg_constraint_create(fsmg_handle h, const fsmg_constraint_config* c, fsmg_constraint* out);
+int fsmg_constraint_destroy(fsmg_handle h, fsmg_constraint con);
+/* out = { V1, S, C, K } */
+int fsmg_constraint_info(fsmg_handle h, fsmg_constraint con, int64_t out[4]);
+/* fsmg_generate_filtered under constraint con (NULL: fsmg_generate_filtered itself) */
+int fsmg_generate_constrained(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f, fsmg_constraint con,
+                              fsmg_constraint_state* cstate_io, const int32_t* primer, int32_t* out_tokens, float* out_logprob);
+/* fsmg_dstate_generate (below) under constraint con: the caller carries cstate_io from call to call, the decode state itself holds
+ * no constraint state */
+int fsmg_dstate_generate_constrained(fsmg_handle h, struct fsmg_dstate_s* st, const fsmg_gen_config* g, const fsmg_gen_filters* f,
+                                     fsmg_constraint con, fsmg_constraint_state* cstate_io, int32_t* out_tokens,
+                                     float* out_logprob);
+/* fsmg_maml_generate_filtered (support_len == NULL) or fsmg_maml_generate_filtered_masked: adapt, generate at theta' under con,
+ * restore theta */
+int fsmg_maml_generate_constrained(fsmg_handle h, const fsmg_gen_config* g, const fsmg_gen_filters* f, fsmg_constraint con,
+                                   fsmg_constraint_state* cstate_io, const int32_t* support, const int32_t* support_len,
+                                   int32_t n_support_rows, int32_t inner_steps, float inner_lr, int32_t support_on_device,
+                                   const int32_t* primer, int32_t* out_tokens, float* out_logprob);
+
 /* ---- batched on-device beam search (DESIGN.md "Beam search").  G independent searches of width W.  Every hypothesis of group g
  * reads [start, primer[g][0..P-1], y_0, y_1, ...] from a zero state, exactly as a row of fsmg_generate does, and the logits are
  * fsmg_generate's (all V1 = input_size + 1 columns).  At generated position t, slot j of a group and column v give
