@@ -50,6 +50,8 @@ struct ConRun {
     int R = 0;
     std::vector<int32_t> host;
     ConstraintDev dev{};
+    ConstraintDev alt{};            // beam search: the second buffer of the rows' states (a new slot gathers its parent's)
+    int* row_dead = nullptr;        // beam search: [R], this position's dead-end rows
     size_t bytes() const { return sizeof(int32_t) * host.size(); }
 };
 
@@ -85,6 +87,7 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
     const size_t o_err = cv.take(sizeof(int));
     const size_t o_extra = cv.take(d.extra_bytes);
     const size_t o_con = cv.take(cr ? cr->bytes() : 0);
+    const size_t o_con_alt = cv.take(cr && beam ? cr->bytes() + sizeof(int) * R : 0);
     int rc = gen_reserve(h, cv.off);
     if (rc != FSMG_OK) return rc;
     char* base = h->gen;
@@ -121,6 +124,13 @@ int begin_decode(fsmg_model* h, Decode& d, int R, int W, int P, int num, bool pr
         cr->dev.dead = cr->dev.state + R;
         cr->dev.open = (unsigned*)(cr->dev.dead + R);
         HIPCK(h, hipMemcpyAsync(cr->dev.state, cr->host.data(), cr->bytes(), hipMemcpyHostToDevice, s));
+        if (beam) {
+            cr->alt = cr->dev;
+            cr->alt.state = (int*)(base + o_con_alt);
+            cr->alt.dead = cr->alt.state + R;
+            cr->alt.open = (unsigned*)(cr->alt.dead + R);
+            cr->row_dead = (int*)(cr->alt.open + (size_t)R * cr->dev.KW);
+        }
     }
     if (st) {
         HIPCK(h, launch_dstate_rows(s, h->L, R, st->R, h->Hp, nullptr, rows_per_primer, st->h, d.h_in, st->c, d.c, st->ctx, st->history + 1, 0,
@@ -362,12 +372,12 @@ int generate_core(fsmg_model* h, const fsmg_gen_config* g, const fsmg_gen_filter
 // fsmg_beam_search's work at the parameters the handle holds now (no BEGIN_CALL, as generate_core).  st != nullptr: group g starts
 // from row g of that decode state, which is only read.
 int beam_core(fsmg_model* h, const fsmg_beam_config* b, const int32_t* primer, int32_t* out_tokens, float* out_scores, float* out_logprob,
-              const fsmg_dstate_s* st = nullptr) {
+              const fsmg_dstate_s* st = nullptr, ConRun* cr = nullptr) {
     const int G = b->n_groups, W = b->beam_width, L = h->L, Hp = h->Hp;
     hipStream_t s = h->stream;
     Decode d;
     // the primer runs on all G * W rows (row r reads primer[r / W]): the slots of a group stay identical until the first pick
-    int rc = begin_decode(h, d, G * W, W, st ? st->kept() : b->primer_len, b->num, b->primer_on_device, primer, st);
+    int rc = begin_decode(h, d, G * W, W, st ? st->kept() : b->primer_len, b->num, b->primer_on_device, primer, st, false, cr);
     if (rc != FSMG_OK) return rc;
     HIPCK(h, launch_beam_init(s, d.cum, d.R, W));
     // position p reads tok[:, p]; generated position t = p - P writes tok[:, p + 1] and par / htok / hlp [t]
@@ -378,16 +388,51 @@ int beam_core(fsmg_model* h, const fsmg_beam_config* b, const int32_t* primer, i
             continue;
         }
         const size_t t = p - d.P, at = t * d.R;
-        HIPCK(h, launch_beam_rowtop(s, d.logits, d.ldl, h->V1, d.R, W, d.cum, d.cand_s, d.cand_lp, d.cand_v));
-        HIPCK(h, launch_beam_select(s, G, W, h->V1, d.cand_s, d.cand_lp, d.cand_v, d.cum, d.tok, d.ldtok, p + 1, d.par + at, d.htok + at,
-                                    d.hlp + at));
+        if (cr) {       // the ranking over the allowed sets; every new slot takes its parent's constraint state, at the last position too
+            HIPCK(h, launch_beam_rowtop_constrained(s, d.logits, d.ldl, h->V1, d.R, W, d.cum, cr->dev, d.cand_s, d.cand_lp, d.cand_v,
+                                                    cr->row_dead));
+            HIPCK(h, launch_beam_select_constrained(s, G, W, h->V1, d.cand_s, d.cand_lp, d.cand_v, cr->row_dead, cr->dev, cr->alt.state,
+                                                    cr->alt.dead, d.cum, d.tok, d.ldtok, p + 1, d.par + at, d.htok + at, d.hlp + at));
+            HIPCK(h, launch_beam_con_reorder(s, d.R, W, cr->dev, d.par + at, d.htok + at, cr->row_dead, cr->alt.open));
+            std::swap(cr->dev, cr->alt);
+        } else {
+            HIPCK(h, launch_beam_rowtop(s, d.logits, d.ldl, h->V1, d.R, W, d.cum, d.cand_s, d.cand_lp, d.cand_v));
+            HIPCK(h, launch_beam_select(s, G, W, h->V1, d.cand_s, d.cand_lp, d.cand_v, d.cum, d.tok, d.ldtok, p + 1, d.par + at, d.htok + at,
+                                        d.hlp + at));
+        }
         if ((int)t + 1 < d.num) {                   // each slot continues from its parent's state
             HIPCK(h, launch_beam_reorder(s, L, d.R, W, Hp, d.par + at, d.h_out, d.h_in, d.c, d.c_spare));
             std::swap(d.c, d.c_spare);
         }
     }
     HIPCK(h, launch_beam_backtrace(s, d.R, W, d.num, d.par, d.htok, d.hlp, d.cum, d.out_tok, d.out_lp, d.out_score));
-    return read_outputs(h, d, out_tokens, out_logprob, out_scores);
+    if (cr && (rc = con_read_back(h, *cr, false)) != FSMG_OK) return rc;
+    if ((rc = read_outputs(h, d, out_tokens, out_logprob, out_scores)) != FSMG_OK) return rc;
+    if (cr) con_scatter(*cr);
+    return FSMG_OK;
+}
+
+// What a constrained beam call checks before any device work: con_prepare over the G groups' states and host primers, then every
+// group's state replicated over its W rows; the final states of the G * W hypotheses go to cstate_out.
+int beam_con_prepare(fsmg_model* h, ConRun& cr, const fsmg_constraint_s* c, const fsmg_constraint_state* in, fsmg_constraint_state* out,
+                     const fsmg_beam_config* b, const int32_t* host_primer) {
+    fsmg_constraint_state io{};
+    if (in) io = *in;               // (only read: con_scatter runs on `out`)
+    const int G = b->n_groups, W = b->beam_width, R = G * W;
+    const int rc = con_prepare(h, cr, c, in ? &io : nullptr, G, host_primer, b->primer_len);
+    if (rc != FSMG_OK) return rc;
+    const size_t KW = (size_t)c->KW;
+    const std::vector<int32_t> grp = cr.host;
+    cr.host.assign((size_t)R * (2 + KW), 0);
+    for (int r = 0; r < R; ++r) {
+        const int g = r / W;
+        cr.host[r] = grp[g];
+        cr.host[(size_t)R + r] = grp[(size_t)G + g];
+        for (size_t i = 0; i < KW; ++i) cr.host[2 * (size_t)R + r * KW + i] = grp[2 * (size_t)G + g * KW + i];
+    }
+    cr.R = R;
+    cr.io = out;
+    return FSMG_OK;
 }
 
 // fsmg_dstate_feed's work: the n given tokens behind the state's tail; position p reads tok[:, p] (the pending token first) and, with
@@ -693,6 +738,43 @@ int fsmg_maml_beam_search_masked(fsmg_handle h, const fsmg_beam_config* b, const
                               [&] { return beam_core(h, b, primer, out_tokens, out_scores, out_logprob); }, support_len, true);
 }
 
+// ---- constrained beam search; con == NULL: the unconstrained twin itself
+int fsmg_beam_search_constrained(fsmg_handle h, const fsmg_beam_config* b, fsmg_constraint con, const fsmg_constraint_state* cstate_in,
+                                 fsmg_constraint_state* cstate_out, const int32_t* primer, int32_t* out_tokens, float* out_scores,
+                                 float* out_logprob) {
+    if (!con) return fsmg_beam_search(h, b, primer, out_tokens, out_scores, out_logprob);
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_constraint_s* c = find_constraint(h, con);
+    if (!c) return FSMG_ERR_INVALID;
+    int rc = check_beam_config(h, b, primer, out_tokens, out_scores);
+    ConRun cr;
+    if (rc == FSMG_OK) rc = beam_con_prepare(h, cr, c, cstate_in, cstate_out, b, b->primer_on_device ? nullptr : primer);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return beam_core(h, b, primer, out_tokens, out_scores, out_logprob, nullptr, &cr);
+}
+
+int fsmg_maml_beam_search_constrained(fsmg_handle h, const fsmg_beam_config* b, fsmg_constraint con, const fsmg_constraint_state* cstate_in,
+                                      fsmg_constraint_state* cstate_out, const int32_t* support, const int32_t* support_len,
+                                      int32_t n_support_rows, int32_t inner_steps, float inner_lr, int32_t support_on_device,
+                                      const int32_t* primer, int32_t* out_tokens, float* out_scores, float* out_logprob) {
+    if (!con)
+        return support_len ? fsmg_maml_beam_search_masked(h, b, support, support_len, n_support_rows, inner_steps, inner_lr, support_on_device,
+                                                          primer, out_tokens, out_scores, out_logprob)
+                           : fsmg_maml_beam_search(h, b, support, n_support_rows, inner_steps, inner_lr, support_on_device, primer, out_tokens,
+                                                   out_scores, out_logprob);
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_constraint_s* c = find_constraint(h, con);
+    if (!c) return FSMG_ERR_INVALID;
+    int rc = check_beam_config(h, b, primer, out_tokens, out_scores);
+    ConRun cr;
+    if (rc == FSMG_OK) rc = beam_con_prepare(h, cr, c, cstate_in, cstate_out, b, b->primer_on_device ? nullptr : primer);
+    if (rc != FSMG_OK) return rc;
+    return with_adapted_theta(h, support, n_support_rows, inner_steps, inner_lr, support_on_device,
+                              [&] { return beam_core(h, b, primer, out_tokens, out_scores, out_logprob, nullptr, &cr); }, support_len,
+                              support_len != nullptr);
+}
+
 // ---- decode states
 int fsmg_dstate_create(fsmg_handle h, const fsmg_dstate_config* c, fsmg_dstate* out) {
     if (!h) return FSMG_ERR_INVALID;
@@ -917,6 +999,28 @@ int fsmg_dstate_beam_search(fsmg_handle h, fsmg_dstate st, const fsmg_beam_confi
     if (!state_call_fits(s, (int64_t)s->R * b->beam_width, b->num)) return fail(h, FSMG_ERR_INVALID, "rows * beam_width * (history + num + 1) too large");
     BEGIN_CALL(h);
     return beam_core(h, b, nullptr, out_tokens, out_scores, out_logprob, s);
+}
+
+// fsmg_dstate_beam_search under a constraint: cstate_in is the groups' constraint state behind what the state has read
+int fsmg_dstate_beam_search_constrained(fsmg_handle h, fsmg_dstate st, const fsmg_beam_config* b, fsmg_constraint con,
+                                        const fsmg_constraint_state* cstate_in, fsmg_constraint_state* cstate_out, int32_t* out_tokens,
+                                        float* out_scores, float* out_logprob) {
+    if (!con) return fsmg_dstate_beam_search(h, st, b, out_tokens, out_scores, out_logprob);
+    if (!h) return FSMG_ERR_INVALID;
+    fsmg_dstate_s* s = find_state(h, st);
+    if (!s) return FSMG_ERR_INVALID;
+    fsmg_constraint_s* c = find_constraint(h, con);
+    if (!c) return FSMG_ERR_INVALID;
+    int rc = check_beam_config(h, b, nullptr, out_tokens, out_scores);
+    if (rc != FSMG_OK) return rc;
+    if (b->n_groups != s->R) return fail(h, FSMG_ERR_INVALID, "n_groups must be the state's row count");
+    if (b->primer_len != 0) return fail(h, FSMG_ERR_INVALID, "primer_len must be 0 with a decode state (feed the primer)");
+    if (!state_call_fits(s, (int64_t)s->R * b->beam_width, b->num)) return fail(h, FSMG_ERR_INVALID, "rows * beam_width * (history + num + 1) too large");
+    ConRun cr;
+    rc = beam_con_prepare(h, cr, c, cstate_in, cstate_out, b, nullptr);
+    if (rc != FSMG_OK) return rc;
+    BEGIN_CALL(h);
+    return beam_core(h, b, nullptr, out_tokens, out_scores, out_logprob, s, &cr);
 }
 
 }  // extern "C"

@@ -827,6 +827,234 @@ __global__ void k_constraint_advance(ConstraintDev c, int ncols, int B, int P, c
     if (bad) atomicOr(err, 1);
 }
 
+// ---------------------------------------------------------------- constrained beam search (fsmg_beam_search_constrained)
+// Every row r = g * W + j carries a constraint state (c.state[r], c.open[r], c.dead[r]).  Per generated position:
+// k_beam_rowtop_constrained (the row's best candidates over Omega only), k_beam_select_constrained (the tiered ranking; the new
+// slots' state and dead ends), k_beam_con_reorder (the new slots' open bits).  The state arrays are double-buffered like h / c: a
+// new slot reads its parent's row of the old buffer.
+
+// block-wide integer sum -- every thread gets the result (integers: the tree's shape cannot change it)
+__device__ __forceinline__ int block_isum(PickShared& sh, int s) {
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh.iv[w] = s;
+    __syncthreads();
+    int t = 0;
+    for (int k = 0; k < PICK_THREADS / 64; ++k) t += sh.iv[k];
+    return t;
+}
+
+// a staged row's excluded columns hold this NaN; an allowed column's NaN is stored as the quiet NaN below, so the two never meet
+constexpr unsigned CON_EXCLUDED = 0xFFFFFFFFu, CON_QNAN = 0x7FC00000u;
+
+// k_beam_rowtop under a constraint; one row per workgroup.  lse comes from the raw row (row_max_lse, the number k_beam_rowtop
+// uses).  The Omega sweep of k_gen_pick_constrained follows (four columns' bias, class and slot loads in flight): STAGED, it rewrites
+// the row to z^c = fl(z + bias) over Omega and marks the other columns CON_EXCLUDED; else it leaves Omega as a bitmap of
+// ceil(ncols / 32) words in the dynamic LDS and val(v) adds the bias on the fly.  The sweep also counts |Omega|.  The row's
+// candidates are its min(W, |Omega|) best columns of Omega by (z^c descending, NaN lowest, v ascending): an excluded column weighs
+// nothing in the radix select and is skipped by the gather, so it ranks below an allowed NaN.  lp = fl(z^c - lse), s = fl(cum + lp);
+// cand_v = -1 pads a short row.  Dead end (Omega empty): k_beam_rowtop's body on z over all columns, row_dead[r] = 1.
+template <bool STAGED>
+__global__ __launch_bounds__(PICK_THREADS) void k_beam_rowtop_constrained(const float* __restrict__ logits, int ldl, int ncols, int W,
+                                                                          const float* __restrict__ cum, ConstraintDev c,
+                                                                          float* __restrict__ cand_s, float* __restrict__ cand_lp,
+                                                                          int* __restrict__ cand_v, int* __restrict__ row_dead) {
+    extern __shared__ float srow[];
+    __shared__ PickShared sh;
+    __shared__ unsigned ck[BEAM_MAX_W];
+    __shared__ int cv[BEAM_MAX_W];
+    __shared__ int wave_eq[PICK_THREADS / 64];
+    __shared__ int n_gt;
+    __shared__ unsigned copen[CON_MAX_SLOTS / 32];
+    __shared__ short nline[CON_MAX_CLASSES];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* row = logits + (long long)r * ldl;
+    const int nw = (ncols + 31) >> 5;
+    unsigned* abits = (unsigned*)srow;          // unstaged: Omega
+    bool dead = false;
+    auto in_set = [&](int v) -> bool {
+        if (dead) return true;
+        return STAGED ? __float_as_uint(srow[v]) != CON_EXCLUDED : ((abits[v >> 5] >> (v & 31)) & 1u) != 0u;
+    };
+    auto val = [&](int v) -> float {            // z^c of a column of the set (z itself at a dead end)
+        if (STAGED) return srow[v];
+        const float z = row[v];
+        return dead ? z : z + c.bias[v];
+    };
+
+    if (tid == 0) n_gt = 0;            // (ordered before its first use by the sweep's barriers)
+    // the row's constraint state -> LDS (ordered before its readers by the sweep's barriers)
+    const int s0 = min(max(c.state[r], 0), c.S - 1);
+    for (int i = tid; i < c.KW && i < CON_MAX_SLOTS / 32; i += PICK_THREADS) copen[i] = c.open[(long long)r * c.KW + i];
+    if (tid < CON_MAX_CLASSES) nline[tid] = tid < c.C ? c.next[s0 * c.C + tid] : (short)-1;
+
+    float mx; int mi;
+    const float lse = row_max_lse<STAGED>(sh, row, srow, ncols, mx, mi);
+
+    int cnt = 0;
+    for (int v0 = tid; v0 - tid < ncols; v0 += 4 * PICK_THREADS) {         // (block-uniform trip count: the ballots below)
+        float bv[4]; unsigned cw[4], sw[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v = v0 + j * PICK_THREADS;
+            const bool in = v < ncols;
+            bv[j] = in ? c.bias[v] : -INFINITY;
+            cw[j] = in ? c.cls[v] : 0u;
+            sw[j] = in ? c.slot[v] : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v = v0 + j * PICK_THREADS;
+            const bool ok = v < ncols && con_ok(bv[j], cw[j], sw[j], copen, nline);
+            cnt += ok ? 1 : 0;
+            if (STAGED) {
+                if (v < ncols) {
+                    const float zc = srow[v] + bv[j];
+                    srow[v] = __uint_as_float(!ok ? CON_EXCLUDED : zc != zc ? CON_QNAN : __float_as_uint(zc));
+                }
+            } else {        // a wave's 64 consecutive columns are two words of the bitmap (v - lane is a multiple of 64)
+                const unsigned long long mk = __ballot(ok);
+                const int wi = (v - lane) >> 5;
+                if (lane == 0 && wi < nw) {
+                    abits[wi] = (unsigned)mk;
+                    if (wi + 1 < nw) abits[wi + 1] = (unsigned)(mk >> 32);
+                }
+            }
+        }
+    }
+    const int n_om = block_isum(sh, cnt);       // (its barriers order the sweep's LDS stores before the reads below)
+    dead = n_om == 0;
+    if (dead && STAGED) {       // nothing is allowed: back to z
+        for (int v = tid; v < ncols; v += PICK_THREADS) srow[v] = row[v];
+        __syncthreads();
+    }
+
+    const int wr = dead ? min(W, ncols) : min(W, n_om);
+    const unsigned kth = radix_select(sh.rs, ncols, [&](int v) { return beam_key(val(v)); }, [&](int v) { return in_set(v) ? 1 : 0; },
+                                      [&](int) { return wr; });
+    const int need_eq = sh.rs.left, n_above = wr - need_eq;
+    int eq_base = 0;
+    for (int v0 = 0; v0 < ncols; v0 += PICK_THREADS) {
+        const int v = v0 + tid;
+        const bool in = v < ncols && in_set(v);
+        const unsigned key = in ? beam_key(val(v)) : 0u;
+        const bool eq = in && key == kth;
+        if (in && key > kth) {                  // fewer than wr of these in the row: slot < n_above
+            const int slot = atomicAdd(&n_gt, 1);
+            if (slot < BEAM_MAX_W) { ck[slot] = key; cv[slot] = v; }
+        }
+        const unsigned long long m = __ballot(eq);
+        if (lane == 0) wave_eq[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < PICK_THREADS / 64; ++w) {
+            const int n = wave_eq[w];
+            if (w < wave) before += n;
+            total += n;
+        }
+        const int gt_seen = n_gt;               // (no thread adds to it before the barrier below)
+        const int rank = eq_base + before + __popcll(m & ((1ull << lane) - 1ull));
+        if (eq && rank < need_eq && n_above + rank < BEAM_MAX_W) { ck[n_above + rank] = key; cv[n_above + rank] = v; }
+        eq_base += total;
+        __syncthreads();
+        if (eq_base >= need_eq && gt_seen == n_above) break;     // uniform: every thread read the same counts
+    }
+    __syncthreads();
+    if (tid == 0) row_dead[r] = dead ? 1 : 0;
+    if (tid < W) {
+        if (tid < wr) {
+            const unsigned ki = ck[tid];
+            const int vi = min(max(cv[tid], 0), ncols - 1);
+            int rank = 0;
+            for (int m = 0; m < wr; ++m) rank += (ck[m] > ki || (ck[m] == ki && cv[m] < vi)) ? 1 : 0;
+            const float lp = val(vi) - lse;
+            const long long o = (long long)r * W + rank;
+            cand_v[o] = vi;
+            cand_lp[o] = lp;
+            cand_s[o] = cum[r] + lp;
+        } else {
+            cand_v[(long long)r * W + tid] = -1;
+        }
+    }
+}
+
+// k_beam_select with the tier above the score: the 64-bit key is [live row:1 | score key:32 | valid:1 | 63 - j:6 | 63 - rank in
+// row:6], so every candidate of a row that is not at a dead end ranks above every candidate of one that is.  The winners' loop also
+// gives each new slot its parent's state advanced by the token (a dead-end parent: the state unchanged, one more dead end), read
+// from the old buffer `c` and written to state_new / dead_new.
+__global__ __launch_bounds__(SEL_THREADS) void k_beam_select_constrained(int W, int ncols, const float* __restrict__ cand_s,
+                                                                         const float* __restrict__ cand_lp, const int* __restrict__ cand_v,
+                                                                         const int* __restrict__ row_dead, ConstraintDev c,
+                                                                         int* __restrict__ state_new, int* __restrict__ dead_new,
+                                                                         float* __restrict__ cum, int* __restrict__ tok, int ldtok, int pos_out,
+                                                                         int* __restrict__ par, int* __restrict__ htok, float* __restrict__ hlp) {
+    __shared__ unsigned long long keys[BEAM_MAX_W * BEAM_MAX_W];
+    const int g = blockIdx.x, tid = threadIdx.x, WW = W * W;
+    int N = 1;
+    while (N < WW) N <<= 1;
+    const long long c0 = (long long)g * WW;
+    for (int i = tid; i < N; i += SEL_THREADS) {
+        unsigned long long k = 0ull;
+        if (i < WW && cand_v[c0 + i] >= 0) {
+            const int j = i / W, q = i - j * W;
+            k = ((unsigned long long)(row_dead[g * W + j] ? 0 : 1) << 45) | ((unsigned long long)beam_key(cand_s[c0 + i]) << 13) | (1ull << 12) |
+                ((unsigned long long)(63 - j) << 6) | (unsigned long long)(63 - q);
+        }
+        keys[i] = k;
+    }
+    __syncthreads();
+    for (int k = 2; k <= N; k <<= 1) {
+        for (int jj = k >> 1; jj > 0; jj >>= 1) {
+            for (int q = tid; q < (N >> 1); q += SEL_THREADS) {      // pair q: i (bit jj clear) and i + jj
+                const int i = ((q & ~(jj - 1)) << 1) | (q & (jj - 1)), ixj = i + jj;
+                const unsigned long long a = keys[i], b = keys[ixj];
+                if (((i & k) == 0) ? (a < b) : (a > b)) { keys[i] = b; keys[ixj] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int n = tid; n < W; n += SEL_THREADS) {
+        const unsigned long long k = keys[n];
+        const int j = 63 - (int)((k >> 6) & 63ull), q = 63 - (int)(k & 63ull);
+        // a valid key always names a live candidate (every row has at least one); the guard only keeps the indices in range
+        const bool ok = ((k >> 12) & 1ull) && j < W && q < W;
+        const long long cd = c0 + (ok ? (long long)j * W + q : 0);
+        const int r = g * W + n, rp = g * W + (ok ? j : 0);
+        const int v = min(max(cand_v[cd], 0), ncols - 1);
+        par[r] = ok ? j : 0;
+        htok[r] = v;
+        hlp[r] = cand_lp[cd];
+        cum[r] = cand_s[cd];
+        tok[(long long)r * ldtok + pos_out] = v;
+        const bool pd = row_dead[rp] != 0;
+        const int s0 = min(max(c.state[rp], 0), c.S - 1);
+        int nx = pd ? s0 : (int)c.next[s0 * c.C + min((int)c.cls[v], c.C - 1)];
+        if (nx < 0 || nx >= c.S) nx = s0;           // (the token lies in Omega: never taken)
+        state_new[r] = nx;
+        dead_new[r] = c.dead[rp] + (pd ? 1 : 0);
+    }
+}
+
+// open_dst[r] = open_src[parent row of r] with the chosen token's slot bit flipped (a dead-end parent: unchanged); one thread per
+// word.  parent row = (r / W) * W + par[r], the token htok[r].
+__global__ void k_beam_con_reorder(int R, int W, int KW, const int* __restrict__ par, const int* __restrict__ htok,
+                                   const int* __restrict__ row_dead, const unsigned* __restrict__ slot, const unsigned* __restrict__ open_src,
+                                   unsigned* __restrict__ open_dst) {
+    const long long n = (long long)R * KW;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int r = (int)(i / KW), wi = (int)(i % KW);
+        const int rp = (r / W) * W + par[r];
+        unsigned word = open_src[(long long)rp * KW + wi];
+        if (!row_dead[rp]) {
+            const unsigned w = slot[htok[r]];
+            const unsigned k = (w & 0x7FFFFFFFu) - 1u;
+            if (w != 0u && (int)(k >> 5) == wi) word ^= 1u << (k & 31u);
+        }
+        open_dst[i] = word;
+    }
+}
+
 // ---------------------------------------------------------------- decode states (fsmg_dstate_*, DESIGN.md "Decode states")
 // The teacher-forced log-prob of fsmg_dstate_feed; one row per workgroup.  lse is the picks' (row_max_lse), so that the log-prob feed
 // returns for a token is bitwise the number a pick that chose it reports: out_lp[b][i] = logit[target] - lse, the target the token
@@ -1174,6 +1402,46 @@ hipError_t launch_beam_select(hipStream_t s, int G, int W, int ncols, const floa
     if (W < 1 || W > BEAM_MAX_W || ncols <= 0 || pos_out >= ldtok) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_beam_select, dim3(G), dim3(SEL_THREADS), 0, s, W, ncols, cand_s, cand_lp, cand_v, cum, tok, ldtok, pos_out, par,
                        htok, hlp);
+    return hipGetLastError();
+}
+
+namespace {
+bool beam_con_ok(const ConstraintDev& c) {
+    return c.S >= 1 && c.S <= CON_MAX_STATES && c.C >= 1 && c.C <= CON_MAX_CLASSES && c.KW >= 0 && c.KW <= CON_MAX_SLOTS / 32 && c.bias &&
+           c.cls && c.slot && c.next && c.state && c.open && c.dead;
+}
+}  // namespace
+
+hipError_t launch_beam_rowtop_constrained(hipStream_t s, const float* logits, int ldl, int ncols, int R, int W, const float* cum,
+                                          const ConstraintDev& c, float* cand_s, float* cand_lp, int* cand_v, int* row_dead) {
+    if (R <= 0) return hipSuccess;
+    if (ncols <= 0 || ncols > ldl || W < 1 || W > BEAM_MAX_W || !beam_con_ok(c) || !row_dead) return hipErrorInvalidValue;
+    // an unstaged row keeps Omega as a bitmap of its columns in LDS
+    const size_t bitmap_bytes = sizeof(unsigned) * (size_t)((ncols + 31) / 32);
+    if (bitmap_bytes > sizeof(float) * PICK_LDS_FLOATS) return hipErrorInvalidValue;
+    return launch_row_kernel<k_beam_rowtop_constrained<true>, k_beam_rowtop_constrained<false>>(s, R, ncols, bitmap_bytes, logits, ldl, ncols, W,
+                                                                                                cum, c, cand_s, cand_lp, cand_v, row_dead);
+}
+
+hipError_t launch_beam_select_constrained(hipStream_t s, int G, int W, int ncols, const float* cand_s, const float* cand_lp,
+                                          const int* cand_v, const int* row_dead, const ConstraintDev& c, int* state_new, int* dead_new,
+                                          float* cum, int* tok, int ldtok, int pos_out, int* par, int* htok, float* hlp) {
+    if (G <= 0) return hipSuccess;
+    if (W < 1 || W > BEAM_MAX_W || ncols <= 0 || pos_out >= ldtok || !beam_con_ok(c) || !row_dead || !state_new || !dead_new ||
+        state_new == c.state || dead_new == c.dead)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_beam_select_constrained, dim3(G), dim3(SEL_THREADS), 0, s, W, ncols, cand_s, cand_lp, cand_v, row_dead, c, state_new,
+                       dead_new, cum, tok, ldtok, pos_out, par, htok, hlp);
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_con_reorder(hipStream_t s, int R, int W, const ConstraintDev& c, const int* par, const int* htok, const int* row_dead,
+                                   unsigned* open_dst) {
+    if (R <= 0 || c.KW == 0) return hipSuccess;
+    if (W < 1 || R % W || !beam_con_ok(c) || !open_dst || open_dst == c.open) return hipErrorInvalidValue;
+    const long long n = (long long)R * c.KW;
+    const int blocks = (int)std::min<long long>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_beam_con_reorder, dim3(blocks), dim3(256), 0, s, R, W, c.KW, par, htok, row_dead, c.slot, c.open, open_dst);
     return hipGetLastError();
 }
 

@@ -557,6 +557,19 @@ hipError_t launch_beam_rowtop(hipStream_t s, const float* logits, int ldl, int n
 // per group: the W best of its W x W candidates -> par / htok / hlp / cum [R] and tok[r * ldtok + pos_out]
 hipError_t launch_beam_select(hipStream_t s, int G, int W, int ncols, const float* cand_s, const float* cand_lp, const int* cand_v,
                               float* cum, int* tok, int ldtok, int pos_out, int* par, int* htok, float* hlp);
+// constrained beam search (fsmg_beam_search_constrained): c.state / c.open / c.dead hold the R rows' constraint states.
+// launch_beam_rowtop over the row's allowed set only (min(W, |Omega|) candidates, z^c = z + bias in place of the logit); a row whose
+// set is empty gets launch_beam_rowtop's candidates and row_dead[r] = 1, every other row row_dead[r] = 0
+hipError_t launch_beam_rowtop_constrained(hipStream_t s, const float* logits, int ldl, int ncols, int R, int W, const float* cum,
+                                          const ConstraintDev& c, float* cand_s, float* cand_lp, int* cand_v, int* row_dead);
+// launch_beam_select with the candidates of dead-end rows ranked below all others; new slot r also gets state_new[r] / dead_new[r] from
+// its parent's row of c (advanced by the token, or at a dead-end parent unchanged with one more dead end); the new arrays are not c's
+hipError_t launch_beam_select_constrained(hipStream_t s, int G, int W, int ncols, const float* cand_s, const float* cand_lp,
+                                          const int* cand_v, const int* row_dead, const ConstraintDev& c, int* state_new, int* dead_new,
+                                          float* cum, int* tok, int ldtok, int pos_out, int* par, int* htok, float* hlp);
+// open_dst [R][KW]: each row takes its parent row's open words of c with the slot bit of its token htok[r] flipped (not c.open itself)
+hipError_t launch_beam_con_reorder(hipStream_t s, int R, int W, const ConstraintDev& c, const int* par, const int* htok, const int* row_dead,
+                                   unsigned* open_dst);
 // h / c [L][R][Hp]: each row takes its parent row's (r / W * W + par[r])
 hipError_t launch_beam_reorder(hipStream_t s, int L, int R, int W, int Hp, const int* par, const float* h_src, float* h_dst,
                                const float* c_src, float* c_dst);

@@ -242,6 +242,13 @@ SIGNATURES = {
                                         _F32P]),
     'fsmg_maml_beam_search_masked': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P,
                                                _F32P, _F32P]),
+    'fsmg_beam_search_constrained': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, C.POINTER(FsmgConstraintState),
+                                               C.POINTER(FsmgConstraintState), _P, _I32P, _F32P, _F32P]),
+    'fsmg_dstate_beam_search_constrained': (C.c_int, [_P, _P, C.POINTER(FsmgBeamConfig), _P, C.POINTER(FsmgConstraintState),
+                                                      C.POINTER(FsmgConstraintState), _I32P, _F32P, _F32P]),
+    'fsmg_maml_beam_search_constrained': (C.c_int, [_P, C.POINTER(FsmgBeamConfig), _P, C.POINTER(FsmgConstraintState),
+                                                    C.POINTER(FsmgConstraintState), _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P,
+                                                    _I32P, _F32P, _F32P]),
     'fsmg_score': (C.c_int, [_P, C.POINTER(FsmgScoreConfig), _P, _F32P, _I32P, _F32P, _I32P, _F32P]),
     'fsmg_maml_score_masked': (C.c_int, [_P, C.POINTER(FsmgScoreConfig), _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _I32P,
                                          _F32P, _I32P, _F32P, _I32P, _F32P]),
@@ -1268,11 +1275,63 @@ class FsmgModel(object):
         self._ck(fn(self._h, C.byref(b), *adapt, pp, toks.ctypes.data_as(_I32P), _f32p(scores), _f32p(lp) if logprobs else None))
         return (toks, scores, lp) if logprobs else (toks, scores)
 
-    def beam_search(self, num, beam_width, n_groups=1, primer=None, logprobs=False, state=None):
+    def _beam_constrained(self, call, head, tail, dc, n_groups, beam_width, num, logprobs, cstate, return_cstate):
+        """one of the three *_beam_search_constrained entry points: call(*head, con, cstate_in*, cstate_out*, *tail, tokens, scores,
+        log-probs); cstate is per group, the returned dict per hypothesis ([G, W, ...])"""
+        G, W, num = int(n_groups), int(beam_width), int(num)
+        cs = cstate or {}
+        keep = []
+
+        def arr(key, dtype, shape):
+            if cs.get(key) is None:
+                return None
+            a = np.ascontiguousarray(cs[key], dtype=dtype).reshape(shape)
+            keep.append(a)
+            return a.ctypes.data if a.size else None
+        cin = None
+        if cstate is not None:
+            cin = FsmgConstraintState(state=arr('state', np.int32, (G,)), open=arr('open', np.uint32, (G, dc.n_words)),
+                                      dead_ends=arr('dead_ends', np.int32, (G,)))
+        out_cs = cout = None
+        if return_cstate:
+            out_cs = dict(state=np.empty((G, W), np.int32), open=np.empty((G, W, dc.n_words), np.uint32),
+                          dead_ends=np.empty((G, W), np.int32))
+            cout = FsmgConstraintState(state=out_cs['state'].ctypes.data, open=out_cs['open'].ctypes.data if dc.n_words else None,
+                                       dead_ends=out_cs['dead_ends'].ctypes.data)
+        toks = np.empty((G, W, num), np.int32)
+        scores = np.empty((G, W), np.float32)
+        lp = np.empty((G, W, num), np.float32) if logprobs else None
+        call(*head, dc._con, C.byref(cin) if cin is not None else None, C.byref(cout) if cout is not None else None, *tail,
+             toks.ctypes.data_as(_I32P), _f32p(scores), _f32p(lp) if logprobs else None)
+        out = (toks, scores, lp) if logprobs else (toks, scores)
+        return out + (out_cs,) if return_cstate else out
+
+    def beam_search(self, num, beam_width, n_groups=1, primer=None, logprobs=False, state=None, constraints=None, cstate=None,
+                    return_cstate=False):
         """n_groups independent beam searches of width beam_width, num tokens each -> tokens int32 [G, W, num], scores float32
         [G, W] (, log-probs float32 [G, W, num] with logprobs=True), each group's hypotheses best first.  primer: int32 [G, P]
         (or [P] for every group) continued by every hypothesis of its group, or (device address, P).
-        state: a DecodeState of n_groups rows, group g searching on from its row g (fsmg_dstate_beam_search; the state is only read)."""
+        state: a DecodeState of n_groups rows, group g searching on from its row g (fsmg_dstate_beam_search; the state is only read).
+        constraints: a data.constraints.Constraints or a DeviceConstraint (fsmg_beam_search_constrained /
+        fsmg_dstate_beam_search_constrained); cstate: the groups' constraint states to start from, a dict with any of 'state' int32
+        [G], 'open' uint32 [G, words], 'dead_ends' int32 [G]; return_cstate: the hypotheses' final states, a dict of 'state' [G, W],
+        'open' [G, W, words], 'dead_ends' [G, W], as the last element of the result."""
+        if constraints is None and (cstate is not None or return_cstate):
+            raise ValueError('cstate / return_cstate need constraints')
+        if state is not None and primer is not None:
+            raise ValueError('a state takes no primer: feed it first')
+        if state is not None and int(n_groups) != state.rows:
+            raise ValueError('n_groups %d is not the row count of the state (%d)' % (int(n_groups), state.rows))
+        if constraints is not None:
+            dc = self._constraint(constraints)
+            if state is None:
+                P, on_device, pp, _keep = self._primer(primer, n_groups, ('n_groups', 'group'))
+                b = self.beam_config(n_groups, beam_width, num, P, on_device)
+                return self._beam_constrained(lambda *a: self._ck(self._lib.fsmg_beam_search_constrained(self._h, *a)), (C.byref(b),),
+                                              (pp,), dc, n_groups, beam_width, num, logprobs, cstate, return_cstate)
+            b = self.beam_config(n_groups, beam_width, num)
+            return self._beam_constrained(lambda *a: state._call(self._lib.fsmg_dstate_beam_search_constrained, *a), (C.byref(b),), (),
+                                          dc, n_groups, beam_width, num, logprobs, cstate, return_cstate)
         if state is None:
             return self._beam_search((), num, beam_width, n_groups, primer, logprobs)
         if primer is not None:
@@ -1289,10 +1348,20 @@ class FsmgModel(object):
         return (toks, scores, lp) if logprobs else (toks, scores)
 
     def maml_beam_search(self, support, num, inner_steps, inner_lr, beam_width, n_groups=1, primer=None, logprobs=False,
-                         n_support_rows=None, support_len=None):
+                         n_support_rows=None, support_len=None, constraints=None, cstate=None, return_cstate=False):
         """adapt on support [rows, max_len] (numpy, or a device address with n_support_rows), beam search at theta', restore theta.
-        support_len int32 [rows]: adapt over the positions inside each support song only (fsmg_maml_beam_search_masked)"""
+        support_len int32 [rows]: adapt over the positions inside each support song only (fsmg_maml_beam_search_masked).
+        constraints, cstate, return_cstate: as in beam_search (fsmg_maml_beam_search_constrained)"""
         masked, adapt, _keep = self._adapt(support, n_support_rows, inner_steps, inner_lr, support_len)
+        if constraints is None and (cstate is not None or return_cstate):
+            raise ValueError('cstate / return_cstate need constraints')
+        if constraints is not None:
+            dc = self._constraint(constraints)
+            P, on_device, pp, _keep_p = self._primer(primer, n_groups, ('n_groups', 'group'))
+            b = self.beam_config(n_groups, beam_width, num, P, on_device)
+            sup = adapt if masked else (adapt[0], None) + adapt[1:]       # (support, support_len or NULL, rows, steps, lr, on device)
+            return self._beam_constrained(lambda *a: self._ck(self._lib.fsmg_maml_beam_search_constrained(self._h, *a)), (C.byref(b),),
+                                          sup + (pp,), dc, n_groups, beam_width, num, logprobs, cstate, return_cstate)
         if not masked:
             return self._beam_search(adapt, num, beam_width, n_groups, primer, logprobs)
         return self._beam_search(adapt, num, beam_width, n_groups, primer, logprobs, masked=True)

@@ -304,13 +304,19 @@ class LSTMBaseline(HIPModel):
                     primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs,
                     top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window)
 
-    def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False):
+    def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False, constraints=None, cstate=None,
+                    return_cstate=False):
         """n independent beam searches of width beam_width, num tokens each, on the device (include/fsmg.h fsmg_beam_search):
         -> tokens int32 [n, beam_width, num], scores float32 [n, beam_width] (, per-token log-probs with logprobs=True), best
-        first.  Group i continues the first primer_len tokens of a support song, dealt round-robin like generate's rows."""
+        first.  Group i continues the first primer_len tokens of a support song, dealt round-robin like generate's rows.
+        constraints: a data.constraints.Constraints the search ranks under (fsmg_beam_search_constrained); cstate / return_cstate:
+        the groups' constraint states to start from and the hypotheses' final ones, as in FsmgModel.beam_search."""
         self._require_init()
+        if constraints is None and (cstate is not None or return_cstate):
+            raise ValueError('cstate / return_cstate need constraints')
+        con = dict(constraints=constraints, cstate=cstate, return_cstate=return_cstate) if constraints is not None else {}
         return self._model.beam_search(int(num), int(beam_width), n_groups=int(n),
-                                       primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs)
+                                       primer=self._primer(support_set, int(n), int(primer_len)), logprobs=logprobs, **con)
 
     def score(self, support_set, songs, **kw):
         """Per-token statistics of the given songs (int32 [R, max_len]) under the model (include/fsmg.h fsmg_score): a dict of

@@ -131,14 +131,19 @@ class MAMLLSTM(LSTMBaseline):
                                          top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, repeat_window=repeat_window,
                                          **self._support_lengths(support, support_len), **con)
 
-    def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False, support_len=None):
+    def beam_search(self, support_set, num, beam_width, n=1, primer_len=0, logprobs=False, support_len=None, constraints=None,
+                    cstate=None, return_cstate=False):
         """like LSTMBaseline.beam_search, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored.
-        support_len [rows]: the support songs' lengths (maml_lengths)"""
+        support_len [rows]: the support songs' lengths (maml_lengths).  constraints, cstate, return_cstate: LSTMBaseline.beam_search's
+        (fsmg_maml_beam_search_constrained)"""
         self._require_init()
         support = self._tokens(support_set, 2)
+        if constraints is None and (cstate is not None or return_cstate):
+            raise ValueError('cstate / return_cstate need constraints')
+        con = dict(constraints=constraints, cstate=cstate, return_cstate=return_cstate) if constraints is not None else {}
         return self._model.maml_beam_search(support, int(num), self._inner_steps, self._inner_lr, int(beam_width), n_groups=int(n),
                                             primer=self._primer(support, int(n), int(primer_len)), logprobs=logprobs,
-                                            **self._support_lengths(support, support_len))
+                                            **self._support_lengths(support, support_len), **con)
 
     def score(self, support_set, songs, support_len=None, **kw):
         """like LSTMBaseline.score, at theta' = theta adapted on the support set (inner_steps, inner_lr); theta is restored.

@@ -73,12 +73,13 @@ def sample_filters(config):
     return {arg: conv(config[key]) for key, arg, conv in SAMPLE_FILTER_KEYS if key in config}
 
 
-def sample_constraints(config, sampler):
+def sample_constraints(config, sampler, key='sample_constraints'):
     """model YAML key sample_constraints: none (the default: nothing is passed to generate) | loader (the loader's constraints,
-    Loader.constraints(); a loader without any gives none)"""
-    mode = str(config.get('sample_constraints', 'none')).lower()
+    Loader.constraints(); a loader without any gives none).  key='sample_beam_constraints': the same choice for the
+    sample_beam_width dump (model.beam_search)"""
+    mode = str(config.get(key, 'none')).lower()
     if mode not in ('none', 'loader'):
-        raise ValueError("sample_constraints must be 'none' or 'loader', got %r" % config.get('sample_constraints'))
+        raise ValueError("%s must be 'none' or 'loader', got %r" % (key, config.get(key)))
     con = sampler.constraints() if mode == 'loader' else None
     return {} if con is None else {'constraints': con}
 
@@ -252,7 +253,8 @@ def main(argv=None):
                 write_seq(episode_sampler['test'].detokenize([int(w) for w in row]), curr_sample_dir, 'model_sample_%d' % j)
         if 'sample_beam_width' in config:      # opt-in: the beam's hypotheses, best first, and their scores
             toks, scores = model.beam_search(support_set, max_len, int(config['sample_beam_width']), n=1,
-                                             primer_len=int(config.get('sample_primer_len', 0)))
+                                             primer_len=int(config.get('sample_primer_len', 0)),
+                                             **sample_constraints(config, episode_sampler['test'], 'sample_beam_constraints'))
             for j, row in enumerate(toks[0]):
                 write_seq(episode_sampler['test'].detokenize([int(w) for w in row]), curr_sample_dir, 'model_beam_%d' % j)
             with open(os.path.join(curr_sample_dir, 'beam_scores.txt'), 'w') as f:

@@ -431,7 +431,8 @@ int fsmg_maml_generate_filtered_masked(fsmg_handle h, const fsmg_gen_config* g, 
  * con == NULL: every call is bitwise its unconstrained twin and launches that twin's kernels (cstate_io is not touched).
  * The rest of fsmg_generate_filtered's contract holds: bitwise deterministic, a row's output independent of n_seq and of the
  * other rows, no handle state changed.  A constraint outlives the calls that use it and is freed by fsmg_constraint_destroy or with
- * the handle.  Not covered: beam search, the cache-conditioned generators and fsmg_dyneval_generate.
+ * the handle.  Beam search under a constraint: fsmg_beam_search_constrained, below.  Not covered: the cache-conditioned generators
+ * and fsmg_dyneval_generate.
  * Errors: fsmg_constraint_create returns FSMG_ERR_INVALID for a bad version or nonzero reserved words, n_columns that is not the
  * handle's V1 = input_size + 1, V1 > 2^19, S, C or K outside their limits, one automaton table without the other, any index out of range, a
  * token with both slot roles, a bias of +inf or NaN.  The generate calls: what their unconstrained twins refuse; FSMG_ERR_INVALID
@@ -518,6 +519,54 @@ int fsmg_maml_beam_search(fsmg_handle h, const fsmg_beam_config* b, const int32_
 int fsmg_maml_beam_search_masked(fsmg_handle h, const fsmg_beam_config* b, const int32_t* support, const int32_t* support_len,
                                  int32_t n_support_rows, int32_t inner_steps, float inner_lr, int32_t support_on_device,
                                  const int32_t* primer, int32_t* out_tokens, float* out_scores, float* out_logprob);
+
+/* ---- constrained beam search: fsmg_beam_search ranked over the allowed set of a constraint (above), every slot
+ * carrying a constraint state.  Everything in fsmg_beam_search's contract holds except what is stated here.
+ * Slot state.  Every slot of every group carries (state, open[ceil(K / 32)], dead_ends).  A group's W slots start from the group's
+ * state: cstate_in[g] (NULL, or a NULL array: start_state, every slot closed, zero dead ends), walked over the group's primer tokens
+ * exactly as fsmg_generate_constrained walks a row's primer, with the same refusals (a host primer token that is not allowed where it
+ * stands: FSMG_ERR_INVALID before any device work, before the adaptation in the MAML variant; a device primer: the primer flag,
+ * FSMG_ERR_TOKEN_RANGE, outputs unwritten).
+ * Candidates.  At a generated position slot j has state (s, open), raw logits z and lse_j, bitwise fsmg_beam_search's number.  With
+ * Omega_j the allowed set of (s, open):
+ *   Omega_j not empty: the slot's candidates are the columns of Omega_j only, z^c_v = fl(z_v + bias_v), lp = fl(z^c_v - lse_j),
+ *     s = fl(cum_j + lp).  A column outside Omega_j is no candidate at all (not one with score -inf: it ranks below an allowed
+ *     column whose z^c is -inf or NaN); a slot with |Omega_j| < W has fewer candidates.
+ *   Omega_j empty (a dead end): the slot's candidates are all V1 columns with z^c = z, as fsmg_beam_search produces them; they
+ *     form a lower tier.
+ * Ranking within a group: slots that are not at a dead end first; then s descending; j ascending; z^c descending; v ascending (NaN
+ * below -inf, -0 equal to +0).  The W best become the next slots.  A live slot always has at least one candidate and a dead-end
+ * slot min(W, V1), so a group always has at least W.
+ * Advance.  A winner from a live slot takes its parent's state advanced by its token (next_state, the slot bit flipped); one from
+ * a dead-end slot takes its parent's state unchanged with dead_ends + 1, so a dead-end state stays one.  A group's output is
+ * therefore its hypotheses with no dead end during the call, best first, followed by those that hit one.  A dead-end hypothesis
+ * survives only while its group has fewer than W candidates from live slots; -inf-scored duplicates of live slots count as such
+ * candidates, exactly as slots 1 .. W-1 count at the first position of fsmg_beam_search.
+ * Outputs.  out_logprob is lp as ranked (the biased value; where the bias is 0 the model's log-prob); out_scores the final cum,
+ * bitwise the fp32 left-to-right sum of the hypothesis's out_logprob; hypotheses with a score above -inf are distinct.  cstate_out
+ * (may be NULL, as may each of its arrays) receives the final state per hypothesis: state [G*W], open [G*W][ceil(K / 32)],
+ * dead_ends [G*W].  cstate_in is per group: state [G], open [G][ceil(K / 32)], dead_ends [G].
+ * con == NULL: the call is bitwise fsmg_beam_search (fsmg_dstate_beam_search, fsmg_maml_beam_search(_masked)) on the same kernels;
+ * neither state struct is touched.
+ * W = 1: the tokens and final constraint states are fsmg_generate_constrained's at temperature 0 with no filters, and the log-probs
+ * are equal as floats when every bias value is 0 or -inf (for rows without NaN logits).
+ * Errors: what fsmg_beam_search and fsmg_generate_constrained refuse: a constraint this handle does not own, a cstate_in state
+ * outside [0, S), negative dead_ends, an open bit at or above K.  Nothing on the handle changes; the MAML variant has
+ * fsmg_maml_beam_search's documented side effects only.  Not covered: length normalisation and end tokens (as fsmg_beam_search). */
+int fsmg_beam_search_constrained(fsmg_handle h, const fsmg_beam_config* b, fsmg_constraint con, const fsmg_constraint_state* cstate_in,
+                                 fsmg_constraint_state* cstate_out, const int32_t* primer, int32_t* out_tokens, float* out_scores,
+                                 float* out_logprob);
+/* fsmg_dstate_beam_search (below) under con: cstate_in is the groups' constraint state behind what the decode state has read; the
+ * decode state is only read */
+int fsmg_dstate_beam_search_constrained(fsmg_handle h, struct fsmg_dstate_s* st, const fsmg_beam_config* b, fsmg_constraint con,
+                                        const fsmg_constraint_state* cstate_in, fsmg_constraint_state* cstate_out,
+                                        int32_t* out_tokens, float* out_scores, float* out_logprob);
+/* fsmg_maml_beam_search (support_len == NULL) or fsmg_maml_beam_search_masked: adapt, search at theta' under con, restore theta */
+int fsmg_maml_beam_search_constrained(fsmg_handle h, const fsmg_beam_config* b, fsmg_constraint con,
+                                      const fsmg_constraint_state* cstate_in, fsmg_constraint_state* cstate_out,
+                                      const int32_t* support, const int32_t* support_len, int32_t n_support_rows, int32_t inner_steps,
+                                      float inner_lr, int32_t support_on_device, const int32_t* primer, int32_t* out_tokens,
+                                      float* out_scores, float* out_logprob);
 
 /* ---- scoring of given songs (DESIGN.md "Scoring").  Row r of tokens [R, max_len] is read exactly as an eval row: the inputs are
  * [start, x_0 .. x_{T-2}] (start = input_size, T = max_len) from a zero state, z the V1 = input_size + 1 logits after input t -- the
