@@ -98,6 +98,7 @@ int fsmg_comm_init(fsmg_handle h, const char id[FSMG_COMM_ID_BYTES], int32_t wor
     if (!h || !id || world_size < 1 || rank < 0 || rank >= world_size) return FSMG_ERR_INVALID;
     if (h->comm) return fail(h, FSMG_ERR_STATE, "a communicator is already attached");
     if (h->msgd_on) return fail(h, FSMG_ERR_STATE, "Meta-SGD is enabled on this handle: the library's exchange does not carry the rate gradient (fsmg_msgd_disable first, or exchange outside the library)");
+    if (h->lopt_on) return fail(h, FSMG_ERR_STATE, "the learned optimiser is enabled on this handle: the library's exchange does not carry GPhi (fsmg_lopt_disable first, or exchange outside the library)");
     int rc = comm_prepare(h);
     if (rc != FSMG_OK) return rc;
     Rccl::UniqueId u;
@@ -113,6 +114,7 @@ int fsmg_comm_attach(fsmg_handle h, void* nccl_comm, int32_t world_size, int32_t
     if (!h || !nccl_comm || world_size < 1 || rank < 0 || rank >= world_size) return FSMG_ERR_INVALID;
     if (h->comm) return fail(h, FSMG_ERR_STATE, "a communicator is already attached");
     if (h->msgd_on) return fail(h, FSMG_ERR_STATE, "Meta-SGD is enabled on this handle: the library's exchange does not carry the rate gradient (fsmg_msgd_disable first, or exchange outside the library)");
+    if (h->lopt_on) return fail(h, FSMG_ERR_STATE, "the learned optimiser is enabled on this handle: the library's exchange does not carry GPhi (fsmg_lopt_disable first, or exchange outside the library)");
     int rc = comm_prepare(h);
     if (rc != FSMG_OK) return rc;
     h->comm = nccl_comm; h->own_comm = false; h->world = world_size; h->rank = rank;

@@ -104,6 +104,7 @@ int fsmg_debug_read(fsmg_handle h, const char* what, float* host, int64_t count)
         if (!h->msgd_state) return fail(h, FSMG_ERR_STATE, "no Meta-SGD state: fsmg_msgd_enable first");
         return download_tensor(h, h->msgd_S, what + 9, host, count);
     }
+    if (!std::strncmp(what, "lopt_", 5)) return lopt_debug_read(h, what, host, count);      // the learned optimiser's gates, store, scalars and replayed theta_K (api_lopt.hip)
     if (!std::strcmp(what, "logits")) { src = h->logits; cap = rows * h->V1p; }
     else if (!std::strcmp(what, "dlogits")) { src = dlogits_buf(h); cap = rows * h->V1p; }
     else if (!std::strcmp(what, "lse")) { src = h->lse; cap = rows; }

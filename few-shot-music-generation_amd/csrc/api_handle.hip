@@ -370,6 +370,9 @@ int fsmg_destroy(fsmg_handle h) {
     if (h->dyn_stats) hipFree(h->dyn_stats);
     if (h->dyn_out) hipFree(h->dyn_out);
     if (h->msgd_state) hipFree(h->msgd_state);
+    if (h->lopt_state) hipFree(h->lopt_state);
+    if (h->lopt_store) hipFree(h->lopt_store);
+    if (h->lopt_replay) hipFree(h->lopt_replay);
     drop_destroy(h);
     for (int* t : h->table) if (t) hipFree(t);
     for (int* t : h->table_len) if (t) hipFree(t);

@@ -114,6 +114,7 @@ int fsmg_msgd_enable(fsmg_handle h, const fsmg_msgd_config* cfg) {
     int rc = check_msgd_config(h, cfg);
     if (rc != FSMG_OK) return rc;
     if (h->comm) return fail(h, FSMG_ERR_STATE, "a communicator is attached: the library's exchange does not carry the rate gradient");
+    if (h->lopt_on) return fail(h, FSMG_ERR_STATE, "the learned optimiser is enabled on this handle (fsmg_lopt_disable first)");
     BEGIN_CALL(h);
     if ((rc = ensure_msgd_state(h, cfg->alpha_init)) != FSMG_OK) return rc;
     HIPCK(h, hipStreamSynchronize(h->stream));

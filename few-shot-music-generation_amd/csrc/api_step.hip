@@ -86,6 +86,7 @@ int forward_backward_core(fsmg_model* h, int32_t N, int32_t K, int32_t Q, Stage&
     h->lastB = B;
     h->have_grads = !with_update;
     h->msgd_pending = false;            // (a rate gradient belongs to the pass it was formed from: msgd_rate_gradient sets it behind the query pass)
+    h->lopt_pending = false;            // (and so does a GPhi: lopt_meta_gradient)
     return FSMG_OK;
 }
 
@@ -311,10 +312,12 @@ int fsmg_apply_update(fsmg_handle h, float grad_scale, float* loss) {
     if (!(grad_scale > 0.f)) return fail(h, FSMG_ERR_INVALID, "grad_scale must be > 0");
     uint32_t bits; std::memcpy(&bits, &grad_scale, 4);
     // a pending Meta-SGD rate gradient: the rates' two launches ride in the update (a graph of its own; fsmg_msgd_enable drops the graphs)
-    const bool rates = msgd_rates_due(h);
-    int rc = run_graphed(h, (rates ? "upr:" : "up:") + std::to_string(bits) + (h->last_bwd_xcd ? "x" : "s"),
+    // (a pending GPhi of the learned optimiser, DESIGN.md 31: one launch, the same way)
+    const bool phi = lopt_phi_due(h), rates = msgd_rates_due(h) || phi;
+    int rc = run_graphed(h, (phi ? "upl:" : rates ? "upr:" : "up:") + std::to_string(bits) + (h->last_bwd_xcd ? "x" : "s"),
                          [&]() -> int { return apply_update(h, grad_scale, false, rates); });
     h->msgd_pending = false;
+    h->lopt_pending = false;
     if (rc != FSMG_OK) return rc;
     return after_update(h, grad_scale, loss);
 }
@@ -415,11 +418,12 @@ int window_rows_pass(fsmg_model* h, const int32_t* rows, const int32_t* len, int
 int maml_adapt(fsmg_model* h, const Episode& e, int32_t inner_steps, float inner_lr, bool train) {
     int rc = save_theta(h);
     if (rc == FSMG_OK && h->msgd_on && train) rc = msgd_begin_sum(h);
+    if (rc == FSMG_OK && h->lopt_on) rc = lopt_begin(h, train);         // the learned optimiser: the gates restart
     const bool suppress0 = h->drop_suppress;
     if (!train) h->drop_suppress = true;        // the adaptation of an eval / decode / score form is never dropped
     for (int i = 0; rc == FSMG_OK && i < inner_steps; ++i) {
         rc = rows_pass(h, e.sup, e.masked ? e.slen : nullptr, e.N, e.K, e.on_device);       // support rows only
-        if (rc == FSMG_OK) rc = h->msgd_on ? msgd_inner_update(h, inner_lr, train) : sgd_update(h, inner_lr);
+        if (rc == FSMG_OK) rc = h->lopt_on ? lopt_inner_update(h, inner_lr) : h->msgd_on ? msgd_inner_update(h, inner_lr, train) : sgd_update(h, inner_lr);
     }
     h->drop_suppress = suppress0;
     return rc;
@@ -492,10 +496,13 @@ int locate_episode(fsmg_model* h, int32_t table_id, bool with_len, const int32_t
 // The prologue is the call's own: a repeat behind an update (step_with_update, dp_train_step) settles that update's pending half
 // before theta is saved.  The gradient of the query pass at theta' stays pending; theta comes back under it.
 int maml_forward_backward(fsmg_model* h, const Episode& e, int32_t inner_steps, float inner_lr) {
+    int rc = lopt_check_train(h, inner_steps);
+    if (rc != FSMG_OK) return rc;
     BEGIN_CALL(h);
-    int rc = maml_adapt(h, e, inner_steps, inner_lr, true);
+    rc = maml_adapt(h, e, inner_steps, inner_lr, true);
     if (rc == FSMG_OK) rc = rows_pass(h, e.qry, e.masked ? e.qlen : nullptr, e.N, e.Q, e.on_device);       // query rows at theta'
     if (rc == FSMG_OK && h->msgd_on) rc = msgd_rate_gradient(h);
+    if (rc == FSMG_OK && h->lopt_on) rc = lopt_meta_gradient(h, true, 1.0);
     const bool pending = h->have_grads;
     const int rc_end = end_adaptation(h);
     h->have_grads = pending;

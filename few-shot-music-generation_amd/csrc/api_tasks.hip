@@ -73,7 +73,8 @@ int fold_artist(fsmg_model* h, int n, int N) {
 
 int tasks_forward_backward(fsmg_model* h, const fsmg_maml_tasks_config* c, const Episode& e) {
     const int N = e.N;
-    int rc = ensure_task_buffers(h, N);
+    int rc = lopt_check_train(h, c->inner_steps);
+    if (rc == FSMG_OK) rc = ensure_task_buffers(h, N);
     if (rc != FSMG_OK) return rc;
     ScopedTimer tm(h, "tasks");
     h->task_loss_n = 0;
@@ -81,6 +82,7 @@ int tasks_forward_backward(fsmg_model* h, const fsmg_maml_tasks_config* c, const
         const Episode a = e.artist(n, h->T);
         rc = maml_adapt(h, a, c->inner_steps, c->inner_lr, true);
         if (rc == FSMG_OK) rc = rows_pass(h, a.qry, a.masked ? a.qlen : nullptr, 1, a.Q, a.on_device);       // query rows at theta'_n
+        if (rc == FSMG_OK && h->lopt_on) rc = lopt_meta_gradient(h, n == 0, 1.0 / (double)N);    // G_n through the learned rule, GPhi's fold
         if (rc == FSMG_OK && n == N - 1) rc = keep_theta_prime(h);
         if (rc == FSMG_OK) rc = fold_artist(h, n, N);
         if (rc != FSMG_OK) break;
@@ -88,6 +90,7 @@ int tasks_forward_backward(fsmg_model* h, const fsmg_maml_tasks_config* c, const
     if (rc != FSMG_OK) {                // theta comes back whatever happened; no fold is pending
         (void)end_adaptation(h);
         h->msgd_pending = false;
+        h->lopt_pending = false;
         return rc;
     }
     // the buckets of an exchange are final behind the last fold, not behind the last pass
@@ -96,6 +99,7 @@ int tasks_forward_backward(fsmg_model* h, const fsmg_maml_tasks_config* c, const
     h->bucket0_recorded = true;
     h->have_grads = true;
     h->msgd_pending = h->msgd_on;
+    h->lopt_pending = h->lopt_on;
     h->task_loss_n = N;
     return FSMG_OK;
 }

@@ -117,7 +117,7 @@ int apply_update(fsmg_model* h, float grad_scale, bool may_defer, bool with_rate
         HIPCK(h, launch_adam_update(s, a));
     }
     // the Meta-SGD rates move with theta: before the launch below counts the step and clears the flags they read
-    if (with_rates) GEMMCK(msgd_update_rates(h, grad_scale));
+    if (with_rates) GEMMCK(h->lopt_on ? lopt_update_phi(h, grad_scale) : msgd_update_rates(h, grad_scale));     // (the learned optimiser's Phi: DESIGN.md 31)
     // refresh the fragment-ordered recurrent weights and close the step (ring[step] = loss, ++step, or the skip tallies) -- one launch
     StepIncArgs inc{};
     inc.step = h->d_step; inc.loss_src = h->G + h->n_flat + 1; inc.loss_scale = grad_scale; inc.ring = h->d_ring; inc.ring_cap = RING_CAP;

@@ -430,6 +430,39 @@ struct MsgdAlphaArgs {
 };
 hipError_t launch_msgd_alpha_update(hipStream_t s, const MsgdAlphaArgs& a);
 
+// ---------------------------------------------------------------- learned optimiser: a meta-learner LSTM cell per element (lopt.hip)
+// The inner step of the MAML-style pass with the learned rule of include/fsmg.h "learned optimiser".  step and the conditions under which
+// nothing is written are launch_sgd_update's, from the same partials / tail / error word; L_t is tail[1].  Per element (lopt_element.h):
+// the gates f, i from (g, L_t, p, F, I) and phi[14] = {wF[6], bF, wI[6], bI}, then p <- f p - step (gate_scale i) g; F <- f, I <- i.
+// 28 B per element.  store != nullptr (the train forms): store[j] = g[j] as well (32 B) and *sc_step = step, *sc_loss = L_t.
+// n a multiple of 4.
+constexpr int LOPT_MAX_BLOCKS = 2048;
+struct LoptUpdateArgs {
+    float* p; const float* g; float* F; float* I; float* store; float* sc_step; float* sc_loss; const float* phi; long long n;
+    const double* partials; int n_partials; const float* tail; int use_slices;
+    float lr, clip, gate_scale; float* gnorm_out; const int* err_flag;
+};
+hipError_t launch_lopt_update(hipStream_t s, const LoptUpdateArgs& a);
+// Back-propagation through the K stored inner steps, one launch: per element the trajectory from p0 (theta_0) and store[t * stride + j]
+// again in registers, then the walk back; G[j] <- D_0 in place, theta_out[j] = the replayed theta_K where given, and
+// part[block][14] = the block's fp64 sums of the fourteen weight gradients (lopt_blocks(n) blocks).  sc: [0, 8) step_t, [8, 16) L_t.
+// Nothing is written where launch_sgd_update skips.  (K + 3) x 4 B per element.  n, stride multiples of 4; K in [1, 8].
+struct LoptBackpropArgs {
+    float* G; const float* p0; const float* store; long long stride; const float* sc; const float* phi; float* theta_out; long long n;
+    double* part; float gate_scale; const float* tail; const int* err_flag; int K;
+};
+hipError_t launch_lopt_backprop(hipStream_t s, const LoptBackpropArgs& a);
+int lopt_blocks(long long n);
+// One block.  reduce: fold[c] = (first ? 0 : fold[c]) + weight * sum over blocks of part[b][c] in fixed order, gphi[c] = (float)fold[c]
+// (n_blocks == 0: the sum is 0).  Otherwise clip + Adam of phi from gphi: skipped where launch_adam_update skips;
+//   gnorm = sqrt(sum gphi^2) * grad_scale;  scale = clip > 0 ? clip / max(gnorm, clip) * grad_scale : grad_scale
+//   step size: launch_adam_update's schedule with `lr`, from *step;  adam_element per weight.
+struct LoptPhiArgs {
+    int reduce; const double* part; int n_blocks; double weight; int first; double* fold; float* gphi;
+    float* phi; float* m; float* v; const float* tail; const int* err_flag; float grad_scale, lr, n_decay, clip; const long long* step;
+};
+hipError_t launch_lopt_phi(hipStream_t s, const LoptPhiArgs& a);
+
 // ---------------------------------------------------------------- per-artist MAML: the fold behind an artist's query pass (tasks.hip)
 // g holds the artist's gradient [n] and its tail (g + n: [0] slice sum of squares, [1] loss, [2..5] indicators), acc [n + FSMG_GRAD_TAIL]
 // the running fold.  first: acc = w * g; otherwise fma(w, g, acc), written to acc or -- last -- to g.  first && last: g is left alone.

@@ -201,6 +201,19 @@ struct fsmg_model {
     float *msgd_A = nullptr, *msgd_AM = nullptr, *msgd_AV = nullptr, *msgd_S = nullptr, *msgd_GA = nullptr;
     double* msgd_part = nullptr;        // [sqnorm_blocks(n_flat)] squared-norm partials of GA (the theta update's live in `partials`)
     fsmg_msgd_config msgd_cfg{};        // the scalars of the last fsmg_msgd_enable
+    // learned optimiser (fsmg_lopt_*): a meta-learner LSTM cell per element in place of the inner step.  One allocation on the
+    // first fsmg_lopt_enable, kept until fsmg_destroy: [Phi 14 | PM 14 | PV 14 | GPhi 14 | scalars 16 | fold 14 d | partials | F | I]; the store of
+    // the train forms' support gradients is an allocation of its own (it grows with max_train_steps), the replayed theta_K another (keep_adapted)
+    bool lopt_on = false;               // every adaptation takes launch_lopt_update in place of launch_sgd_update
+    bool lopt_pending = false;          // GPhi belongs to the gradient that is pending (have_grads): fsmg_apply_update moves Phi with it
+    char* lopt_state = nullptr;
+    float *lopt_phi = nullptr, *lopt_pm = nullptr, *lopt_pv = nullptr, *lopt_gphi = nullptr, *lopt_sc = nullptr, *lopt_F = nullptr, *lopt_I = nullptr;
+    double *lopt_fold = nullptr, *lopt_part = nullptr;
+    float* lopt_store = nullptr; int lopt_store_steps = 0;      // [lopt_store_steps][n_flat]
+    float* lopt_replay = nullptr; bool lopt_have_replay = false;
+    int lopt_t = 0;                     // inner steps the adaptation in progress has taken
+    bool lopt_storing = false;          // ... and whether it is a train form's (its steps are stored)
+    fsmg_lopt_config lopt_cfg{};        // the scalars of the last fsmg_lopt_enable
     // dropout of the train passes (fsmg_dropout_*): masks regenerated from (seed, pass, site, row, unit), never stored
     bool drop_on = false;               // fsmg_dropout_enable / _disable
     bool drop_ever = false;             // enabled at least once (fsmg_dropout_mask / _set_pass need the scalars)
@@ -752,6 +765,17 @@ int msgd_begin_sum(fsmg_model* h);
 int msgd_rate_gradient(fsmg_model* h);
 inline bool msgd_rates_due(const fsmg_model* h) { return h->msgd_on && h->msgd_pending && h->msgd_cfg.alpha_lr > 0.f; }
 int msgd_update_rates(fsmg_model* h, float grad_scale);
+// api_lopt.hip.  lopt_check_train: a train form's inner_steps against max_train_steps, before any device work; lopt_begin:
+// F <- 1, I <- 0 where an adaptation begins (train: its steps are stored); lopt_inner_update: sgd_update with the learned rule;
+// lopt_meta_gradient: behind a query pass -- G rewritten, GPhi folded (first / weight: the per-artist forms), marked pending;
+// lopt_phi_due: fsmg_apply_update has Phi to move; lopt_update_phi: the launch inside apply_update
+int lopt_check_train(fsmg_model* h, int inner_steps);
+int lopt_begin(fsmg_model* h, bool train);
+int lopt_inner_update(fsmg_model* h, float lr);
+int lopt_meta_gradient(fsmg_model* h, bool first, double weight);
+inline bool lopt_phi_due(const fsmg_model* h) { return h->lopt_on && h->lopt_pending && h->lopt_cfg.phi_lr > 0.f; }
+int lopt_update_phi(fsmg_model* h, float grad_scale);
+int lopt_debug_read(fsmg_model* h, const char* what, float* host, int64_t count);      // fsmg_debug_read's "lopt_*" keys
 // api_dropout.hip.  drop_begin_pass: forward_backward_core, before choose_schedule -- decides drop_call and makes sure the
 // masked copies hold B sequences; drop_take_index: behind the staging, where nothing host-side can refuse the pass any more -- a dropped
 // pass takes its index.  drop_site_on: the site is masked in the pass in progress (its keep is below 1).

@@ -148,6 +148,11 @@ class FsmgMsgdConfig(C.Structure):
                 ('alpha_max', C.c_float), ('alpha_clip_norm', C.c_float), ('reserved', C.c_int32)]
 
 
+class FsmgLoptConfig(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('bF_init', C.c_float), ('bI_init', C.c_float), ('gate_scale', C.c_float),
+                ('phi_lr', C.c_float), ('phi_clip_norm', C.c_float), ('max_train_steps', C.c_int32), ('reserved', C.c_int32)]
+
+
 class FsmgDropoutConfig(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('keep_input', C.c_float), ('keep_output', C.c_float), ('variational', C.c_int32),
                 ('seed', C.c_uint64)]
@@ -331,6 +336,15 @@ SIGNATURES = {
     'fsmg_msgd_set_opt_state': (C.c_int, [_P, C.c_char_p, _F32P, _F32P, C.c_int64]),
     'fsmg_msgd_get_grad': (C.c_int, [_P, C.c_char_p, _F32P, C.c_int64]),
     'fsmg_msgd_grad_buffer': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    'fsmg_lopt_enable': (C.c_int, [_P, C.POINTER(FsmgLoptConfig)]),
+    'fsmg_lopt_disable': (C.c_int, [_P]),
+    'fsmg_lopt_info': (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    'fsmg_lopt_get_phi': (C.c_int, [_P, _F32P]),
+    'fsmg_lopt_set_phi': (C.c_int, [_P, _F32P]),
+    'fsmg_lopt_get_opt_state': (C.c_int, [_P, _F32P, _F32P]),
+    'fsmg_lopt_set_opt_state': (C.c_int, [_P, _F32P, _F32P]),
+    'fsmg_lopt_get_grad': (C.c_int, [_P, _F32P]),
+    'fsmg_lopt_grad_buffer': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
     'fsmg_dropout_enable': (C.c_int, [_P, C.POINTER(FsmgDropoutConfig)]),
     'fsmg_dropout_disable': (C.c_int, [_P]),
     'fsmg_dropout_info': (C.c_int, [_P, C.POINTER(C.c_int64)]),
@@ -1950,6 +1964,87 @@ class FsmgModel(object):
         """S of the last train-form adaptation, shaped like get_param(name)"""
         shape = self._shape(name)
         return self.debug_read('msgd_sum:' + name, int(np.prod(shape))).reshape(shape)
+
+    # -- learned optimiser: a meta-learner LSTM cell per element (include/fsmg.h "learned optimiser") ----------------
+    LOPT_NPHI = 14                      # wF[6], bF, wI[6], bI
+
+    @staticmethod
+    def lopt_config(bF_init=6.0, bI_init=0.0, gate_scale=2.0, phi_lr=0.0, phi_clip_norm=0.0, max_train_steps=4):
+        """the fsmg_lopt_config struct"""
+        return FsmgLoptConfig(struct_size=C.sizeof(FsmgLoptConfig), bF_init=float(bF_init), bI_init=float(bI_init), gate_scale=float(gate_scale),
+                              phi_lr=float(phi_lr), phi_clip_norm=float(phi_clip_norm), max_train_steps=int(max_train_steps), reserved=0)
+
+    def lopt_enable(self, cfg=None, **kw):
+        """every adaptation of this handle takes the learned rule from here on; cfg: FsmgLoptConfig, a dict of lopt_config's keywords, or keywords"""
+        c = cfg if isinstance(cfg, FsmgLoptConfig) else self.lopt_config(**dict(cfg or {}, **kw))
+        self._ck(self._lib.fsmg_lopt_enable(self._h, C.byref(c)))
+
+    def lopt_disable(self):
+        self._ck(self._lib.fsmg_lopt_disable(self._h))
+
+    def lopt_info(self):
+        """-> dict(enabled, allocated, max_train_steps, pending)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.fsmg_lopt_info(self._h, out))
+        return dict(enabled=bool(out[0]), allocated=bool(out[1]), max_train_steps=int(out[2]), pending=bool(out[3]))
+
+    def lopt_get_phi(self):
+        """-> float32 [14]: wF[6], bF, wI[6], bI"""
+        out = np.empty(self.LOPT_NPHI, np.float32)
+        self._ck(self._lib.fsmg_lopt_get_phi(self._h, _f32p(out)))
+        return out
+
+    def _phi14(self, value):
+        a = np.ascontiguousarray(value, dtype=np.float32).reshape(-1)
+        if a.size != self.LOPT_NPHI:
+            raise ValueError('Phi holds %d floats, got %d' % (self.LOPT_NPHI, a.size))
+        return a
+
+    def lopt_set_phi(self, phi):
+        a = self._phi14(phi)
+        self._ck(self._lib.fsmg_lopt_set_phi(self._h, _f32p(a)))
+
+    def lopt_get_opt_state(self):
+        m, v = np.empty(self.LOPT_NPHI, np.float32), np.empty(self.LOPT_NPHI, np.float32)
+        self._ck(self._lib.fsmg_lopt_get_opt_state(self._h, _f32p(m), _f32p(v)))
+        return m, v
+
+    def lopt_set_opt_state(self, m, v):
+        m, v = self._phi14(m), self._phi14(v)
+        self._ck(self._lib.fsmg_lopt_set_opt_state(self._h, _f32p(m), _f32p(v)))
+
+    def lopt_get_grad(self):
+        """GPhi of the pending gradient (a train form of maml_* on an enabled handle, before apply_update)"""
+        out = np.empty(self.LOPT_NPHI, np.float32)
+        self._ck(self._lib.fsmg_lopt_get_grad(self._h, _f32p(out)))
+        return out
+
+    def lopt_grad_buffer(self):
+        """-> (device pointer, 14) of GPhi: what a data-parallel wrapper all-reduces next to grad_buffer()"""
+        ptr, count = _P(), C.c_int64()
+        self._ck(self._lib.fsmg_lopt_grad_buffer(self._h, C.byref(ptr), C.byref(count)))
+        return ptr.value, count.value
+
+    def lopt_get_gates(self, name):
+        """-> (F, I) after the last inner step, shaped like get_param(name)"""
+        shape = self._shape(name)
+        n = int(np.prod(shape))
+        return self.debug_read('lopt_F:' + name, n).reshape(shape), self.debug_read('lopt_I:' + name, n).reshape(shape)
+
+    def lopt_get_stored(self, t, name):
+        """the support gradient a train form stored for inner step t (from 0), shaped like get_param(name)"""
+        shape = self._shape(name)
+        return self.debug_read('lopt_g%d:%s' % (int(t), name), int(np.prod(shape))).reshape(shape)
+
+    def lopt_get_scalars(self):
+        """-> (step_t[8], L_t[8]) of the last train-form adaptation"""
+        sc = self.debug_read('lopt_scalars', 16)
+        return sc[:8].copy(), sc[8:].copy()
+
+    def lopt_get_replayed(self, name):
+        """theta_K as the back-propagation replayed it; needs debug_set('keep_adapted', 1) before the train form"""
+        shape = self._shape(name)
+        return self.debug_read('lopt_theta:' + name, int(np.prod(shape))).reshape(shape)
 
     def debug_set(self, what, value):
         """run-time knob of the handle (include/fsmg.h: chain_spin_limit, fallback_steps, persistent, eager, inplace_dlogits,

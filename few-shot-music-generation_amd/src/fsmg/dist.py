@@ -148,6 +148,15 @@ class EpisodeParallel(object):
                     dist.all_reduce(rate_grad, op=dist.ReduceOp.SUM, group=self.group)
             else:
                 dist.all_reduce(rate_grad, op=dist.ReduceOp.SUM, group=self.group)
+        # the learned optimiser: the 14 floats of GPhi, formed per rank from ITS rewritten query gradient, the same way
+        lopt_grad = getattr(self.engine, 'lopt_grad_tensor', None) if maml is not None else None
+        if self.exchange and self.world > 1 and lopt_grad is not None:
+            ctx = getattr(self.engine, 'stream_context', None)
+            if ctx is not None:
+                with ctx():
+                    dist.all_reduce(lopt_grad, op=dist.ReduceOp.SUM, group=self.group)
+            else:
+                dist.all_reduce(lopt_grad, op=dist.ReduceOp.SUM, group=self.group)
         return self.engine.apply_update(1.0 / self.world, want_loss=want_loss)
 
     def mean_scalar(self, value):

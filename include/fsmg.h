@@ -1111,6 +1111,79 @@ int fsmg_msgd_set_opt_state(fsmg_handle h, const char* name, const float* m, con
 int fsmg_msgd_get_grad(fsmg_handle h, const char* name, float* host, int64_t count);
 int fsmg_msgd_grad_buffer(fsmg_handle h, void** device_ptr, int64_t* count);
 
+/* ---- Learned optimiser: a meta-learner LSTM for the MAML-style step (Ravi & Larochelle 2017, first order).
+ * Meta-SGD learns one fixed rate per element; this learns a RULE: a forget gate and an input gate per parameter element, computed from
+ * that element's support gradient, the support loss, the element's value and the previous gates, with fourteen weights Phi shared by
+ * all elements and trained with theta by the outer update.  While enabled, EVERY adaptation in the library takes step 1 below in place
+ * of the plain inner step (the forms Meta-SGD lists).  First order like the step it extends: the support gradients g_t, the support
+ * losses L_t and the clip scales are constants of the meta-gradient (the paper's own assumption).  No existing signature changes;
+ * never enabled, or disabled, every path is bit for bit what it was.  Meta-SGD and the learned optimiser exclude each other.
+ *
+ * State, created by the first fsmg_lopt_enable and kept until fsmg_destroy (not counted by fsmg_state_bytes): Phi = {wF[6], bF, wI[6],
+ * bI}, its Adam slots and gradient GPhi[14]; two buffers F, I laid out like the flat parameter buffer (the gates of the previous inner
+ * step); a store of max_train_steps flat support gradients with the scalars step_t, L_t per step; reduction partials.
+ *
+ *   1. Inner step t (1-based), element j.  The pass, the norm, the conditions under which the step is skipped and the fp32 scalar
+ *      step_t = (float)(clip / max(gnorm, clip)) * inner_lr are those of the plain inner step; L_t is the support loss of the pass.
+ *        prep(x) = (log|x| / 10, sign x)  where |x| >= e^-10,   (-1, e^10 x)  otherwise
+ *        (a1, a2) = prep(g_t[j]);  (c1, c2) = prep(L_t)
+ *        xF = (a1, a2, c1, c2, theta_{t-1}[j], F_{t-1}[j]);  xI = (a1, a2, c1, c2, theta_{t-1}[j], I_{t-1}[j]);  F_0 = 1, I_0 = 0
+ *        f = sigmoid(wF . xF + bF);  i = sigmoid(wI . xI + bI)       (the dot product: fma by fma from the bias, in the order of x)
+ *        q = f * theta_{t-1}[j]                                      (one rounding, never contracted)
+ *        st = step_t * (gate_scale * i)                              (two roundings)
+ *        theta_t[j] = q - st * g_t[j]                                (the plain step's expression with q for p and st for step)
+ *      F, I restart from F_0, I_0 whenever an adaptation begins (a repeat after a time-out is a beginning).  With w = 0, bF large
+ *      (f == 1), bI = 0 and gate_scale = 2 the step is the plain step bit for bit.  The train forms (fsmg_maml_forward_backward*,
+ *      fsmg_maml_step*, fsmg_maml_tasks_forward_backward / _step) also store g_t, step_t, L_t and refuse inner_steps >
+ *      max_train_steps (FSMG_ERR_INVALID) before any pass; eval, scoring and decoding forms store nothing and take up to 64 steps.
+ *   2. Meta-gradient, behind the query pass of a train form (per-artist forms: behind each artist's query pass, before the fold).
+ *      Per element D = G[j], carryF = carryI = 0; for t = K .. 1:
+ *        dF = D theta_{t-1} + carryF;  dI = -D step_t gate_scale g_t + carryI;  pf = dF f(1 - f);  pi = dI i(1 - i)
+ *        GwF += pf xF;  GbF += pf;  GwI += pi xI;  GbI += pi
+ *        D <- D f + pf wF[4] + pi wI[4];  carryF = pf wF[5];  carryI = pi wI[5]
+ *      then G[j] <- D: the outer gradient of theta is the gradient through the learned rule.  GPhi is the sum over elements in fp64
+ *      (pads contribute an exact 0), rounded to fp32 once; the per-artist forms fold the artists' sums with weight 1 / N in fixed
+ *      order in fp64.  inner_steps == 0: G stays, GPhi = 0.  Pending until the next fsmg_apply_update or backward pass.
+ *   3. Outer update, in fsmg_apply_update while a GPhi is pending and phi_lr > 0.  theta's clip + Adam runs unchanged on the rewritten
+ *      G.  Phi: gnorm = sqrt(sum GPhi^2) * grad_scale; scale = phi_clip_norm > 0 ? phi_clip_norm / max(gnorm, phi_clip_norm) *
+ *      grad_scale : grad_scale; theta's schedule with phi_lr in place of lr at the same global_step; theta's Adam element.  Skipped
+ *      wherever theta's step is skipped.  phi_lr == 0: Phi and its slots stay bitwise.
+ *   4. Data-parallel.  GPhi is formed per rank BEFORE any exchange: all-reduce the 14 floats of fsmg_lopt_grad_buffer beside
+ *      fsmg_grad_buffer, then fsmg_apply_update(1 / world).  A handle with a library communicator refuses fsmg_lopt_enable, and an
+ *      enabled handle refuses fsmg_comm_init / _attach (FSMG_ERR_STATE).
+ *
+ * fsmg_lopt_enable: the first call allocates and sets w = 0, bF = bF_init, bI = bI_init, slots 0; a later call keeps Phi and the
+ * slots and takes the new scalars (the store grows where max_train_steps did); captured graphs are dropped.  fsmg_lopt_disable: every
+ * path is the old one; the state is kept.  fsmg_lopt_info: out = {enabled, allocated, max_train_steps, GPhi pending}.  _get_phi /
+ * _set_phi / _get_grad move 14 floats, _get_opt_state / _set_opt_state 14 + 14; _get_grad returns FSMG_ERR_STATE without a pending
+ * GPhi.  fsmg_debug_read: "lopt_F:<name>", "lopt_I:<name>" the gates after the last inner step, "lopt_g<t>:<name>" the stored g_t
+ * (t from 0), "lopt_scalars" {step_t[8], L_t[8]}, "lopt_theta:<name>" the theta_K the back-propagation replayed (written only while
+ * keep_adapted is set).
+ * Errors, before any device work: FSMG_ERR_INVALID for a NULL handle / config, struct_size not sizeof(fsmg_lopt_config), nonzero
+ * reserved, a NaN or non-finite value anywhere, phi_lr or phi_clip_norm negative, gate_scale <= 0, max_train_steps outside [1, 8], a
+ * non-finite value given to _set_phi / _set_opt_state; FSMG_ERR_STATE with Meta-SGD enabled (and fsmg_msgd_enable with the learned
+ * optimiser enabled), with a communicator, and for the calls that need the state before the first fsmg_lopt_enable. */
+typedef struct {
+    int32_t struct_size;      /* sizeof(fsmg_lopt_config), else FSMG_ERR_INVALID            */
+    float bF_init;            /* bF of the first enable (6: f = 0.9975)                     */
+    float bI_init;            /* bI of the first enable (0: i = 1/2)                        */
+    float gate_scale;         /* > 0; 2: bI = 0 is the plain rate                           */
+    float phi_lr;             /* >= 0; 0: Phi is not trained                                */
+    float phi_clip_norm;      /* 0: no clipping of GPhi                                     */
+    int32_t max_train_steps;  /* 1 .. 8: inner steps a train form may take (and store)      */
+    int32_t reserved;         /* 0                                                          */
+} fsmg_lopt_config;
+#define FSMG_LOPT_NPHI 14
+int fsmg_lopt_enable(fsmg_handle h, const fsmg_lopt_config* cfg);
+int fsmg_lopt_disable(fsmg_handle h);
+int fsmg_lopt_info(fsmg_handle h, int64_t out[4]);
+int fsmg_lopt_get_phi(fsmg_handle h, float phi[FSMG_LOPT_NPHI]);
+int fsmg_lopt_set_phi(fsmg_handle h, const float phi[FSMG_LOPT_NPHI]);
+int fsmg_lopt_get_opt_state(fsmg_handle h, float m[FSMG_LOPT_NPHI], float v[FSMG_LOPT_NPHI]);
+int fsmg_lopt_set_opt_state(fsmg_handle h, const float m[FSMG_LOPT_NPHI], const float v[FSMG_LOPT_NPHI]);
+int fsmg_lopt_get_grad(fsmg_handle h, float gphi[FSMG_LOPT_NPHI]);
+int fsmg_lopt_grad_buffer(fsmg_handle h, void** device_ptr, int64_t* count);
+
 /* ---- Dropout for the train passes (Zaremba et al. 2014: non-recurrent connections only).  Never enabled, or
  * disabled, every path is what it was, bit for bit.  The masks are never stored: forward and backward regenerate them from a
  * counter-based generator (Philox4x32-10, Salmon et al. 2011), so a test can rebuild every mask on the host.
